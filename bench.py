@@ -14,11 +14,21 @@ decides every one of them exactly but evaluates ~1 %; value = all ranks' pairs /
 `config.workload` says whether the step is PREPARED (default: the k-d order of each cloud was computed
 once, outside the timed region -- rrl_cloud_order, config.prepare_us -- as a training loop does per
 dataset item; a target that has not moved keeps its records) or COLD (--cold: records + cell sort +
-tree of both clouds in every step).  Whichever one is timed, the other is measured right after on the
-same inputs and printed at top level (`value_cold` / `ms_per_step_cold`, or `value_prepared` / ...):
+tree of both clouds in every step).  With --full, whichever one is timed, the other is measured right after
+on the same inputs and printed at top level (`value_cold` / `ms_per_step_cold`, or `value_prepared` / ...):
 round-over-round comparisons of rounds 1-3 must use the cold number.
 
-Measured in the same run, outside the timed region, in the same JSON line:
+A plain run does only what the headline needs: it makes the workload, warms up, times the K steps, writes
+the last timed step's outputs if --dump-outputs DIR is given, and prints the line.  Its `extras` hold the
+timed step's own payload (`loss_sum`, `valid`) and nothing that takes a run of its own.
+
+--dump-outputs DIR: after the timed steps, what the last one computed -- what a caller of ops.LossStep
+receives -- as DIR/<name>.npy (float32 / float64): loss (B,), points1_grad (B, N, 9), info (B, 4) and the
+all-reduced payload (14,); with more than one rank every rank writes its own shard as <name>.rank<r>.npy.
+A points1_grad beyond DUMP_GRAD_BYTES is written as a seeded sample of its rows (points1_grad_rows.npy).
+The inputs are seeded: the same arguments give the same inputs in every run.
+
+With --full, measured in the same run, outside the timed region, in the same JSON line:
   * `variants.fused_dRdT`: the fused TRAINING op (ops.RegistrationStep: backward straight to (dR, dT),
     the headline of rounds 3-4); `variants.points1_grad_autograd`: section 8(d) through the drop-in
     callables chained by autograd (hipGraph replay); `variants.dropin_loop`: the reference trainers'
@@ -33,7 +43,7 @@ Measured in the same run, outside the timed region, in the same JSON line:
     stated baseline), the C/OpenMP port nested as `c_port`; bounded samples of the same workload.
 Weak scaling by default (B = 8 per GPU); --global-batch 64 fixes the total (BASELINE configs[2]).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -61,6 +71,8 @@ HBM_PEAK_GBS = 8000.0
 # sphere test = 3 sub + 3 (dot) + 3 (|a|^2) + 2 fma + add + mul = 12 (compares excluded); exact test = dist_sq's 16;
 # a resolved candidate = points 1 and 2; a fallback pair = 3 points
 OPS_SPHERE, OPS_EXACT, OPS_CAND, OPS_FALLBACK = 12, 11, 48, 48  # level-D prefilter: 10 FMA-chain ops + sign; candidate: 3 exact points
+# --dump-outputs stays under 64 MB over all ranks: points1_grad beyond this is sampled by rows (their float64 indices: 2/9 more)
+DUMP_GRAD_BYTES = 48 << 20
 
 
 def csrc_sha():
@@ -317,6 +329,12 @@ def main():
     ap.add_argument("--no-dist", action="store_true",
                     help="single process without a process group (default: even a plain 1-GPU run creates a 1-rank "
                          "RCCL group, so that the timed step carries the same all-reduce as N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every auxiliary measurement and check (host time, parity_in_run, "
+                         "the other build, fresh-input loops, roofline, variants, extras, B=64, CPU baseline); the --no-* "
+                         "options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (loss, points1_grad, info, payload)")
     args = ap.parse_args()
     if "RANK" not in os.environ and not args.no_dist and args.gpus == 1:
         # not under torchrun: a standalone 1-rank group on a free local port
@@ -358,7 +376,9 @@ def main():
     prepared = can_prepare and not args.cold
     order1 = order2 = None
     prepare_us = None
-    if can_prepare:
+    if can_prepare and not args.full:
+        order1, order2 = ops.cloud_order(w["tri1"]), ops.cloud_order(w["tri2"])
+    elif can_prepare:
         ops.cloud_order(w["tri1"])  # (first call: scratch allocation, code load)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -483,6 +503,18 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     payload = payload.clone()
+    if args.dump_outputs:  # the last timed step's results, as its caller receives them (ops.LossStep's outputs + the reduced payload)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f".rank{rank}" if world > 1 else ""
+        for name, t in (("loss", ls.st.loss), ("points1_grad", ls.grad), ("info", ls.st.info), ("payload", payload)):
+            a = t.detach().cpu().numpy()
+            if name == "points1_grad" and a.nbytes > DUMP_GRAD_BYTES // world:  # a fixed, seeded sample of the B * N rows
+                a = a.reshape(-1, 9)
+                rows = np.sort(np.random.default_rng(0).choice(len(a), DUMP_GRAD_BYTES // world // (9 * 4), replace=False))
+                np.save(os.path.join(args.dump_outputs, f"points1_grad_rows{sfx}.npy"), rows.astype(np.float64))
+                a = a[rows]
+            np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"),
+                    a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
     # ---- everything below is outside the timed region (rank 0 only, no collectives: the other ranks wait at the end)
     def time_loop(fn, n, warm=10):
@@ -505,13 +537,13 @@ def main():
     extras, variants, roofline = {}, {}, None
     pairs_step = B * L * 3 * (N + M)
     dense_flops = FLOPS_PER_PAIR * pairs_step
-    do_extras = rank == 0 and not args.no_extras
+    do_extras = rank == 0 and args.full and not args.no_extras
     other = None
     # ---- host time per step: what the CPU spends inside the calls that issue one step (the C call of
     # ops.LossStep + the reducer), measured while the GPU works through them asynchronously -- the step is GPU-bound as long as
     # this stays below ms_per_step; every rank measures (no collective inside), rank 0 reports
     host_us = None
-    if graphed is None:
+    if graphed is None and args.full:
         torch.cuda.synchronize()
         acc_h, nh = 0.0, 100
         for _ in range(nh):
@@ -527,6 +559,7 @@ def main():
         grad_default = ls.grad.clone()
         info_default = ls.st.info.clone()
         chained_step = bool(getattr(ls, "fused", False))  # the library's own word: the timed calls' records + scans were ONE launch
+    if rank == 0 and args.full:
         if not args.no_parity:
             try:
                 parity = parity_in_run(w, Rd, Td, ls.st.tri1t.clone(), loss_default, grad_default, info_default, sorted({0, B - 1}))
@@ -828,50 +861,53 @@ def main():
 
     if rank == 0:
         value = sum_pairs(world, B, args, L, N, M) * args.steps / dt
-        alg_bytes = B * (N + M) * 48 + B * L * 24 + 2 * B * L * 4  # ptri + lines + counts
-        if chained_step:  # + the records body of the same launch: raw row in; record, (P0, thr2), index, NaN reach, moved row, tree out; clearing
-            alg_bytes += int(B * N * (36 + 48 + 16 + 4 + 4 + 36 + 13 * 16 / 64 + 36))
-        cull_ms = roofline["launch_ms"]
-        cull_s = cull_ms * 1e-3
-        if "frac" not in roofline:
-            if args.mode != "cull":  # a dense mode was asked for: the timed kernel does evaluate every pair
-                roofline.update({"achieved": dense_flops / cull_s / 1e12, "frac": dense_flops / cull_s / 1e12 / VALU_PEAK_TFLOPS})
-            else:
-                roofline.update({"achieved": None, "frac": None})
-        attach_pmc(roofline, B, N, L, args.mode)
-        roofline.update({
-            "bound": "valu",
-            "note": "fp32 VALU / latency-bound, not HBM- or MFMA-bound (no FMA allowed where labels are decided; O(L (N+M)) "
-                    "elementwise geometry).  peak = 157.3 / 2 TFLOP/s (one flop per lane-op: 256 CU x 4 SIMD-32 x 2.4 GHz).  "
-                    "achieved / frac = arithmetic the kernel EXECUTED (in-kernel counters, this run: sphere tests x 12 + "
-                    "point-0 prefilter x 11 + resolved candidates x 48 lane-ops; queue / ballot / bookkeeping instructions not "
-                    "counted) / its launch time by HIP events on the launch stream (this run); frac_rocprof = the same / "
-                    "rocprof's average kernel duration of the committed profile of exactly this build; issue_frac = "
-                    "SQ_INSTS_VALU x 64 of the committed PMC pass / launch time; the dense work this kernel decides "
-                    "(18 flops per pair) is work_ratio x executed.",
-            "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-            "kernel": (("cull_scan_build_kernel (the CHAINED step's launch: the source's records body in its leading workgroups + the "
-                        "culled scan of both clouds; launch time = the whole launch, executed flops = the scan's, counted by the "
-                        "instrumented plain scan of the same step)") if chained_step else
-                       "cull_scan_kernel<false> (scan mode cull: the dominant kernel of the timed step)") if args.mode == "cull"
-                      else f"scan_kernel (scan mode {args.mode})",
-            "ops_per_test": {"sphere": OPS_SPHERE, "point0_prefilter": OPS_EXACT, "candidate": OPS_CAND,
-                             "fallback_pair": OPS_FALLBACK},
-            "csrc_sha": csrc_sha(),
-            "hbm": {"algorithmic_bytes": alg_bytes, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "achieved": alg_bytes / cull_s / 1e9, "frac": alg_bytes / cull_s / 1e9 / HBM_PEAK_GBS,
-                    "kernel": "scan launch of the timed step"}})
         ms_step = dt / args.steps * 1e3
+        if args.full:  # the roofline of the timed step's dominant launch, measured above
+            alg_bytes = B * (N + M) * 48 + B * L * 24 + 2 * B * L * 4  # ptri + lines + counts
+            if chained_step:  # + the records body of the same launch: raw row in; record, (P0, thr2), index, NaN reach, moved row, tree out; clearing
+                alg_bytes += int(B * N * (36 + 48 + 16 + 4 + 4 + 36 + 13 * 16 / 64 + 36))
+            cull_ms = roofline["launch_ms"]
+            cull_s = cull_ms * 1e-3
+            if "frac" not in roofline:
+                if args.mode != "cull":  # a dense mode was asked for: the timed kernel does evaluate every pair
+                    roofline.update({"achieved": dense_flops / cull_s / 1e12, "frac": dense_flops / cull_s / 1e12 / VALU_PEAK_TFLOPS})
+                else:
+                    roofline.update({"achieved": None, "frac": None})
+            attach_pmc(roofline, B, N, L, args.mode)
+            roofline.update({
+                "bound": "valu",
+                "note": "fp32 VALU / latency-bound, not HBM- or MFMA-bound (no FMA allowed where labels are decided; O(L (N+M)) "
+                        "elementwise geometry).  peak = 157.3 / 2 TFLOP/s (one flop per lane-op: 256 CU x 4 SIMD-32 x 2.4 GHz).  "
+                        "achieved / frac = arithmetic the kernel EXECUTED (in-kernel counters, this run: sphere tests x 12 + "
+                        "point-0 prefilter x 11 + resolved candidates x 48 lane-ops; queue / ballot / bookkeeping instructions not "
+                        "counted) / its launch time by HIP events on the launch stream (this run); frac_rocprof = the same / "
+                        "rocprof's average kernel duration of the committed profile of exactly this build; issue_frac = "
+                        "SQ_INSTS_VALU x 64 of the committed PMC pass / launch time; the dense work this kernel decides "
+                        "(18 flops per pair) is work_ratio x executed.",
+                "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "kernel": (("cull_scan_build_kernel (the CHAINED step's launch: the source's records body in its leading workgroups + the "
+                            "culled scan of both clouds; launch time = the whole launch, executed flops = the scan's, counted by the "
+                            "instrumented plain scan of the same step)") if chained_step else
+                           "cull_scan_kernel<false> (scan mode cull: the dominant kernel of the timed step)") if args.mode == "cull"
+                          else f"scan_kernel (scan mode {args.mode})",
+                "ops_per_test": {"sphere": OPS_SPHERE, "point0_prefilter": OPS_EXACT, "candidate": OPS_CAND,
+                                 "fallback_pair": OPS_FALLBACK},
+                "csrc_sha": csrc_sha(),
+                "hbm": {"algorithmic_bytes": alg_bytes, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "achieved": alg_bytes / cull_s / 1e9, "frac": alg_bytes / cull_s / 1e9 / HBM_PEAK_GBS,
+                        "kernel": "scan launch of the timed step"}})
         extras.update({"loss_sum": float(payload[0]), "valid": float(payload[1]),
-                       "line_sampling_s": w["sample_s"], "scan_launch_ms": cull_ms,
-                       "scan_share_of_step": cull_ms / ms_step,
-                       "host_us_per_step": host_us,
-                       "host_margin": (1.0 - host_us / (ms_step * 1e3)) if host_us else None,
-                       "host_note": "CPU time inside the calls that issue one step (ops.LossStep's C call: 3 launches chained, + the "
-                                    "reducer), 100 steps issued asynchronously behind the timed region; host_margin = 1 - host / "
-                                    "ms_per_step: the step is GPU-bound while it is positive (a slower host moves the crossover; a "
-                                    "hipGraph replay costs ~8 us + 1.5 us per node on this stack and is measured in warm-up: "
-                                    "config.allreduce.warmup_ms_per_step)"})
+                       "line_sampling_s": w["sample_s"]})
+        if args.full:
+            extras.update({"scan_launch_ms": cull_ms,
+                           "scan_share_of_step": cull_ms / ms_step,
+                           "host_us_per_step": host_us,
+                           "host_margin": (1.0 - host_us / (ms_step * 1e3)) if host_us else None,
+                           "host_note": "CPU time inside the calls that issue one step (ops.LossStep's C call: 3 launches chained, + "
+                                        "the reducer), 100 steps issued asynchronously behind the timed region; host_margin = 1 - "
+                                        "host / ms_per_step: the step is GPU-bound while it is positive (a slower host moves the "
+                                        "crossover; a hipGraph replay costs ~8 us + 1.5 us per node on this stack and is measured "
+                                        "in warm-up: config.allreduce.warmup_ms_per_step)"})
         out = {
             "metric": "point-pairs/sec for loss fwd+bwd at B=8, N=M=4096",
             "value": value, "unit": "point-pairs/s", "n_gpus": world, "steps": args.steps,
@@ -912,18 +948,16 @@ def main():
                                      "warmup_ms_per_step": choice_note}},
             "value_is": "SURVEY section 8(d) as defined: rigid apply + loss forward + backward to points1.grad (B, N, 9), "
                         "dense-equivalent pairs, " + ("prepared orders" if prepared else "cold build")
-                        + "; the other build of the same step is value_" + ("cold" if prepared else "prepared")
-                        + " (this rank, no all-reduce); round-over-round comparisons with rounds 1-3 must use the cold number; "
-                          "variants.fused_dRdT = the fused training op (rounds 3-4's headline)",
-            "roofline": roofline,
-            "parity_in_run": parity,
-            "variants": variants,
+                        + ("; the other build of the same step is value_" + ("cold" if prepared else "prepared")
+                           + " (this rank, no all-reduce); round-over-round comparisons with rounds 1-3 must use the cold number; "
+                             "variants.fused_dRdT = the fused training op (rounds 3-4's headline)" if args.full else ""),
+            **({"roofline": roofline, "parity_in_run": parity, "variants": variants} if args.full else {}),
             "extras": extras,
         }
         if other is not None:
             out["value_" + ("cold" if prepared else "prepared")] = other["value"]
             out["ms_per_step_" + ("cold" if prepared else "prepared")] = other["ms_per_step"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, M, L)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

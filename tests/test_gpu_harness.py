@@ -535,7 +535,7 @@ def test_bench_under_torchrun_uses_rccl_in_graph():
     comes up (communicator of 1 rank), the 14-float all-reduce is a node of the captured step, the
     reduced payload equals the local one.  STRUCTURAL assertions only: every timing of the children is
     reported in the line (and printed here), never compared -- a stopwatch must not decide a test."""
-    run = _bench_child(["--issue", "graph"], launcher=True)
+    run = _bench_child(["--issue", "graph", "--full"], launcher=True)
     ar = run["config"]["allreduce"]
     assert ar["reducer"] == "RcclReducer" and ar["placement"] == "inline" and ar["in_graph"] is True
     assert ar["backend"] == "nccl" and ar["rccl"]["nranks"] == 1 and ar["rccl"]["rank"] == 0
@@ -555,7 +555,7 @@ def test_bench_under_torchrun_uses_rccl_in_graph():
     assert direct["config"]["issue"] == "direct" and direct["config"]["allreduce"]["reducer"] == "RcclReducer"
     assert direct["extras"]["loss_sum"] == run["extras"]["loss_sum"]
     # the cold build of the same step: same sums, and each line carries the other build's figure at top level
-    cold = _bench_child(["--cold", "--issue", "direct"], launcher=False)
+    cold = _bench_child(["--cold", "--issue", "direct", "--full"], launcher=False)
     assert cold["config"]["prepared_order"] is False and "COLD" in cold["config"]["workload"]
     assert cold["extras"]["loss_sum"] == run["extras"]["loss_sum"] and cold["value_prepared"] > 0
     assert run["config"]["prepared_order"] is True and run["value_cold"] > 0 and run["ms_per_step_cold"] > 0
@@ -572,7 +572,7 @@ def test_bench_line_describes_what_it_times():
     scan sits under dense_reference; the fused dR/dT op, the autograd chain and the reference trainers' literal per-sample
     loop are variants of the same line with the same loss bits; a plain `--no-dist` invocation runs without a process
     group.  No assertion here compares two wall-clock figures."""
-    run = _bench_child(["--no-dist"], launcher=False, base=("--steps", "60", "--warmup", "10", "--no-cpu-baseline"))
+    run = _bench_child(["--no-dist"], launcher=False, base=("--steps", "60", "--warmup", "10", "--no-cpu-baseline", "--full"))
     assert run["config"]["step"].startswith("loss_step") and "points1.grad" in run["config"]["workload"]
     assert run["config"]["prepared_order"] is True and run["config"]["prepare_us"] > 0 and "PREPARED" in run["config"]["workload"]
     assert run["config"]["allreduce"]["process_group"] is False
@@ -609,6 +609,32 @@ def test_bench_line_describes_what_it_times():
     assert run["config"]["break_even_steps"] is None or run["config"]["break_even_steps"] > 0
     print("ms_per_step:", {"timed": run["ms_per_step"], "cold": run["ms_per_step_cold"], "B64": b64["ms_per_step"],
                            **{k: x["ms_per_step"] for k, x in v.items()}})
+
+
+def test_bench_plain_run_dumps_the_timed_outputs(tmp_path):
+    """A plain run (no --full) prints the headline of exactly --steps timed steps and nothing that takes a run of its own;
+    --dump-outputs writes the last timed step's outputs.  The inputs are seeded, so two runs with different step counts agree
+    output for output: loss, counts and payload bit for bit, points1.grad to the rounding of the scatter's float atomics."""
+    got = []
+    for k, steps in enumerate((30, 50)):
+        d = tmp_path / f"out{k}"
+        run = _bench_child(["--dump-outputs", str(d)], launcher=False, base=("--steps", str(steps), "--warmup", "5"))
+        assert run["steps"] == steps and run["ms_per_step"] > 0 and run["higher_is_better"] is True and run["dtype"] == "f32"
+        assert run["value"] == pytest.approx(8 * 10000 * 3 * 8192 / (run["ms_per_step"] * 1e-3), rel=1e-9)
+        for key in ("roofline", "parity_in_run", "variants", "cpu_baseline", "value_cold"):
+            assert key not in run, key
+        out = {f.stem: np.load(f) for f in d.glob("*.npy")}
+        assert sorted(out) == ["info", "loss", "payload", "points1_grad"]
+        assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+        assert out["loss"].shape == (8,) and out["points1_grad"].shape == (8, 4096, 9) and out["info"].shape == (8, 4)
+        assert float(out["payload"][0]) == run["extras"]["loss_sum"] and float(out["payload"][1]) == run["extras"]["valid"] == 8.0
+        assert float(out["loss"].astype(np.float64).sum()) == pytest.approx(run["extras"]["loss_sum"], rel=1e-6)
+        got.append(out)
+    a, b = got
+    for name in ("loss", "info", "payload"):
+        assert np.array_equal(a[name], b[name]), name
+    assert np.abs(a["points1_grad"] - b["points1_grad"]).max() <= 1e-5 * np.abs(a["points1_grad"]).max()
+    assert (np.abs(a["points1_grad"]).sum(-1) > 0).sum() > 0
 
 
 def test_fragments_multi_pose_equals_the_loop(C, G):

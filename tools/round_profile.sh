@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box, repo root): tools/round_profile.sh <tag>
-# Produces under gpurun_out/: the default bench line, the rocprofv3 --kernel-trace --stats summary of
+# Produces in its output directory ($O): the full bench line (--full), the rocprofv3 --kernel-trace --stats summary of
 # the SAME command, separate PMC passes for FETCH_SIZE / WRITE_SIZE (HBM traffic per kernel, the
 # guide's recipe: own runs, --kernel-trace only) and two SQ counter passes -- for the TIMED shape (B = 8) and for the
 # chip-filling shape bench.py reports under roofline.at_B64 (B = 64 on one GPU).
@@ -10,8 +10,8 @@
 TAG=${1:-r}
 R=$PWD; O=$R/gpurun_out; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-python3 $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o s -- python3 $R/bench.py --no-cpu-baseline > $O/${TAG}_bench_prof.json 2> $O/${TAG}_bench_prof.err
+python3 $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o s -- python3 $R/bench.py --full --no-cpu-baseline > $O/${TAG}_bench_prof.json 2> $O/${TAG}_bench_prof.err
 STEPARGS="--no-cpu-baseline --no-extras --no-other --issue direct --no-dist --no-fresh --no-parity"
 passes() {  # $1 = suffix ("" or "_b64"), $2 = extra bench arguments
   # the timed step alone (no variant / strict / counter / drop-in / Chamfer passes): per-kernel averages of the headline path
@@ -115,6 +115,6 @@ PY
 # the bench line once more, now that the traffic / PMC object of exactly this build exists: the committed line carries it
 if [ -f $O/${TAG}_scan_hbm_traffic.json ]; then
   cp $O/${TAG}_scan_hbm_traffic.json $R/profiles/scan_hbm_traffic.json
-  (cd /tmp; python3 $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err)
+  (cd /tmp; python3 $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err)
 fi
 tail -c 1500 $O/${TAG}_bench.json
