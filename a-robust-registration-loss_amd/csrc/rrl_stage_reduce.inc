@@ -3,10 +3,7 @@
 // ---------------------------------------------------------------------------------------
 // K3+K4: one 1024-lane workgroup per sample
 // ---------------------------------------------------------------------------------------
-// Welsch1(x, c) = 1 - exp(-(x / c) / 2), code/loss.py:20-21
-__device__ __forceinline__ float welsch(float d, float med) {
-    return 1.0f - expf(-(d / med) / 2.0f);
-}
+// welsch(): rrl_arith.h (shared with the wide pipeline, rrl_wide.hip)
 
 // The k x j block of D values is stored row-major with stride j; bring it into a 4 x 4
 // register tile (static indices only; entries outside the block are +inf).

@@ -63,7 +63,7 @@ def cal_intersection_batch2_points_with_line(point_neis, line):
 
 
 def cal_loss_intersection_batch_whole_median_pts_lines(s_m, s_n, e_m, e_n, points1, points2, line,
-                                                       device='cpu', *, mode=None, chunk=0):
+                                                       device='cpu', *, mode=None, chunk=0, max_hits=4):
     """The intersected-line robust registration loss (code/loss.py:170-232).
 
     points1 (B, N, 9) transformed source pseudo-triangles (receives the gradient),
@@ -74,6 +74,12 @@ def cal_loss_intersection_batch_whole_median_pts_lines(s_m, s_n, e_m, e_n, point
     median and so does this function -- use `batched_intersection_loss` for B
     independent losses in one launch.
 
+    Bucket ranges: by default within 1..4 hits per line and cloud (1 <= s_m, s_n and e_m, e_n <= 5,
+    every reference caller's (1, 1, 5, 5)), the tuned path; a wider range raises ValueError.
+    max_hits=8 (keyword-only; code/loss.py:10-17 names the maximum number of hits per line as the
+    metric's approximation knob) also accepts ranges up to 8 hits (e_m, e_n <= 9): those run the wide
+    pipeline (one call per slice, one host read-back).  Any other range raises ValueError.
+
     Raises ValueError on a NaN distance (non-unit line direction), where the reference prints
     "Exit the systerm" and exits with status 0 (code/loss.py:89-91).
     mode: "cull" (default: strict semantics; sphere-culled, lazy evaluation where a NaN is
@@ -81,6 +87,11 @@ def cal_loss_intersection_batch_whole_median_pts_lines(s_m, s_n, e_m, e_n, point
     """
     if points1.dim() != 3 or line.dim() != 3 or points2.dim() != 3:
         raise ValueError("Input is wrong")  # code/loss.py:69-71
+    if max_hits not in (4, 8):
+        raise ValueError("max_hits must be 4 (the default) or 8")
+    if max_hits == 4 and _ops._is_wide((s_m, s_n, e_m, e_n)):
+        raise ValueError("bucket range must lie within 1..4 hits per line (e_m, e_n <= 5); pass max_hits=8 for "
+                         "ranges up to 8 hits per line (e_m, e_n <= 9)")
     pool = points1.shape[0] > 1
     # forward + the call's single host sync in one C call: (nbuckets, nselected, nvalues, NaN flag) arrive through a
     # 16-byte pinned copy; the workspace is leased from a per-shape pool (rrl_hip.ops._DropinLoss)
@@ -100,7 +111,8 @@ def batched_intersection_loss(points1, points2, line, rng=(1, 1, 5, 5), *, mode=
     """B independent losses in one set of launches -- what the reference's callers compute
     with `for j in range(B): loss += cal_loss_...(…[j:j+1]…)` (rpm/Train_RPM.py:226-231,
     dcp/Train_DCP.py:266-270, fmr/model.py:302-306).  Returns (loss (B,), valid (B,) bool) on
-    the GPU without any host synchronisation; loss[b] is 0 where valid[b] is False."""
+    the GPU without any host synchronisation; loss[b] is 0 where valid[b] is False.  rng: as above, up to
+    8 hits per line (a wide range synchronises once: its hit-recovery check)."""
     loss, info, _ = _ops.intersection_loss(points1, points2, line, rng, pool=False,
                                            mode=_scan_mode(mode), chunk=chunk)
     return loss, info[:, 0] > 0

@@ -18,6 +18,9 @@ _I = _c.c_int
 _Z = _c.c_size_t
 _SIGS = {
     "rrl_workspace_layout": [_I, _I, _I, _I, _P],
+    "rrl_wide_workspace_layout": [_I, _I, _I, _I, _P],
+    "rrl_loss_forward_wide": [_P, _P, _P, _P, _Z, _P, _Z, _P] + [_I] * 11 + [_P, _P],
+    "rrl_loss_backward_wide": [_P, _Z, _P, _P, _P] + [_I] * 5 + [_P],
     "rrl_loss_forward": [_P, _P, _P, _P, _Z, _P] + [_I] * 11 + [_P],
     "rrl_loss_backward": [_P, _P, _P, _Z, _P, _P, _P] + [_I] * 5 + [_P],
     "rrl_registration_forward": [_P] * 6 + [_Z, _P] + [_I] * 11 + [_P],
@@ -79,7 +82,7 @@ _SIGS = {
     "rrl_sample_lines_rng": [_P] * 8 + [_I] * 3 + [_P],
 }
 EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamfer_workspace_bytes",
-                                 "rrl_cloud_order_workspace_bytes"])
+                                 "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes"])
 
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
 F_CHAIN = 2        # RRL_F_CHAIN: leave the hit counts / CHAIN words cleared for the next step on this workspace
@@ -143,6 +146,8 @@ def load():
     lib.rrl_version.restype = ctypes.c_char_p
     lib.rrl_workspace_bytes.argtypes = [_I, _I, _I, _I]
     lib.rrl_workspace_bytes.restype = _Z
+    lib.rrl_wide_workspace_bytes.argtypes = [_I, _I, _I, _I]
+    lib.rrl_wide_workspace_bytes.restype = _Z
     lib.rrl_chamfer_workspace_bytes.argtypes = [_I, _I, _I]
     lib.rrl_chamfer_workspace_bytes.restype = _Z
     lib.rrl_cloud_order_workspace_bytes.argtypes = [_I, _I]

@@ -108,7 +108,10 @@ class PayloadReducer:
 def sharded_batch_loss(points1, points2, line, rng=(1, 1, 5, 5), loss_fn=None, group=None):
     """points1/points2/line hold the GLOBAL batch on every rank (or identical seeds); each rank
     evaluates its shard and the result is the global (loss_sum, n_valid).  loss_fn(p1, p2, ln,
-    rng) -> (loss (b,), valid (b,)); defaults to the HIP batched loss."""
+    rng) -> (loss (b,), valid (b,)); defaults to the HIP batched loss.  Bucket ranges within 1..4 hits per line only."""
+    from . import ops
+    if ops._is_wide(rng):
+        raise ValueError(ops._wide_refusal("rrl_hip.dist.sharded_batch_loss"))
     if loss_fn is None:
         import loss as _loss  # the drop-in module one directory up (on sys.path)
         loss_fn = lambda a, b, c, r: _loss.batched_intersection_loss(a, b, c, r)  # noqa: E731
@@ -170,7 +173,7 @@ def line_shard_local(tri1, tri2, line, rng=(1, 1, 5, 5), mode="cull", chunk=0):
     if tri1.shape[0] != 1 or tri2.shape[0] != 1 or line.shape[0] != 1:
         raise ValueError("the line-sharded mode evaluates ONE sample (B == 1); batches shard by samples (sharded_batch_loss)")
     N, M, L = tri1.shape[1], tri2.shape[1], line.shape[1]
-    s_m, s_n, e_m, e_n = ops._check_range(rng)
+    s_m, s_n, e_m, e_n = ops._check_range(rng, "the line-sharded loss (rrl_hip.dist)")
     dev = tri1.device
     st = ops.LossState(1, N, M, max(L, 1), 1, dev)
     st.status.zero_()
@@ -196,7 +199,7 @@ def line_shard_merge(st, rows, kj, rng=(1, 1, 5, 5), nan_flag=None):
     uses the statistics of ALL lines.  nan_flag: the scan's NaN flag over all ranks (int tensor) or None."""
     from . import ops
     lib = ops._lib.load()
-    s_m, s_n, e_m, e_n = ops._check_range(rng)
+    s_m, s_n, e_m, e_n = ops._check_range(rng, "the line-sharded loss (rrl_hip.dist)")
     dev = st.ws.device
     if nan_flag is not None:
         st.status[0] = nan_flag.to(st.status.dtype)
@@ -268,5 +271,7 @@ def line_sharded_loss(points1, points2, line, rng=(1, 1, 5, 5), mode="cull", gro
     status (4,)) like ops.intersection_loss; the loss is bit-identical to the unsharded one and the same on all ranks,
     its gradient w.r.t. points1 / points2 is the full gradient (summed over the ranks) on every rank.  Collectives per
     call: the shares' sizes with the NaN flag (16 bytes), the selected lines' rows (68 bytes each); per backward: the
-    point gradients (every rank takes part, with zeros when its own loss is not used)."""
+    point gradients (every rank takes part, with zeros when its own loss is not used).  Bucket ranges within 1..4 only."""
+    from . import ops
+    ops._check_range(rng, "rrl_hip.dist.line_sharded_loss")
     return _LineShardedLoss.apply(points1, points2, line, tuple(rng), mode, group)

@@ -76,6 +76,7 @@ _spec_cache = {}  # (dims) -> {field: (offset, nbytes, dtype, shape)}
 
 
 _gpu_ok = False
+_deterministic = [os.environ.get("RRL_DETERMINISTIC", "")[:1] == "1"]  # mirrors the library's default (rrl_set_deterministic)
 
 
 def require_gpu():
@@ -255,12 +256,104 @@ class LossState:
         return self.info[:, 0]
 
 
-def _check_range(rng):
+# wide workspace fields, in the order of include/rrl.h's RRL_WW_* enum: (name, dtype, shape)
+_WW_FIELDS = [
+    ("status", torch.int32, lambda B, N, M, L, G: (4,)),
+    ("nsel", torch.int32, lambda B, N, M, L, G: (B,)),
+    ("rec", torch.int32, lambda B, N, M, L, G: (2 * B * L,)),
+    ("sel", torch.int32, lambda B, N, M, L, G: (B, L)),
+    ("kj", torch.uint8, lambda B, N, M, L, G: (B, L)),
+    ("hs1", torch.int32, lambda B, N, M, L, G: (B, L, 8)),
+    ("hs2", torch.int32, lambda B, N, M, L, G: (B, L, 8)),
+    ("w1", torch.float32, lambda B, N, M, L, G: (B, L, 8, 3)),
+    ("w2", torch.float32, lambda B, N, M, L, G: (B, L, 8, 3)),
+    ("Q1", torch.float32, lambda B, N, M, L, G: (B, L, 8, 4)),
+    ("Q2", torch.float32, lambda B, N, M, L, G: (B, L, 8, 4)),
+    ("D", torch.float32, lambda B, N, M, L, G: (B, L, 8, 8)),
+    ("med", torch.float32, lambda B, N, M, L, G: (G,)),
+    ("bcnt", torch.int32, lambda B, N, M, L, G: (G, 64)),
+    ("bsum", torch.int64, lambda B, N, M, L, G: (G, 64, 2)),
+    ("info", torch.int32, lambda B, N, M, L, G: (G, 4)),
+]
+_WW_INDEX = {name: i for i, (name, _, _) in enumerate(_WW_FIELDS)}
+_wide_layout_cache = {}
+
+
+def _wide_layout(B, N, M, L):
+    key = (B, N, M, L)
+    if key not in _wide_layout_cache:
+        lib = _lib.load()
+        offs = (ctypes.c_size_t * len(_WW_FIELDS))()
+        check(lib.rrl_wide_workspace_layout(B, N, M, L, offs), "rrl_wide_workspace_layout")
+        _wide_layout_cache[key] = (int(lib.rrl_wide_workspace_bytes(B, N, M, L)), [int(o) for o in offs])
+    return _wide_layout_cache[key]
+
+
+class WideState:
+    """One evaluation of the wide pipeline (bucket ranges up to 8 hits per line, include/rrl.h rrl_loss_forward_wide):
+    the scan's loss workspace (`scan`, a LossState), the wide workspace (RRL_WW_*) and loss[G].  Named fields of the wide
+    workspace are lazy views (status, info, med, D, ...)."""
+    wide = True
+
+    def __init__(self, B, N, M, L, G, dev):
+        self.dims = (B, N, M, L, G)
+        self.scan = LossState(B, N, M, L, G, dev)
+        self.loss = self.scan.loss
+        self.wnbytes, self.woffsets = _wide_layout(B, N, M, L)
+        self.wws = torch.empty(self.wnbytes, dtype=torch.uint8, device=dev)
+        self.host_flags = None
+
+    def __getattr__(self, name):
+        i = _WW_INDEX.get(name)
+        if i is None:
+            raise AttributeError(name)
+        _, dtype, shape = _WW_FIELDS[i]
+        shp = shape(*self.dims)
+        n = 1
+        for d in shp:
+            n *= d
+        off = self.woffsets[i]
+        return self.wws[off:off + n * _ITEMSIZE[dtype]].view(dtype).reshape(shp)
+
+    @property
+    def nbuckets(self):
+        return self.info[:, 0]
+
+
+def _classify_range(rng):
+    """((s_m, s_n, e_m, e_n), wide): a range within 1..4 hits per line (RRL_MAX_HITS: e_m, e_n <= 5, every reference
+    caller's (1, 1, 5, 5)) is served by the narrow, tuned path; a WIDE one (up to 8 hits: e_m, e_n <= 9) by the wide
+    pipeline (include/rrl.h rrl_loss_forward_wide); anything else is a ValueError."""
     s_m, s_n, e_m, e_n = (int(v) for v in rng)
-    if not (1 <= s_m and 1 <= s_n and e_m <= 5 and e_n <= 5):
-        raise ValueError("bucket range must lie within 1..4 (RRL_MAX_HITS), as every reference "
-                         "caller's (1, 1, 5, 5) does")
-    return s_m, s_n, e_m, e_n
+    if 1 <= s_m and 1 <= s_n and e_m <= 5 and e_n <= 5:
+        return (s_m, s_n, e_m, e_n), False
+    if 1 <= s_m and 1 <= s_n and e_m <= 9 and e_n <= 9:
+        return (s_m, s_n, e_m, e_n), True
+    raise ValueError("bucket range must lie within 1..8 hits per line and cloud (1 <= s_m, s_n and e_m, e_n <= 9; "
+                     "every reference caller passes (1, 1, 5, 5))")
+
+
+def _is_wide(rng):
+    """True for a valid wide range (never raises)."""
+    try:
+        return _classify_range(rng)[1]
+    except (TypeError, ValueError):
+        return False
+
+
+def _wide_refusal(what):
+    return (f"{what} serves bucket ranges within 1..4 hits per line (RRL_MAX_HITS, e_m, e_n <= 5) only; a wide range "
+            "(up to 8 hits, e_m, e_n <= 9) goes through ops.intersection_loss (or loss.batched_intersection_loss / "
+            "loss.cal_loss_intersection_batch_whole_median_pts_lines)")
+
+
+def _check_range(rng, what="this entry"):
+    """The gate of the entries that serve the narrow ranges only (within 1..4): a wide range raises a ValueError that
+    names ops.intersection_loss, anything else the range error of _classify_range."""
+    r, wide = _classify_range(rng)
+    if wide:
+        raise ValueError(_wide_refusal(what))
+    return r
 
 
 def _target_ws(target_from, B, N, M, L):
@@ -411,7 +504,7 @@ def loss_forward_raw(tri1, tri2, line, rng=(1, 1, 5, 5), pool=False, mode="cull"
     B, N, _ = tri1.shape
     M, L = tri2.shape[1], line.shape[1]
     G = 1 if pool else B
-    s_m, s_n, e_m, e_n = _check_range(rng)
+    s_m, s_n, e_m, e_n = _check_range(rng, "loss_forward_raw (target_from / cached forwards)")
     dev = tri1.device
     if tri2.device != dev or line.device != dev:
         raise ValueError("tri1, tri2 and line must live on the same GPU")
@@ -447,9 +540,49 @@ def loss_forward_raw(tri1, tri2, line, rng=(1, 1, 5, 5), pool=False, mode="cull"
     return st
 
 
+def loss_forward_wide(tri1, tri2, line, rng, pool=False, mode="cull", chunk=0, opts=None):
+    """Forward of the wide pipeline (include/rrl.h rrl_loss_forward_wide: any range with 1 <= s_m, s_n and e_m, e_n <= 9)
+    on already-prepared GPU tensors; returns the WideState.  opts: make_opts(order1=, order2=) and the scan knobs.
+    Synchronises once: the hit-recovery invariant (STATUS[0] of the wide workspace: the hits found again for the lines
+    with more than 4 must number what the scan counted) is checked on the host together with INFO (st.host_flags), and
+    an inconsistent evaluation raises RRLError instead of returning a loss."""
+    if _deterministic[0] or (opts is not None and opts.deterministic == 1):
+        raise ValueError(_wide_refusal("deterministic-gradient mode (set_deterministic(True))"))
+    (s_m, s_n, e_m, e_n), _ = _classify_range(rng)
+    B, N, _ = tri1.shape
+    M, L = tri2.shape[1], line.shape[1]
+    G = 1 if pool else B
+    dev = tri1.device
+    if tri2.device != dev or line.device != dev:
+        raise ValueError("tri1, tri2 and line must live on the same GPU")
+    st = WideState(B, N, M, L, G, dev)
+    st.pool = bool(pool)
+    with _guard(dev):
+        check(_lib.load().rrl_loss_forward_wide(_p(tri1), _p(tri2), _p(line), _p(st.scan.ws), st.scan.nbytes, _p(st.wws),
+                                                st.wnbytes, _p(st.loss), B, N, M, L, s_m, s_n, e_m, e_n, int(pool),
+                                                _MODES[mode], int(chunk), _optr(opts), _stream(dev)), "rrl_loss_forward_wide")
+        fl = torch.cat([st.status[:1], st.info.reshape(-1)]).tolist()  # the one read-back
+    if fl[0]:
+        raise RRLError(f"rrl_loss_forward_wide: the hits of {fl[0]} selected line(s) found again by the hit recovery do not "
+                       "number what the scan counted; the result is refused")
+    st.host_flags = fl[1:]
+    return st
+
+
+def _wide_backward(st, tri1, tri2, g, want2, dev):
+    """(grad points1, grad points2 or None) of a wide evaluation for dL/dloss = g (G,)."""
+    B, N, M, L, _ = st.dims
+    g1 = torch.empty_like(tri1)  # zeroed by rrl_loss_backward_wide
+    g2 = torch.empty_like(tri2) if want2 else None
+    with _guard(dev):
+        check(_lib.load().rrl_loss_backward_wide(_p(st.wws), st.wnbytes, _p(g), _p(g1), _p(g2), B, N, M, L,
+                                                 int(st.pool), _stream(dev)), "rrl_loss_backward_wide")
+    return g1, g2
+
+
 class _IntersectionLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, points1, points2, line, rng, pool, mode, chunk, target_from=None, opts=None):
+    def forward(ctx, points1, points2, line, rng, pool, mode, chunk, target_from=None, opts=None, force_wide=False):
         dev = _home(points1, points2, line)
         tri1, tri2 = _prep(points1, "points1", 9, dev), _prep(points2, "points2", 9, dev)
         ln = _prep(line, "line", 6, dev)
@@ -465,10 +598,16 @@ class _IntersectionLoss(torch.autograd.Function):
                    torch.zeros(4, dtype=torch.int32, device=dev))
             ctx.mark_non_differentiable(out[1], out[2])
             return out
-        st = loss_forward_raw(tri1, tri2, ln, rng, pool, mode, chunk, target_from=target_from, opts=opts)
+        ctx.wide = force_wide or _is_wide(rng)
+        if ctx.wide:
+            if target_from is not None:
+                raise ValueError(_wide_refusal("target_from (a carried-over target scan)"))
+            st = loss_forward_wide(tri1, tri2, ln, rng, pool, mode, chunk, opts=opts)
+        else:
+            st = loss_forward_raw(tri1, tri2, ln, rng, pool, mode, chunk, target_from=target_from, opts=opts)
         ctx.st, ctx.tri1, ctx.tri2, ctx.pool = st, tri1, tri2, bool(pool)
         ctx.in_devs = (points1.device, points2.device)
-        info, status = st.info, st.status
+        info, status = st.info, (st.scan.status if ctx.wide else st.status)
         ctx.mark_non_differentiable(info, status)
         ctx.set_materialize_grads(False)  # no zero-filled grads for the integer outputs
         _IntersectionLoss.last_state = st  # for shard_payload(): the newest evaluation
@@ -479,9 +618,16 @@ class _IntersectionLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g1, _g2):
         if g_loss is None or ctx.st is None:
-            return (None,) * 9
+            return (None,) * 10
         lib = _lib.load()
         st, tri1, tri2 = ctx.st, ctx.tri1, ctx.tri2
+        if ctx.wide:
+            g = g_loss.detach().to(device=tri1.device, dtype=torch.float32).contiguous()
+            g1, g2 = _wide_backward(st, tri1, tri2, g, ctx.needs_input_grad[1], tri1.device)
+            g1 = g1.to(ctx.in_devs[0]) if ctx.needs_input_grad[0] else None
+            if g2 is not None:
+                g2 = g2.to(ctx.in_devs[1])
+            return g1, g2, None, None, None, None, None, None, None, None
         B, N, _ = tri1.shape
         M, L = tri2.shape[1], st.dims[3]
         g = g_loss.detach().to(device=tri1.device, dtype=torch.float32).contiguous()
@@ -493,7 +639,7 @@ class _IntersectionLoss(torch.autograd.Function):
         g1 = g1.to(ctx.in_devs[0]) if ctx.needs_input_grad[0] else None
         if g2 is not None:
             g2 = g2.to(ctx.in_devs[1])
-        return g1, g2, None, None, None, None, None, None, None
+        return g1, g2, None, None, None, None, None, None, None, None
 
 
 # ---- the reference-signature call (loss.cal_loss_intersection_batch_whole_median_pts_lines) ----------------------
@@ -555,7 +701,16 @@ def _dropin_forward(ctx, points1, points2, line, rng, pool, mode, chunk):
         _DropinLoss.flags_all = [0, 0, 0, 0] * max(G, 1)
         _DropinLoss.flags = [0, 0, 0, 0]
         return torch.zeros(max(G, 1), device=dev)
-    s_m, s_n, e_m, e_n = _check_range(rng)
+    (s_m, s_n, e_m, e_n), wide = _classify_range(rng)
+    ctx.wide = wide
+    if wide:  # the wide pipeline (ranges up to 8 hits per line): a workspace of its own per call, one read-back
+        st = loss_forward_wide(tri1, tri2, ln, (s_m, s_n, e_m, e_n), pool, mode, chunk)
+        _DropinLoss.flags_all = fl = st.host_flags
+        _DropinLoss.flags = fl[:4]
+        ctx.st, ctx.tri1, ctx.tri2, ctx.pool = st, tri1, tri2, bool(pool)
+        ctx.in_devs = (points1.device, points2.device)
+        _IntersectionLoss.last_state = st
+        return st.loss
     st = _lease_state(B, N, M, L, G, dev)
     if not hasattr(st, "hostp"):  # created while capturing: no read-back possible there
         raise RRLError("the reference-signature loss synchronises (it returns None / raises on the host): "
@@ -580,11 +735,14 @@ def _dropin_backward(ctx, g_loss):
     dev = tri1.device
     g = g_loss if (g_loss.device == dev and g_loss.dtype == torch.float32 and g_loss.is_contiguous()) else \
         g_loss.detach().to(device=dev, dtype=torch.float32).contiguous()
-    g1 = torch.empty_like(tri1)  # zeroed by rrl_loss_backward
-    g2 = torch.empty_like(tri2) if ctx.needs_input_grad[1] else None
-    with _guard(dev):
-        check(_lib.load().rrl_loss_backward(_p(tri1), _p(tri2), st.wsp, st.nbytes, _p(g), _p(g1), _p(g2),
-                                            B, N, M, L, int(ctx.pool), _stream(dev)), "rrl_loss_backward")
+    if getattr(ctx, "wide", False):
+        g1, g2 = _wide_backward(st, tri1, tri2, g, ctx.needs_input_grad[1], dev)
+    else:
+        g1 = torch.empty_like(tri1)  # zeroed by rrl_loss_backward
+        g2 = torch.empty_like(tri2) if ctx.needs_input_grad[1] else None
+        with _guard(dev):
+            check(_lib.load().rrl_loss_backward(_p(tri1), _p(tri2), st.wsp, st.nbytes, _p(g), _p(g1), _p(g2),
+                                                B, N, M, L, int(ctx.pool), _stream(dev)), "rrl_loss_backward")
     if not ctx.needs_input_grad[0]:
         g1 = None
     elif ctx.in_devs[0] != dev:
@@ -734,7 +892,8 @@ def intersection_loss_dropin(points1, points2, line, rng=(1, 1, 5, 5), pool=Fals
     reference-signature call with its single host read-back inside (one C call).  See _DropinLoss; a call whose three
     arguments are the [j:j+1] slices of batch tensors is served from one evaluation of the whole batch (above)."""
     rng = tuple(rng)
-    if DROPIN_BATCH and isinstance(points1, torch.Tensor) and points1.dim() == 3 and points1.shape[0] == 1 \
+    # (a wide range skips the whole-batch serving: the per-call path below serves it)
+    if DROPIN_BATCH and not _is_wide(rng) and isinstance(points1, torch.Tensor) and points1.dim() == 3 and points1.shape[0] == 1 \
             and isinstance(points2, torch.Tensor) and isinstance(line, torch.Tensor):
         hit = _serve_from_batch(points1, points2, line, rng, mode, chunk)
         if hit is not None:
@@ -760,7 +919,7 @@ def _with_ride(opts, order1, order2, chamfer, B, N, M, dev, problems=0):
 
 
 def intersection_loss(points1, points2, line, rng=(1, 1, 5, 5), pool=False, mode="cull", chunk=0,
-                      target_from=None, order1=None, order2=None, opts=None, chamfer=False):
+                      target_from=None, order1=None, order2=None, opts=None, chamfer=False, _force_wide=False):
     """Batched loss: returns (loss[G], info[G,4] = (nbuckets, nselected, nvalues, NaN flag), status[4])
     on the GPU, G = 1 if pool else B.  Each sample is an independent loss (what every reference
     caller obtains by looping B=1 calls); pool=True reproduces the reference's own B>1 behaviour
@@ -768,11 +927,17 @@ def intersection_loss(points1, points2, line, rng=(1, 1, 5, 5), pool=False, mode
     order1 / order2: ops.cloud_order of the two clouds (in any rigid pose of them) -- the per-call cell sort is skipped,
     same results; opts: make_opts(...) for anything else per call.
     chamfer=True: the Chamfer monitor between the clouds' first points (chamfer_from_state) is issued inside this
-    evaluation's scan launch (ChamferRide); chamfer_from_state(last_state()) then returns it without a launch."""
+    evaluation's scan launch (ChamferRide); chamfer_from_state(last_state()) then returns it without a launch.
+    Bucket ranges: within 1..4 hits per line (e_m, e_n <= 5) the narrow path above; up to 8 (e_m, e_n <= 9) the wide
+    pipeline (include/rrl.h rrl_loss_forward_wide) -- gradients to points1 and points2, pool, mode, order1 / order2 as
+    above; it synchronises once (its hit-recovery check) and takes neither target_from, chamfer=True nor the
+    deterministic-gradient mode.  _force_wide (tests): run a range within 1..4 through the wide pipeline."""
+    if (_force_wide or _is_wide(rng)) and chamfer:
+        raise ValueError(_wide_refusal("chamfer=True (the Chamfer walk riding in the scan launch)"))
     if opts is None and (chamfer or order1 is not None or order2 is not None):
         opts = _with_ride(None, order1, order2, chamfer and not pool, points1.shape[0], points1.shape[1], points2.shape[1],
                           _home(points1, points2, line))
-    return _IntersectionLoss.apply(points1, points2, line, tuple(rng), pool, mode, chunk, target_from, opts)
+    return _IntersectionLoss.apply(points1, points2, line, tuple(rng), pool, mode, chunk, target_from, opts, bool(_force_wide))
 
 
 def shard_payload(loss, gR=None, gt=None, state=None):
@@ -821,7 +986,7 @@ class _RegistrationLoss(torch.autograd.Function):
             _IntersectionLoss.last_state = None
             ctx.mark_non_differentiable(out[1], out[2])
             return out
-        s_m, s_n, e_m, e_n = _check_range(rng)
+        s_m, s_n, e_m, e_n = _check_range(rng, "registration_loss")
         st = LossState(B, N, M, L, B, src.device)
         ride = _arm_ride(opts)
         with _guard(dev):
@@ -957,7 +1122,7 @@ class RegistrationStep:
         if self.poses > 1:
             self._extra["problems"] = Bt
         self.dims = (B, N, M, L)
-        self.rng = _check_range(rng)
+        self.rng = _check_range(rng, "RegistrationStep")
         self.tr, self.mode, self.chunk = int(bool(transpose_r)), _MODES[mode], int(chunk)
         self.st = LossState(B, N, M, L, B, dev)
         if self._want_chamfer:
@@ -1132,7 +1297,7 @@ class LossStep:
         self.ride = ChamferRide(B, N, M, dev) if chamfer else None
         self.chamfer_value = None
         self.dims = (B, N, M, L)
-        self.rng = _check_range(rng)
+        self.rng = _check_range(rng, "LossStep")
         self.tr, self.mode, self.chunk = int(bool(transpose_r)), _MODES[mode], int(chunk)
         self.st = LossState(B, N, M, L, B, dev)
         self.ones = torch.ones(B, dtype=torch.float32, device=dev)
@@ -1229,7 +1394,7 @@ def registration_step_raw(src_tri, R, t, tar_tri, line, rng=(1, 1, 5, 5), transp
     if not (tar_tri.shape[0] == line.shape[0] == Bt and t.shape[0] == B) or Bt == 0 or B % Bt or L <= 0:
         raise ValueError("src_tri / tar_tri / line share B_t > 0; R, t hold k * B_t poses; L > 0")
     problems = Bt if B != Bt else 0
-    s_m, s_n, e_m, e_n = _check_range(rng)
+    s_m, s_n, e_m, e_n = _check_range(rng, "registration_step_raw")
     st = LossState(B, N, M, L, B, dev)
     ride = ChamferRide(B, N, M, dev) if chamfer else None
     opts = make_opts(order1=_check_order(order1, Bt, N, dev, "order1"), order2=_check_order(order2, Bt, M, dev, "order2"),
@@ -1259,6 +1424,7 @@ def set_deterministic(on):
     """Bit-reproducible direct backward of registration_loss (fixed-order partial sums, one more tiny
     launch) instead of float atomics; include/rrl.h rrl_set_deterministic.  Process-wide."""
     check(_lib.load().rrl_set_deterministic(int(bool(on))), "rrl_set_deterministic")
+    _deterministic[0] = bool(on)
 
 
 def set_reduce_mode(mode):

@@ -43,8 +43,9 @@ extern "C" {
 #endif
 
 #define RRL_MAX_HITS 4 /* hits kept per line and cloud: callers use buckets 1..4 */
+#define RRL_WIDE_MAX_HITS 8 /* ... by the wide pipeline (rrl_loss_forward_wide): buckets 1..8 */
 #define RRL_E_ARG (-1)
-#define RRL_E_RANGE (-2) /* bucket range outside 1..RRL_MAX_HITS */
+#define RRL_E_RANGE (-2) /* bucket range outside 1..RRL_MAX_HITS (the wide entries: 1..RRL_WIDE_MAX_HITS) */
 #define RRL_E_WS (-3)    /* workspace too small */
 
 /* scan modes */
@@ -145,6 +146,41 @@ enum {
                           rrl_loss_backward): fixed-point accumulators of dL/dpoints1 (and dL/dpoints2), order-independent like MSUM;
                           behind them one non-finite flag per sample and cloud                                              */
     RRL_WS_FIELDS
+};
+
+/* ---- wide bucket ranges -----------------------------------------------------------------------
+ * Every entry above serves bucket ranges within 1..RRL_MAX_HITS (e_m, e_n <= 5: every reference caller's
+ * (1, 1, 5, 5)) and returns RRL_E_RANGE beyond.  The reference accepts any range (code/loss.py:170-232; its header,
+ * code/loss.py:10-17, names the maximum number of intersections per line as the metric's approximation knob).  The
+ * WIDE pipeline serves 1 <= s_m, s_n and e_m, e_n <= RRL_WIDE_MAX_HITS + 1: up to 8 hits per line and cloud.  It runs the
+ * scan of any mode into an ordinary loss workspace (ws, rrl_workspace_bytes) and its own stages into a second, WIDE
+ * workspace (wws, rrl_wide_workspace_bytes): the lines of the range that have more than 4 hits in a cloud are
+ * re-evaluated against all of that cloud's triangles with the scan's strict predicate (hit recovery; the number of hits
+ * found must equal the scan's count, else STATUS[0] of the wide workspace is non-zero and the result must not be used),
+ * then weights, intersection points, the k x j block of D (<= 64 values), exact lower median, Welsch row / column minima
+ * and 2^-40 fixed-point bucket sums over 64 buckets, as the narrow stages do over 16.  Same results as the reference
+ * (the forward is deterministic); for a range within 1..4 it gives the narrow entries' loss bits.  Not served by the
+ * wide entries: carried-over targets, chained steps, riders, multi-pose evaluation, deterministic gradients, the fused
+ * registration steps.  DESIGN.md "Wide bucket ranges". */
+enum {
+    RRL_WW_STATUS = 0, /* int32[4]   [0] lines whose recovered hits disagree with the scan's count (must be 0); [1] hit-recovery
+                          entries (selected line, cloud with > 4 hits); [2], [3] zero */
+    RRL_WW_NSEL,       /* int32[B]   selected lines per sample                                                   */
+    RRL_WW_REC,        /* int32[2 B L] hit-recovery entries: slot | cloud << 31                                    */
+    RRL_WW_SEL,        /* int32[B][L] line index of each selected line, compacted (any order): the SLOT of a line  */
+    RRL_WW_KJ,         /* uint8[B][L] k | j << 4 by slot                                                          */
+    RRL_WW_HS1,        /* int32[B][L][8] ascending hit indices by slot (nonzero() order)                           */
+    RRL_WW_HS2,
+    RRL_WW_W1,         /* float[B][L][8][3] weights d / sum d (loss.py:92)                                         */
+    RRL_WW_W2,
+    RRL_WW_Q1,         /* float[B][L][8][4] intersection points (xyz, 0)                                           */
+    RRL_WW_Q2,
+    RRL_WW_D,          /* float[B][L][8][8] the k x j block of |q1 - q2|^2 by slot (entries outside it undefined)    */
+    RRL_WW_MED,        /* float[G]  lower median                                                                   */
+    RRL_WW_BCNT,       /* int32[G][64] lines per (k, j) bucket, index (k - 1) 8 + (j - 1)                           */
+    RRL_WW_BSUM,       /* int64[G][64][2] bucket sums of row / column minima, 2^-40 fixed point                    */
+    RRL_WW_INFO,       /* int32[G][4] nbuckets, nselected, nvalues, the scan's NaN flag (STATUS[0] of ws)            */
+    RRL_WW_FIELDS
 };
 
 const char *rrl_version(void);
@@ -385,6 +421,22 @@ int rrl_loss_step_ex(const float *tri1, const float *R, const float *t, const fl
                      void *ws, size_t ws_bytes, float *loss, const float *grad_loss, float *grad_tri1,
                      float *grad_tri2, int B, int N, int M, int L, int transpose_r, int s_m, int s_n, int e_m,
                      int e_n, int mode, int chunk, const void *target_ws, const rrl_opts *opts, void *stream);
+
+/* ---- the wide pipeline (RRL_WW_* above: bucket ranges up to RRL_WIDE_MAX_HITS hits per line) ------------------- */
+size_t rrl_wide_workspace_bytes(int B, int N, int M, int L);
+/* offsets[RRL_WW_FIELDS] in bytes from the wide workspace's base */
+int rrl_wide_workspace_layout(int B, int N, int M, int L, size_t *offsets);
+/* Forward of code/loss.py:170-232 for any range 1 <= s_m, s_n, e_m, e_n <= 9: scan into ws (any mode; opts: prepared
+ * orders and the scan knobs -- flags, riders, payload and multi-pose are ignored), then 4 launches into wws.  loss [G],
+ * pool as rrl_loss_forward; INFO of wws as RRL_WS_INFO.  Range inside 1..4 allowed (the same loss bits as the narrow
+ * entries).  The caller must check STATUS[0] of wws (hit recovery) before using the result. */
+int rrl_loss_forward_wide(const float *tri1, const float *tri2, const float *line, void *ws, size_t ws_bytes, void *wws,
+                          size_t wws_bytes, float *loss, int B, int N, int M, int L, int s_m, int s_n, int e_m, int e_n,
+                          int pool, int mode, int chunk, const rrl_opts *opts, void *stream);
+/* Backward of a wide forward: grad_loss [G]; grad_tri1 [B][N][9] (and grad_tri2 [B][M][9], or NULL) are zeroed and
+ * accumulated with float atomics (dL/dD at the first-occurrence argmin entries; median, weights and labels detached). */
+int rrl_loss_backward_wide(const void *wws, size_t wws_bytes, const float *grad_loss, float *grad_tri1, float *grad_tri2,
+                           int B, int N, int M, int L, int pool, void *stream);
 
 /* ---- the four forward stages, individually (tests, profiling) ------------------------- */
 
