@@ -973,7 +973,7 @@ static CullGeom cull_geometry(int B, int N, int M, int L, int clouds, const RrlC
 }
 
 // Can the chained step's ONE launch (source records + target scan + source scan: cull_scan_build_kernel) serve this call?
-// Both clouds scanned here with full 512-lane workgroups, no rider, no counters; the caller (loss_forward_impl) checks the
+// Both clouds scanned here with full 512-lane workgroups, no rider, no counters; the caller (rrl_plan) checks the
 // rest (prepared orders, kept target, the per-line stage + tail kernel behind it).
 int rrl_cull_scan_can_fuse(int B, int N, int M, int L, const RrlCall &o) {
     if (B <= 0 || N <= 0 || M <= 0 || L <= 0 || (N > M ? N : M) > SORT_CAP) return 0;
@@ -1002,8 +1002,8 @@ int rrl_cull_scan_can_fuse(int B, int N, int M, int L, const RrlCall &o) {
 int rrl_launch_cull_scan(const float *line, void *ws, const WsLayout &w, int B, int N, int M, int L,
                          int clouds, int lmax_ready, const RrlCall &o, hipStream_t s) {
     const CullGeom g = cull_geometry(B, N, M, L, clouds, o);
-    if (o.fused_build && (clouds != 2 || g.waves != scan8::kWPB)) return RRL_E_ARG;  // (rrl_cull_scan_can_fuse said otherwise)
-    if (!lmax_ready && !o.fused_build)  // the triangles were prepared without the lines: their partial maxima first (a tiny launch)
+    if (o.plan.fused_build && (clouds != 2 || g.waves != scan8::kWPB)) return RRL_E_ARG;  // (rrl_cull_scan_can_fuse said otherwise)
+    if (!lmax_ready && !o.plan.fused_build)  // the triangles were prepared without the lines: their partial maxima first (a tiny launch)
         hipLaunchKernelGGL(line_max_kernel, dim3(LMAX_CHUNKS, (unsigned)B), dim3(REC_BLK), 0, s, line, L,
                            (float2 *)w.f32(ws, RRL_WS_LMAX), o.problems);
     // (A PERSISTENT variant -- as many workgroups as fit on the chip, each keeping one line tile staged and pulling

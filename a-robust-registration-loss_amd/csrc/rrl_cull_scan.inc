@@ -999,7 +999,7 @@ static int launch_variant(const float *line, void *ws, const WsLayout &w, int B,
                        o.counters, o.counter_rows, o.problems)
     const float *apart = o.prepared() ? w.f32(ws, RRL_WS_APART) : nullptr;  // prepared build: PMAX comes from the partial rows
     const int nblk_apart = ((N > M ? N : M) + REC_BLK - 1) / REC_BLK;
-    if (o.fused_build) {  // the chained step: source records + target scan + source scan as ONE launch (cull_scan_build_kernel)
+    if (o.plan.fused_build) {  // the chained step: source records + target scan + source scan as ONE launch (cull_scan_build_kernel)
         if (waves != WPB || clouds != 2 || !o.prepared()) return RRL_E_ARG;
         CullKArgs a;
         a.ptri1 = w.f32(ws, RRL_WS_PTRI1); a.ptri2 = w.f32(ws, RRL_WS_PTRI2);

@@ -20,7 +20,7 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
     const char *env = getenv("RRL_DEMO_RIDE");  // (read per call: tests switch it between epochs) 0: no launch carries another's work
     const bool rides = !(env && env[0] == '0');
     int32_t *pipe = a->struct_bytes >= (int32_t)sizeof(rrl_demo_epoch_args) && rides ? a->pipeline : nullptr;
-    if (pipe && ((long)((L + 1023) / 1024) * a->rounds >= 512 || L <= 1024)) pipe = nullptr;  // (the rider's limits: line_pair_dist_impl)
+    if (pipe && ((long)((L + 1023) / 1024) * a->rounds >= 512 || L <= 1024)) pipe = nullptr;  // (the rider's limits: rrl_plan)
     int rc;
     if (pipe && *pipe == 3) {  // ... and its backward launch the write pass too: this epoch's lines are in place
         rc = 0;

@@ -130,7 +130,6 @@ int rrl_launch_tri_build(const float *tri1, const float *tri2, void *ws, const W
                          hipStream_t s);
 int rrl_launch_cull_scan(const float *line, void *ws, const WsLayout &w, int B, int N, int M, int L,
                          int clouds, int lmax_ready, const RrlCall &o, hipStream_t s);
-int rrl_sort_capacity(void);
 
 // clouds = 2: both clouds; clouds = 1: the source only (the target's scan results are carried
 // over from an earlier call with the same target and lines, see rrl_loss_forward_cached).  The
@@ -148,7 +147,7 @@ int rrl_tri_prepare_clouds(const float *tri1, const float *tri2, void *ws, size_
     WsLayout w(B, N, M, L);
     if (ws_bytes < w.total) return RRL_E_WS;
     hipStream_t s = (hipStream_t)stream;
-    const bool sorted = (N > M ? N : M) <= rrl_sort_capacity();
+    const bool sorted = rrl_sorted_layout(N, M);
     const int nmax = clouds == 2 && M > N ? M : N;
     uint4 *zb = (uint4 *)((char *)ws + w.off[RRL_WS_STATUS]);
     if (!sorted || B == 0 || nmax == 0) {
@@ -182,8 +181,7 @@ int rrl_tri_prepare_clouds(const float *tri1, const float *tri2, void *ws, size_
 extern "C" int rrl_tri_prepare_ex(const float *tri1, const float *tri2, void *ws, size_t ws_bytes,
                                   int B, int N, int M, int L, const rrl_opts *opts, void *stream) {
     RrlCall o = rrl_resolve_opts(opts);
-    if (o.prepared() && (!o.order2 || (N > M ? N : M) > rrl_sort_capacity())) o.order1 = o.order2 = nullptr;  // both orders, sorted layout
-    o.flags &= ~RRL_F_TARGET_KEPT;  // a stage call builds both clouds
+    rrl_plan(o, B, N, M, L, 0, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE);  // (prepared orders: both, sorted layout)
     int rc = rrl_tri_prepare_clouds(tri1, tri2, ws, ws_bytes, B, N, M, L, 2, nullptr, nullptr, o, stream);
     if (rc || !o.prepared() || B <= 0 || (N <= 0 && M <= 0)) return rc;
     // prepared build: PMAX is normally reduced by the culled scan's prologue; a stage call leaves it complete itself
@@ -437,8 +435,7 @@ int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B
     WsLayout w(B, N, M, L);
     if (ws_bytes < w.total) return RRL_E_WS;
     if (B == 0 || L == 0 || (N == 0 && (M == 0 || clouds == 1))) return 0;
-    const int nmax0 = N > M ? N : M;
-    if (mode == RRL_SCAN_CULL && nmax0 > rrl_sort_capacity()) mode = RRL_SCAN_AUTO;
+    if (mode == RRL_SCAN_CULL && !rrl_sorted_layout(N, M)) mode = RRL_SCAN_AUTO;  // (the wide pipeline's calls: no plan)
     hipStream_t s = (hipStream_t)stream;
     const bool timed = g_timing_on && (g_timing_seen++ % g_timing_on) == 0 && g_timing_n < TIMING_RING;
     if (mode == RRL_SCAN_CULL) {  // one launch: sphere-culled scan with an inline strict fallback
@@ -488,8 +485,8 @@ int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B
 extern "C" int rrl_line_tri_scan_ex(const float *line, void *ws, size_t ws_bytes, int B, int N, int M,
                                     int L, int mode, int chunk, const rrl_opts *opts, void *stream) {
     RrlCall o = rrl_resolve_opts(opts);
-    if (o.prepared() && (!o.order2 || (N > M ? N : M) > rrl_sort_capacity())) o.order1 = o.order2 = nullptr;
-    return rrl_line_tri_scan_clouds(line, ws, ws_bytes, B, N, M, L, mode, chunk, 2, 0, o, stream);
+    rrl_plan(o, B, N, M, L, 0, mode, nullptr, nullptr, RRL_WANT_STAGE);
+    return rrl_line_tri_scan_clouds(line, ws, ws_bytes, B, N, M, L, o.plan.scan_mode, chunk, o.plan.clouds, o.plan.lmax_ready, o, stream);
 }
 extern "C" int rrl_line_tri_scan(const float *line, void *ws, size_t ws_bytes, int B, int N, int M,
                                  int L, int mode, int chunk, void *stream) {

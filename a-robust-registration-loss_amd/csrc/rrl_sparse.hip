@@ -77,13 +77,8 @@ static PairArgs pair_args(const float *tri1, const float *tri2, const float *lin
     return a;
 }
 
-static int reduce_kind(int mode, int B, int nblk, int pool, bool with_bwd);
-
-// with_bwd: the reduce that follows will carry the direct backward (rrl_registration_step) -- it decides, with the shape,
-// whether the tail kernel runs and wants the dense value lists
 static int line_pair_dist_impl(const float *tri1, const float *tri2, const float *line, void *ws, size_t ws_bytes, int B,
-                               int N, int M, int L, int s_m, int s_n, int e_m, int e_n, int pool,
-                               const RrlCall &o, void *stream, bool with_bwd = false) {
+                               int N, int M, int L, int s_m, int s_n, int e_m, int e_n, const RrlCall &o, void *stream) {
     if (!tri1 || !tri2 || !line || !ws || B < 0 || N < 0 || M < 0 || L < 0 || L >= (1 << 24)) return RRL_E_ARG;  // 24-bit line ids in LDS
     if (s_m < 1 || s_n < 1 || e_m > RRL_MAX_HITS + 1 || e_n > RRL_MAX_HITS + 1) return RRL_E_RANGE;
     WsLayout w(B, N, M, L);
@@ -91,20 +86,19 @@ static int line_pair_dist_impl(const float *tri1, const float *tri2, const float
     if (B == 0 || L == 0) return 0;
     PairArgs pa = pair_args(tri1, tri2, line, ws, w, B, N, M, L, s_m, s_n, e_m, e_n, true, o.tar_ws);
     pa.Bt = o.problems;
-    if (o.leave_clean && !o.problems && !o.tar_ws) { pa.zc1 = w.i32(ws, RRL_WS_COUNT1); pa.zc2 = w.i32(ws, RRL_WS_COUNT2); }
-    if (reduce_kind(o.reduce_mode, B, (L + 1023) / 1024, pool, with_bwd) != 2) pa.vlist = nullptr;  // only the tail kernel reads VLIST
-    if (RrlCountRider *cr = o.count_rider) {  // the next epoch's count pass rides along (pair_count_kernel)
+    if (o.plan.leave_clean) { pa.zc1 = w.i32(ws, RRL_WS_COUNT1); pa.zc2 = w.i32(ws, RRL_WS_COUNT2); }
+    if (o.plan.reduce != RRL_RED_TAIL) pa.vlist = nullptr;  // only the tail kernel reads VLIST
+    if (o.plan.count_rides) {  // the next epoch's count pass rides along (pair_count_kernel)
+        RrlCountRider *cr = o.count_rider;
         const int ctiles = (cr->n + 1023) / 1024;
-        if (B == 1 && cr->rounds > 0 && cr->n > 0 && (long)ctiles * cr->rounds < 512 && cr->rows && cr->n_rows > 0) {
-            const CountKArgs c = {cr->rng_state, cr->r, cr->centers, cr->aabb2, cr->rows, cr->accept, cr->n_rows, cr->n,
-                                  cr->rounds, rrl_sample_prefilter(), ctiles, cr->rounds};
-            const int pgx = (L + 1023) / 1024;
-            hipLaunchKernelGGL(pair_count_kernel, dim3((unsigned)(ctiles * cr->rounds + pgx * B)), dim3(1024), 0,
-                               (hipStream_t)stream, pa, c, pgx);
-            RRL_LAUNCH_CHECK();
-            cr->done = 1;
-            return 0;
-        }
+        const CountKArgs c = {cr->rng_state, cr->r, cr->centers, cr->aabb2, cr->rows, cr->accept, cr->n_rows, cr->n,
+                              cr->rounds, rrl_sample_prefilter(), ctiles, cr->rounds};
+        const int pgx = (L + 1023) / 1024;
+        hipLaunchKernelGGL(pair_count_kernel, dim3((unsigned)(ctiles * cr->rounds + pgx * B)), dim3(1024), 0,
+                           (hipStream_t)stream, pa, c, pgx);
+        RRL_LAUNCH_CHECK();
+        cr->done = 1;
+        return 0;
     }
     hipLaunchKernelGGL(line_pair_dist_kernel, dim3((unsigned)((L + 1023) / 1024), (unsigned)B), dim3(1024), 0,
                        (hipStream_t)stream, pa);
@@ -115,7 +109,9 @@ static int line_pair_dist_impl(const float *tri1, const float *tri2, const float
 extern "C" int rrl_line_pair_dist_ex(const float *tri1, const float *tri2, const float *line,
                                      void *ws, size_t ws_bytes, int B, int N, int M, int L, int s_m,
                                      int s_n, int e_m, int e_n, int pool, const rrl_opts *opts, void *stream) {
-    return line_pair_dist_impl(tri1, tri2, line, ws, ws_bytes, B, N, M, L, s_m, s_n, e_m, e_n, pool, rrl_resolve_opts(opts), stream);
+    RrlCall o = rrl_resolve_opts(opts);
+    rrl_plan(o, B, N, M, L, pool, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE);
+    return line_pair_dist_impl(tri1, tri2, line, ws, ws_bytes, B, N, M, L, s_m, s_n, e_m, e_n, o, stream);
 }
 extern "C" int rrl_line_pair_dist(const float *tri1, const float *tri2, const float *line,
                                   void *ws, size_t ws_bytes, int B, int N, int M, int L, int s_m,
@@ -144,15 +140,9 @@ static int default_reduce_mode() {
 }
 static bool default_deterministic();
 // include/rrl.h rrl_opts -> the options of one call (csrc/rrl_ws.h RrlCall).  Fields the caller's struct does not
-// reach (struct_bytes), -1 and NULL mean the process-wide default.
+// reach (struct_bytes), -1 and NULL mean the process-wide default.  The internal fields start zero: an empty plan.
 RrlCall rrl_resolve_opts(const rrl_opts *p) {
-    RrlCall o;
-    o.clear_ptr = nullptr;
-    o.clear_bytes = 0;
-    o.rider = nullptr;  // (set below from rrl_opts.chamfer)
-    o.count_rider = nullptr;
-    o.write_rider = nullptr;
-    o.tar_ws = nullptr;
+    RrlCall o{};
     rrl_opts v;
     memset(&v, 0, sizeof v);
     v.reduce_mode = v.deterministic = v.sort_parts = v.scan_variant = -1;
@@ -169,18 +159,14 @@ RrlCall rrl_resolve_opts(const rrl_opts *p) {
     else rrl_default_scan_counters(&o.counters, &o.counter_rows);
     o.rider = v.chamfer;  // (done is the caller's to clear; the scan's launcher sets it when the walk rides along)
     o.payload = v.payload;
-    o.payload_in_reduce = 0;
     o.problems = v.problems > 0 ? v.problems : 0;
     o.chain_left = v.chain_left;
-    o.leave_clean = o.fused_build = 0;
-    o.xf = nullptr;
-    o.tri1_in = nullptr;
     return o;
 }
-// Which reduce kernel: 0 one workgroup per sample, 1 tiled with the candidate exchange (loss_reduce_tiled_kernel), 2 the
-// tail kernel (no exchange: every workgroup streams its sample's dense value lists; one 512-lane workgroup or two
-// per compute unit, so it serves the small, latency-bound grids: B x tiles <= 256, <= 32 tiles per sample).
-// mode 0 (auto): the tail kernel where the direct backward rides along (with_bwd: rrl_registration_step -- measured
+// Which reduce kernel (rrl_ws.h RRL_RED_*): one workgroup per sample, tiled with the candidate exchange
+// (loss_reduce_tiled_kernel), or the tail kernel (no exchange: every workgroup streams its sample's dense value lists; one
+// 512-lane workgroup or two per compute unit, so it serves the small, latency-bound grids: B x tiles <= 256, <= 32 tiles
+// per sample).  mode 0 (auto): the tail kernel where the backward rides along (with_bwd: rrl_registration_step -- measured
 // -1.9 .. -3.4 us per step at C2 / L = 4096 / C4, round 5b: -6 us at the demo's 20 tiles; as a reduce alone it is within
 // +-1 % of the exchange kernel), else the exchange kernel for >= 2 tiles while the grid
 // is co-resident, else the single workgroup; 1: single; 2 ("tiled"): the tail kernel wherever it is legal (also forward
@@ -238,14 +224,75 @@ static long tail_max_wg() {
     return v;
 }
 static int reduce_kind(int mode, int B, int nblk, int pool, bool with_bwd) {
-    if (pool || mode == 1) return 0;
+    if (pool || mode == 1) return RRL_RED_SINGLE;
     const bool xchg_ok = (long)B * nblk <= xchg_capacity();
-    if (mode == 3) return xchg_ok && nblk >= 1 ? 1 : 0;
+    if (mode == 3) return xchg_ok && nblk >= 1 ? RRL_RED_XCHG : RRL_RED_SINGLE;
     const bool tail_ok = nblk <= TAIL_MAX_TILES && (long)B * nblk <= tail_max_wg();
-    if (mode == 2 && tail_ok && nblk >= 1) return 2;
+    if (mode == 2 && tail_ok && nblk >= 1) return RRL_RED_TAIL;
     // (round 5: up to TAIL_MAX_TILES line tiles, not 16 -- the demo's 20: tail 11.1 us against tiled reduce 10.6 + backward 5.8 / 7.2)
-    if (mode == 0 && tail_ok && with_bwd && nblk >= 2) return 2;
-    return xchg_ok && nblk >= 2 ? 1 : 0;
+    if (mode == 0 && tail_ok && with_bwd && nblk >= 2) return RRL_RED_TAIL;
+    return xchg_ok && nblk >= 2 ? RRL_RED_XCHG : RRL_RED_SINGLE;
+}
+int rrl_cull_scan_can_fuse(int B, int N, int M, int L, const RrlCall &o);  // rrl_cull.hip
+
+// The plan of one call (rrl_ws.h RrlPlan).  target_ws != NULL: the target's scan is carried over from it (one cloud scanned);
+// xf != NULL: the call moves the source; want: RRL_WANT_*.  A stage entry (RRL_WANT_STAGE) takes the options as given --
+// no whole forward, so no single-tile kernel, chain, rider or multi-pose check -- and builds both clouds.
+int rrl_plan(RrlCall &o, int B, int N, int M, int L, int pool, int mode, const void *target_ws, const RrlXform *xf, int want) {
+    RrlPlan &p = o.plan;
+    p = RrlPlan{};
+    const bool stage = want == RRL_WANT_STAGE, sorted = rrl_sorted_layout(N, M);
+    const int nblk = (L + 1023) / 1024;
+    p.scan_mode = mode == RRL_SCAN_CULL && !sorted ? RRL_SCAN_AUTO : mode;
+    p.clouds = target_ws ? 1 : 2;
+    const bool cull = p.scan_mode == RRL_SCAN_CULL;
+    o.tar_ws = target_ws;
+    o.xf = xf;
+    if (stage) o.flags = 0;
+    else if (o.problems >= B) o.problems = 0;
+    // multi-pose evaluation (rrl_opts.problems = Bt): the B instances are B / Bt poses of Bt problems; the inputs have Bt
+    // entries.  Served by the sorted layout of scan mode cull through the fused entries that move the source (xf)
+    if (!stage && o.problems > 0 && (B % o.problems != 0 || !xf || pool || target_ws || !cull || N <= 0 || M <= 0)) return RRL_E_ARG;
+    // prepared clouds (include/rrl.h rrl_opts): honoured by the sorted layout of scan mode cull, with the orders of every
+    // cloud this call builds; anything else takes the plain path (same results)
+    if (o.prepared() && (!cull || (p.clouds == 2 && !o.order2 && !(o.flags & RRL_F_TARGET_KEPT)))) o.order1 = o.order2 = nullptr;
+    // a kept target: cloud 2's records / tree / partials stay as the previous call on this workspace left them
+    p.build_clouds = o.target_kept() ? 1 : p.clouds;
+    // (the records kernel of a forward reduces the lines' maxima whenever it runs: the sorted path)
+    p.lmax_ready = !stage && sorted && B > 0 && (p.clouds == 2 && M > N ? M : N) > 0 && L > 0;
+    // The reduce, and whether the wanted backward rides in its launch: not deterministic (the fixed-point scatter), not with
+    // grad_tri2; the scatter backward rides in the single-tile kernel and, beyond one tile of lines, in the tail kernel
+    const bool tile = !stage && L >= 1 && L <= 1024 && !pool && B > 0 && o.reduce_mode < 2;
+    const bool ride = (want == RRL_WANT_DIRECT || (want == RRL_WANT_SCATTER && (tile || nblk >= 2))) && B > 0 && L > 0 &&
+                      !o.deterministic;
+    p.reduce = tile ? RRL_RED_TILE : reduce_kind(o.reduce_mode, B, nblk, pool, ride);
+    p.tail_rpl2 = p.reduce == RRL_RED_TAIL && TAIL_LANES / nblk >= 48;  // (see tail_body: groups per lane and round)
+    p.bwd_rides = ride && (p.reduce == RRL_RED_TILE || p.reduce == RRL_RED_TAIL);
+    // no riding backward, but the exchange reduce serves a step: its last arrivers add the payload (no payload launch)
+    p.payload_in_reduce = (want == RRL_WANT_SCATTER || want == RRL_WANT_SCATTER2) && o.payload && !p.bwd_rides && B > 0 &&
+                          L > 1024 && p.reduce == RRL_RED_XCHG;
+    // Chained steps (include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED).  The chain lives where the per-line stage + the tail kernel or
+    // the exchange reduce serve the call: they are the ones that leave COUNT1 / COUNT2 and the CHAIN words cleared ...
+    const bool chain_path = B > 0 && L > 1024 && !pool && p.clouds == 2 && !o.problems && cull && N > 0 && M > 0 &&
+                            (p.reduce == RRL_RED_XCHG || p.reduce == RRL_RED_TAIL);
+    p.leave_clean = (o.flags & RRL_F_CHAIN) && chain_path;
+    // ... and a step that FINDS them cleared runs source records + target scan + source scan as ONE launch.  Only a step that
+    // also leaves them cleared: the reduce of a fused build writes the CHAIN words it clears (else the plain build serves)
+    p.fused_build = p.leave_clean && (o.flags & RRL_F_CHAINED) && o.target_kept() && !o.count_rider && !o.write_rider &&
+                    rrl_cull_scan_can_fuse(B, N, M, L, o);
+    // the next epoch's sampler passes (rrl_demo_epoch): the count pass in the per-line launch, the write pass -- with the
+    // ballots of THAT count pass -- in the launch that carries the direct backward (nothing after it reads the lines)
+    if (const RrlCountRider *cr = o.count_rider)
+        p.count_rides = p.reduce != RRL_RED_TILE && B == 1 && L > 0 && cr->rounds > 0 && cr->n > 0 &&
+                        (long)((cr->n + 1023) / 1024) * cr->rounds < 512 && cr->rows && cr->n_rows > 0;
+    if (const RrlWriteRider *wr = o.write_rider) {
+        const long wtiles = (wr->n + 1023) / 1024;
+        const bool in_tail = p.bwd_rides && p.reduce == RRL_RED_TAIL, in_bwd = want == RRL_WANT_DIRECT && !p.bwd_rides;
+        p.write_rides = (in_tail || in_bwd) && (!o.count_rider || p.count_rides) && B == 1 && L > 0 && wr->n > 0 &&
+                        wr->rounds > 0 && wtiles * wr->rounds < 512 &&
+                        sizeof(int32_t) * (size_t)wr->rounds * wtiles <= (in_tail ? 32 : 48) * 1024;
+    }
+    return 0;
 }
 // the direct backward that may ride in the tail kernel's launch (rrl_registration_step)
 struct TailBwd {
@@ -266,18 +313,16 @@ static ReduceArgs reduce_args(void *ws, const WsLayout &w, float *loss, int B, i
     return r;
 }
 
-// tb != NULL: the caller wants the direct backward too; *bwd_done tells whether this launch carried it
+// o.plan: rrl_plan; tb: the backward that rides in the launch (o.plan.bwd_rides), else NULL
 static int loss_reduce_impl(void *ws, size_t ws_bytes, float *loss, int B, int N, int M, int L, int s_m, int s_n, int e_m,
-                            int e_n, int pool, const TailBwd *tb, bool *bwd_done, const RrlCall &o, void *stream) {
-    if (bwd_done) *bwd_done = false;
+                            int e_n, int pool, const TailBwd *tb, const RrlCall &o, void *stream) {
     if (!ws || !loss || B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
     if (s_m < 1 || s_n < 1 || e_m > RRL_MAX_HITS + 1 || e_n > RRL_MAX_HITS + 1) return RRL_E_RANGE;
     WsLayout w(B, N, M, L);
     if (ws_bytes < w.total) return RRL_E_WS;
     if (B == 0) return 0;
     const int nblk = (L + 1023) / 1024;
-    const int kind = reduce_kind(o.reduce_mode, B, nblk, pool, tb != nullptr);
-    if (kind == 2) {
+    if (o.plan.reduce == RRL_RED_TAIL) {
         TailArgs t;
         t.lidc = w.u32(ws, RRL_WS_LIDC); t.dc = w.f32(ws, RRL_WS_VALS); t.blkcnt = w.i32(ws, RRL_WS_BLKCNT);
         t.vlist = w.f32(ws, RRL_WS_VLIST); t.vlcnt = w.i32(ws, RRL_WS_VLCNT);
@@ -294,15 +339,11 @@ static int loss_reduce_impl(void *ws, size_t ws_bytes, float *loss, int B, int N
         t.grad_tri1 = tb ? tb->grad_tri1 : nullptr;
         t.Bt = o.problems;
         t.xcd_align = B % 8 == 0 && xcd_align_on();
-        t.chain = o.leave_clean ? w.u32(ws, RRL_WS_CHAIN) : nullptr;
-        t.chain_flags = o.fused_build ? 1 : 0;
-        // the next epoch's sampler write pass rides along (tail_write_kernel; rrl_demo_epoch) -- when this launch carries the
-        // backward (nothing after it reads the line buffer the pass overwrites) and the ballots of THAT count pass are there
-        RrlWriteRider *wr = tb ? o.write_rider : nullptr;
-        const int wtiles = wr ? (wr->n + 1023) / 1024 : 0;
-        const bool ride = wr && (!o.count_rider || o.count_rider->done) && B == 1 && wr->n > 0 && wr->rounds > 0 &&
-                          (long)wtiles * wr->rounds < 512 && sizeof(int32_t) * (size_t)wr->rounds * wtiles <= 32 * 1024;
-        if (ride) {
+        t.chain = o.plan.leave_clean ? w.u32(ws, RRL_WS_CHAIN) : nullptr;
+        t.chain_flags = o.plan.fused_build;
+        if (tb && o.plan.write_rides) {  // the next epoch's sampler write pass rides along (tail_write_kernel; rrl_demo_epoch)
+            RrlWriteRider *wr = o.write_rider;
+            const int wtiles = (wr->n + 1023) / 1024;
             const WriteKArgs wk = {wr->rng_state, wr->r, wr->centers, wr->accept, wr->lines, wr->filled, wr->n, wr->rounds, wtiles, wr->rounds};
             const dim3 g((unsigned)(wk.gx * wk.gy + nblk * B * TAIL_SUBS));
             const size_t lds = sizeof(int32_t) * (size_t)wk.rounds * wk.gx;
@@ -311,17 +352,15 @@ static int loss_reduce_impl(void *ws, size_t ws_bytes, float *loss, int B, int N
             wr->done = 1;
         } else {
             const dim3 g((unsigned)nblk, (unsigned)B, TAIL_SUBS);
-            const bool two = TAIL_LANES / nblk >= 48;  // (see tail_body: groups per lane and round)
 #define RRL_TAIL(S_, R_) hipLaunchKernelGGL((loss_tail_kernel<S_, R_>), g, dim3(TAIL_LANES), 0, (hipStream_t)stream, t)
-            if (t.grad_tri1) { if (two) RRL_TAIL(true, 2); else RRL_TAIL(true, TAIL_RPL); }
-            else { if (two) RRL_TAIL(false, 2); else RRL_TAIL(false, TAIL_RPL); }
+            if (t.grad_tri1) { if (o.plan.tail_rpl2) RRL_TAIL(true, 2); else RRL_TAIL(true, TAIL_RPL); }
+            else { if (o.plan.tail_rpl2) RRL_TAIL(false, 2); else RRL_TAIL(false, TAIL_RPL); }
 #undef RRL_TAIL
         }
         RRL_LAUNCH_CHECK();
-        if (bwd_done) *bwd_done = tb != nullptr;
         return 0;
     }
-    if (kind == 1) {
+    if (o.plan.reduce == RRL_RED_XCHG) {
         TiledArgs t;
         t.kjc = w.u8(ws, RRL_WS_KJC); t.dc = w.f32(ws, RRL_WS_VALS); t.blkcnt = w.i32(ws, RRL_WS_BLKCNT);
         t.mhist = w.u32(ws, RRL_WS_MHIST); t.mctl = w.u32(ws, RRL_WS_MCTL); t.mcand = w.u32(ws, RRL_WS_MCAND);
@@ -331,13 +370,14 @@ static int loss_reduce_impl(void *ws, size_t ws_bytes, float *loss, int B, int N
         t.B = B; t.nblk = nblk; t.s_m = s_m; t.s_n = s_n; t.e_m = e_m; t.e_n = e_n;
         t.spin_limit = spin_limit();
         t.xcd_align = B % 8 == 0 && xcd_align_on();
-        t.payload = o.payload_in_reduce ? o.payload : nullptr;
-        t.chain = o.leave_clean ? w.u32(ws, RRL_WS_CHAIN) : nullptr;
-        t.chain_flags = o.fused_build ? 1 : 0;
+        t.payload = o.plan.payload_in_reduce ? o.payload : nullptr;
+        t.chain = o.plan.leave_clean ? w.u32(ws, RRL_WS_CHAIN) : nullptr;
+        t.chain_flags = o.plan.fused_build;
         hipLaunchKernelGGL(loss_reduce_tiled_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, (hipStream_t)stream, t);
         RRL_LAUNCH_CHECK();
         return 0;
     }
+    // (RRL_RED_TILE here: the reduce stage of a one-tile call issued stage by stage)
     hipLaunchKernelGGL(loss_reduce_kernel, dim3((unsigned)(pool ? 1 : B)), dim3(1024), sizeof(int) * (size_t)(nblk + 1),
                        (hipStream_t)stream, reduce_args(ws, w, loss, B, L, s_m, s_n, e_m, e_n, pool));
     RRL_LAUNCH_CHECK();
@@ -346,7 +386,9 @@ static int loss_reduce_impl(void *ws, size_t ws_bytes, float *loss, int B, int N
 
 extern "C" int rrl_loss_reduce_ex(void *ws, size_t ws_bytes, float *loss, int B, int N, int M, int L,
                                   int s_m, int s_n, int e_m, int e_n, int pool, const rrl_opts *opts, void *stream) {
-    return loss_reduce_impl(ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, nullptr, nullptr, rrl_resolve_opts(opts), stream);
+    RrlCall o = rrl_resolve_opts(opts);
+    rrl_plan(o, B, N, M, L, pool, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE);
+    return loss_reduce_impl(ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, nullptr, o, stream);
 }
 extern "C" int rrl_loss_reduce(void *ws, size_t ws_bytes, float *loss, int B, int N, int M, int L,
                                int s_m, int s_n, int e_m, int e_n, int pool, void *stream) {
@@ -479,78 +521,43 @@ int rrl_tri_prepare_clouds(const float *tri1, const float *tri2, void *ws, size_
                            void *stream);
 int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B, int N, int M, int L,
                              int mode, int chunk, int clouds, int lmax_ready, const RrlCall &o, void *stream);
-int rrl_sort_capacity(void);
-int rrl_cull_scan_can_fuse(int B, int N, int M, int L, const RrlCall &o);  // rrl_cull.hip
 
-// target_ws != NULL: a workspace of the same (B, N, M, L) that already went through a forward with
-// the SAME tri2 and line (RPM / FMR evaluate several source poses against one target and one
-// line set, rpm/Train_RPM.py:204-231): the target's hit counts and hit lists are copied from it
-// and only the source cloud is prepared, sorted and scanned.
-// xf != NULL: tri1 is the workspace field TRI1, filled by the prepare step from xf->src.
+// The forward of one planned call (o.plan: rrl_plan).  o.tar_ws != NULL: a workspace of the same (B, N, M, L) that already
+// went through a forward with the SAME tri2 and line (RPM / FMR evaluate several source poses against one target and one
+// line set, rpm/Train_RPM.py:204-231): only the source cloud is prepared, sorted and scanned.  o.xf != NULL: tri1 is the
+// workspace field TRI1, filled from o.xf->src.  tb: the backward that rides in the reduce's launch (o.plan.bwd_rides).
 static int loss_forward_impl(const float *tri1, const float *tri2, const float *line, void *ws,
                              size_t ws_bytes, float *loss, int B, int N, int M, int L, int s_m,
-                             int s_n, int e_m, int e_n, int pool, int mode, int chunk,
-                             const void *target_ws, const RrlXform *xf, RrlCall o, void *stream,
-                             const TailBwd *tb = nullptr, bool *bwd_done = nullptr) {
-    if (bwd_done) *bwd_done = false;
+                             int s_n, int e_m, int e_n, int pool, int chunk, RrlCall o, void *stream,
+                             const TailBwd *tb = nullptr) {
     if (!tri1 || !tri2 || !line || !ws || !loss) return RRL_E_ARG;
     if (s_m < 1 || s_n < 1 || e_m > RRL_MAX_HITS + 1 || e_n > RRL_MAX_HITS + 1) return RRL_E_RANGE;
-    if (target_ws == ws) return RRL_E_ARG;
-    const int clouds = target_ws ? 1 : 2;
-    o.tar_ws = target_ws;
-    // multi-pose evaluation (rrl_opts.problems = Bt): the B instances are B / Bt poses of Bt problems; the inputs have Bt
-    // entries.  Served by the sorted layout of scan mode cull through the fused entries that move the source (xf); anything
-    // else is an argument error (the caller evaluates pose after pose then)
-    if (o.problems >= B) o.problems = 0;
-    if (o.problems > 0 && (B % o.problems != 0 || !xf || pool || target_ws || mode != RRL_SCAN_CULL ||
-                           (N > M ? N : M) > rrl_sort_capacity() || N <= 0 || M <= 0))
-        return RRL_E_ARG;
-    // prepared clouds (include/rrl.h rrl_opts): honoured by the sorted layout of scan mode cull, with the orders of every
-    // cloud this call builds; anything else takes the plain path (same results)
-    if (o.prepared() && (mode != RRL_SCAN_CULL || (N > M ? N : M) > rrl_sort_capacity() ||
-                         (clouds == 2 && !o.order2 && !(o.flags & RRL_F_TARGET_KEPT))))
-        o.order1 = o.order2 = nullptr;
-    // a kept target: cloud 2's records / tree / partials stay as the previous call on this workspace left them
-    const int build_clouds = o.target_kept() ? 1 : clouds;
-    // Chained steps (include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED).  The chain lives where the per-line stage + the tail kernel or
-    // the exchange reduce serve the call: they are the ones that leave COUNT1 / COUNT2 and the CHAIN words cleared.
-    const bool chain_path = B > 0 && L > 1024 && !pool && clouds == 2 && !o.problems && mode == RRL_SCAN_CULL &&
-                            (N > M ? N : M) <= rrl_sort_capacity() && N > 0 && M > 0 &&
-                            reduce_kind(o.reduce_mode, B, (L + 1023) / 1024, pool, tb != nullptr) >= 1;
-    o.leave_clean = (o.flags & RRL_F_CHAIN) && chain_path ? 1 : 0;
-    // ... and a step that FINDS them cleared runs source records + target scan + source scan as ONE launch
-    o.fused_build = (o.flags & RRL_F_CHAINED) && chain_path && o.target_kept() && !o.count_rider && !o.write_rider &&
-                    rrl_cull_scan_can_fuse(B, N, M, L, o) ? 1 : 0;
-    if (o.chain_left) *o.chain_left = o.leave_clean | (o.fused_build << 1);  // bit 0: leaves the workspace chain-clean; bit 1: THIS call's build is fused
-    o.xf = xf;
+    if (o.tar_ws == ws) return RRL_E_ARG;
+    const RrlPlan &p = o.plan;
+    if (o.chain_left) *o.chain_left = p.leave_clean | (p.fused_build << 1);  // bit 0: leaves the workspace chain-clean; bit 1: THIS call's build is fused
     o.tri1_in = tri1;
     int rc;
     RrlRange step("rrl forward");
-    if (!o.fused_build) {
+    if (!p.fused_build) {
         RrlRange r("K1' records + sort + tree");
-        if ((rc = rrl_tri_prepare_clouds(tri1, tri2, ws, ws_bytes, B, N, M, L, build_clouds, xf, line, o, stream))) return rc;
+        if ((rc = rrl_tri_prepare_clouds(tri1, tri2, ws, ws_bytes, B, N, M, L, p.build_clouds, o.xf, line, o, stream))) return rc;
     }
-    // (a carried-over target: the per-line stage reads cloud 2's hit counts and lists in `target_ws` itself -- pair_args)
     {
         RrlRange r("K1 line<->triangle scan");
-        // (the records kernel reduced the lines' maxima whenever it ran: the sorted path)
-        const int lmax_ready = (N > M ? N : M) <= rrl_sort_capacity() && B > 0 && (clouds == 2 && M > N ? M : N) > 0 && L > 0;
-        if ((rc = rrl_line_tri_scan_clouds(line, ws, ws_bytes, B, N, M, L, mode, chunk, clouds, lmax_ready, o, stream))) return rc;
+        if ((rc = rrl_line_tri_scan_clouds(line, ws, ws_bytes, B, N, M, L, p.scan_mode, chunk, p.clouds, p.lmax_ready, o, stream)))
+            return rc;
     }
-    if (L >= 1 && L <= 1024 && !pool && B > 0 && o.reduce_mode < 2) {  // one tile of lines per sample: K2 + K3 + K4 in one launch
+    if (p.reduce == RRL_RED_TILE) {  // one tile of lines per sample: K2 + K3 + K4 in one launch
         RrlRange r("K2 + K3 + K4 (single tile)");
         WsLayout w(B, N, M, L);
         if (ws_bytes < w.total) return RRL_E_WS;
+        const PairArgs pa = pair_args(tri1, tri2, line, ws, w, B, N, M, L, s_m, s_n, e_m, e_n, false, o.tar_ws, o.problems);
+        const ReduceArgs ra = reduce_args(ws, w, loss, B, L, s_m, s_n, e_m, e_n, 0);
+        const hipStream_t s = (hipStream_t)stream;
         if (tb && tb->grad_tri1) {  // ... and the scatter backward to points1.grad too (rrl_loss_step_ex)
-            hipLaunchKernelGGL(pair_reduce_scatter_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, (hipStream_t)stream,
-                               pair_args(tri1, tri2, line, ws, w, B, N, M, L, s_m, s_n, e_m, e_n, false, target_ws, o.problems),
-                               reduce_args(ws, w, loss, B, L, s_m, s_n, e_m, e_n, 0),
+            hipLaunchKernelGGL(pair_reduce_scatter_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, s, pa, ra,
                                scat_args(ws, w, tb->grad_loss, tb->grad_tri1, nullptr, N, M, L), tb->payload, w.u32(ws, RRL_WS_MCTL));
-            RRL_LAUNCH_CHECK();
-            if (bwd_done) *bwd_done = true;
-            return 0;
-        }
-        if (tb && !tb->grad_tri1) {  // ... and the direct backward too (rrl_registration_step)
+        } else if (tb) {  // ... and the direct backward too (rrl_registration_step)
             SoloBwd sb;
             sb.kj = w.u8(ws, RRL_WS_KJ); sb.sel = w.i32(ws, RRL_WS_SEL); sb.nsel = w.i32(ws, RRL_WS_NSEL);
             sb.hs1 = w.i32(ws, RRL_WS_HS1); sb.bcnt = w.i32(ws, RRL_WS_BCNT); sb.info = w.i32(ws, RRL_WS_INFO);
@@ -559,35 +566,28 @@ static int loss_forward_impl(const float *tri1, const float *tri2, const float *
             sb.Q1 = (const float4 *)w.f32(ws, RRL_WS_Q1); sb.Q2 = (const float4 *)w.f32(ws, RRL_WS_Q2);
             sb.gR = tb->gR; sb.gt = tb->gt; sb.payload = tb->payload; sb.mctl = w.u32(ws, RRL_WS_MCTL);
             sb.B = B; sb.N = N; sb.L = L; sb.transpose_r = tb->transpose_r; sb.Bt = o.problems;
-            hipLaunchKernelGGL(pair_reduce_bwd_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, (hipStream_t)stream,
-                               pair_args(tri1, tri2, line, ws, w, B, N, M, L, s_m, s_n, e_m, e_n, false, target_ws, o.problems),
-                               reduce_args(ws, w, loss, B, L, s_m, s_n, e_m, e_n, 0), sb);
-            RRL_LAUNCH_CHECK();
-            if (bwd_done) *bwd_done = true;
-            return 0;
+            hipLaunchKernelGGL(pair_reduce_bwd_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, s, pa, ra, sb);
+        } else {
+            hipLaunchKernelGGL(pair_reduce_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, s, pa, ra);
         }
-        hipLaunchKernelGGL(pair_reduce_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, (hipStream_t)stream,
-                           pair_args(tri1, tri2, line, ws, w, B, N, M, L, s_m, s_n, e_m, e_n, false, target_ws, o.problems),
-                           reduce_args(ws, w, loss, B, L, s_m, s_n, e_m, e_n, 0));
         RRL_LAUNCH_CHECK();
         return 0;
     }
     {
         RrlRange r("K2 per-line distances");
-        if ((rc = line_pair_dist_impl(tri1, tri2, line, ws, ws_bytes, B, N, M, L, s_m, s_n, e_m,
-                                      e_n, pool, o, stream, tb != nullptr)))
-            return rc;
+        if ((rc = line_pair_dist_impl(tri1, tri2, line, ws, ws_bytes, B, N, M, L, s_m, s_n, e_m, e_n, o, stream))) return rc;
     }
     RrlRange r("K3+K4 median + Welsch reduce");
-    return loss_reduce_impl(ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, tb, bwd_done, o, stream);
+    return loss_reduce_impl(ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, tb, o, stream);
 }
 
 extern "C" int rrl_loss_forward_ex(const float *tri1, const float *tri2, const float *line,
                                    void *ws, size_t ws_bytes, float *loss, int B, int N, int M,
                                    int L, int s_m, int s_n, int e_m, int e_n, int pool, int mode,
                                    int chunk, const void *target_ws, const rrl_opts *opts, void *stream) {
-    return loss_forward_impl(tri1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n,
-                             pool, mode, chunk, target_ws, nullptr, rrl_resolve_opts(opts), stream);
+    RrlCall o = rrl_resolve_opts(opts);
+    const int rc = rrl_plan(o, B, N, M, L, pool, mode, target_ws, nullptr, RRL_WANT_FORWARD);
+    return rc ? rc : loss_forward_impl(tri1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, chunk, o, stream);
 }
 extern "C" int rrl_loss_forward_cached(const float *tri1, const float *tri2, const float *line,
                                        void *ws, size_t ws_bytes, float *loss, int B, int N, int M,
@@ -608,8 +608,8 @@ extern "C" int rrl_loss_forward_info(const float *tri1, const float *tri2, const
                                      int s_n, int e_m, int e_n, int pool, int mode, int chunk,
                                      const void *target_ws, int32_t *host_info, void *stream) {
     if (!host_info) return RRL_E_ARG;
-    int rc = loss_forward_impl(tri1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n,
-                               pool, mode, chunk, target_ws, nullptr, rrl_resolve_opts(nullptr), stream);
+    int rc = rrl_loss_forward_ex(tri1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, mode, chunk,
+                                 target_ws, nullptr, stream);
     if (rc) return rc;
     const int G = pool ? 1 : B;
     if (G <= 0) return 0;
@@ -644,8 +644,10 @@ extern "C" int rrl_registration_forward_ex(const float *src, const float *R, con
     if (ws_bytes < w.total) return RRL_E_WS;
     // the transform runs inside the prepare step
     const RrlXform xf = {src, R, t, transpose_r, 1};  // 1: clear GACC for the backward's atomics
-    return loss_forward_impl(w.f32(ws, RRL_WS_TRI1), tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m,
-                             s_n, e_m, e_n, 0, mode, chunk, target_ws, &xf, rrl_resolve_opts(opts), stream);
+    RrlCall o = rrl_resolve_opts(opts);
+    const int rc = rrl_plan(o, B, N, M, L, 0, mode, target_ws, &xf, RRL_WANT_FORWARD);
+    return rc ? rc : loss_forward_impl(w.f32(ws, RRL_WS_TRI1), tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0,
+                                       chunk, o, stream);
 }
 extern "C" int rrl_registration_forward_cached(const float *src, const float *R, const float *t,
                                                const float *tri2, const float *line, void *ws,
@@ -672,6 +674,16 @@ static int registration_backward_impl(const float *src, const float *R, const fl
                                       const float *grad_loss, float *grad_src, float *gR, float *gt,
                                       float *payload, int B, int N, int M, int L, int transpose_r,
                                       const RrlCall &o, void *stream);
+// The direct backward accumulates (gR, gt, payload) with atomics: clear them unless they are the workspace's GACC field,
+// which the forward's first launch clears
+static int clear_direct_grads(void *ws, const WsLayout &w, float *gR, float *gt, float *payload, int B, hipStream_t s) {
+    const float *gacc = w.f32(ws, RRL_WS_GACC);
+    if (gR == gacc && gt == gacc + 9 * (size_t)B && (!payload || payload == gacc + 12 * (size_t)B)) return 0;
+    int rc = rrl_fill(gR, 0u, sizeof(float) * 9 * (size_t)B, s);
+    if (!rc) rc = rrl_fill(gt, 0u, sizeof(float) * 3 * (size_t)B, s);
+    if (!rc && payload) rc = rrl_fill(payload, 0u, sizeof(float) * 14, s);
+    return rc;
+}
 
 // Forward + direct backward of the fused training op in ONE call (dL/dloss is an input, so nothing has to come back
 // to the host in between): when the tail kernel serves the shape, the backward rides in its launch (5 launches per
@@ -689,34 +701,20 @@ extern "C" int rrl_registration_step_ex(const float *src, const float *R, const 
 int rrl_registration_step_call(const float *src, const float *R, const float *t, const float *tri2, const float *line,
                                void *ws, size_t ws_bytes, float *loss, const float *grad_loss, float *gR, float *gt,
                                float *payload, int B, int N, int M, int L, int transpose_r, int s_m, int s_n, int e_m, int e_n,
-                               int mode, int chunk, const void *target_ws, const RrlCall &o, void *stream) {
+                               int mode, int chunk, const void *target_ws, RrlCall o, void *stream) {
     if (!src || !R || !t || !tri2 || !line || !ws || !loss || !grad_loss || !gR || !gt) return RRL_E_ARG;
     if (B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
     WsLayout w(B, N, M, L);
     if (ws_bytes < w.total) return RRL_E_WS;
-    const int nblk = (L + 1023) / 1024;
-    bool done = false;
-    int rc;
-    const bool solo = L <= 1024 && o.reduce_mode < 2;  // one tile of lines: per-line stage + reduce + backward by one workgroup per sample
-    if (B > 0 && L > 0 && !o.deterministic && (solo || reduce_kind(o.reduce_mode, B, nblk, 0, true) == 2)) {
-        float *gacc = w.f32(ws, RRL_WS_GACC);
-        hipStream_t s = (hipStream_t)stream;
-        if (gR != gacc || gt != gacc + 9 * (size_t)B || (payload && payload != gacc + 12 * (size_t)B)) {
-            if ((rc = rrl_fill(gR, 0u, sizeof(float) * 9 * (size_t)B, s))) return rc;
-            if ((rc = rrl_fill(gt, 0u, sizeof(float) * 3 * (size_t)B, s))) return rc;
-            if (payload && (rc = rrl_fill(payload, 0u, sizeof(float) * 14, s))) return rc;
-        }
-        const RrlXform xf = {src, R, t, transpose_r, 1};
-        const TailBwd tb = {grad_loss, src, gR, gt, payload, transpose_r, nullptr};
-        rc = loss_forward_impl(w.f32(ws, RRL_WS_TRI1), tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0,
-                               mode, chunk, target_ws, &xf, o, stream, &tb, &done);
-        if (rc || done) return rc;
-    } else {
-        const RrlXform xf = {src, R, t, transpose_r, 1};
-        rc = loss_forward_impl(w.f32(ws, RRL_WS_TRI1), tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0,
-                               mode, chunk, target_ws, &xf, o, stream);
-        if (rc) return rc;
-    }
+    const RrlXform xf = {src, R, t, transpose_r, 1};
+    int rc = rrl_plan(o, B, N, M, L, 0, mode, target_ws, &xf, RRL_WANT_DIRECT);
+    if (rc) return rc;
+    const bool ride = o.plan.bwd_rides;
+    if (ride && (rc = clear_direct_grads(ws, w, gR, gt, payload, B, (hipStream_t)stream))) return rc;
+    const TailBwd tb = {grad_loss, src, gR, gt, payload, transpose_r, nullptr};
+    rc = loss_forward_impl(w.f32(ws, RRL_WS_TRI1), tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0, chunk, o,
+                           stream, ride ? &tb : nullptr);
+    if (rc || ride) return rc;
     return registration_backward_impl(src, R, tri2, ws, ws_bytes, loss, grad_loss, nullptr, gR, gt, payload, B, N, M, L,
                                       transpose_r, o, stream);
 }
@@ -745,34 +743,24 @@ extern "C" int rrl_loss_step_ex(const float *tri1, const float *R, const float *
     RrlCall o = rrl_resolve_opts(opts);
     o.clear_ptr = grad_tri1;
     o.clear_bytes = sizeof(float) * 9 * (size_t)B * N;
-    const int nblk = (L + 1023) / 1024;
     // the shard payload of the step (rrl_opts.payload): in the workspace's GACC field the records launch clears it with the
     // rest of the accumulator (the fused op's convention); any other buffer is cleared here first
     float *payload = o.payload;
     const bool pay_in_ws = payload && R && payload == w.f32(ws, RRL_WS_GACC) + 12 * (size_t)B;
-    if (payload && !pay_in_ws) {
-        int rcf = rrl_fill(payload, 0u, sizeof(float) * 14, (hipStream_t)stream);
-        if (rcf) return rcf;
-    }
     const RrlXform xf = {tri1, R, t, transpose_r, pay_in_ws ? 1 : 0};
+    int rc = rrl_plan(o, B, N, M, L, 0, mode, target_ws, R ? &xf : nullptr, grad_tri2 ? RRL_WANT_SCATTER2 : RRL_WANT_SCATTER);
+    if (rc) return rc;
+    if (payload && !pay_in_ws && (rc = rrl_fill(payload, 0u, sizeof(float) * 14, (hipStream_t)stream))) return rc;
     const float *p1 = R ? w.f32(ws, RRL_WS_TRI1) : tri1;  // points1: the moved source, or the caller's triangles as given
-    // (the tail kernel, or -- one tile of lines per sample -- the single-tile kernel: loss_forward_impl's own conditions)
-    // (deterministic: the fixed-point scatter of loss_bwd_kernel + its conversion launch, never the riding float atomics)
-    const bool ride = B > 0 && L > 0 && !grad_tri2 && !o.deterministic &&
-                      (L > 1024 ? reduce_kind(o.reduce_mode, B, nblk, 0, true) == 2 : o.reduce_mode < 2);
-    // no riding backward, but the exchange reduce serves the call: its last arrivers add the payload (no payload launch)
-    const bool pay_in_reduce = payload && !ride && B > 0 && L > 1024 && reduce_kind(o.reduce_mode, B, nblk, 0, false) == 1;
-    o.payload_in_reduce = pay_in_reduce ? 1 : 0;
     const TailBwd tb = {grad_loss, nullptr, nullptr, nullptr, payload, 0, grad_tri1};
-    bool done = false;
-    int rc = loss_forward_impl(p1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0, mode, chunk, target_ws,
-                               R ? &xf : nullptr, o, stream, ride ? &tb : nullptr, &done);
-    if (rc || done) return rc;
+    rc = loss_forward_impl(p1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0, chunk, o, stream,
+                           o.plan.bwd_rides ? &tb : nullptr);
+    if (rc || o.plan.bwd_rides) return rc;
     // (grad_tri1 was cleared by the build step's first launch -- or by its fill on the unsorted path; an empty batch /
     //  cloud launches nothing: clear here)
     if (B == 0 || (N == 0 && M == 0)) return rrl_fill(grad_tri1, 0u, o.clear_bytes, (hipStream_t)stream);
     rc = loss_backward_impl(p1, tri2, ws, ws_bytes, grad_loss, grad_tri1, grad_tri2, B, N, M, L, 0, false, stream, o.deterministic != 0);
-    if (rc || !payload || L <= 0 || pay_in_reduce) return rc;
+    if (rc || !payload || L <= 0 || o.plan.payload_in_reduce) return rc;
     return rrl_shard_payload(loss, ws, ws_bytes, nullptr, nullptr, payload, B, N, M, L, stream);
 }
 
@@ -807,10 +795,7 @@ static int registration_backward_impl(const float *src, const float *R, const fl
     hipStream_t s = (hipStream_t)stream;
     RrlRange step("K5 rrl backward");
     if (!grad_src && B > 0 && L > 0) {
-        // only dL/dR, dL/dt (+ payload): ONE launch, straight from the selected lines; the outputs
-        // are accumulated with atomics -- clear them unless they are the workspace's GACC field,
-        // which the forward left zeroed
-        float *gacc = w.f32(ws, RRL_WS_GACC);
+        // only dL/dR, dL/dt (+ payload): ONE launch, straight from the selected lines
         const int nblk = o.deterministic ? 16 * ((L + 1023) / 1024) : (L + BWD_LINES - 1) / BWD_LINES;
 #define RRL_BWD_RT(DET, PART)                                                                                  \
         hipLaunchKernelGGL(loss_bwd_rt_kernel<DET>, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, s,            \
@@ -820,12 +805,9 @@ static int registration_backward_impl(const float *src, const float *R, const fl
                            w.i32(ws, RRL_WS_BCNT), w.i32(ws, RRL_WS_INFO), grad_loss, src, gR, gt, payload, loss,  \
                            B, N, L, transpose_r, PART, o.problems, B % 8 == 0 && xcd_align_on() ? 1 : 0)
         // the next epoch's sampler write pass rides along (bwd_write_kernel; rrl_demo_epoch)
-        RrlWriteRider *wr = o.write_rider;
+        RrlWriteRider *wr = o.plan.write_rides ? o.write_rider : nullptr;
         const int wtiles = wr ? (wr->n + 1023) / 1024 : 0;
-        const bool ride = wr && (!o.count_rider || o.count_rider->done) &&  // (the ballots of THAT count pass: it must have ridden)
-                          B == 1 && wr->n > 0 && wr->rounds > 0 && (long)wtiles * wr->rounds < 512 &&
-                          sizeof(int32_t) * (size_t)wr->rounds * wtiles <= 48 * 1024;
-        const WriteKArgs wk = ride ? WriteKArgs{wr->rng_state, wr->r, wr->centers, wr->accept, wr->lines, wr->filled, wr->n,
+        const WriteKArgs wk = wr ? WriteKArgs{wr->rng_state, wr->r, wr->centers, wr->accept, wr->lines, wr->filled, wr->n,
                                                 wr->rounds, wtiles, wr->rounds}
                                    : WriteKArgs{};
 #define RRL_BWD_WRITE(DET, PART)                                                                               \
@@ -843,20 +825,15 @@ static int registration_backward_impl(const float *src, const float *R, const fl
             // partials in VALS (the reduce kernel's input tiles: dead after the forward; B * Lp * 16 floats
             // >= B * 16 ceil(L / 1024) * 12), fixed-order sums by a second launch: nothing to clear
             float *part = w.f32(ws, RRL_WS_VALS);
-            if (ride) RRL_BWD_WRITE(true, part);
+            if (wr) RRL_BWD_WRITE(true, part);
             else RRL_BWD_RT(true, part);
             hipLaunchKernelGGL(loss_bwd_rt_finalize_kernel, dim3(1), dim3(256), 0, s, part, w.i32(ws, RRL_WS_INFO), loss,
                                gR, gt, payload, B, nblk);
             RRL_LAUNCH_CHECK();
             return 0;
         }
-        if (gR != gacc || gt != gacc + 9 * (size_t)B || (payload && payload != gacc + 12 * (size_t)B)) {
-            int rc;
-            if ((rc = rrl_fill(gR, 0u, sizeof(float) * 9 * (size_t)B, s))) return rc;
-            if ((rc = rrl_fill(gt, 0u, sizeof(float) * 3 * (size_t)B, s))) return rc;
-            if (payload && (rc = rrl_fill(payload, 0u, sizeof(float) * 14, s))) return rc;
-        }
-        if (ride) RRL_BWD_WRITE(false, nullptr);
+        if (int rc = clear_direct_grads(ws, w, gR, gt, payload, B, s)) return rc;
+        if (wr) RRL_BWD_WRITE(false, nullptr);
         else RRL_BWD_RT(false, nullptr);
 #undef RRL_BWD_RT
 #undef RRL_BWD_WRITE

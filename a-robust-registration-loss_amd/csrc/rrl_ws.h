@@ -117,6 +117,23 @@ struct RrlWriteRider {
 };
 
 struct RrlXform;
+// What an entry runs besides the forward (STAGE: one stage entry on its own, no whole forward; SCATTER2: grad_tri2 too);
+// the reduce that serves a call (TILE: one tile of lines per sample, per-line stage + reduce + a backward in one launch).
+enum { RRL_WANT_STAGE, RRL_WANT_FORWARD, RRL_WANT_SCATTER, RRL_WANT_SCATTER2, RRL_WANT_DIRECT };
+enum { RRL_RED_SINGLE, RRL_RED_XCHG, RRL_RED_TAIL, RRL_RED_TILE };
+// Which kernels serve ONE call of the narrow pipeline, decided by rrl_plan (rrl_sparse.hip) before its first launch; the
+// launchers read it and derive none of it again.  All zero (rrl_resolve_opts): nothing rides, nothing chains.
+struct RrlPlan {
+    int scan_mode;          // cull demoted to auto beyond the sort capacity
+    int clouds, build_clouds;  // clouds scanned (1: the target's scan carried over) / built (1: a kept target)
+    int lmax_ready;         // the records launch reduced the lines' maxima (no launch of the culled scan's own)
+    int reduce, tail_rpl2;  // RRL_RED_*; the tail kernel's <S, 2> instantiation rather than <S, TAIL_RPL>
+    int bwd_rides;          // the wanted backward rides in the reduce's launch (single-tile or tail kernel)
+    int payload_in_reduce;  // rrl_loss_step_ex: the exchange reduce's last arrivers add payload[0 .. 1]
+    int leave_clean;        // include/rrl.h RRL_F_CHAIN: the per-line stage zeroes COUNT1 / COUNT2, the reduce the CHAIN words
+    int fused_build;        // RRL_F_CHAINED honoured (only with leave_clean): records + both scans as ONE launch
+    int count_rides, write_rides;  // the RrlCountRider rides in the per-line launch, the RrlWriteRider in the backward's
+};
 struct RrlCall {
     int flags;
     int reduce_mode;    // 0 auto, 1 single, 2 tiled, 3 xchg
@@ -135,19 +152,20 @@ struct RrlCall {
     RrlWriteRider *write_rider;  // (internal) see RrlWriteRider
     int problems;         // rrl_opts.problems (multi-pose evaluation): 0, or Bt < B with B % Bt == 0
     float *payload;       // rrl_opts.payload (rrl_loss_step_ex): [sum of valid losses, #valid, 0 x 12], or NULL
-    int payload_in_reduce;  // (internal) rrl_loss_step_ex: the tiled reduce's last arrivers add payload[0 .. 1] (no payload launch)
     const void *tar_ws;   // (internal) the workspace that holds cloud 2's records when the target's scan is carried over
                           // (rrl_*_forward_cached: `target_ws`): the riding walk takes the target from there
     int32_t *chain_left;  // rrl_opts.chain_left (host int, or NULL)
-    // (internal, chained steps: include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED) decided once per call by loss_forward_impl:
-    int leave_clean;      //   the per-line stage zeroes COUNT1 / COUNT2 behind its read, the tail kernel the CHAIN words
-    int fused_build;      //   records + target scan + source scan as ONE launch (rrl_launch_cull_scan issues it; the
-    const RrlXform *xf;   //   source's transform for its records body)
+    const RrlXform *xf;   // (internal) the source's transform, for the fused build's records body (plan.fused_build) ...
     const float *tri1_in; //   ... and the caller's source rows when there is no transform
+    RrlPlan plan;
     __host__ bool prepared() const { return order1 != nullptr; }
     __host__ bool target_kept() const { return order1 != nullptr && (flags & RRL_F_TARGET_KEPT); }
 };
 RrlCall rrl_resolve_opts(const rrl_opts *o);  // rrl_sparse.hip
+// the plan of one call (o.plan; also settles o.problems, the orders, o.tar_ws, o.xf); RRL_E_ARG: an illegal multi-pose call
+int rrl_plan(RrlCall &o, int B, int N, int M, int L, int pool, int mode, const void *target_ws, const RrlXform *xf, int want);
+int rrl_sort_capacity(void);  // rrl_cull.hip: the sorted layout (records kernel, sphere tree, culled scan) serves up to it
+inline bool rrl_sorted_layout(int N, int M) { return (N > M ? N : M) <= rrl_sort_capacity(); }
 // the sampler's two passes on their own (rrl_geom.hip; rrl_sample_lines_rng = both): rrl_demo_epoch pipelines them
 int rrl_sample_count_pass(const uint64_t *rng_state, const float *r, const float *centers, const float *aabb1, const float *aabb2,
                           int32_t *tile_counts, int B, int n, int rounds, void *stream);
@@ -158,7 +176,7 @@ int rrl_sample_prefilter(void);
 int rrl_registration_step_call(const float *src, const float *R, const float *t, const float *tri2, const float *line,
                                void *ws, size_t ws_bytes, float *loss, const float *grad_loss, float *gR, float *gt,
                                float *payload, int B, int N, int M, int L, int transpose_r, int s_m, int s_n, int e_m, int e_n,
-                               int mode, int chunk, const void *target_ws, const RrlCall &o, void *stream);
+                               int mode, int chunk, const void *target_ws, RrlCall o, void *stream);
 // the process-wide defaults, one accessor per translation unit that owns one
 int rrl_default_sort_parts(void);                                           // rrl_cull.hip
 void rrl_default_scan_counters(unsigned long long **buf, long long *rows);  // rrl_cull.hip

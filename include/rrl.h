@@ -212,7 +212,8 @@ const char *rrl_version(void);
  *     THIS call's build ran fused (RRL_F_CHAINED was honoured);
  *   - RRL_F_CHAINED is valid only when the PREVIOUS call on this workspace reported chain_left bit 0 and nothing else has
  *     written the workspace since; it needs RRL_F_TARGET_KEPT and is ignored (plain 4-launch step) whenever the fused
- *     launch cannot serve the call (rider, counters, multi-pose, other reduce kernels, thin grids);
+ *     launch cannot serve the call (rider, counters, multi-pose, other reduce kernels, thin grids); a step without
+ *     RRL_F_CHAIN takes the plain build too, for the fused launch only serves a step that leaves the workspace chain-clean;
  *   - after a step with RRL_F_CHAIN COUNT1 / COUNT2 read zero (KJ / HS1 / HS2 hold what the per-line stage read), so its
  *     workspace cannot serve as another call's target_ws; after a step whose build was fused STATUS is not updated:
  *     INFO[b][3] carries each sample's OWN NaN flag (the plain step reports the batch-wide STATUS[0] in every row), and a

@@ -182,6 +182,34 @@ def test_chained_step_under_graph_replay(L):
         assert bool((st.st.lmax == -7.0).all())
 
 
+def test_chained_without_chain_takes_the_plain_build(L):
+    """RRL_F_CHAINED | RRL_F_TARGET_KEPT without RRL_F_CHAIN (a C caller's choice; LossStep always passes both) on a
+    chain-clean workspace: the fused launch only serves a step that leaves the workspace chain-clean again, so this one
+    takes the plain build -- chain_left reads 0 -- and equals the unchained step (include/rrl.h RRL_F_CHAINED)."""
+    import ctypes
+    from rrl_hip import _lib, ops
+    B, n, m, nl = 2, 1200, 1000, 6000
+    prs, src, tar = _pairs(900, B, n, m)
+    ln = _new_lines(L, prs, nl, 0)
+    R, t = _poses(B, 0)
+    ref = ops.LossStep(src, tar, nl)
+    ref.chain = False
+    want = _snapshot(ref, ref(R, t, ln))
+    st = ops.LossStep(src, tar, nl)
+    st(R, t, ln)  # RRL_F_CHAIN: leaves the workspace chain-clean
+    assert st._chain_ready
+    left = ctypes.c_int32(-1)
+    opts = ops.make_opts(order1=st.order1, order2=st.order2, target_kept=True, chain=_lib.F_CHAINED, chain_left=left)
+    st.st.lmax.fill_(-7.0)
+    with ops._guard(st.dev):
+        ops.check(_lib.load().rrl_loss_step_ex(ops._p(st.src), ops._p(R), ops._p(t), ops._p(st.tar), ops._p(ln), *st._c_fixed,
+                                               st._p_ones, *st._c_tail, ops._optr(opts), ops._stream(st.dev)), "rrl_loss_step")
+    torch.cuda.synchronize()
+    assert left.value == 0
+    assert not bool((st.st.lmax == -7.0).all())  # (the separate records launch rewrote LMAX)
+    _assert_same(want, _snapshot(st, st._out), "RRL_F_CHAINED alone")
+
+
 @pytest.mark.parametrize("B,n,m,nl", [(2, 1200, 1000, 6000), (8, 4096, 4096, 10000), (1, 1024, 1024, 20000)])
 def test_chained_registration_steps(L, B, n, m, nl):
     """The fused training op (ops.RegistrationStep: backward straight to (dR, dt) in the tail kernel) chains the same way:
