@@ -69,10 +69,7 @@ _WS_FIELDS = [
     ("chain", torch.int32, lambda B, N, M, L, G: (B, 4)),
     ("gfix", torch.int64, lambda B, N, M, L, G: (B * (N + M) * 9 + B,)),
 ]
-_layout_cache = {}
-_FIELD_INDEX = {name: i for i, (name, _, _) in enumerate(_WS_FIELDS)}
 _ITEMSIZE = {torch.int32: 4, torch.float32: 4, torch.uint8: 1, torch.int64: 8}
-_spec_cache = {}  # (dims) -> {field: (offset, nbytes, dtype, shape)}
 
 
 _gpu_ok = False
@@ -209,14 +206,49 @@ def _prep(t, name, last=None, dev=None):
     return t.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
-def _layout(B, N, M, L):
-    key = (B, N, M, L)
-    if key not in _layout_cache:
-        lib = _lib.load()
-        offs = (ctypes.c_size_t * len(_WS_FIELDS))()
-        check(lib.rrl_workspace_layout(B, N, M, L, offs), "rrl_workspace_layout")
-        _layout_cache[key] = (int(lib.rrl_workspace_bytes(B, N, M, L)), [int(o) for o in offs])
-    return _layout_cache[key]
+class _Workspace:
+    """One kind of device workspace: its field table (name, dtype, shape), the library's layout entry for it
+    (`<entry>_layout` / `<entry>_bytes`, include/rrl.h) and the attribute of a state that holds its bytes.  Layouts and
+    per-shape view specs are cached here; states call view() from their __getattr__ (nothing here refers to a state)."""
+
+    def __init__(self, fields, entry, attr):
+        self.fields, self.entry, self.attr = fields, entry, attr
+        self.index = {name: i for i, (name, _, _) in enumerate(fields)}
+        self.layouts = {}  # (B, N, M, L) -> (bytes, [offset of each field])
+        self.specs = {}    # (B, N, M, L, G) -> {field: (offset, nbytes, dtype, shape)}
+
+    def layout(self, B, N, M, L):
+        key = (B, N, M, L)
+        if key not in self.layouts:
+            lib = _lib.load()
+            offs = (ctypes.c_size_t * len(self.fields))()
+            check(getattr(lib, self.entry + "_layout")(B, N, M, L, offs), self.entry + "_layout")
+            self.layouts[key] = (int(getattr(lib, self.entry + "_bytes")(B, N, M, L)), [int(o) for o in offs])
+        return self.layouts[key]
+
+    def view(self, st, name):
+        """Field `name` of state `st`'s workspace as a typed view (a fresh one per access); AttributeError for any
+        other name."""
+        i = self.index.get(name)
+        if i is None:
+            raise AttributeError(name)
+        dims = st.dims
+        specs = self.specs.get(dims)
+        if specs is None:
+            specs = self.specs[dims] = {}
+        spec = specs.get(name)
+        if spec is None:
+            _, dtype, shape = self.fields[i]
+            shp = shape(*dims)
+            n = 1
+            for d in shp:
+                n *= d
+            spec = specs[name] = (self.layout(*dims[:4])[1][i], n * _ITEMSIZE[dtype], dtype, shp)
+        off, nb, dtype, shp = spec
+        return st.__dict__[self.attr][off:off + nb].view(dtype).reshape(shp)
+
+
+_WS = _Workspace(_WS_FIELDS, "rrl_workspace", "ws")
 
 
 class LossState:
@@ -225,31 +257,17 @@ class LossState:
 
     def __init__(self, B, N, M, L, G, dev):
         self.dims = (B, N, M, L, G)
-        self.nbytes, self.offsets = _layout(B, N, M, L)
+        self.nbytes, self.offsets = _WS.layout(B, N, M, L)
         self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.wsp = _p(self.ws)
         self.loss = torch.empty(G, dtype=torch.float32, device=dev)
 
     def __getattr__(self, name):
-        i = _FIELD_INDEX.get(name)
-        if i is None:
-            raise AttributeError(name)
         if name in ("count2", "hit2"):  # a carried-over target: its hit counts / lists live where its scan left them
             tgt = self.__dict__.get("target_state")
             if tgt is not None and tgt is not self:
                 return getattr(tgt, name)
-        specs = _spec_cache.get(self.dims)
-        if specs is None:
-            specs = _spec_cache[self.dims] = {}
-        spec = specs.get(name)
-        if spec is None:
-            _, dtype, shape = _WS_FIELDS[i]
-            shp = shape(*self.dims)
-            n = 1
-            for d in shp:
-                n *= d
-            spec = specs[name] = (self.offsets[i], n * _ITEMSIZE[dtype], dtype, shp)
-        off, nb, dtype, shp = spec
-        return self.ws[off:off + nb].view(dtype).reshape(shp)
+        return _WS.view(self, name)
 
     @property
     def nbuckets(self):
@@ -275,18 +293,7 @@ _WW_FIELDS = [
     ("bsum", torch.int64, lambda B, N, M, L, G: (G, 64, 2)),
     ("info", torch.int32, lambda B, N, M, L, G: (G, 4)),
 ]
-_WW_INDEX = {name: i for i, (name, _, _) in enumerate(_WW_FIELDS)}
-_wide_layout_cache = {}
-
-
-def _wide_layout(B, N, M, L):
-    key = (B, N, M, L)
-    if key not in _wide_layout_cache:
-        lib = _lib.load()
-        offs = (ctypes.c_size_t * len(_WW_FIELDS))()
-        check(lib.rrl_wide_workspace_layout(B, N, M, L, offs), "rrl_wide_workspace_layout")
-        _wide_layout_cache[key] = (int(lib.rrl_wide_workspace_bytes(B, N, M, L)), [int(o) for o in offs])
-    return _wide_layout_cache[key]
+_WW = _Workspace(_WW_FIELDS, "rrl_wide_workspace", "wws")
 
 
 class WideState:
@@ -299,21 +306,12 @@ class WideState:
         self.dims = (B, N, M, L, G)
         self.scan = LossState(B, N, M, L, G, dev)
         self.loss = self.scan.loss
-        self.wnbytes, self.woffsets = _wide_layout(B, N, M, L)
+        self.wnbytes, self.woffsets = _WW.layout(B, N, M, L)
         self.wws = torch.empty(self.wnbytes, dtype=torch.uint8, device=dev)
         self.host_flags = None
 
     def __getattr__(self, name):
-        i = _WW_INDEX.get(name)
-        if i is None:
-            raise AttributeError(name)
-        _, dtype, shape = _WW_FIELDS[i]
-        shp = shape(*self.dims)
-        n = 1
-        for d in shp:
-            n *= d
-        off = self.woffsets[i]
-        return self.wws[off:off + n * _ITEMSIZE[dtype]].view(dtype).reshape(shp)
+        return _WW.view(self, name)
 
     @property
     def nbuckets(self):
@@ -371,7 +369,15 @@ def _target_ws(target_from, B, N, M, L):
     return _p(tgt.ws)
 
 
-_order_ws_bytes = {}  # (B, n) -> scratch bytes of rrl_cloud_order
+_scratch_bytes = {}  # (size entry, *dims) -> bytes
+
+
+def _scratch_size(entry, *dims):
+    """Bytes of a scratch workspace (rrl_cloud_order_workspace_bytes, rrl_chamfer_workspace_bytes), cached per shape."""
+    nb = _scratch_bytes.get((entry, *dims))
+    if nb is None:
+        nb = _scratch_bytes[(entry, *dims)] = int(getattr(_lib.load(), entry)(*dims))
+    return nb
 
 
 def cloud_order(tri):
@@ -394,10 +400,7 @@ def cloud_order(tri):
     # scratch per CALL from torch's caching allocator, which is stream-aware: two calls of one shape on two streams /
     # from two threads never sort in the same memory (a per-shape global buffer did); the call runs once per
     # cloud, so the allocation is not on any step's path
-    nb = _order_ws_bytes.get((B, n))
-    if nb is None:
-        nb = _order_ws_bytes[(B, n)] = int(_lib.load().rrl_cloud_order_workspace_bytes(B, n))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    ws = torch.empty(_scratch_size("rrl_cloud_order_workspace_bytes", B, n), dtype=torch.uint8, device=dev)
     _run(dev, "rrl_cloud_order" if t.shape[-1] == 9 else "rrl_cloud_order_points", _p(t), _p(order), _p(ws), ws.numel(), B, n)
     return order
 
@@ -431,9 +434,7 @@ class ChamferRide:
     `.done` says whether it rode (else: chamfer_from_state, which looks here first).  Buffers are this object's own."""
 
     def __init__(self, B, N, M, dev):
-        nb = _chamfer_ws_bytes.get((B, N, M))
-        if nb is None:
-            nb = _chamfer_ws_bytes[(B, N, M)] = int(_lib.load().rrl_chamfer_workspace_bytes(B, N, M))
+        nb = _scratch_size("rrl_chamfer_workspace_bytes", B, N, M)
         self.dims = (B, N, M)
         self.ws = torch.empty(nb, dtype=torch.uint8, device=dev)
         self.bx = torch.empty(B, N, dtype=torch.int64, device=dev)
@@ -580,20 +581,53 @@ def _wide_backward(st, tri1, tri2, g, want2, dev):
     return g1, g2
 
 
+def _node_inputs(ctx, points1, points2, line):
+    """Input preparation of the loss nodes (_IntersectionLoss, _DropinLoss, _DropinBatch): (dev, tri1, tri2, line) --
+    fp32, contiguous, on the op's GPU, 3-D with one batch dimension -- kept on ctx for the backward (_node_backward)."""
+    dev = _home(points1, points2, line)
+    tri1, tri2 = _prep(points1, "points1", 9, dev), _prep(points2, "points2", 9, dev)
+    ln = _prep(line, "line", 6, dev)
+    if tri1.dim() != 3 or tri2.dim() != 3 or ln.dim() != 3:
+        raise ValueError("Input is wrong: points1/points2/line must be 3-D (B, n, c)")
+    if not (tri1.shape[0] == tri2.shape[0] == ln.shape[0]):
+        raise ValueError("points1, points2 and line must share the batch dimension")
+    ctx.set_materialize_grads(False)  # no zero-filled grads for the integer outputs
+    ctx.tri1, ctx.tri2, ctx.in_devs = tri1, tri2, (points1.device, points2.device)
+    return dev, tri1, tri2, ln
+
+
+def _node_backward(ctx, g_loss):
+    """(grad points1, grad points2) of a loss node's evaluation ctx.st (narrow or wide) for dL/dloss = g_loss (G,),
+    on the devices the inputs came from."""
+    st, tri1, tri2 = ctx.st, ctx.tri1, ctx.tri2
+    B, N, M, L, _ = st.dims
+    dev = tri1.device
+    g = g_loss if (g_loss.device == dev and g_loss.dtype == torch.float32 and g_loss.is_contiguous()) else \
+        g_loss.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if ctx.wide:
+        g1, g2 = _wide_backward(st, tri1, tri2, g, ctx.needs_input_grad[1], dev)
+    else:
+        g1 = torch.empty_like(tri1)  # zeroed by rrl_loss_backward
+        g2 = torch.empty_like(tri2) if ctx.needs_input_grad[1] else None
+        with _guard(dev):
+            check(_lib.load().rrl_loss_backward(_p(tri1), _p(tri2), st.wsp, st.nbytes, _p(g), _p(g1), _p(g2),
+                                                B, N, M, L, int(ctx.pool), _stream(dev)), "rrl_loss_backward")
+    if not ctx.needs_input_grad[0]:
+        g1 = None
+    elif ctx.in_devs[0] != dev:
+        g1 = g1.to(ctx.in_devs[0])
+    if g2 is not None and ctx.in_devs[1] != dev:
+        g2 = g2.to(ctx.in_devs[1])
+    return g1, g2
+
+
 class _IntersectionLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points1, points2, line, rng, pool, mode, chunk, target_from=None, opts=None, force_wide=False):
-        dev = _home(points1, points2, line)
-        tri1, tri2 = _prep(points1, "points1", 9, dev), _prep(points2, "points2", 9, dev)
-        ln = _prep(line, "line", 6, dev)
-        if tri1.dim() != 3 or tri2.dim() != 3 or ln.dim() != 3:
-            raise ValueError("Input is wrong: points1/points2/line must be 3-D (B, n, c)")
-        if not (tri1.shape[0] == tri2.shape[0] == ln.shape[0]):
-            raise ValueError("points1, points2 and line must share the batch dimension")
+        dev, tri1, tri2, ln = _node_inputs(ctx, points1, points2, line)
         if tri1.shape[0] == 0 or ln.shape[1] == 0:  # empty batch / no lines: nothing to launch
             ctx.st = None
-            ctx.set_materialize_grads(False)
-            dev, G = tri1.device, (1 if pool else tri1.shape[0])
+            G = 1 if pool else tri1.shape[0]
             out = (torch.zeros(G, device=dev), torch.zeros(G, 4, dtype=torch.int32, device=dev),
                    torch.zeros(4, dtype=torch.int32, device=dev))
             ctx.mark_non_differentiable(out[1], out[2])
@@ -605,11 +639,9 @@ class _IntersectionLoss(torch.autograd.Function):
             st = loss_forward_wide(tri1, tri2, ln, rng, pool, mode, chunk, opts=opts)
         else:
             st = loss_forward_raw(tri1, tri2, ln, rng, pool, mode, chunk, target_from=target_from, opts=opts)
-        ctx.st, ctx.tri1, ctx.tri2, ctx.pool = st, tri1, tri2, bool(pool)
-        ctx.in_devs = (points1.device, points2.device)
+        ctx.st, ctx.pool = st, bool(pool)
         info, status = st.info, (st.scan.status if ctx.wide else st.status)
         ctx.mark_non_differentiable(info, status)
-        ctx.set_materialize_grads(False)  # no zero-filled grads for the integer outputs
         _IntersectionLoss.last_state = st  # for shard_payload(): the newest evaluation
         # return a view: st.loss itself must not become the autograd output, or last_state would
         # keep the graph (and the AccumulateGrad nodes of the inputs) alive across iterations
@@ -619,27 +651,7 @@ class _IntersectionLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g1, _g2):
         if g_loss is None or ctx.st is None:
             return (None,) * 10
-        lib = _lib.load()
-        st, tri1, tri2 = ctx.st, ctx.tri1, ctx.tri2
-        if ctx.wide:
-            g = g_loss.detach().to(device=tri1.device, dtype=torch.float32).contiguous()
-            g1, g2 = _wide_backward(st, tri1, tri2, g, ctx.needs_input_grad[1], tri1.device)
-            g1 = g1.to(ctx.in_devs[0]) if ctx.needs_input_grad[0] else None
-            if g2 is not None:
-                g2 = g2.to(ctx.in_devs[1])
-            return g1, g2, None, None, None, None, None, None, None, None
-        B, N, _ = tri1.shape
-        M, L = tri2.shape[1], st.dims[3]
-        g = g_loss.detach().to(device=tri1.device, dtype=torch.float32).contiguous()
-        g1 = torch.empty_like(tri1)  # zeroed by rrl_loss_backward
-        g2 = torch.empty_like(tri2) if ctx.needs_input_grad[1] else None
-        with _guard(tri1.device):
-            check(lib.rrl_loss_backward(_p(tri1), _p(tri2), _p(st.ws), st.nbytes, _p(g), _p(g1), _p(g2),
-                                        B, N, M, L, int(ctx.pool), _stream(tri1.device)), "rrl_loss_backward")
-        g1 = g1.to(ctx.in_devs[0]) if ctx.needs_input_grad[0] else None
-        if g2 is not None:
-            g2 = g2.to(ctx.in_devs[1])
-        return g1, g2, None, None, None, None, None, None, None, None
+        return (*_node_backward(ctx, g_loss), None, None, None, None, None, None, None, None)
 
 
 # ---- the reference-signature call (loss.cal_loss_intersection_batch_whole_median_pts_lines) ----------------------
@@ -669,7 +681,6 @@ def _lease_state(B, N, M, L, G, dev):
             st.target_state = None
             return st
     st = LossState(B, N, M, L, G, dev)
-    st.wsp = _p(st.ws)
     st.host_info = torch.empty(4 * G, dtype=torch.int32).pin_memory()
     st.hostp = ctypes.c_void_p(st.host_info.data_ptr())
     if _pool_bytes[0] + st.nbytes > _POOL_CAP:  # many distinct shapes (ragged data): start over
@@ -685,71 +696,35 @@ def _lease_state(B, N, M, L, G, dev):
 def _dropin_forward(ctx, points1, points2, line, rng, pool, mode, chunk):
     """Forward of the reference-signature call: rrl_loss_forward_info on a leased workspace (one C call incl. the read-back
     of the flags).  Returns loss (G,) -- a fresh tensor -- and leaves the flags of all groups in _DropinLoss.flags_all."""
-    dev = _home(points1, points2, line)
-    tri1, tri2 = _prep(points1, "points1", 9, dev), _prep(points2, "points2", 9, dev)
-    ln = _prep(line, "line", 6, dev)
-    if tri1.dim() != 3 or tri2.dim() != 3 or ln.dim() != 3:
-        raise ValueError("Input is wrong: points1/points2/line must be 3-D (B, n, c)")
+    dev, tri1, tri2, ln = _node_inputs(ctx, points1, points2, line)
     B, N, _ = tri1.shape
     M, L = tri2.shape[1], ln.shape[1]
-    if not (tri2.shape[0] == ln.shape[0] == B):
-        raise ValueError("points1, points2 and line must share the batch dimension")
     G = 1 if pool else B
-    ctx.set_materialize_grads(False)
     if B == 0 or L == 0:  # empty batch / no lines: nothing to launch, no bucket
         ctx.st = None
         _DropinLoss.flags_all = [0, 0, 0, 0] * max(G, 1)
         _DropinLoss.flags = [0, 0, 0, 0]
         return torch.zeros(max(G, 1), device=dev)
     (s_m, s_n, e_m, e_n), wide = _classify_range(rng)
-    ctx.wide = wide
     if wide:  # the wide pipeline (ranges up to 8 hits per line): a workspace of its own per call, one read-back
         st = loss_forward_wide(tri1, tri2, ln, (s_m, s_n, e_m, e_n), pool, mode, chunk)
-        _DropinLoss.flags_all = fl = st.host_flags
-        _DropinLoss.flags = fl[:4]
-        ctx.st, ctx.tri1, ctx.tri2, ctx.pool = st, tri1, tri2, bool(pool)
-        ctx.in_devs = (points1.device, points2.device)
-        _IntersectionLoss.last_state = st
-        return st.loss
-    st = _lease_state(B, N, M, L, G, dev)
-    if not hasattr(st, "hostp"):  # created while capturing: no read-back possible there
-        raise RRLError("the reference-signature loss synchronises (it returns None / raises on the host): "
-                       "it cannot be captured into a graph; use batched_intersection_loss / ops.registration_loss")
-    st.loss = loss = torch.empty(G, dtype=torch.float32, device=dev)
-    with _guard(dev):
-        check(_lib.load().rrl_loss_forward_info(_p(tri1), _p(tri2), _p(ln), st.wsp, st.nbytes, _p(loss), B, N, M, L,
-                                                s_m, s_n, e_m, e_n, int(pool), _MODES[mode], int(chunk), None,
-                                                st.hostp, _stream(dev)), "rrl_loss_forward_info")
-    _DropinLoss.flags_all = fl = st.host_info.tolist()  # 4 per group
+        loss, fl = st.loss, st.host_flags
+    else:
+        st = _lease_state(B, N, M, L, G, dev)
+        if not hasattr(st, "hostp"):  # created while capturing: no read-back possible there
+            raise RRLError("the reference-signature loss synchronises (it returns None / raises on the host): "
+                           "it cannot be captured into a graph; use batched_intersection_loss / ops.registration_loss")
+        st.loss = loss = torch.empty(G, dtype=torch.float32, device=dev)
+        with _guard(dev):
+            check(_lib.load().rrl_loss_forward_info(_p(tri1), _p(tri2), _p(ln), st.wsp, st.nbytes, _p(loss), B, N, M, L,
+                                                    s_m, s_n, e_m, e_n, int(pool), _MODES[mode], int(chunk), None,
+                                                    st.hostp, _stream(dev)), "rrl_loss_forward_info")
+        fl = st.host_info.tolist()  # 4 per group
+    _DropinLoss.flags_all = fl
     _DropinLoss.flags = fl[:4]
-    ctx.st, ctx.tri1, ctx.tri2, ctx.pool = st, tri1, tri2, bool(pool)
-    ctx.in_devs = (points1.device, points2.device)
+    ctx.st, ctx.pool, ctx.wide = st, bool(pool), wide
     _IntersectionLoss.last_state = st
     return loss
-
-
-def _dropin_backward(ctx, g_loss):
-    """(grad points1, grad points2) of a _dropin_forward evaluation for dL/dloss = g_loss (G,)."""
-    st, tri1, tri2 = ctx.st, ctx.tri1, ctx.tri2
-    B, N, M, L, _ = st.dims
-    dev = tri1.device
-    g = g_loss if (g_loss.device == dev and g_loss.dtype == torch.float32 and g_loss.is_contiguous()) else \
-        g_loss.detach().to(device=dev, dtype=torch.float32).contiguous()
-    if getattr(ctx, "wide", False):
-        g1, g2 = _wide_backward(st, tri1, tri2, g, ctx.needs_input_grad[1], dev)
-    else:
-        g1 = torch.empty_like(tri1)  # zeroed by rrl_loss_backward
-        g2 = torch.empty_like(tri2) if ctx.needs_input_grad[1] else None
-        with _guard(dev):
-            check(_lib.load().rrl_loss_backward(_p(tri1), _p(tri2), st.wsp, st.nbytes, _p(g), _p(g1), _p(g2),
-                                                B, N, M, L, int(ctx.pool), _stream(dev)), "rrl_loss_backward")
-    if not ctx.needs_input_grad[0]:
-        g1 = None
-    elif ctx.in_devs[0] != dev:
-        g1 = g1.to(ctx.in_devs[0])
-    if g2 is not None and ctx.in_devs[1] != dev:
-        g2 = g2.to(ctx.in_devs[1])
-    return g1, g2
 
 
 class _DropinLoss(torch.autograd.Function):
@@ -767,7 +742,7 @@ class _DropinLoss(torch.autograd.Function):
     def backward(ctx, g_loss):
         if g_loss is None or ctx.st is None:
             return (None,) * 7
-        return (*_dropin_backward(ctx, g_loss), None, None, None, None, None)
+        return (*_node_backward(ctx, g_loss), None, None, None, None, None)
 
 
 class _DropinBatch(torch.autograd.Function):
@@ -796,7 +771,7 @@ class _DropinBatch(torch.autograd.Function):
                     zero = ctx.tri1.new_zeros(1)
                 g = zero
             parts.append(g.reshape(1))
-        return (*_dropin_backward(ctx, torch.cat(parts)), None, None, None, None)
+        return (*_node_backward(ctx, torch.cat(parts)), None, None, None, None)
 
 
 # ---- the trainers' literal loop, served by ONE evaluation of the whole batch (round 4) ----------------------------
@@ -1065,7 +1040,109 @@ def registration_loss(src_tri, R, t, tar_tri, line, rng=(1, 1, 5, 5), transpose_
                                    chunk, want_payload, target_from, opts)
 
 
-class RegistrationStep:
+class _Step:
+    """What RegistrationStep and LossStep share: the clouds, their orders and the state built once; the kept target;
+    the option variants of a call (built once: plain, kept target and, prepared, the chained ones) and the choice among
+    them per call (_pick); the bookkeeping after the C call (_done).  A subclass adds its own rrl_opts fields to ._extra
+    before it calls _set_opts(), and keeps its own outputs, argument tuples and C calls."""
+
+    def __init__(self, what, src_tri, tar_tri, n_lines, rng, transpose_r, mode, chunk, prepared, src_order, tar_order,
+                 chamfer, poses, chain):
+        dev = _home(src_tri, tar_tri)
+        self.dev = dev
+        self.src = _prep(src_tri, "src_tri", 9, dev)
+        self.tar = _prep(tar_tri, "tar_tri", 9, dev)
+        if self.src.dim() != 3 or self.tar.dim() != 3 or self.src.shape[0] != self.tar.shape[0]:
+            raise ValueError("src_tri/tar_tri must be (B, n, 9) with the same B")
+        Bt, N, _ = self.src.shape
+        M, L = self.tar.shape[1], int(n_lines)
+        if Bt == 0 or L <= 0:
+            raise ValueError(f"{what} needs a non-empty batch and line set")
+        self.poses, self.Bt = int(poses), Bt
+        if self.poses < 1 or (self.poses > 1 and (mode != "cull" or max(N, M) > 65536)):
+            raise ValueError("poses must be >= 1; a multi-pose step runs scan mode cull on clouds <= 65536 triangles")
+        B = Bt * self.poses  # instances of one call
+        self.dims = (B, N, M, L)
+        self.rng = _check_range(rng, what)
+        self.tr, self.mode, self.chunk = int(bool(transpose_r)), _MODES[mode], int(chunk)
+        self.st = LossState(B, N, M, L, B, dev)
+        # the Chamfer monitor of every step, issued inside its scan launch (ChamferRide): .chamfer_value after each call
+        self.ride = ChamferRide(B, N, M, dev) if chamfer else None
+        self.chamfer_value = None
+        self._extra = dict(chamfer=self.ride, problems=Bt if self.poses > 1 else None)
+        self.ones = torch.ones(B, dtype=torch.float32, device=dev)
+        if prepared is None:  # default: on (RRL_PREPARED=0 turns the default off: A/B runs of unmodified callers)
+            prepared = os.environ.get("RRL_PREPARED", "1") != "0"
+        self.prepared = bool(prepared) and mode == "cull" and max(N, M) <= 65536
+        self._kept_key = None  # _write_key of the target whose records the workspace holds
+        self.keep_target = True  # False: rebuild the target's records in every call (see invalidate_target)
+        # CHAINED steps (round 6; include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED): a prepared step asks the library to leave the
+        # workspace's hit counts cleared (the library says through _chain_left whether it did); a step that follows such a
+        # step with the target still kept runs records + target scan + source scan as ONE launch.  chain = False turns it
+        # off for this object (RRL_CHAIN=0 for the process).
+        self.chain = bool(chain)
+        self._chain_left = ctypes.c_int32(0)
+        self._chain_ready = False  # the previous call on self.st left it chain-clean and nothing has touched it since
+        self.fused = False
+        self.order1 = self.order2 = None
+        if self.prepared:
+            self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src)
+            self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar)
+        self._lib = _lib.load()
+
+    def invalidate_target(self):
+        """Forget the kept target: the next call rebuilds cloud 2's records and tree.  The step notices a changed target by
+        itself through (data_ptr, torch's version counter, the library's own raw-write serial); what it cannot see is a
+        write that bypasses both -- `tar.data.copy_()`, a custom kernel or another raw-pointer library writing into the
+        same buffer -- : call this after such a write, or set `.keep_target = False` to rebuild in every call.  (A hipGraph
+        capture bakes in whichever variant is active at capture time: capture with keep_target = False when the target's
+        CONTENT changes between replays.)"""
+        self._kept_key = None
+
+    def _set_opts(self):
+        """The option variants of this step's calls (never built per call, only when an order changes): plain, kept
+        target (the plain ones again when not prepared) and, prepared, first / kept / chained with chain_left."""
+        kw = dict(order1=self.order1, order2=self.order2, **self._extra)
+        self._opts = make_opts(**kw)
+        self._opts_kept = make_opts(target_kept=True, **kw) if self.prepared else self._opts
+        self._optr, self._optr_kept = _optr(self._opts), _optr(self._opts_kept)
+        self._chain_ready = False
+        if self.prepared:
+            kw["chain_left"] = self._chain_left
+            self._opts_c = (make_opts(chain=_lib.F_CHAIN, **kw), make_opts(target_kept=True, chain=_lib.F_CHAIN, **kw),
+                            make_opts(target_kept=True, chain=_lib.F_CHAIN | _lib.F_CHAINED, **kw))
+            self._optr_c = tuple(_optr(o) for o in self._opts_c)  # first / kept / chained
+
+    def _pick(self, chain, target_from=None):
+        """(options pointer, target key) of this call: plain, kept target, or -- chain -- first / kept / chained."""
+        op, key = self._optr, None
+        if self.prepared:
+            key = _write_key(self.tar) if (self.keep_target and target_from is None) else None
+            kept = key is not None and key == self._kept_key
+            if chain:
+                op = self._optr_c[2 if (kept and self._chain_ready) else (1 if kept else 0)]
+            elif kept:
+                op = self._optr_kept
+            self._kept_key = None  # (set again by _done, once the call has been issued: a call that raises keeps nothing)
+        self._chain_ready = False
+        self._chain_left.value = 0
+        return op, key
+
+    def _done(self, key):
+        """After the C call: the kept target (key: None for a carried-over target -- it is not built here -- and with
+        keep_target off), the chain state, last_state and the Chamfer monitor; returns the outputs."""
+        self._kept_key = key
+        self._chain_ready = self.prepared and bool(self._chain_left.value & 1)
+        self.fused = bool(self._chain_left.value & 2)  # THIS call's records + scans ran as one launch
+        self.st.counts_cleared = self._chain_ready
+        _IntersectionLoss.last_state = self.st
+        if self.ride is not None:  # .chamfer_value: this step's monitor (it rode in the scan's launch, or one launch now)
+            _keep_ride(self.st, self.ride)
+            self.chamfer_value = chamfer_from_state(self.st)
+        return self._out
+
+
+class RegistrationStep(_Step):
     """The fused training op WITHOUT autograd and without a graph: forward + backward to (dR, dt) as ONE C call
     (rrl_registration_step: where the tail kernel serves the shape the backward rides in the reduce's launch, 5 launches
     per step) on buffers allocated once -- what a training loop needs when (R, t) come out of a network:
@@ -1100,39 +1177,16 @@ class RegistrationStep:
         poses = k > 1 (round 5): a MULTI-POSE step (rrl_opts.problems) -- every call takes R (k * B, 3, 3), t (k * B, 3): k
         poses of each of the B problems (instance i * B + b = pose i of problem b; RPM's num_iter, FMR's last estimates),
         evaluated in ONE set of launches with the target scanned once per problem; loss (k * B,), gR (k * B, 3, 3),
-        gt (k * B, 3), bit-identical per instance to k single-pose steps.  Scan mode cull, clouds <= 65536 triangles."""
-        dev = _home(src_tri, tar_tri)
-        self.dev = dev
-        self._extra = dict(reduce_mode=reduce_mode, deterministic=deterministic, sort_parts=sort_parts)
-        self._want_chamfer = bool(chamfer)  # the Chamfer monitor of every step, issued inside its scan launch (ChamferRide)
-        self.ride = self.chamfer_value = None
-        self.src = _prep(src_tri, "src_tri", 9, dev)
-        self.tar = _prep(tar_tri, "tar_tri", 9, dev)
-        if self.src.dim() != 3 or self.tar.dim() != 3 or self.src.shape[0] != self.tar.shape[0]:
-            raise ValueError("src_tri/tar_tri must be (B, n, 9) with the same B")
-        Bt, N, _ = self.src.shape
-        M, L = self.tar.shape[1], int(n_lines)
-        if Bt == 0 or L <= 0:
-            raise ValueError("RegistrationStep needs a non-empty batch and line set")
-        self.poses = int(poses)
-        if self.poses < 1 or (self.poses > 1 and (mode != "cull" or max(N, M) > 65536)):
-            raise ValueError("poses must be >= 1; a multi-pose step runs scan mode cull on clouds <= 65536 triangles")
-        B = Bt * self.poses  # instances of one call
-        self.Bt = Bt
-        if self.poses > 1:
-            self._extra["problems"] = Bt
-        self.dims = (B, N, M, L)
-        self.rng = _check_range(rng, "RegistrationStep")
-        self.tr, self.mode, self.chunk = int(bool(transpose_r)), _MODES[mode], int(chunk)
-        self.st = LossState(B, N, M, L, B, dev)
-        if self._want_chamfer:
-            self.ride = ChamferRide(B, N, M, dev)
-            self._extra["chamfer"] = self.ride
-        self.ones = torch.ones(B, dtype=torch.float32, device=dev)
+        gt (k * B, 3), bit-identical per instance to k single-pose steps.  Scan mode cull, clouds <= 65536 triangles.
+        chain: OFF by default here (see _Step): a chained step clears its hit counts on exit, and this step's state is
+        what callers hand on as target_from= (RPM / FMR)."""
+        super().__init__("RegistrationStep", src_tri, tar_tri, n_lines, rng, transpose_r, mode, chunk, prepared, src_order,
+                         tar_order, chamfer, poses, chain)
+        self._extra.update(reduce_mode=reduce_mode, deterministic=deterministic, sort_parts=sort_parts)
+        B, N, M, L = self.dims
         gacc = self.st.gacc
         self.gR, self.gt = gacc[:B * 9].view(B, 3, 3), gacc[B * 9:B * 12].view(B, 3)
         self.payload = gacc[B * 12:B * 12 + 14] if want_payload else None
-        self._lib = _lib.load()
         self._fixed_f = (_p(self.st.ws), self.st.nbytes, _p(self.st.loss), B, N, M, L, self.tr, *self.rng, self.mode,
                          self.chunk, None)
         self._fixed_b = (_p(self.st.ws), self.st.nbytes, _p(self.st.loss))
@@ -1140,44 +1194,8 @@ class RegistrationStep:
         self._head_s = (_p(self.st.ws), self.st.nbytes, _p(self.st.loss))
         self._tail_s = (_p(gacc[:B * 9]), _p(gacc[B * 9:B * 12]), _p(self.payload), B, N, M, L, self.tr, *self.rng,
                         self.mode, self.chunk, None)
-        if prepared is None:  # default: on (RRL_PREPARED=0 turns the default off: A/B runs of unmodified callers)
-            prepared = os.environ.get("RRL_PREPARED", "1") != "0"
-        self.prepared = bool(prepared) and mode == "cull" and max(N, M) <= 65536
         self._out = (self.st.loss.view(-1), self.gR, self.gt, self.payload, self.st.info)  # (static views: built once)
-        self._kept_key = None  # _write_key of the target whose records the workspace holds
-        self.keep_target = True  # False: rebuild the target's records in every call (see invalidate_target)
-        # chained steps (round 6; include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED; see LossStep).  OFF by default here: a chained
-        # step clears its hit counts on exit, and this step's state is what callers hand on as target_from= (RPM / FMR)
-        self.chain = bool(chain)
-        self._chain_left = ctypes.c_int32(0)
-        self._chain_ready = False
-        self.fused = False
-        self.order1 = self.order2 = None
-        if self.prepared:
-            self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src)
-            self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar)
         self._set_opts()
-
-    def invalidate_target(self):
-        """Forget the kept target: the next call rebuilds cloud 2's records and tree.  The step notices a changed target by
-        itself through (data_ptr, torch's version counter, the library's own raw-write serial); what it cannot see is a
-        write that bypasses both -- `tar.data.copy_()`, a custom kernel or another raw-pointer library writing into the
-        same buffer -- : call this after such a write, or set `.keep_target = False` to rebuild in every call.  (A hipGraph
-        capture bakes in whichever variant is active at capture time: capture with keep_target = False when the target's
-        CONTENT changes between replays.)"""
-        self._kept_key = None
-
-    def _set_opts(self):
-        self._opts = make_opts(order1=self.order1, order2=self.order2, **self._extra)
-        self._opts_kept = make_opts(order1=self.order1, order2=self.order2, target_kept=True, **self._extra) if self.prepared else self._opts
-        self._optr = ctypes.byref(self._opts) if self._opts is not None else None
-        self._optr_kept = ctypes.byref(self._opts_kept) if self._opts_kept is not None else None
-        self._chain_ready = False
-        if self.prepared:  # first / kept / chained (as LossStep)
-            kw = dict(order1=self.order1, order2=self.order2, chain_left=self._chain_left, **self._extra)
-            self._opts_c = (make_opts(chain=_lib.F_CHAIN, **kw), make_opts(target_kept=True, chain=_lib.F_CHAIN, **kw),
-                            make_opts(target_kept=True, chain=_lib.F_CHAIN | _lib.F_CHAINED, **kw))
-            self._optr_c = tuple(ctypes.byref(o) for o in self._opts_c)
 
     def __call__(self, R, t, line, grad_loss=None, src_tri=None, tar_tri=None, target_from=None, src_order=None,
                  tar_order=None):
@@ -1197,24 +1215,14 @@ class RegistrationStep:
             raise ValueError(f"src_tri {(Bt, N, 9)} / tar_tri {(Bt, M, 9)} expected")
         if self.poses > 1 and target_from is not None:
             raise ValueError("a multi-pose step scans its target itself")
-        op = self._optr
-        if self.prepared:
-            if src_tri is not None or src_order is not None or tar_tri is not None or tar_order is not None:
-                if src_tri is not None or src_order is not None:  # a new source: its order comes along, or is taken now
-                    self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src)
-                if tar_tri is not None or tar_order is not None:
-                    self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar)
-                    self._kept_key = None
-                self._set_opts()
-            key = _write_key(self.tar) if (self.keep_target and target_from is None) else None
-            kept = key is not None and key == self._kept_key
-            if self.chain and RegistrationStep.ONE_CALL and target_from is None:
-                op = self._optr_c[2 if (kept and self._chain_ready) else (1 if kept else 0)]
-            elif kept:
-                op = self._optr_kept
-            self._kept_key = None  # (set again below, once the call has been issued: a call that raises keeps nothing)
-        self._chain_ready = False
-        self._chain_left.value = 0
+        if self.prepared and (src_tri is not None or src_order is not None or tar_tri is not None or tar_order is not None):
+            if src_tri is not None or src_order is not None:  # a new source: its order comes along, or is taken now
+                self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src)
+            if tar_tri is not None or tar_order is not None:
+                self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar)
+                self._kept_key = None
+            self._set_opts()
+        op, key = self._pick(self.chain and RegistrationStep.ONE_CALL and target_from is None, target_from)
         Rm, tv, ln = _prep(R, "R", None, dev), _prep(t, "t", None, dev), _prep(line, "line", 6, dev)
         if Rm.numel() != B * 9 or tv.numel() != B * 3 or tuple(ln.shape) != (Bt, L, 6):
             raise ValueError("R (poses * B, 3, 3), t (poses * B, 3), line (B, L, 6) expected")
@@ -1238,19 +1246,10 @@ class RegistrationStep:
                       "rrl_registration_forward")
                 check(lib.rrl_registration_backward_ex(_p(self.src), _p(Rm), _p(self.tar), *self._fixed_b, _p(g), *self._tail_b, op, s),
                       "rrl_registration_backward")
-        if self.prepared:
-            self._kept_key = key  # (None for a carried-over target -- it is not built here -- and with keep_target off)
-            self._chain_ready = bool(self._chain_left.value & 1)
-            self.fused = bool(self._chain_left.value & 2)  # THIS call's records + scans ran as one launch
-        self.st.counts_cleared = self._chain_ready
-        _IntersectionLoss.last_state = self.st
-        if self.ride is not None:  # .chamfer_value: this step's monitor (it rode in the scan's launch, or one launch now)
-            _keep_ride(self.st, self.ride)
-            self.chamfer_value = chamfer_from_state(self.st)
-        return self._out
+        return self._done(key)
 
 
-class LossStep:
+class LossStep(_Step):
     """SURVEY 8(d)'s definition by direct issue (round 4): rigid apply of the source + loss + backward to points1.grad
     (B, N, 9) as ONE C call (rrl_loss_step_ex) on buffers allocated once, no autograd node, no graph -- the drop-in
     chain `tri = rigid_apply(src, R, t); loss = intersection_loss(tri, tar, line); loss.backward()` without its host cost:
@@ -1279,67 +1278,22 @@ class LossStep:
         contributes to the all-reduce of the scalar loss (rrl_hip.dist; points1.grad stays local).
         poses = k > 1: a multi-pose step as RegistrationStep's -- R (k * B, 3, 3), t (k * B, 3) (required), loss (k * B,),
         grad (k * B, N, 9) = dL/d(moved triangles) of every instance."""
-        dev = _home(src_tri, tar_tri)
-        self.dev = dev
-        self.src = _prep(src_tri, "src_tri", 9, dev)
-        self.tar = _prep(tar_tri, "tar_tri", 9, dev)
-        if self.src.dim() != 3 or self.tar.dim() != 3 or self.src.shape[0] != self.tar.shape[0]:
-            raise ValueError("src_tri/tar_tri must be (B, n, 9) with the same B")
-        Bt, N, _ = self.src.shape
-        M, L = self.tar.shape[1], int(n_lines)
-        if Bt == 0 or L <= 0:
-            raise ValueError("LossStep needs a non-empty batch and line set")
-        self.poses, self.Bt = int(poses), Bt
-        if self.poses < 1 or (self.poses > 1 and (mode != "cull" or max(N, M) > 65536)):
-            raise ValueError("poses must be >= 1; a multi-pose step runs scan mode cull on clouds <= 65536 triangles")
-        B = Bt * self.poses
-        prob = Bt if self.poses > 1 else None
-        self.ride = ChamferRide(B, N, M, dev) if chamfer else None
-        self.chamfer_value = None
-        self.dims = (B, N, M, L)
-        self.rng = _check_range(rng, "LossStep")
-        self.tr, self.mode, self.chunk = int(bool(transpose_r)), _MODES[mode], int(chunk)
-        self.st = LossState(B, N, M, L, B, dev)
-        self.ones = torch.ones(B, dtype=torch.float32, device=dev)
-        self.grad = torch.empty(B, N, 9, dtype=torch.float32, device=dev)
-        if prepared is None:
-            prepared = os.environ.get("RRL_PREPARED", "1") != "0"
-        self.prepared = bool(prepared) and mode == "cull" and max(N, M) <= 65536
-        self._kept_key = None
-        self.keep_target = True  # see RegistrationStep.invalidate_target
+        super().__init__("LossStep", src_tri, tar_tri, n_lines, rng, transpose_r, mode, chunk, prepared, src_order,
+                         tar_order, chamfer, poses, chain)
+        B, N, M, L = self.dims
+        self.grad = torch.empty(B, N, 9, dtype=torch.float32, device=self.dev)
         # (in the workspace's accumulator field: the step's first launch clears it, as for RegistrationStep)
         self.payload = self.st.gacc[B * 12:B * 12 + 14] if want_payload else None
-        self._opts = self._opts_kept = make_opts(chamfer=self.ride, payload=self.payload, problems=prob, deterministic=deterministic)  # (None without any)
-        # CHAINED steps (round 6; include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED): every prepared step asks the library to leave
-        # the workspace's hit counts cleared (the library says through _chain_left whether it did); a step that follows such
-        # a step with the target still kept runs records + target scan + source scan as ONE launch.  chain = False turns
-        # it off for this object (RRL_CHAIN=0 for the process).
-        self.chain = bool(chain)
-        self._chain_left = ctypes.c_int32(0)
-        self._chain_ready = False  # the previous call on self.st left it chain-clean and nothing has touched it since
-        self.fused = False
-        if self.prepared:
-            self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src)
-            self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar)
-            kw = dict(order1=self.order1, order2=self.order2, chamfer=self.ride, payload=self.payload, problems=prob,
-                      chain_left=self._chain_left, deterministic=deterministic)
-            self._opts = make_opts(**kw)  # (.chain = False: no chain flags at all -- the hit counts stay readable)
-            self._opts_kept = make_opts(target_kept=True, **kw)
-            self._opts_c = (make_opts(chain=_lib.F_CHAIN, **kw), make_opts(target_kept=True, chain=_lib.F_CHAIN, **kw),
-                            make_opts(target_kept=True, chain=_lib.F_CHAIN | _lib.F_CHAINED, **kw))
-            self._optr_c = tuple(_optr(o) for o in self._opts_c)  # first / kept / chained
-        self._optr, self._optr_kept = _optr(self._opts), _optr(self._opts_kept)
-        self._lib = _lib.load()
+        self._extra.update(payload=self.payload, deterministic=deterministic)
+        if self.prepared:  # its plain and kept calls report through chain_left too (.chain = False: no chain flags at all)
+            self._extra["chain_left"] = self._chain_left
         # what every call hands over / returns unchanged: built once (a LossState field is a fresh view per access: ~6 us of host
         # time per step for `.info` alone)
         self._out = (self.st.loss.view(-1), self.grad, self.st.info)
         self._c_fixed = (_p(self.st.ws), self.st.nbytes, _p(self.st.loss))
         self._c_tail = (_p(self.grad), None, B, N, M, L, self.tr, *self.rng, self.mode, self.chunk, None)
         self._p_ones = _p(self.ones)
-
-    def invalidate_target(self):
-        """As RegistrationStep.invalidate_target: the next call rebuilds the target's records."""
-        self._kept_key = None
+        self._set_opts()
 
     def __call__(self, R, t, line, grad_loss=None):
         B, N, M, L = self.dims
@@ -1351,32 +1305,14 @@ class LossStep:
                 or tuple(ln.shape) != (self.Bt, L, 6) or (self.poses > 1 and Rm is None):
             raise ValueError("R (poses * B, 3, 3) and t (poses * B, 3) (or both None for poses = 1), line (B, L, 6) expected")
         g = self.ones if grad_loss is None else _prep(grad_loss, "grad_loss", None, dev)
-        op, key = self._optr, None
-        if self.prepared:
-            key = _write_key(self.tar) if self.keep_target else None
-            kept = key is not None and key == self._kept_key
-            if self.chain:
-                op = self._optr_c[2 if (kept and self._chain_ready) else (1 if kept else 0)]
-            elif kept:
-                op = self._optr_kept
-            self._kept_key = None  # (set below, once the call has been issued)
-        self._chain_ready = False
-        self._chain_left.value = 0
+        op, key = self._pick(self.chain)
         if self.ride is not None:
             self.ride.arm()
         with _guard(dev):
             check(self._lib.rrl_loss_step_ex(_p(self.src), _p(Rm), _p(tv), _p(self.tar), _p(ln), *self._c_fixed,
                                              self._p_ones if g is self.ones else _p(g), *self._c_tail, op, _stream(dev)),
                   "rrl_loss_step")
-        self._kept_key = key
-        self._chain_ready = self.prepared and bool(self._chain_left.value & 1)
-        self.fused = bool(self._chain_left.value & 2)  # THIS call's records + scans ran as one launch
-        self.st.counts_cleared = self._chain_ready
-        _IntersectionLoss.last_state = self.st
-        if self.ride is not None:
-            _keep_ride(self.st, self.ride)
-            self.chamfer_value = chamfer_from_state(self.st)
-        return self._out
+        return self._done(key)
 
 
 def registration_step_raw(src_tri, R, t, tar_tri, line, rng=(1, 1, 5, 5), transpose_r=True, order1=None, order2=None,
@@ -1430,7 +1366,7 @@ def set_deterministic(on):
 def set_reduce_mode(mode):
     """Which reduce kernel the forwards launch: "auto" (tiled where legal and worthwhile), "single", "tiled"
     (include/rrl.h rrl_set_reduce_mode).  Process-wide; same bits either way."""
-    check(_lib.load().rrl_set_reduce_mode({"auto": 0, "single": 1, "tiled": 2, "xchg": 3}[mode]), "rrl_set_reduce_mode")
+    check(_lib.load().rrl_set_reduce_mode(_REDUCE[mode]), "rrl_set_reduce_mode")
 
 
 def set_spin_limit(polls):
@@ -1590,7 +1526,6 @@ def adam_gated(param, grad, m, v, state, lr, gate=None, betas=(0.9, 0.999), eps=
 
 # ---------------------------------------------------------------------------------------
 CHAMFER_TREE = True   # False: the brute-force kernel (every pair evaluated); same keys, same value
-_chamfer_ws_bytes = {}
 
 
 class _Chamfer(torch.autograd.Function):
@@ -1607,9 +1542,7 @@ class _Chamfer(torch.autograd.Function):
         val = torch.empty(1, device=xs.device)
         if CHAMFER_TREE and 0 < B <= 32767 and 0 < max(N, M) <= 65536 and min(N, M) > 0:
             # sorted clouds + sphere tree + pruned walk (rrl_chamfer.hip): keys identical to brute force
-            nb = _chamfer_ws_bytes.get((B, N, M))
-            if nb is None:
-                nb = _chamfer_ws_bytes[(B, N, M)] = int(_lib.load().rrl_chamfer_workspace_bytes(B, N, M))
+            nb = _scratch_size("rrl_chamfer_workspace_bytes", B, N, M)
             ws = torch.empty(nb, dtype=torch.uint8, device=dev)
             if order_x is not None and order_y is not None:  # prepared clouds: no sort in this call
                 ox, oy = _check_order(order_x, B, N, dev, "order_x"), _check_order(order_y, B, M, dev, "order_y")
@@ -1657,21 +1590,26 @@ def chamfer_from_state(state=None, keys=False):
     ride = getattr(st, "cham_ride", None)
     if ride is not None:  # the walk rode in this evaluation's own scan launch (ChamferRide): nothing left to launch
         return (ride.val.reshape(()), ride.bx, ride.by) if keys else ride.val.reshape(())
+    _, bx, by, val = _chamfer_from_loss(st)
+    return (val.reshape(()), bx, by) if keys else val.reshape(())
+
+
+def _chamfer_from_loss(st):
+    """(ws, bx, by, val): rrl_chamfer_from_loss on the workspace of evaluation `st` (and of the state holding its
+    target), into fresh buffers."""
     B, N, M, L, _ = st.dims
     dev = st.ws.device
     tar = getattr(st, "target_state", None) or st
     if tuple(tar.dims[:4]) != (B, N, M, L) or tar.ws.device != dev:
         raise ValueError("the carried-over target state does not match")
-    nb = _chamfer_ws_bytes.get((B, N, M))
-    if nb is None:
-        nb = _chamfer_ws_bytes[(B, N, M)] = int(_lib.load().rrl_chamfer_workspace_bytes(B, N, M))
+    nb = _scratch_size("rrl_chamfer_workspace_bytes", B, N, M)
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
     bx = torch.empty(B, N, dtype=torch.int64, device=dev)
     by = torch.empty(B, M, dtype=torch.int64, device=dev)
     val = torch.empty(1, device=dev)
     _run(dev, "rrl_chamfer_from_loss", _p(st.ws), _p(tar.ws), st.nbytes, B, N, M, L, _p(ws), nb, _p(bx), _p(by),
          _p(val))
-    return (val.reshape(()), bx, by) if keys else val.reshape(())
+    return ws, bx, by, val
 
 
 def chamfer_group_means(state=None, groups=1):
@@ -1687,18 +1625,7 @@ def chamfer_group_means(state=None, groups=1):
         raise ValueError("groups must divide the evaluation's instances")
     dev = st.ws.device
     ride = getattr(st, "cham_ride", None)
-    if ride is not None:
-        ws = ride.ws
-    else:
-        tar = getattr(st, "target_state", None) or st
-        nb = _chamfer_ws_bytes.get((B, N, M))
-        if nb is None:
-            nb = _chamfer_ws_bytes[(B, N, M)] = int(_lib.load().rrl_chamfer_workspace_bytes(B, N, M))
-        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-        bx = torch.empty(B, N, dtype=torch.int64, device=dev)
-        by = torch.empty(B, M, dtype=torch.int64, device=dev)
-        val = torch.empty(1, device=dev)
-        _run(dev, "rrl_chamfer_from_loss", _p(st.ws), _p(tar.ws), st.nbytes, B, N, M, L, _p(ws), nb, _p(bx), _p(by), _p(val))
+    ws = ride.ws if ride is not None else _chamfer_from_loss(st)[0]
     out = torch.empty(groups, device=dev)
     _run(dev, "rrl_chamfer_group_means", _p(ws), ws.numel(), _p(out), int(groups), B, N, M)
     return out
