@@ -39,6 +39,7 @@ static_assert(SPW <= (1 << SG_BITS), "slot bits of the queue entries");
 //                          twelve cross-lane reads per pass cost more than the extra residency returns; the launch is
 //                          paced by each wavefront's own chain of dependent steps, not by the number of resident ones.
 constexpr int kSPW = SPW, kWPB = WPB, kLPW = LPW;  // (for the launcher: the macros are redefined per variant)
+static_assert(LPW <= (1 << (32 - CAND_POS_BITS)), "line-in-wave bits of the candidates (rrl_tree.h CAND_POS_BITS)");
 
 struct WaveCtx {
 #if CULL_REGLINES
@@ -94,13 +95,13 @@ __device__ __forceinline__ LineRow line_get(const WaveCtx &c, int ll) {
 }
 #endif
 
-// cand = line_in_wave << 16 | sorted triangle position: a triangle whose point 0 passed the conservative
+// cand = line_in_wave << CAND_POS_BITS | sorted triangle position: a triangle whose point 0 passed the conservative
 // prefilter of level D.  The reference's own arithmetic (dist_sq, bit-identical to the strict scan) decides
 // on all three points here.
 // SC1: the rows may have been written by another workgroup of THIS launch (write-through): loads that bypass the CU's L1.
 template <bool SC1 = false>
 __device__ __forceinline__ void resolve_candidate(const WaveCtx &c, unsigned cand, const LineRow &lrw) {
-    const int ll = cand >> 16, spos = cand & 0xffff;
+    const int ll = cand >> CAND_POS_BITS, spos = cand & CAND_POS_MASK;
     const float4 la = lrw.la;
     const float2 lb = lrw.lb;
     // original-order rows: one more dependent load for the row index (staging the slice's indices in LDS measured 0.8 us
@@ -203,11 +204,11 @@ __device__ __forceinline__ void flush_cands(WaveCtx &c) {
     for (int i0 = 0; i0 < nc; i0 += 64) {  // uniform trip count: every lane fetches (line_get), the live ones resolve
         const int i = i0 + c.lane;
         const unsigned cand = i < nc ? c.cands[i] : 0u;
-        const LineRow lrw = line_get(c, (int)(cand >> 16));
+        const LineRow lrw = line_get(c, (int)(cand >> CAND_POS_BITS));
         if (i < nc) resolve_candidate<SC1>(c, cand, lrw);
     }
 #else
-    for (int i = c.lane; i < nc; i += 64) { const unsigned cand = c.cands[i]; resolve_candidate<SC1>(c, cand, line_row(c.lr, (int)(cand >> 16))); }
+    for (int i = c.lane; i < nc; i += 64) { const unsigned cand = c.cands[i]; resolve_candidate<SC1>(c, cand, line_row(c.lr, (int)(cand >> CAND_POS_BITS))); }
 #endif
     c.ncand = 0;
 }
@@ -231,7 +232,7 @@ __device__ __forceinline__ void proc_c(WaveCtx &c, bool all) {
         if constexpr (COUNT) c.td += 8u * (unsigned)take;
         wave_lds_fence();
         uint32_t passbits = 0;
-        unsigned lh = 0;  // line << 16 | first sorted position of the half
+        unsigned lh = 0;  // line << CAND_POS_BITS | first sorted position of the half
 #if CULL_REGLINES
         const unsigned e = c.lane < take ? c.qc[base + c.lane] : 0u;
         const int ll = e >> HF_BITS, h = e & ((1 << HF_BITS) - 1);
@@ -255,7 +256,7 @@ __device__ __forceinline__ void proc_c(WaveCtx &c, bool all) {
                 const float ev = fmaf(-dot, dot, q);
                 passbits = __builtin_amdgcn_alignbit(passbits, __float_as_uint(ev), 31);  // passbits << 1 | sign(ev)
             }
-            lh = ((unsigned)ll << 16) | (unsigned)(c.pos0 + h * 8);
+            lh = ((unsigned)ll << CAND_POS_BITS) | (unsigned)(c.pos0 + h * 8);
         }
         while (__any(passbits != 0)) {
 #if CULL_REGLINES
@@ -272,7 +273,7 @@ __device__ __forceinline__ void proc_c(WaveCtx &c, bool all) {
                 c.cands[pos] = cand;
 #else
                 if (pos < WCCAP) c.cands[pos] = cand;
-                else resolve_candidate<SC1>(c, cand, line_row(c.lr, (int)(cand >> 16)));
+                else resolve_candidate<SC1>(c, cand, line_row(c.lr, (int)(cand >> CAND_POS_BITS)));
 #endif
             }
             c.ncand += __popcll(m);

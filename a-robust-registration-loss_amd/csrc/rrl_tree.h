@@ -8,7 +8,16 @@
 #define SGG 4            // groups per supergroup
 #define SGT (GRP * SGG)  // triangles per supergroup
 #define NODE 13          // float4 per supergroup in the sphere tree: [0] supergroup, [1..4] groups, [5..12] halves
-#define SORT_CAP 65536   // largest cloud of the sorted / culled layout (16-bit sorted positions in the scan)
+#define SORT_CAP (1 << 20)  // largest cloud of the sorted / culled layout (include/rrl.h rrl_sort_capacity)
+// The culled scan's point-0 candidates are 32-bit words  line_in_wave << CAND_POS_BITS | sorted position  (rrl_cull_scan.inc):
+// the top 8 bits hold one of the 128 lines of a wavefront, the low 24 a sorted position (24, not 25: a position below 2^24
+// keeps the row offset a v_mul_u32_u24, and the scan kernels compile to the same instructions as with the 16-bit field of
+// the 65536-triangle layout, only the shift and mask constants differ).  Nothing else in the sorted layout is narrower than
+// int32 positions: the queue entries of levels A and B are slice-local, and the sort chunks, the k-d order and the Chamfer
+// walk index with int / size_t.
+#define CAND_POS_BITS 24
+#define CAND_POS_MASK ((1u << CAND_POS_BITS) - 1u)
+static_assert(SORT_CAP <= (1 << CAND_POS_BITS), "sorted positions of the culled scan's candidates");
 
 // Position of the 16^3 grid cell (q0, q1, q2) along a 3-D Hilbert curve (12 bits).  Consecutive
 // cells of the curve are always face neighbours, so a group of 16 consecutive sorted triangles

@@ -33,7 +33,6 @@ int rrl_tri_prepare_clouds(const float *tri1, const float *tri2, void *ws, size_
                            int clouds, const RrlXform *xf, const float *line, const RrlCall &o, void *stream);  // rrl_scan.hip
 int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B, int N, int M, int L, int mode,
                              int chunk, int clouds, int lmax_ready, const RrlCall &o, void *stream);         // rrl_scan.hip
-int rrl_sort_capacity(void);                                                                                 // rrl_cull.hip
 
 // ---- layout of the wide workspace (include/rrl.h RRL_WW_*); every field on a 256-byte boundary, STATUS and NSEL first
 //      (one fill clears both)

@@ -164,7 +164,7 @@ struct RrlCall {
 RrlCall rrl_resolve_opts(const rrl_opts *o);  // rrl_sparse.hip
 // the plan of one call (o.plan; also settles o.problems, the orders, o.tar_ws, o.xf); RRL_E_ARG: an illegal multi-pose call
 int rrl_plan(RrlCall &o, int B, int N, int M, int L, int pool, int mode, const void *target_ws, const RrlXform *xf, int want);
-int rrl_sort_capacity(void);  // rrl_cull.hip: the sorted layout (records kernel, sphere tree, culled scan) serves up to it
+// include/rrl.h rrl_sort_capacity (rrl_cull.hip): the sorted layout (records kernel, sphere tree, culled scan) serves up to it
 inline bool rrl_sorted_layout(int N, int M) { return (N > M ? N : M) <= rrl_sort_capacity(); }
 // the sampler's two passes on their own (rrl_geom.hip; rrl_sample_lines_rng = both): rrl_demo_epoch pipelines them
 int rrl_sample_count_pass(const uint64_t *rng_state, const float *r, const float *centers, const float *aabb1, const float *aabb2,

@@ -82,7 +82,7 @@ _SIGS = {
     "rrl_sample_lines_rng": [_P] * 8 + [_I] * 3 + [_P],
 }
 EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamfer_workspace_bytes",
-                                 "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes"])
+                                 "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes", "rrl_sort_capacity"])
 
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
 F_CHAIN = 2        # RRL_F_CHAIN: leave the hit counts / CHAIN words cleared for the next step on this workspace
@@ -152,6 +152,8 @@ def load():
     lib.rrl_chamfer_workspace_bytes.restype = _Z
     lib.rrl_cloud_order_workspace_bytes.argtypes = [_I, _I]
     lib.rrl_cloud_order_workspace_bytes.restype = _Z
+    lib.rrl_sort_capacity.argtypes = []
+    lib.rrl_sort_capacity.restype = _I
     _lib = lib
     return lib
 

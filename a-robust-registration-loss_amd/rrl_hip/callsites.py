@@ -42,7 +42,6 @@ CHAMFER_FROM_LOSS = "auto"  # the Chamfer monitor walks the clouds the loss eval
 #   that contract holds for the batch -- taken from the dataset's per-item flag `p0_rows` (pre_dataloader sets it when it
 #   builds an item: checked once per dataset item on the host), else checked once per data dict on the device and
 #   remembered in it.  True: always (the caller vouches), False: never.
-_SORT_CAP = 65536  # the loss sorts clouds up to this size (larger ones: dense scan, no sorted records to walk)
 
 
 def _first_points_contract(data, channel_first=False):
@@ -102,7 +101,7 @@ def _monitor(moved, tar, data=None, channel_first=False):
     """The trainers' Chamfer monitor next to a loss evaluation: from the evaluation's own sorted clouds when that is
     the same quantity (CHAMFER_FROM_LOSS), else the standalone kernel on (moved, tar)."""
     st = _ops.last_state()
-    if CHAMFER_FROM_LOSS and st is not None and max(st.dims[1], st.dims[2]) <= _SORT_CAP and \
+    if CHAMFER_FROM_LOSS and st is not None and max(st.dims[1], st.dims[2]) <= _ops.sort_capacity() and \
             st.dims[1] == moved.shape[1] and st.dims[2] == tar.shape[1]:
         if CHAMFER_FROM_LOSS is True or (data is not None and _first_points_contract(data, channel_first)):
             return _ops.chamfer_from_state(st)
@@ -155,7 +154,7 @@ def per_sample_loss(src_nb, R, t, tar_tri, lines, mode=None, target_from=None, d
     B = src_nb.shape[0]
     src_tri, tar_tri = src_nb.reshape(B, -1, 9), tar_tri.reshape(B, -1, 9)
     o1, o2 = _orders(data, src_tri.shape[1], tar_tri.shape[1], B, src_tri.device if src_tri.is_cuda else None)
-    ride = bool(chamfer) and max(src_tri.shape[1], tar_tri.shape[1]) <= _SORT_CAP
+    ride = bool(chamfer) and max(src_tri.shape[1], tar_tri.shape[1]) <= _ops.sort_capacity()
     loss, info, _ = _ops.registration_loss(src_tri, R, t, tar_tri, lines, RNG, transpose_r=True, mode=_mode(mode),
                                            target_from=target_from, order1=o1, order2=o2, chamfer=ride)
     return loss, info[:, 0] > 0
@@ -221,7 +220,7 @@ def multi_pose_loss(src_nb, transforms, tar_tri, lines, mode=None, data=None, ch
     k = len(transforms)
     B = src_nb.shape[0]
     src_tri, tar_tri = src_nb.reshape(B, -1, 9), tar_tri.reshape(B, -1, 9)
-    if not MULTI_POSE or k < 1 or _mode(mode) != "cull" or max(src_tri.shape[1], tar_tri.shape[1]) > _SORT_CAP:
+    if not MULTI_POSE or k < 1 or _mode(mode) != "cull" or max(src_tri.shape[1], tar_tri.shape[1]) > _ops.sort_capacity():
         return None
     #  the packed node differentiates with respect to the TRANSFORMS only: a source (or target) that requires grad
     # takes the per-pose loop, whose registration_loss produces dL/dsrc (or raises for the target) -- never a silent None
@@ -262,7 +261,7 @@ def rpm_intersection_loss(pred_transforms, data, n_lines=10000, lines=None, mode
             loss, ok = got
             st = _ops.last_state()
             disc = [0.5 ** (num_iter - ni - 1) for ni in range(num_iter)]
-            own = CHAMFER_FROM_LOSS and max(st.dims[1], st.dims[2]) <= _SORT_CAP and st.dims[1] == src.shape[1] and \
+            own = CHAMFER_FROM_LOSS and max(st.dims[1], st.dims[2]) <= _ops.sort_capacity() and st.dims[1] == src.shape[1] and \
                 st.dims[2] == tar.shape[1] and (CHAMFER_FROM_LOSS is True or _first_points_contract(data))
             if own:  # the monitor of every iteration from the evaluation's own clouds (the walk rode in its scan launch)
                 cham = (_ops.chamfer_group_means(st, num_iter) * _instance_weights(disc, 1, loss.device)).sum()
@@ -343,7 +342,7 @@ def fmr_intersection_loss(g_series, data, n_lines=15000, lines=None, last=3, mod
             loss, ok = got
             st = _ops.last_state()
             w = _instance_weights([0.5 ** (maxiter - i - 1) / 5.0 / B for i in idx], B, loss.device)
-            own = CHAMFER_FROM_LOSS and max(st.dims[1], st.dims[2]) <= _SORT_CAP and st.dims[1] == moved.shape[1] and \
+            own = CHAMFER_FROM_LOSS and max(st.dims[1], st.dims[2]) <= _ops.sort_capacity() and st.dims[1] == moved.shape[1] and \
                 st.dims[2] == tar.shape[1] and (CHAMFER_FROM_LOSS is True or _first_points_contract(data))
             cham = _ops.chamfer_group_means(st, len(idx))[-1] if own else _ops.chamfer(tar, moved)  # the LAST estimate's monitor
             return (loss * w).sum().reshape(1), cham, lines, ok

@@ -380,6 +380,17 @@ def _scratch_size(entry, *dims):
     return nb
 
 
+_sort_cap = []
+
+
+def sort_capacity():
+    """Largest cloud (triangles of either cloud) of the sorted layout -- culled scan, prepared orders, multi-pose steps, the
+    Chamfer tree and its rider: include/rrl.h rrl_sort_capacity(), read once.  Larger clouds take the dense scan."""
+    if not _sort_cap:
+        _sort_cap.append(int(_lib.load().rrl_sort_capacity()))
+    return _sort_cap[0]
+
+
 def cloud_order(tri):
     """Spatial order of the clouds tri (B, n, 9) -- pseudo-triangles; only the first point of a row places it -- or of
     point clouds (B, n, 3) (the Chamfer monitor's inputs: ops.chamfer(x, y, order_x=, order_y=)), computed
@@ -392,8 +403,8 @@ def cloud_order(tri):
         raise ValueError("cloud_order takes pseudo-triangles (B, n, 9) or points (B, n, 3)")
     t = _prep(tri, "tri", None, dev)
     B, n, _ = t.shape
-    if n > 65536:
-        raise ValueError("clouds beyond 65536 triangles are not sorted (the dense scan serves them)")
+    if n > sort_capacity():
+        raise ValueError(f"clouds beyond {sort_capacity()} triangles are not sorted (the dense scan serves them)")
     order = torch.zeros(B, (n + 63) // 64 * 64, dtype=torch.int32, device=dev)
     if B == 0 or n == 0:
         return order
@@ -1059,8 +1070,9 @@ class _Step:
         if Bt == 0 or L <= 0:
             raise ValueError(f"{what} needs a non-empty batch and line set")
         self.poses, self.Bt = int(poses), Bt
-        if self.poses < 1 or (self.poses > 1 and (mode != "cull" or max(N, M) > 65536)):
-            raise ValueError("poses must be >= 1; a multi-pose step runs scan mode cull on clouds <= 65536 triangles")
+        if self.poses < 1 or (self.poses > 1 and (mode != "cull" or max(N, M) > sort_capacity())):
+            raise ValueError(f"poses must be >= 1; a multi-pose step runs scan mode cull on clouds <= {sort_capacity()} "
+                             "triangles")
         B = Bt * self.poses  # instances of one call
         self.dims = (B, N, M, L)
         self.rng = _check_range(rng, what)
@@ -1073,7 +1085,7 @@ class _Step:
         self.ones = torch.ones(B, dtype=torch.float32, device=dev)
         if prepared is None:  # default: on (RRL_PREPARED=0 turns the default off: A/B runs of unmodified callers)
             prepared = os.environ.get("RRL_PREPARED", "1") != "0"
-        self.prepared = bool(prepared) and mode == "cull" and max(N, M) <= 65536
+        self.prepared = bool(prepared) and mode == "cull" and max(N, M) <= sort_capacity()
         self._kept_key = None  # _write_key of the target whose records the workspace holds
         self.keep_target = True  # False: rebuild the target's records in every call (see invalidate_target)
         # CHAINED steps (round 6; include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED): a prepared step asks the library to leave the
@@ -1177,7 +1189,7 @@ class RegistrationStep(_Step):
         poses = k > 1 (round 5): a MULTI-POSE step (rrl_opts.problems) -- every call takes R (k * B, 3, 3), t (k * B, 3): k
         poses of each of the B problems (instance i * B + b = pose i of problem b; RPM's num_iter, FMR's last estimates),
         evaluated in ONE set of launches with the target scanned once per problem; loss (k * B,), gR (k * B, 3, 3),
-        gt (k * B, 3), bit-identical per instance to k single-pose steps.  Scan mode cull, clouds <= 65536 triangles.
+        gt (k * B, 3), bit-identical per instance to k single-pose steps.  Scan mode cull, clouds <= sort_capacity() triangles.
         chain: OFF by default here (see _Step): a chained step clears its hit counts on exit, and this step's state is
         what callers hand on as target_from= (RPM / FMR)."""
         super().__init__("RegistrationStep", src_tri, tar_tri, n_lines, rng, transpose_r, mode, chunk, prepared, src_order,
@@ -1540,7 +1552,7 @@ class _Chamfer(torch.autograd.Function):
         bx = torch.empty(B, N, dtype=torch.int64, device=xs.device)
         by = torch.empty(B, M, dtype=torch.int64, device=xs.device)
         val = torch.empty(1, device=xs.device)
-        if CHAMFER_TREE and 0 < B <= 32767 and 0 < max(N, M) <= 65536 and min(N, M) > 0:
+        if CHAMFER_TREE and 0 < B <= 32767 and 0 < max(N, M) <= sort_capacity() and min(N, M) > 0:
             # sorted clouds + sphere tree + pruned walk (rrl_chamfer.hip): keys identical to brute force
             nb = _scratch_size("rrl_chamfer_workspace_bytes", B, N, M)
             ws = torch.empty(nb, dtype=torch.uint8, device=dev)

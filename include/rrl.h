@@ -69,7 +69,7 @@ extern "C" {
                              radius) the walk is widened by every triangle's NaN reach (DEL1 / DEL2), so
                              that each triangle one of whose three points could see a negative sqrt
                              argument is evaluated exactly (csrc/rrl_cull.hip, "NaN").
-                             Needs N, M <= 65536, else behaves like AUTO. */
+                             Needs N, M <= rrl_sort_capacity() (2^20), else behaves like AUTO. */
 
 /* workspace fields (indices into rrl_workspace_layout's offset array) */
 enum {
@@ -184,6 +184,11 @@ enum {
 };
 
 const char *rrl_version(void);
+/* Largest cloud (triangles of either cloud) that the SORTED layout serves: the per-step cell sort and sphere tree, the
+ * culled scan (RRL_SCAN_CULL), prepared orders (rrl_cloud_order, rrl_opts.order1 / order2), multi-pose evaluation
+ * (rrl_opts.problems), the Chamfer tree (rrl_chamfer_tree_fwd, rrl_chamfer_from_loss) and its rider.  2^20 = 1048576.
+ * Larger clouds take the dense scan: scan mode cull behaves like AUTO there. */
+int rrl_sort_capacity(void);
 
 /* ---- per-call options ------------------------------------------------------------------------
  * Every entry point that has an `_ex` twin takes `const rrl_opts *opts` in front of the stream; NULL (and the
@@ -271,7 +276,8 @@ typedef struct rrl_opts {
      * R [B][3][3], t [B][3]: instance s = pose (s / Bt) of problem (s % Bt).  Every output (loss [B], gR [B][9], gt [B][3],
      * grad_tri1 [B][N][9], the workspace of B instances) is per instance and bit-identical to evaluating the B / Bt poses one
      * after the other; the target's scan runs ONCE per problem (instances < Bt), the sources' scans side by side in the same
-     * launch.  Scan mode cull, clouds within the sort capacity, no target_ws, pool = 0; RRL_E_ARG otherwise. */
+     * launch.  Scan mode cull, clouds within the sort capacity (rrl_sort_capacity), no target_ws, pool = 0; RRL_E_ARG
+     * otherwise. */
     int32_t problems;
     int32_t *chain_left;     /* NULL, or a HOST int32 that receives the two bits above at issue time (RRL_F_CHAIN) */
 } rrl_opts;
@@ -381,7 +387,7 @@ int rrl_registration_step(const float *src, const float *R, const float *t, cons
  * power-of-two windows, every window sorted along the longest axis of its records' bounding box, down to halves of
  * 8 -- so the scan's tree nodes (aligned runs of 64 / 16 / 8 positions) are compact k-d cells of the WHOLE cloud
  * (the per-step sort orders clouds beyond 4096 triangles in four or more interleaved chunks).  Only the first point
- * of a row places it.  ws: scratch of rrl_cloud_order_workspace_bytes(B, n) bytes.  n <= 65536. */
+ * of a row places it.  ws: scratch of rrl_cloud_order_workspace_bytes(B, n) bytes.  n <= rrl_sort_capacity(). */
 size_t rrl_cloud_order_workspace_bytes(int B, int n);
 int rrl_cloud_order(const float *tri, int32_t *order, void *ws, size_t ws_bytes, int B, int n, void *stream);
 /* the same for point clouds pts [B][n][3] (the Chamfer monitor's inputs: rrl_chamfer_tree_fwd_ex); a cloud of
@@ -650,7 +656,7 @@ int rrl_chamfer_fwd(const float *x, const float *y, uint64_t *best_x, uint64_t *
 /* The same result (keys bit-identical, value from a fixed-order sum) through the scan's spatial
  * structures: both clouds in grid-cell (Hilbert) order under the sphere tree, nearest neighbours by a
  * pruned tree walk, the mean folded into the same launch (2 launches for N, M <= 4096).  ws: scratch of
- * rrl_chamfer_workspace_bytes(B, N, M) bytes.  N, M in [1, 65536].  best_x / best_y need no
+ * rrl_chamfer_workspace_bytes(B, N, M) bytes.  N, M in [1, rrl_sort_capacity()].  best_x / best_y need no
  * initialisation.  A NaN coordinate in a target cloud makes every minimum of that sample NaN and a
  * NaN query its own minimum, as torch.min does. */
 size_t rrl_chamfer_workspace_bytes(int B, int N, int M);
@@ -665,7 +671,7 @@ int rrl_chamfer_tree_fwd(const float *x, const float *y, void *ws, size_t ws_byt
  * point sets ARE the triangles' first points: keys and value equal rrl_chamfer_fwd on (P0 of cloud 1,
  * P0 of cloud 2).  ws_src: the evaluation's workspace; ws_tar: the workspace holding cloud 2's records
  * (the same one, or the target_ws the evaluation was carried over from); both of layout (B, N, M, L).
- * ws: scratch of rrl_chamfer_workspace_bytes(B, N, M).  N, M <= 65536 (larger clouds are not sorted).
+ * ws: scratch of rrl_chamfer_workspace_bytes(B, N, M).  N, M <= rrl_sort_capacity() (larger clouds are not sorted).
  * ONE launch (round 3: the mean is finished by the last workgroups to arrive; their counters are words of ws_src's MCTL
  * field, which is why ws_src is not const).  A non-finite (or overflowing) coordinate anywhere in a cloud gives NaN minima. */
 int rrl_chamfer_from_loss(void *ws_src, const void *ws_tar, size_t loss_ws_bytes, int B, int N, int M,
