@@ -65,6 +65,13 @@ static inline int rrl_copy(void *d, const void *src, size_t nbytes, hipStream_t 
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// Ragged batches (include/rrl.h rrl_opts.count1 / count2 / nlines): the rows sample b really has -- its entry of the call's
+// count array, clamped to the capacity (memory safety only), or the capacity itself when the call has no counts.  b is
+// workgroup-uniform wherever this is used, so the load is a scalar one; the capacity stays the stride of every array.
+__device__ __forceinline__ int rrl_rows(const int32_t *__restrict__ cnt, int b, int cap) {
+    return cnt ? min(max(cnt[b], 0), cap) : cap;
+}
+
 // (dAC - proj) + eps of code/loss.py:84-88 for scalar (T = float) or two lines at
 // once (T = v2f -> v_pk_mul_f32 / v_pk_add_f32, each half rounded like the scalar op).
 template <typename T>

@@ -144,6 +144,8 @@ struct BuildArgs {
                                    // the culled scan's workgroups of that pair run (its grid has the pair on the fast index)
     int Bt;                        // multi-pose evaluation (rrl_opts.problems): the INPUT clouds, orders and lines have Bt
                                    // entries and instance b uses entry b % Bt; 0 / B: every instance has its own
+    const int32_t *cnt1, *cnt2;    // ragged batches (rrl_opts.count1 / count2 / nlines): rows per sample, or NULL = N / M / L;
+    const int32_t *nlines;         //   N, M, L stay the strides.  Rows beyond a count are not read
 };
 // the input entry of instance b (multi-pose: rrl_opts.problems)
 __device__ __forceinline__ int input_of(int b, int Bt) { return (Bt > 0 && b >= Bt) ? b % Bt : b; }
@@ -176,13 +178,14 @@ __device__ __forceinline__ bool line_cullable(float s, float o2) { return s <= 1
 // Chunks ch0, ch0 + stride, ... (< LMAX_CHUNKS) of sample b's lines by one 256-lane workgroup: lmax[b][ch] =
 // (max |dir|^2, max |x0|^2) over the chunk's cullable lines (0, 0 for none).  The culled scan derives its slacks
 // from the maxima over the 64 chunks, identically in every wavefront -- no exchange inside that kernel.
+// nl <= L: the lines the sample really has (a ragged batch; rows [nl, L) are not read) -- L stays the stride.
 __device__ __forceinline__ void line_max_chunks(const float *__restrict__ line, int L, float2 *__restrict__ lmax, int b,
-                                                int ch0, int stride, float (*red2)[2], int bl /* the lines' entry */) {
+                                                int ch0, int stride, float (*red2)[2], int bl /* the lines' entry */, int nl) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int CL = (L + LMAX_CHUNKS - 1) / LMAX_CHUNKS;
+    const int CL = (nl + LMAX_CHUNKS - 1) / LMAX_CHUNKS;
     for (int ch = ch0; ch < LMAX_CHUNKS; ch += stride) {  // uniform
         float sm = 0.0f, om = 0.0f;
-        const int lend = min(L, (ch + 1) * CL);
+        const int lend = min(nl, (ch + 1) * CL);
         for (int l = ch * CL + tid; l < lend; l += REC_BLK) {
             const float2 *p = (const float2 *)(line + ((size_t)bl * L + l) * 6);  // 24-byte rows: 8-byte aligned
             const float2 q0 = p[0], q1 = p[1], q2 = p[2];                       // dir.xy | dir.z x0.x | x0.yz
@@ -204,15 +207,18 @@ __device__ __forceinline__ void line_max_chunks(const float *__restrict__ line, 
 }
 
 // the same pass on its own, for callers that prepared the triangles without the lines (rrl_tri_prepare + rrl_line_tri_scan)
-__global__ __launch_bounds__(REC_BLK) void line_max_kernel(const float *__restrict__ line, int L, float2 *__restrict__ lmax, int Bt) {
+__global__ __launch_bounds__(REC_BLK) void line_max_kernel(const float *__restrict__ line, int L, float2 *__restrict__ lmax, int Bt,
+                                                           const int32_t *__restrict__ nlines) {
     __shared__ float red2[REC_BLK / 64][2];
-    line_max_chunks(line, L, lmax, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, red2, input_of((int)blockIdx.y, Bt));
+    const int bl = input_of((int)blockIdx.y, Bt);
+    line_max_chunks(line, L, lmax, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, red2, bl, rrl_rows(nlines, bl, L));
 }
 
 // One triangle of the build step (both records kernels): the raw row, moved by the sample's rigid transform when it
 // belongs to the source of the fused op (-> TRI1), its thresholds (code/loss.py:94-110), NaN reach (DEL) and 48-byte
 // prepared record (PTRI, original order).  c: the (moved) coordinates, x: thr2, p2: max |P|^2 of its three points
 // (+inf for non-finite coordinates).
+// n: the cloud's CAPACITY (the stride of every per-triangle array; a ragged batch has fewer rows, the caller bounds f).
 // prow: the row of PTRI the record goes to -- f (original order: the cold build) or the triangle's SORTED position (prepared
 // build: the culled scan then resolves a candidate from its position alone, without the IDX hop; the record carries f).
 // PUB (the chained step's build + scan launch): the record and its NaN reach are read by other workgroups of the SAME launch
@@ -328,18 +334,21 @@ __global__ __launch_bounds__(REC_BLK) void tri_records_kernel(const BuildArgs a)
     const RecPlace pl = rec_place(a, a.clouds, (int)blockIdx.x);  // (uniform)
     const int cloud = pl.cloud, b = pl.b, bxr = pl.bxr;
     build_clear_state(a);  // per-call state and gradient accumulator
-    const int n = cloud ? a.M : a.N;
+    const int ncap = cloud ? a.M : a.N;                          // capacity = stride
+    const int n = rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);    // rows of this sample (uniform)
     if (pl.lch >= 0) {  // uniform: the launch's LMAX_CHUNKS extra workgroups per sample reduce its lines
-        if (a.lmax != nullptr)  // (one chunk each: they run beside the triangle workgroups)
-            line_max_chunks(a.line, a.L, a.lmax, b, pl.lch, LMAX_CHUNKS, red2, input_of(b, a.Bt));
+        if (a.lmax != nullptr) {  // (one chunk each: they run beside the triangle workgroups)
+            const int bl = input_of(b, a.Bt);
+            line_max_chunks(a.line, a.L, a.lmax, b, pl.lch, LMAX_CHUNKS, red2, bl, rrl_rows(a.nlines, bl, a.L));
+        }
         return;
     }
     const int f = bxr * REC_BLK + tid;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY}, p2 = 0.0f;
     if (f < n) {
         float c[9], x;
-        tri_record_row(a, cloud, b, n, f, f, c, x, p2);
-        const int ngp = (n + GRP - 1) / GRP * GRP;
+        tri_record_row(a, cloud, b, ncap, f, f, c, x, p2);
+        const int ngp = (ncap + GRP - 1) / GRP * GRP;
         ((cloud ? a.crec2 : a.crec1) + (size_t)b * ngp)[f] = make_float4(c[0], c[1], c[2], x);
 #pragma unroll
         for (int d = 0; d < 3; ++d) { mn[d] = c[d]; mx[d] = c[d]; }
@@ -414,9 +423,10 @@ __device__ __forceinline__ void records_sorted_body(const BuildArgs &a, const in
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int B = a.B;
     const int cloud = pl.cloud, b = pl.b, bxr = pl.bxr;
-    const int n = cloud ? a.M : a.N;
-    const int npad = (n + SGT - 1) / SGT * SGT;
-    if (bxr * (int)blockDim.x >= npad) return;  // uniform: the smaller cloud has fewer workgroups
+    const int ncap = cloud ? a.M : a.N;                          // capacity: the stride of the cloud's arrays
+    const int n = rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);    // rows of this sample (uniform; a ragged batch: <= ncap)
+    const int npad = (ncap + SGT - 1) / SGT * SGT, nown = (n + SGT - 1) / SGT * SGT;  // stride | the sample's own supergroups
+    if (bxr * (int)blockDim.x >= nown) return;  // uniform: the smaller cloud (or sample) has fewer workgroups
     const int s = bxr * (int)blockDim.x + tid;
     const bool valid = s < n;  // real records occupy the sorted positions [0, n)
     float c[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, x = 0.0f, p2 = 0.0f;
@@ -424,10 +434,10 @@ __device__ __forceinline__ void records_sorted_body(const BuildArgs &a, const in
     if (valid) {
         f = (cloud ? order2 : order1)[(size_t)input_of(b, a.Bt) * npad + s];
         f = min(max(f, 0), n - 1);  // memory safety only: the order must be a permutation of [0, n)
-        tri_record_row<PUB>(a, cloud, b, n, f, s, c, x, p2);
+        tri_record_row<PUB>(a, cloud, b, ncap, f, s, c, x, p2);
     }
     if (threadIdx.x < 64 && __float_as_int(c[0] + c[4] + c[8] + x) != 0x12345678) STAMPR(2);
-    if (s - lane < npad) {  // wave-uniform: this wavefront holds a supergroup
+    if (s - lane < nown) {  // wave-uniform: this wavefront holds a supergroup
         const float4 rec = valid ? make_float4(c[0], c[1], c[2], x) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if constexpr (!PUB) (cloud ? a.idx2 : a.idx1)[(size_t)b * npad + s] = f;
         if (late) {
@@ -461,7 +471,7 @@ __device__ __forceinline__ void records_sorted_body(const BuildArgs &a, const in
     if (threadIdx.x < 64) STAMPR(4);
     const int q = tid & (REC_BLK - 1), w0 = (tid / REC_BLK) * (REC_BLK / 64);  // slot of the row; first wavefront of its 256 lanes
     const int row = s / REC_BLK;
-    if (q < 8 && row * REC_BLK < npad) {
+    if (q < 8 && row * REC_BLK < nown) {
         float r = 1.0f;  // slot 7: PTRI layout of this cloud = sorted positions
         if (q < 7) {
             r = red[w0][q];
@@ -482,7 +492,8 @@ __global__ __launch_bounds__(REC_BLK) void tri_records_sorted_kernel(const Build
     if (threadIdx.x < 64) STAMPR(1);
     if (pl.lch >= 0) {  // uniform: the line maxima, beside the triangle workgroups (tri_records_kernel)
         if (a.lmax != nullptr)
-            line_max_chunks(a.line, a.L, a.lmax, pl.b, pl.lch, LMAX_CHUNKS, red2, input_of(pl.b, a.Bt));
+            line_max_chunks(a.line, a.L, a.lmax, pl.b, pl.lch, LMAX_CHUNKS, red2, input_of(pl.b, a.Bt),
+                            rrl_rows(a.nlines, input_of(pl.b, a.Bt), a.L));
         if (threadIdx.x < 64) STAMPR(5);
         return;
     }
@@ -492,9 +503,10 @@ __global__ __launch_bounds__(REC_BLK) void tri_records_sorted_kernel(const Build
 // PMAX from the partial rows, for callers of the prepared build that do not run the culled scan next (rrl_tri_prepare_ex
 // on its own; the scan does this reduction in its prologue): one wavefront per (cloud, sample).
 __global__ __launch_bounds__(64) void pmax_from_partials_kernel(const float *__restrict__ apart, uint32_t *__restrict__ pmax,
-                                                                int B, int N, int M, int nblk) {
+                                                                int B, int N, int M, int nblk, const int32_t *__restrict__ cnt1,
+                                                                const int32_t *__restrict__ cnt2) {
     const int cb = blockIdx.x, cloud = cb >= B ? 1 : 0;
-    const int nb = ((cloud ? M : N) + REC_BLK - 1) / REC_BLK;
+    const int nb = (rrl_rows(cloud ? cnt2 : cnt1, cb - cloud * B, cloud ? M : N) + REC_BLK - 1) / REC_BLK;  // the sample's own rows
     float v = 0.0f;
     for (int j = threadIdx.x; j < nb; j += 64) v = fmaxf(v, apart[((size_t)cb * nblk + j) * 8 + 6]);
     v = wave_max(v);
@@ -533,11 +545,12 @@ __global__ __launch_bounds__(1024) void tri_sort_kernel(const BuildArgs a) {
     const int part = (int)blockIdx.y, nparts = (int)gridDim.y;
     const int chunk = (int)blockIdx.x % nch, cb = (int)blockIdx.x / nch;
     const int cloud = cb >= B ? 1 : 0, b = cb - cloud * B;
-    const int nfull = cloud ? a.M : a.N;                 // records of the whole cloud
+    const int ncap = cloud ? a.M : a.N;                  // capacity of the cloud: the stride of its arrays
+    const int nfull = RAW ? ncap : rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);  // records of the whole cloud (a ragged batch: this sample's)
     const int base0 = chunk * (1024 * NPT);              // first record of the chunk (multiple of 64)
-    if (base0 >= nfull) return;                          // uniform: the smaller cloud has fewer chunks
+    if (base0 >= nfull) return;                          // uniform: the smaller cloud (or sample) has fewer chunks
     const int n = min(1024 * NPT, nfull - base0);        // records of this chunk
-    const int ngf = (nfull + GRP - 1) / GRP, nsgf = (nfull + SGT - 1) / SGT;
+    const int ngf = (ncap + GRP - 1) / GRP, nsgf = (ncap + SGT - 1) / SGT;
     const int nsg = (n + SGT - 1) / SGT;
     const float4 *crec = (cloud ? a.crec2 : a.crec1) + (size_t)b * ngf * GRP + base0;
     float4 *p0s = (cloud ? a.p0s2 : a.p0s1) + (size_t)b * nsgf * SGT + base0;
@@ -978,6 +991,9 @@ static CullGeom cull_geometry(int B, int N, int M, int L, int clouds, const RrlC
 int rrl_cull_scan_can_fuse(int B, int N, int M, int L, const RrlCall &o) {
     if (B <= 0 || N <= 0 || M <= 0 || L <= 0 || (N > M ? N : M) > SORT_CAP) return 0;
     if (o.rider || o.counters || o.problems || o.tar_ws) return 0;
+    // a ragged batch (rrl_opts.count1 / count2 / nlines): the ready count a source workgroup waits for is derived from the
+    // capacity, and a records piece / source workgroup beyond its sample's rows leaves early -- the plain build serves (same bits)
+    if (o.ragged()) return 0;
     if (const char *e = getenv("RRL_CHAIN")) if (e[0] == '0') return 0;  // (A/B runs)
     const CullGeom g = cull_geometry(B, N, M, L, 2, o);
     if (g.waves != scan8::kWPB) return 0;
@@ -1005,7 +1021,7 @@ int rrl_launch_cull_scan(const float *line, void *ws, const WsLayout &w, int B, 
     if (o.plan.fused_build && (clouds != 2 || g.waves != scan8::kWPB)) return RRL_E_ARG;  // (rrl_cull_scan_can_fuse said otherwise)
     if (!lmax_ready && !o.plan.fused_build)  // the triangles were prepared without the lines: their partial maxima first (a tiny launch)
         hipLaunchKernelGGL(line_max_kernel, dim3(LMAX_CHUNKS, (unsigned)B), dim3(REC_BLK), 0, s, line, L,
-                           (float2 *)w.f32(ws, RRL_WS_LMAX), o.problems);
+                           (float2 *)w.f32(ws, RRL_WS_LMAX), o.problems, o.nlines);
     // (A PERSISTENT variant -- as many workgroups as fit on the chip, each keeping one line tile staged and pulling
     // (cloud, slice) items from per-tile work queues, the next slice's records prefetched during the walk -- was built
     // and measured in round 3: exact, but 40.7 us against 30.4 at C2 and 29.0 against 13.8 at the demo's shape.  A slot
@@ -1106,6 +1122,7 @@ static BuildArgs make_build_args(const float *tri1, const float *tri2, void *ws,
     a.B = B; a.N = N; a.M = M; a.clouds = clouds;
     a.transpose_r = xf ? xf->transpose_r : 0;
     a.Bt = o.problems;
+    a.cnt1 = o.count1; a.cnt2 = o.count2; a.nlines = o.nlines;
     a.xcd_align = 0;
     const int nall = N > M ? N : M;  // APART is laid out for the larger cloud
     a.nblk = (nall + REC_BLK - 1) / REC_BLK;
@@ -1138,7 +1155,8 @@ int rrl_launch_tri_build(const float *tri1, const float *tri2, void *ws, const W
     // ~27 triangles per cell at N = 16384, in arbitrary order, so its groups are no tighter).
     // RRL_SORT_WIDE=1 keeps the wide sort (experiments / tests; it still serves the Chamfer path).
     const char *wide_env = getenv("RRL_SORT_WIDE");
-    const bool chunked = nmax > 4096 && !(wide_env && atoi(wide_env) != 0);
+    // (a ragged batch always takes the chunked sort: the wide kernels know one size per call)
+    const bool chunked = nmax > 4096 && (o.ragged() || !(wide_env && atoi(wide_env) != 0));
     const size_t ngps = nmax <= 4096 ? ngpmax : (size_t)(4096 / GRP);
     const int parts = sort_parts((int)(ngps / SGG), o.sort_parts);
     const size_t lds = nmax <= 4096 || chunked ? sort_lds_bytes((int)(ngps / SGG), parts, 0) : 16;
@@ -1168,10 +1186,10 @@ int rrl_launch_tri_build(const float *tri1, const float *tri2, void *ws, const W
 }
 
 // PMAX of a prepared build for consumers other than the culled scan (include/rrl.h rrl_tri_prepare_ex)
-int rrl_launch_pmax_from_partials(void *ws, const WsLayout &w, int B, int N, int M, int clouds, hipStream_t s) {
+int rrl_launch_pmax_from_partials(void *ws, const WsLayout &w, int B, int N, int M, int clouds, const RrlCall &o, hipStream_t s) {
     const int nall = N > M ? N : M;
     hipLaunchKernelGGL(pmax_from_partials_kernel, dim3((unsigned)(clouds * B)), dim3(64), 0, s, w.f32(ws, RRL_WS_APART),
-                       (uint32_t *)w.i32(ws, RRL_WS_PMAX), B, N, M, (nall + REC_BLK - 1) / REC_BLK);
+                       (uint32_t *)w.i32(ws, RRL_WS_PMAX), B, N, M, (nall + REC_BLK - 1) / REC_BLK, o.count1, o.count2);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -488,7 +488,9 @@ __device__ __forceinline__ void cull_scan_body(
     const float *__restrict__ del1, const float *__restrict__ del2, const float2 *__restrict__ lmax,
     const float *__restrict__ apart, const float *__restrict__ aflag, int nblk_apart, int B,
     int N, int M, int L, int spw, unsigned long long *__restrict__ counters, long long counter_rows,
-    const int bx, const int by, const int bz, const int gx, const int gy, const int Bt, Wait wait_ready = Wait()) {
+    const int bx, const int by, const int bz, const int gx, const int gy, const int Bt,
+    const int32_t *__restrict__ cnt1, const int32_t *__restrict__ cnt2, const int32_t *__restrict__ nlines,
+    Wait wait_ready = Wait()) {
 #if !CULL_REGLINES
     float2 (&line_lds)[WPB][LPW * 3] = lds_.line_lds;
 #endif
@@ -513,16 +515,22 @@ __device__ __forceinline__ void cull_scan_body(
     // index -- with (cloud, sample) on x, all workgroups of one cloud land on the same XCD (when
     // 2B is a multiple of 8), so each XCD's L2 holds 1/8 of the records instead of a copy of all
     const int z = bx, cloud = z >= B ? 1 : 0, b = z - cloud * B;
-    const int n = cloud ? M : N;
-    const int nsg = (n + SGT - 1) / SGT;
+    // N, M, L: the capacities = the strides of every array.  A ragged batch (include/rrl.h rrl_opts.count1 / count2 / nlines)
+    // has n <= ncap records of this cloud and sample -- at the sorted positions [0, n), like the pad of any cloud with
+    // n % 64 != 0 -- and nl <= L lines: two uniform loads; without counts the capacities themselves
+    const int ncap = cloud ? M : N;
+    const int n = rrl_rows(cloud ? cnt2 : cnt1, b, ncap);
+    const int nsg = (n + SGT - 1) / SGT, nsgc = (ncap + SGT - 1) / SGT;
     const int sg0 = bz * spw;
-    if (sg0 >= nsg) return;  // uniform: the smaller cloud has fewer slices
+    if (sg0 >= nsg) return;  // uniform: the smaller cloud (or sample) has fewer slices
+    const int nl = rrl_rows(nlines, input_of(b, Bt), L);
+    if (by * (int)(blockDim.x >> 6) * LPW >= nl) return;  // uniform: a tile of lines the sample does not have (nl < L only)
     // multi-pose evaluation (rrl_opts.problems): instance b has the target and lines of problem b % Bt -- the target's scan
     // is the same for every pose, so only the first Bt instances scan cloud 2 (the per-line stage reads it there)
     if (cloud && Bt > 0 && b >= Bt) return;  // uniform
     const int nsl = min(spw, nsg - sg0);
-    const float4 *p0s = (cloud ? p0s2 : p0s1) + (size_t)b * nsg * SGT;
-    const float4 *tree = (cloud ? tree2 : tree1) + (size_t)b * nsg * NODE;
+    const float4 *p0s = (cloud ? p0s2 : p0s1) + (size_t)b * nsgc * SGT;
+    const float4 *tree = (cloud ? tree2 : tree1) + (size_t)b * nsgc * NODE;
 
     // ---- everything the prologue needs is requested up front, in one round of independent loads: the slice's
     //      records and nodes (one per lane in the usual 8-wavefront workgroup), the sample's line maxima, this
@@ -530,7 +538,7 @@ __device__ __forceinline__ void cull_scan_body(
     constexpr int RPT = (SPW * SGT + 64 * WPB - 1) / (64 * WPB);  // records per lane of a full workgroup
     static_assert(SPW * NODE <= 64 * WPB, "one node per lane");
     const bool one_each = (int)blockDim.x == 64 * WPB;
-    const int32_t *idx = (cloud ? idx2 : idx1) + (size_t)b * nsg * SGT;
+    const int32_t *idx = (cloud ? idx2 : idx1) + (size_t)b * nsgc * SGT;
     float4 rec0[RPT], nd0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     static_assert(LMAX_CHUNKS == 64, "one partial row per lane");
     // (the line maxima and max |P|^2 are requested FIRST: vector loads return in order, so the slack arithmetic below can
@@ -578,8 +586,8 @@ __device__ __forceinline__ void cull_scan_body(
     const float *ln = line + (size_t)input_of(b, Bt) * L * 6;
     const int lw0 = (by * (int)(blockDim.x >> 6) + wave) * LPW;
     const int l0 = lw0 + lane, l1 = l0 + 64;
-    const bool live0 = l0 < L, live1 = l1 < L;
-    const bool has_lines = lw0 < L;  // a wave without lines (the last tile of the line set) still stages records
+    const bool live0 = l0 < nl, live1 = l1 < nl;
+    const bool has_lines = lw0 < nl;  // a wave without lines (the last tile of the line set) still stages records
 #if CULL_REGLINES
     // each lane's own two lines straight into registers: three 8-byte loads per line (rows are 24 bytes, 8-byte aligned;
     // the three instructions of a line cover the wavefront's 1536 contiguous bytes completely); rows past L: zero lines
@@ -592,7 +600,7 @@ __device__ __forceinline__ void cull_scan_body(
 #else
     float2 *lr = line_lds[wave];
     const float *lsrc = ln + (size_t)lw0 * 6;
-    const bool full_tile = has_lines && lw0 + LPW <= L && (((uintptr_t)lsrc) & 15) == 0;  // uniform
+    const bool full_tile = has_lines && lw0 + LPW <= nl && (((uintptr_t)lsrc) & 15) == 0;  // uniform
     float4 t0, t1, t2;
     if (full_tile) {
         const float4 *s4 = (const float4 *)lsrc;
@@ -621,7 +629,7 @@ __device__ __forceinline__ void cull_scan_body(
             d4[lane] = t0; d4[64 + lane] = t1; d4[128 + lane] = t2;
         } else if (has_lines) {  // ragged tail / odd alignment: 8-byte pieces (a row is 24 bytes), zeros past the end
             const float2 *s2 = (const float2 *)lsrc;
-            const int nf2 = (L - lw0) * 3;
+            const int nf2 = (nl - lw0) * 3;
             for (int i = lane; i < LPW * 3; i += 64) lr[i] = i < nf2 ? s2[i] : make_float2(0.0f, 0.0f);
         }
 
@@ -664,7 +672,7 @@ __device__ __forceinline__ void cull_scan_body(
     float dv[RPT];
     const bool psorted = __builtin_amdgcn_readfirstlane(__float_as_int(play)) != 0;  // (1.0f: PTRI / DEL rows at sorted positions)
     if (nanwide && one_each) {
-        const float *del = (cloud ? del2 : del1) + (size_t)b * n;
+        const float *del = (cloud ? del2 : del1) + (size_t)b * ncap;
         if (psorted) {  // uniform: the prepared build left DEL at the sorted positions -- no dependent gather through IDX
 #pragma unroll
             for (int k = 0; k < RPT; ++k)
@@ -684,7 +692,7 @@ __device__ __forceinline__ void cull_scan_body(
     const bool fallback = !cs.ok || !__all(line_cullable(sa, oa) && line_cullable(sb, ob));
     unsigned long long fb_pairs = 0;
 
-    const float *ptri = (cloud ? ptri2 : ptri1) + (size_t)b * n * PTRI_STRIDE;
+    const float *ptri = (cloud ? ptri2 : ptri1) + (size_t)b * ncap * PTRI_STRIDE;
     int32_t *cnt = (cloud ? count2 : count1) + (size_t)b * L;
     int32_t *hit = (cloud ? hit2 : hit1) + (size_t)b * L * RRL_MAX_HITS;
 
@@ -697,7 +705,7 @@ __device__ __forceinline__ void cull_scan_body(
             for (int k = 0; k < RPT; ++k)
                 if (tid + 64 * WPB * k < nsl * SGT) dl[tid + 64 * WPB * k] = dv[k];
         } else {
-            const float *del = (cloud ? del2 : del1) + (size_t)b * n;
+            const float *del = (cloud ? del2 : del1) + (size_t)b * ncap;
             for (int i = tid; i < nsl * SGT; i += blockDim.x) {
                 const int sp = sg0 * SGT + i;
                 dl[i] = sp < n ? del[psorted ? sp : idx[sp]] : 0.0f;
@@ -767,7 +775,7 @@ __device__ __forceinline__ void cull_scan_body(
     ctx.cands = cands_lds[wave];
     ctx.idx = idx;
     ctx.ptri = ptri;
-    ctx.ptri_rs = rrl_rsrc(ptri, (size_t)n * PTRI_STRIDE * 4);
+    ctx.ptri_rs = rrl_rsrc(ptri, (size_t)ncap * PTRI_STRIDE * 4);
     ctx.sc1 = TILEMAX && cloud == 0;
     ctx.psorted = psorted;
     ctx.cnt = cnt;
@@ -784,11 +792,11 @@ __device__ __forceinline__ void cull_scan_body(
 
     if (fallback) {  // rare: kept out of line so that its registers do not count against the culled walk
         const int f0 = sg0 * SGT, f1 = min(n, f0 + nsl * SGT);  // real records sit at sorted positions [0, n)
-        strict_slice(ptri, idx, ctx.psorted, f0, f1, ux, uy, uz, ox, oy, oz, l0, l1, L, cnt, hit, status);
+        strict_slice(ptri, idx, ctx.psorted, f0, f1, ux, uy, uz, ox, oy, oz, l0, l1, nl, cnt, hit, status);
         if (lane == 0) atomicAdd(&status[1], 1);  // always on: wavefronts that left the culled path
-        fb_pairs = (unsigned long long)(f1 - f0) * (unsigned long long)min(LPW, L - lw0);
+        fb_pairs = (unsigned long long)(f1 - f0) * (unsigned long long)min(LPW, nl - lw0);
     } else {
-    ta = (unsigned long long)nsl * (unsigned long long)min(LPW, L - lw0);
+    ta = (unsigned long long)nsl * (unsigned long long)min(LPW, nl - lw0);
 
     unsigned long long stamps[3] = {0ull, 0ull, 0ull};
     cull_walk<COUNT, TILEMAX>(ctx, node_lds, nsl, lane, live0, live1, ux, uy, uz, ox, oy, oz, stamps);
@@ -820,11 +828,12 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
     int32_t *__restrict__ hit2, int32_t *__restrict__ status, uint32_t *pmax,
     const float *__restrict__ del1, const float *__restrict__ del2, const float2 *__restrict__ lmax,
     const float *__restrict__ apart, const float *__restrict__ aflag, int nblk_apart, int B,
-    int N, int M, int L, int spw, unsigned long long *__restrict__ counters, long long counter_rows, int Bt) {
+    int N, int M, int L, int spw, unsigned long long *__restrict__ counters, long long counter_rows, int Bt,
+    const int32_t *__restrict__ cnt1, const int32_t *__restrict__ cnt2, const int32_t *__restrict__ nlines) {
     __shared__ CullLds lds_;
     cull_scan_body<COUNT>(lds_, ptri1, ptri2, p0s1, p0s2, idx1, idx2, tree1, tree2, line, count1, hit1, count2, hit2, status,
                           pmax, del1, del2, lmax, apart, aflag, nblk_apart, B, N, M, L, spw, counters, counter_rows,
-                          (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y, Bt);
+                          (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y, Bt, cnt1, cnt2, nlines);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -877,7 +886,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int l2 = lin - ncham, bx = l2 % a.gx, r = l2 / a.gx;
     cull_scan_body<false>(lds_.scan, a.ptri1, a.ptri2, a.p0s1, a.p0s2, a.idx1, a.idx2, a.tree1, a.tree2, a.line, a.count1,
                           a.hit1, a.count2, a.hit2, a.status, a.pmax, a.del1, a.del2, a.lmax, a.apart, a.aflag, a.nblk_apart,
-                          a.B, a.N, a.M, a.L, a.spw, nullptr, 0, bx, r % a.gy, r / a.gy, a.gx, a.gy, a.Bt);
+                          a.B, a.N, a.M, a.L, a.spw, nullptr, 0, bx, r % a.gy, r / a.gy, a.gx, a.gy, a.Bt,
+                          nullptr, nullptr, nullptr);  // (a riding walk and counts exclude each other: rrl_plan)
 }
 
 // ---------------------------------------------------------------------------------------
@@ -979,7 +989,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
     };
     cull_scan_body<false, true>(lds_.scan, ptri1, ptri2, p0s1, p0s2, idx1, idx2, tree1, tree2, line, count1, hit1, count2, hit2,
                                 (int32_t *)(ch.chain + 4 * b + 1), pmax, del1, del2, nullptr, apart, apart, nblk_apart, B, N, M, L,
-                                spw, nullptr, 0, cloud * B + b, by, bz, 2 * B, (int)gridDim.y, 0, wait_ready);
+                                spw, nullptr, 0, cloud * B + b, by, bz, 2 * B, (int)gridDim.y, 0, nullptr, nullptr, nullptr,
+                                wait_ready);  // (no counts: rrl_cull_scan_can_fuse declines ragged calls)
     STAMPR(6);
 }
 
@@ -997,7 +1008,7 @@ static int launch_variant(const float *line, void *ws, const WsLayout &w, int B,
                        w.i32(ws, RRL_WS_STATUS), (uint32_t *)w.i32(ws, RRL_WS_PMAX),                         \
                        w.f32(ws, RRL_WS_DEL1), w.f32(ws, RRL_WS_DEL2), (const float2 *)w.f32(ws, RRL_WS_LMAX),   \
                        apart, w.f32(ws, RRL_WS_APART), nblk_apart, B, N, M, L, spw,                          \
-                       o.counters, o.counter_rows, o.problems)
+                       o.counters, o.counter_rows, o.problems, o.count1, o.count2, o.nlines)
     const float *apart = o.prepared() ? w.f32(ws, RRL_WS_APART) : nullptr;  // prepared build: PMAX comes from the partial rows
     const int nblk_apart = ((N > M ? N : M) + REC_BLK - 1) / REC_BLK;
     if (o.plan.fused_build) {  // the chained step: source records + target scan + source scan as ONE launch (cull_scan_build_kernel)

@@ -17,6 +17,7 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
     if (!a || a->struct_bytes < (int32_t)offsetof(rrl_demo_epoch_args, pipeline)) return RRL_E_ARG;  // (pipeline: appended in round 4b)
     const int N = a->N, M = a->M, L = a->L;
     if (N <= 0 || M <= 0 || L <= 0 || a->rounds <= 0) return RRL_E_ARG;
+    if (rrl_resolve_opts(a->opts).ragged()) return RRL_E_ARG;  // (one sample, the sampler's own line set: no counts)
     const char *env = getenv("RRL_DEMO_RIDE");  // (read per call: tests switch it between epochs) 0: no launch carries another's work
     const bool rides = !(env && env[0] == '0');
     int32_t *pipe = a->struct_bytes >= (int32_t)sizeof(rrl_demo_epoch_args) && rides ? a->pipeline : nullptr;

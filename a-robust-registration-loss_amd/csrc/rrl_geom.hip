@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void reg_bwd_kernel(const float *__restrict__ 
                                                       const float *__restrict__ loss,
                                                       const int32_t *__restrict__ info,
                                                       int32_t *__restrict__ done, int n, int B,
-                                                      int transpose_r) {
+                                                      int transpose_r, const int32_t *__restrict__ cnt) {
     __shared__ float red[4][12];
     __shared__ int ticket;
     __shared__ double psum[14];
@@ -204,7 +204,14 @@ __global__ __launch_bounds__(256) void reg_bwd_kernel(const float *__restrict__ 
 #pragma unroll
     for (int q = 0; q < 12; ++q) acc[q] = 0.0f;
     const int i0 = blockIdx.x * REG_BWD_PTS, i1 = min(n, i0 + REG_BWD_PTS);
+    const int nv = 3 * rrl_rows(cnt, b, n / 3);  // points of the sample's own triangles (a ragged batch: rrl_opts.count1)
     for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+        if (i >= nv) {  // an absent row: its source coordinates are not read, its gradient is exactly zero
+            if (gx)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) gx[base + 3 * (size_t)i + c] = 0.0f;
+            continue;
+        }
         float v[3], g[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -309,11 +316,11 @@ int rrl_fused_backward(int B, int N, int M) { return B > 0 && N > 0 && (N > M ? 
 
 int rrl_launch_reg_bwd(const float *src, const float *R, float *g1, float *grad_src, float *partial,
                        float *gR, float *gt, float *payload, const float *loss, const int32_t *info,
-                       int32_t *done, int B, int N, int transpose_r, hipStream_t s) {
+                       int32_t *done, int B, int N, int transpose_r, const int32_t *count1, hipStream_t s) {
     const int n = 3 * N;
     hipLaunchKernelGGL(reg_bwd_kernel, dim3((unsigned)((n + REG_BWD_PTS - 1) / REG_BWD_PTS), (unsigned)B),
                        dim3(256), 0, s, src, R, g1, grad_src, partial, gR, gt, payload, loss, info, done, n,
-                       B, transpose_r);
+                       B, transpose_r, count1);
     RRL_LAUNCH_CHECK();
     return 0;
 }
@@ -737,12 +744,14 @@ extern "C" int rrl_chamfer_bwd(const float *x, const float *y, const uint64_t *b
 // ---------------------------------------------------------------------------------------
 // K8 line sampler
 // ---------------------------------------------------------------------------------------
+// cnt: NULL, or the points each sample really has (a ragged batch: rrl_aabb_counted); n stays the stride
 __global__ __launch_bounds__(1024) void aabb_kernel(const float *__restrict__ v,
-                                                    float *__restrict__ aabb, int n) {
+                                                    float *__restrict__ aabb, int n, const int32_t *__restrict__ cnt) {
     __shared__ float red[16][6];
     const int b = blockIdx.x;
+    const int nown = rrl_rows(cnt, b, n);
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = threadIdx.x; i < n; i += 1024)
+    for (int i = threadIdx.x; i < nown; i += 1024)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             float f = v[((size_t)b * n + i) * 3 + c];
@@ -770,12 +779,15 @@ __global__ __launch_bounds__(1024) void aabb_kernel(const float *__restrict__ v,
     }
 }
 
-extern "C" int rrl_aabb(const float *v, float *aabb, int B, int n, void *stream) {
+extern "C" int rrl_aabb_counted(const float *v, const int32_t *counts, float *aabb, int B, int n, void *stream) {
     if (!v || !aabb || B < 0 || n <= 0) return RRL_E_ARG;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(aabb_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)stream, v, aabb, n);
+    hipLaunchKernelGGL(aabb_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)stream, v, aabb, n, counts);
     RRL_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int rrl_aabb(const float *v, float *aabb, int B, int n, void *stream) {
+    return rrl_aabb_counted(v, nullptr, aabb, B, n, stream);
 }
 
 // y = x R + t AND the AABB of y, one 1024-lane workgroup per sample: the demo's epoch needs both (the moved

@@ -192,9 +192,12 @@ __global__ __launch_bounds__(KD_THREADS) void kd_window_kernel(const float *__re
 }
 
 // ---- levels above one LDS window (clouds beyond 4096 positions) --------------------------------------------------
-__global__ void kd_init_kernel(int32_t *__restrict__ idx_g, uint32_t *__restrict__ nodebb, int n, int P, int nbb) {
+// cnt: NULL, or the rows each cloud really has (rrl_cloud_order_counted): the others start as pads, which sort last in every
+// window, so the real records end at the positions [0, cnt[b]) and no later kernel reads an absent row
+__global__ void kd_init_kernel(int32_t *__restrict__ idx_g, uint32_t *__restrict__ nodebb, int n, int P, int nbb,
+                               const int32_t *__restrict__ cnt) {
     const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < P) idx_g[(size_t)b * P + p] = p < n ? p : -1;
+    if (p < P) idx_g[(size_t)b * P + p] = p < (cnt ? min(max(cnt[b], 0), n) : n) ? p : -1;
     if (p < nbb) nodebb[(size_t)b * nbb + p] = (p % 6) < 3 ? 0xffffffffu : 0u;
 }
 __global__ void kd_aabb_kernel(const float *__restrict__ tri, const int32_t *__restrict__ idx_g, uint32_t *__restrict__ nodebb,
@@ -287,7 +290,8 @@ extern "C" size_t rrl_cloud_order_workspace_bytes(int B, int n) {
     return KdScratch(B > 0 ? B : 0, n > 0 ? n : 0).total + 256;
 }
 
-static int cloud_order_impl(const float *tri, int stride, int32_t *order, void *ws, size_t ws_bytes, int B, int n, void *stream) {
+static int cloud_order_impl(const float *tri, int stride, int32_t *order, void *ws, size_t ws_bytes, int B, int n, void *stream,
+                            const int32_t *counts = nullptr) {
     if (!tri || !order || !ws || B < 0 || n < 0 || n > SORT_CAP || B > 65535) return RRL_E_ARG;
     if (B == 0 || n == 0) return 0;
     const KdScratch L(B, n);
@@ -297,7 +301,7 @@ static int cloud_order_impl(const float *tri, int stride, int32_t *order, void *
     uint32_t *key_g = (uint32_t *)((char *)ws + L.key), *bb = (uint32_t *)((char *)ws + L.bb);
     const int P = L.P, npad = (n + SGT - 1) / SGT * SGT;
     const dim3 gp((unsigned)((P + 255) / 256), (unsigned)B);
-    hipLaunchKernelGGL(kd_init_kernel, gp, dim3(256), 0, s, idx_g, bb, n, P, L.nbb);
+    hipLaunchKernelGGL(kd_init_kernel, gp, dim3(256), 0, s, idx_g, bb, n, P, L.nbb, counts);
     for (int S = P; S > KD_WIN; S >>= 1) {  // levels whose windows exceed one workgroup's LDS
         hipLaunchKernelGGL(kd_aabb_kernel, gp, dim3(256), 0, s, tri, idx_g, bb, n, P, S, L.nbb, stride);
         hipLaunchKernelGGL(kd_keys_kernel, gp, dim3(256), 0, s, tri, idx_g, bb, key_g, n, P, S, L.nbb, stride);
@@ -317,6 +321,10 @@ static int cloud_order_impl(const float *tri, int stride, int32_t *order, void *
 }
 extern "C" int rrl_cloud_order(const float *tri, int32_t *order, void *ws, size_t ws_bytes, int B, int n, void *stream) {
     return cloud_order_impl(tri, 9, order, ws, ws_bytes, B, n, stream);
+}
+extern "C" int rrl_cloud_order_counted(const float *tri, const int32_t *counts, int32_t *order, void *ws, size_t ws_bytes, int B,
+                                       int n, void *stream) {
+    return cloud_order_impl(tri, 9, order, ws, ws_bytes, B, n, stream, counts);
 }
 // the same for point clouds pts [B][n][3] (the Chamfer monitor's inputs, rrl_chamfer_tree_fwd_ex)
 extern "C" int rrl_cloud_order_points(const float *pts, int32_t *order, void *ws, size_t ws_bytes, int B, int n, void *stream) {

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64) void tri_prepare_kernel(const float *__restrict
     }
 }
 
-int rrl_launch_pmax_from_partials(void *ws, const WsLayout &w, int B, int N, int M, int clouds, hipStream_t s);
+int rrl_launch_pmax_from_partials(void *ws, const WsLayout &w, int B, int N, int M, int clouds, const RrlCall &o, hipStream_t s);
 int rrl_launch_tri_build(const float *tri1, const float *tri2, void *ws, const WsLayout &w, int B,
                          int N, int M, int clouds, const RrlXform *xf, const float *line, int L, const RrlCall &o,
                          hipStream_t s);
@@ -181,11 +181,11 @@ int rrl_tri_prepare_clouds(const float *tri1, const float *tri2, void *ws, size_
 extern "C" int rrl_tri_prepare_ex(const float *tri1, const float *tri2, void *ws, size_t ws_bytes,
                                   int B, int N, int M, int L, const rrl_opts *opts, void *stream) {
     RrlCall o = rrl_resolve_opts(opts);
-    rrl_plan(o, B, N, M, L, 0, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE);  // (prepared orders: both, sorted layout)
+    if (const int prc = rrl_plan(o, B, N, M, L, 0, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE)) return prc;  // (prepared orders: both, sorted layout)
     int rc = rrl_tri_prepare_clouds(tri1, tri2, ws, ws_bytes, B, N, M, L, 2, nullptr, nullptr, o, stream);
     if (rc || !o.prepared() || B <= 0 || (N <= 0 && M <= 0)) return rc;
     // prepared build: PMAX is normally reduced by the culled scan's prologue; a stage call leaves it complete itself
-    return rrl_launch_pmax_from_partials(ws, WsLayout(B, N, M, L), B, N, M, 2, (hipStream_t)stream);
+    return rrl_launch_pmax_from_partials(ws, WsLayout(B, N, M, L), B, N, M, 2, o, (hipStream_t)stream);
 }
 extern "C" int rrl_tri_prepare(const float *tri1, const float *tri2, void *ws, size_t ws_bytes,
                                int B, int N, int M, int L, void *stream) {
@@ -327,22 +327,27 @@ __global__ __launch_bounds__(256) void scan_kernel(
     const float *__restrict__ ptri1, const float *__restrict__ ptri2,
     const float *__restrict__ line, int32_t *__restrict__ count1, int32_t *__restrict__ hit1,
     int32_t *__restrict__ count2, int32_t *__restrict__ hit2, int32_t *__restrict__ status,
-    const uint32_t *__restrict__ pmax, int B, int N, int M, int L,
-    int chunk, int mode) {
+    const uint32_t *__restrict__ pmax, int B, int N, int M, int Lcap,
+    int chunk, int mode, const int32_t *__restrict__ cnt1, const int32_t *__restrict__ cnt2,
+    const int32_t *__restrict__ nlines) {
     constexpr int W = Lanes<T>::W;
     constexpr int R = W * NP;  // lines per lane
     const int z = blockIdx.z;
     const int cloud = z >= B ? 1 : 0;
     const int b = z - cloud * B;
-    const int n = cloud ? M : N;
+    // N, M, Lcap: capacities = strides; a ragged batch (rrl_opts.count1 / count2 / nlines) has n triangles and L lines in
+    // this sample (uniform loads), and a workgroup beyond either leaves before its first load
+    const int ncap = cloud ? M : N;
+    const int n = rrl_rows(cloud ? cnt2 : cnt1, b, ncap);
+    const int L = rrl_rows(nlines, b, Lcap);
     const int t0 = blockIdx.y * chunk;
-    if (t0 >= n) return;
+    if (t0 >= n || (int)blockIdx.x * (256 * R) >= L) return;
     const int t1 = min(n, t0 + chunk);
-    const float *tri = (cloud ? ptri2 : ptri1) + (size_t)b * n * PTRI_STRIDE;
-    const float *ln = line + (size_t)b * L * 6;
+    const float *tri = (cloud ? ptri2 : ptri1) + (size_t)b * ncap * PTRI_STRIDE;
+    const float *ln = line + (size_t)b * Lcap * 6;
     HitSink sink;
-    sink.cnt = (cloud ? count2 : count1) + (size_t)b * L;
-    sink.hit = (cloud ? hit2 : hit1) + (size_t)b * L * RRL_MAX_HITS;
+    sink.cnt = (cloud ? count2 : count1) + (size_t)b * Lcap;
+    sink.hit = (cloud ? hit2 : hit1) + (size_t)b * Lcap * RRL_MAX_HITS;
     sink.L = L;
     // lines of this lane: l = tile*256*R + r*256 + tid (adjacent lanes = adjacent lines)
     sink.lbase = blockIdx.x * (256 * R) + threadIdx.x;
@@ -471,7 +476,7 @@ int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B
                        w.f32(ws, RRL_WS_PTRI2), line, w.i32(ws, RRL_WS_COUNT1),                  \
                        w.i32(ws, RRL_WS_HIT1), w.i32(ws, RRL_WS_COUNT2), w.i32(ws, RRL_WS_HIT2), \
                        w.i32(ws, RRL_WS_STATUS), (const uint32_t *)w.i32(ws, RRL_WS_PMAX), B, N, \
-                       M, L, chunk, mode)
+                       M, L, chunk, mode, o.count1, o.count2, o.nlines)
     if (R == 1) RRL_SCAN_LAUNCH(float, 1);
     else if (R == 2) RRL_SCAN_LAUNCH(v2f, 1);
     else if (R == 4) RRL_SCAN_LAUNCH(v2f, 2);
@@ -485,7 +490,7 @@ int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B
 extern "C" int rrl_line_tri_scan_ex(const float *line, void *ws, size_t ws_bytes, int B, int N, int M,
                                     int L, int mode, int chunk, const rrl_opts *opts, void *stream) {
     RrlCall o = rrl_resolve_opts(opts);
-    rrl_plan(o, B, N, M, L, 0, mode, nullptr, nullptr, RRL_WANT_STAGE);
+    if (const int rc = rrl_plan(o, B, N, M, L, 0, mode, nullptr, nullptr, RRL_WANT_STAGE)) return rc;
     return rrl_line_tri_scan_clouds(line, ws, ws_bytes, B, N, M, L, o.plan.scan_mode, chunk, o.plan.clouds, o.plan.lmax_ready, o, stream);
 }
 extern "C" int rrl_line_tri_scan(const float *line, void *ws, size_t ws_bytes, int B, int N, int M,

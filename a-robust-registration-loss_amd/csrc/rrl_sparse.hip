@@ -110,7 +110,7 @@ extern "C" int rrl_line_pair_dist_ex(const float *tri1, const float *tri2, const
                                      void *ws, size_t ws_bytes, int B, int N, int M, int L, int s_m,
                                      int s_n, int e_m, int e_n, int pool, const rrl_opts *opts, void *stream) {
     RrlCall o = rrl_resolve_opts(opts);
-    rrl_plan(o, B, N, M, L, pool, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE);
+    if (const int rc = rrl_plan(o, B, N, M, L, pool, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE)) return rc;
     return line_pair_dist_impl(tri1, tri2, line, ws, ws_bytes, B, N, M, L, s_m, s_n, e_m, e_n, o, stream);
 }
 extern "C" int rrl_line_pair_dist(const float *tri1, const float *tri2, const float *line,
@@ -161,6 +161,7 @@ RrlCall rrl_resolve_opts(const rrl_opts *p) {
     o.payload = v.payload;
     o.problems = v.problems > 0 ? v.problems : 0;
     o.chain_left = v.chain_left;
+    o.count1 = v.count1; o.count2 = v.count2; o.nlines = v.nlines;
     return o;
 }
 // Which reduce kernel (rrl_ws.h RRL_RED_*): one workgroup per sample, tiled with the candidate exchange
@@ -253,6 +254,9 @@ int rrl_plan(RrlCall &o, int B, int N, int M, int L, int pool, int mode, const v
     // multi-pose evaluation (rrl_opts.problems = Bt): the B instances are B / Bt poses of Bt problems; the inputs have Bt
     // entries.  Served by the sorted layout of scan mode cull through the fused entries that move the source (xf)
     if (!stage && o.problems > 0 && (B % o.problems != 0 || !xf || pool || target_ws || !cull || N <= 0 || M <= 0)) return RRL_E_ARG;
+    // ragged batches (rrl_opts.count1 / count2 / nlines): independent samples on the sorted layout's builds (every scan mode),
+    // each scanning its own target; no rider reads a count
+    if (o.ragged() && (pool || o.problems > 0 || o.rider || target_ws || !sorted || o.count_rider || o.write_rider)) return RRL_E_ARG;
     // prepared clouds (include/rrl.h rrl_opts): honoured by the sorted layout of scan mode cull, with the orders of every
     // cloud this call builds; anything else takes the plain path (same results)
     if (o.prepared() && (!cull || (p.clouds == 2 && !o.order2 && !(o.flags & RRL_F_TARGET_KEPT)))) o.order1 = o.order2 = nullptr;
@@ -387,7 +391,7 @@ static int loss_reduce_impl(void *ws, size_t ws_bytes, float *loss, int B, int N
 extern "C" int rrl_loss_reduce_ex(void *ws, size_t ws_bytes, float *loss, int B, int N, int M, int L,
                                   int s_m, int s_n, int e_m, int e_n, int pool, const rrl_opts *opts, void *stream) {
     RrlCall o = rrl_resolve_opts(opts);
-    rrl_plan(o, B, N, M, L, pool, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE);
+    if (const int rc = rrl_plan(o, B, N, M, L, pool, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE)) return rc;
     return loss_reduce_impl(ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, nullptr, o, stream);
 }
 extern "C" int rrl_loss_reduce(void *ws, size_t ws_bytes, float *loss, int B, int N, int M, int L,
@@ -502,7 +506,7 @@ extern "C" int rrl_loss_backward(const float *tri1, const float *tri2, const voi
 int rrl_fused_backward(int B, int N, int M);
 int rrl_launch_reg_bwd(const float *src, const float *R, float *g1, float *grad_src, float *partial,
                        float *gR, float *gt, float *payload, const float *loss, const int32_t *info,
-                       int32_t *done, int B, int N, int transpose_r, hipStream_t s);
+                       int32_t *done, int B, int N, int transpose_r, const int32_t *count1, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // workspace + fused forward
@@ -789,6 +793,8 @@ static int registration_backward_impl(const float *src, const float *R, const fl
     if (!src || !R || !tri2 || !ws || !grad_loss || !gR || !gt) return RRL_E_ARG;
     if (payload && !loss) return RRL_E_ARG;
     if (o.problems > 0 && o.problems < B && grad_src) return RRL_E_ARG;  // multi-pose: the direct backward only (dL/dsrc would sum over the poses)
+    // a ragged batch (the counts of the forward, again): the sorted layout's fused tail, which skips the absent source rows
+    if (o.ragged() && (o.problems > 0 || !rrl_sorted_layout(N, M))) return RRL_E_ARG;
     WsLayout w(B, N, M, L);
     if (ws_bytes < w.total) return RRL_E_WS;
     float *g1 = w.f32(ws, RRL_WS_G1);
@@ -848,7 +854,7 @@ static int registration_backward_impl(const float *src, const float *R, const fl
         if (rc) return rc;
         return rrl_launch_reg_bwd(src, R, g1, grad_src, w.f32(ws, RRL_WS_RPART), gR, gt, payload, loss,
                                   w.i32(ws, RRL_WS_INFO), w.i32(ws, RRL_WS_STATUS) + 3, B, N, transpose_r,
-                                  s);
+                                  o.count1, s);
     }
     int rc = rrl_loss_backward(w.f32(ws, RRL_WS_TRI1), tri2, ws, ws_bytes, grad_loss, g1, nullptr, B,
                                N, M, L, 0, stream);

@@ -508,6 +508,7 @@ extern "C" int rrl_loss_forward_wide(const float *tri1, const float *tri2, const
         mode > RRL_SCAN_CULL)
         return RRL_E_ARG;
     if (s_m < 1 || s_n < 1 || e_m > RRL_WIDE_MAX_HITS + 1 || e_n > RRL_WIDE_MAX_HITS + 1) return RRL_E_RANGE;
+    if (rrl_resolve_opts(opts).ragged()) return RRL_E_ARG;  // (rrl_opts.count1 / count2 / nlines: the narrow entries only)
     const WsLayout w(B, N, M, L);
     const WwLayout v(B, N, M, L);
     if (ws_bytes < w.total || wws_bytes < v.total) return RRL_E_WS;

@@ -155,14 +155,17 @@ struct RrlCall {
     const void *tar_ws;   // (internal) the workspace that holds cloud 2's records when the target's scan is carried over
                           // (rrl_*_forward_cached: `target_ws`): the riding walk takes the target from there
     int32_t *chain_left;  // rrl_opts.chain_left (host int, or NULL)
+    const int32_t *count1, *count2, *nlines;  // rrl_opts: per-sample rows of a RAGGED batch (device int32 [B]), or NULL
     const RrlXform *xf;   // (internal) the source's transform, for the fused build's records body (plan.fused_build) ...
     const float *tri1_in; //   ... and the caller's source rows when there is no transform
     RrlPlan plan;
     __host__ bool prepared() const { return order1 != nullptr; }
     __host__ bool target_kept() const { return order1 != nullptr && (flags & RRL_F_TARGET_KEPT); }
+    __host__ bool ragged() const { return count1 != nullptr || count2 != nullptr || nlines != nullptr; }
 };
 RrlCall rrl_resolve_opts(const rrl_opts *o);  // rrl_sparse.hip
-// the plan of one call (o.plan; also settles o.problems, the orders, o.tar_ws, o.xf); RRL_E_ARG: an illegal multi-pose call
+// the plan of one call (o.plan; also settles o.problems, the orders, o.tar_ws, o.xf); RRL_E_ARG: an illegal multi-pose call,
+// or a ragged one (counts) combined with what does not serve it (include/rrl.h rrl_opts.count1)
 int rrl_plan(RrlCall &o, int B, int N, int M, int L, int pool, int mode, const void *target_ws, const RrlXform *xf, int want);
 // include/rrl.h rrl_sort_capacity (rrl_cull.hip): the sorted layout (records kernel, sphere tree, culled scan) serves up to it
 inline bool rrl_sorted_layout(int N, int M) { return (N > M ? N : M) <= rrl_sort_capacity(); }

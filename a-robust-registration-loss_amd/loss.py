@@ -107,14 +107,22 @@ def cal_loss_intersection_batch_whole_median_pts_lines(s_m, s_n, e_m, e_n, point
     return loss  # shape (1,): one group (B = 1, or the pooled B > 1 of SURVEY Q2)
 
 
-def batched_intersection_loss(points1, points2, line, rng=(1, 1, 5, 5), *, mode=None, chunk=0):
+def batched_intersection_loss(points1, points2, line, rng=(1, 1, 5, 5), *, mode=None, chunk=0, counts1=None, counts2=None,
+                             nlines=None):
     """B independent losses in one set of launches -- what the reference's callers compute
     with `for j in range(B): loss += cal_loss_...(…[j:j+1]…)` (rpm/Train_RPM.py:226-231,
     dcp/Train_DCP.py:266-270, fmr/model.py:302-306).  Returns (loss (B,), valid (B,) bool) on
     the GPU without any host synchronisation; loss[b] is 0 where valid[b] is False.  rng: as above, up to
-    8 hits per line (a wide range synchronises once: its hit-recovery check)."""
+    8 hits per line (a wide range synchronises once: its hit-recovery check).
+    counts1 / counts2 / nlines (int32 (B,), on the GPU or a list / CPU tensor): a RAGGED batch -- samples with different
+    numbers of source triangles, target triangles and lines in one call.  points1 (B, N, 9), points2 (B, M, 9) and
+    line (B, L, 6) are then capacities, filled from the front (rrl_hip.ragged.pack_clouds / pack_lines build them from
+    lists); sample b gives exactly what the B = 1 call on points1[b, :counts1[b]], points2[b, :counts2[b]],
+    line[b, :nlines[b]] gives, the rows beyond a count are never read as data (any filler, NaN included) and get zero
+    gradient.  Ranges within 1..4 hits only."""
     loss, info, _ = _ops.intersection_loss(points1, points2, line, rng, pool=False,
-                                           mode=_scan_mode(mode), chunk=chunk)
+                                           mode=_scan_mode(mode), chunk=chunk, counts1=counts1, counts2=counts2,
+                                           nlines=nlines)
     return loss, info[:, 0] > 0
 
 

@@ -36,6 +36,7 @@ _SIGS = {
     "rrl_loss_step_ex": [_P] * 6 + [_Z] + [_P] * 4 + [_I] * 11 + [_P, _P, _P],
     "rrl_cloud_order": [_P, _P, _P, _Z, _I, _I, _P],
     "rrl_cloud_order_points": [_P, _P, _P, _Z, _I, _I, _P],
+    "rrl_cloud_order_counted": [_P, _P, _P, _P, _Z, _I, _I, _P],
     "rrl_tri_prepare_ex": [_P, _P, _P, _Z, _I, _I, _I, _I, _P, _P],
     "rrl_line_tri_scan_ex": [_P, _P, _Z] + [_I] * 6 + [_P, _P],
     "rrl_loss_reduce_ex": [_P, _Z, _P] + [_I] * 9 + [_P, _P],
@@ -68,6 +69,7 @@ _SIGS = {
     "rrl_chamfer_tree_fwd_ex": [_P, _P, _P, _Z, _P, _P, _P, _I, _I, _I, _P, _P, _P, _c.c_longlong, _P],
     "rrl_chamfer_from_loss_ex": [_P, _P, _Z, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _c.c_longlong, _P],
     "rrl_aabb": [_P, _P, _I, _I, _P],
+    "rrl_aabb_counted": [_P, _P, _P, _I, _I, _P],
     "rrl_box_accept": [_P, _P, _P, _P, _P, _I, _I, _P],
     "rrl_log_row": [_P, _P, _P, _P, _P, _c.c_longlong, _P, _P],
     "rrl_se3_adam_step": [_P] * 8 + [_c.c_double] * 3 + [_P] * 7 + [_c.c_longlong, _P, _P, _I, _P, _P],
@@ -99,14 +101,15 @@ class Opts(ctypes.Structure):
     _fields_ = [("struct_bytes", _c.c_int32), ("flags", _c.c_int32), ("reduce_mode", _c.c_int32),
                 ("deterministic", _c.c_int32), ("sort_parts", _c.c_int32), ("scan_variant", _c.c_int32),
                 ("order1", _P), ("order2", _P), ("scan_counters", _P), ("scan_counter_rows", _c.c_longlong),
-                ("chamfer", _P), ("payload", _P), ("problems", _c.c_int32), ("chain_left", _P)]
+                ("chamfer", _P), ("payload", _P), ("problems", _c.c_int32), ("chain_left", _P),
+                ("count1", _P), ("count2", _P), ("nlines", _P)]
 
     def __init__(self, flags=0, reduce_mode=-1, deterministic=-1, sort_parts=-1, scan_variant=-1, order1=None,
                  order2=None, scan_counters=None, scan_counter_rows=0, chamfer=None, payload=None, problems=0,
-                 chain_left=None):
+                 chain_left=None, count1=None, count2=None, nlines=None):
         super().__init__(ctypes.sizeof(Opts), int(flags), int(reduce_mode), int(deterministic), int(sort_parts),
                          int(scan_variant), order1, order2, scan_counters, int(scan_counter_rows), chamfer, payload,
-                         int(problems), chain_left)
+                         int(problems), chain_left, count1, count2, nlines)
 
 class DemoEpochArgs(ctypes.Structure):
     """include/rrl.h rrl_demo_epoch_args (same field order)."""

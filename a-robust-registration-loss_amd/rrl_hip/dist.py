@@ -265,7 +265,8 @@ class _LineShardedLoss(torch.autograd.Function):
         return g1, g2, None, None, None, None
 
 
-def line_sharded_loss(points1, points2, line, rng=(1, 1, 5, 5), mode="cull", group=None):
+def line_sharded_loss(points1, points2, line, rng=(1, 1, 5, 5), mode="cull", group=None, counts1=None, counts2=None,
+                      nlines=None):
     """The loss of ONE sample (points1 (1, N, 9), points2 (1, M, 9), line (1, L, 6): the same on every rank) with its L
     lines partitioned over the ranks of `group` (contiguous shares, shard_bounds).  Returns (loss (1,), info (1, 4),
     status (4,)) like ops.intersection_loss; the loss is bit-identical to the unsharded one and the same on all ranks,
@@ -273,5 +274,8 @@ def line_sharded_loss(points1, points2, line, rng=(1, 1, 5, 5), mode="cull", gro
     call: the shares' sizes with the NaN flag (16 bytes), the selected lines' rows (68 bytes each); per backward: the
     point gradients (every rank takes part, with zeros when its own loss is not used).  Bucket ranges within 1..4 only."""
     from . import ops
+    if counts1 is not None or counts2 is not None or nlines is not None:  # one sample by contract: nothing is ragged
+        raise ValueError(ops._ragged_refusal("rrl_hip.dist.line_sharded_loss (one sample, its lines sharded over the ranks)",
+                                             "truncate the sample's tensors, or shard a ragged BATCH by samples"))
     ops._check_range(rng, "rrl_hip.dist.line_sharded_loss")
     return _LineShardedLoss.apply(points1, points2, line, tuple(rng), mode, group)

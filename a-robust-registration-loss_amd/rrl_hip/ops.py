@@ -363,6 +363,7 @@ def _target_ws(target_from, B, N, M, L):
     # the workspace that HOLDS the target's scan (records, hit counts and lists): of the full evaluation at the end of a chain
     # of carried-over ones
     tgt = getattr(target_from, "target_state", None) or target_from
+    _refuse_ragged_state(tgt, "target_from", "let the call scan its target itself")
     if getattr(tgt, "counts_cleared", False):
         raise ValueError("target_from: that state's hit counts were cleared by a chained step (RRL_F_CHAIN); build the step "
                          "whose target is carried over with chain=False")
@@ -391,13 +392,47 @@ def sort_capacity():
     return _sort_cap[0]
 
 
-def cloud_order(tri):
+def _ragged_refusal(what, instead):
+    return (f"counts1 / counts2 / nlines (a ragged batch) are not served together with {what}; {instead}")
+
+
+def _refuse_ragged_state(st, what, instead):
+    """A LossState whose evaluation had counts (st.ragged) holds records, tree nodes and partial boxes only for each sample's
+    own rows -- the rest of the capacity is not written -- so nothing that walks the workspace at its capacities may read it."""
+    if getattr(st, "ragged", False) or getattr(getattr(st, "target_state", None), "ragged", False):
+        raise ValueError(f"{what}: that evaluation was a ragged batch (counts1 / counts2 / nlines), whose workspace holds each "
+                         f"sample's own rows only; {instead}")
+
+
+def check_counts(counts, B, cap, dev, name):
+    """The per-sample row counts of a ragged batch as the kernels read them: None, or int32 (B,) on the op's GPU.  A CUDA
+    tensor is DEVICE data -- taken as it is (int32, contiguous, (B,), on `dev`; the kernels clamp it to [0, cap], nothing is
+    read back) --; a CPU tensor, numpy array or list is validated here (0 <= c <= cap, else ValueError) and uploaded."""
+    if counts is None:
+        return None
+    if isinstance(counts, torch.Tensor) and counts.is_cuda:
+        if counts.dtype != torch.int32 or not counts.is_contiguous() or tuple(counts.shape) != (B,) or counts.device != dev:
+            raise ValueError(f"{name} on the GPU must be a contiguous int32 ({B},) tensor on {dev}; got {counts.dtype} "
+                             f"{tuple(counts.shape)} on {counts.device}")
+        return counts
+    host = torch.as_tensor(counts)
+    if host.dtype.is_floating_point or host.dtype == torch.bool or tuple(host.shape) != (B,):
+        raise ValueError(f"{name} must hold {B} integers (one per sample); got {host.dtype} {tuple(host.shape)}")
+    if B and (int(host.min()) < 0 or int(host.max()) > cap):
+        raise ValueError(f"{name}: every count must lie in [0, {cap}] (the capacity: the tensor's dimension); got "
+                         f"{int(host.min())} .. {int(host.max())}")
+    return host.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def cloud_order(tri, counts=None):
     """Spatial order of the clouds tri (B, n, 9) -- pseudo-triangles; only the first point of a row places it -- or of
     point clouds (B, n, 3) (the Chamfer monitor's inputs: ops.chamfer(x, y, order_x=, order_y=)), computed
     ONCE per cloud (include/rrl.h rrl_cloud_order): int32 (B, 64 ceil(n / 64)), sorted position -> triangle index.
     A rigid motion preserves the order, so the same tensor serves every pose of the cloud: hand it to
     RegistrationStep / intersection_loss / registration_loss (order1= / order2=) and the per-step cell sort
-    disappears.  Any permutation gives identical labels and loss; this one makes the culled scan fast."""
+    disappears.  Any permutation gives identical labels and loss; this one makes the culled scan fast.
+    counts (ragged clouds, (B,) int32 on the GPU, or a list / CPU tensor): row b's first counts[b] entries are a
+    permutation of [0, counts[b]) and tri[b, counts[b]:] is not read (include/rrl.h rrl_cloud_order_counted)."""
     dev = _home(tri)
     if not isinstance(tri, torch.Tensor) or tri.dim() != 3 or tri.shape[-1] not in (3, 9):
         raise ValueError("cloud_order takes pseudo-triangles (B, n, 9) or points (B, n, 3)")
@@ -412,6 +447,12 @@ def cloud_order(tri):
     # from two threads never sort in the same memory (a per-shape global buffer did); the call runs once per
     # cloud, so the allocation is not on any step's path
     ws = torch.empty(_scratch_size("rrl_cloud_order_workspace_bytes", B, n), dtype=torch.uint8, device=dev)
+    if counts is not None:
+        if t.shape[-1] != 9:
+            raise ValueError("cloud_order(counts=) takes pseudo-triangles (B, n, 9)")
+        cnt = check_counts(counts, B, n, dev, "counts")
+        _run(dev, "rrl_cloud_order_counted", _p(t), _p(cnt), _p(order), _p(ws), ws.numel(), B, n)
+        return order
     _run(dev, "rrl_cloud_order" if t.shape[-1] == 9 else "rrl_cloud_order_points", _p(t), _p(order), _p(ws), ws.numel(), B, n)
     return order
 
@@ -463,14 +504,22 @@ class ChamferRide:
 
 
 def make_opts(order1=None, order2=None, target_kept=False, reduce_mode=None, deterministic=None, sort_parts=None,
-              scan_variant=None, counters=None, chamfer=None, payload=None, problems=None, chain=0, chain_left=None):
+              scan_variant=None, counters=None, chamfer=None, payload=None, problems=None, chain=0, chain_left=None,
+              counts1=None, counts2=None, nlines=None):
     """include/rrl.h rrl_opts for one call (None = the library default everywhere); the returned object keeps the
     tensors it points at alive (.keep).  chain: _lib.F_CHAIN [| _lib.F_CHAINED] (chained steps, include/rrl.h), chain_left:
-    the ctypes.c_int32 that receives "this call leaves the workspace chain-clean"."""
+    the ctypes.c_int32 that receives "this call leaves the workspace chain-clean".
+    counts1 / counts2 / nlines: a RAGGED batch -- int32 (B,) tensors ON THE GPU (check_counts) with the source triangles,
+    target triangles and lines each sample really has; the kernels read them, the dense tensors are capacities."""
     if order1 is None and order2 is None and not target_kept and reduce_mode is None and deterministic is None \
             and sort_parts is None and scan_variant is None and counters is None and chamfer is None and payload is None \
-            and not problems and not chain:
+            and not problems and not chain and counts1 is None and counts2 is None and nlines is None:
         return None
+    for c in (counts1, counts2, nlines):
+        if c is not None and not (isinstance(c, torch.Tensor) and c.is_cuda and c.dtype == torch.int32 and c.is_contiguous()):
+            raise ValueError("make_opts: counts1 / counts2 / nlines must be contiguous int32 tensors on the GPU (ops.check_counts)")
+    if (counts1 is not None or counts2 is not None or nlines is not None) and (chamfer is not None or problems):
+        raise ValueError(_ragged_refusal("a Chamfer rider or a multi-pose evaluation", "evaluate those on uniform batches"))
     o = _lib.Opts(flags=(_lib.F_TARGET_KEPT if target_kept else 0) | int(chain),
                   chain_left=ctypes.addressof(chain_left) if chain_left is not None else None,
                   reduce_mode=-1 if reduce_mode is None else _REDUCE.get(reduce_mode, reduce_mode),
@@ -482,8 +531,12 @@ def make_opts(order1=None, order2=None, target_kept=False, reduce_mode=None, det
                   scan_counters=counters.data_ptr() if counters is not None else None,
                   scan_counter_rows=counters.shape[0] if counters is not None else 0,
                   chamfer=ctypes.addressof(chamfer.c) if chamfer is not None else None,
-                  payload=payload.data_ptr() if payload is not None else None, problems=int(problems or 0))
-    o.keep = (order1, order2, counters, chamfer, payload, chain_left)  # (o.problems: the ctypes field itself)
+                  payload=payload.data_ptr() if payload is not None else None, problems=int(problems or 0),
+                  count1=counts1.data_ptr() if counts1 is not None else None,
+                  count2=counts2.data_ptr() if counts2 is not None else None,
+                  nlines=nlines.data_ptr() if nlines is not None else None)
+    o.keep = (order1, order2, counters, chamfer, payload, chain_left, counts1, counts2, nlines)  # (o.problems: the ctypes field itself)
+    o.ragged = counts1 is not None or counts2 is not None or nlines is not None
     o.ride = chamfer  # a ChamferRide (or None): the forwards arm it before the call and leave it on the LossState when it rode
     return o
 
@@ -527,6 +580,7 @@ def loss_forward_raw(tri1, tri2, line, rng=(1, 1, 5, 5), pool=False, mode="cull"
     else:
         st = LossState(B, N, M, L, G, dev)
     st.target_state = getattr(target_from, "target_state", None) or target_from  # whose workspace holds cloud 2
+    st.ragged = bool(getattr(opts, "ragged", False))  # (the workspace then holds each sample's own rows only)
     ws, nb = _p(st.ws), st.nbytes
     op = _optr(opts)
     ride = _arm_ride(opts)
@@ -888,24 +942,52 @@ def intersection_loss_dropin(points1, points2, line, rng=(1, 1, 5, 5), pool=Fals
     return loss, _DropinLoss.flags
 
 
-def _with_ride(opts, order1, order2, chamfer, B, N, M, dev, problems=0):
+def _with_ride(opts, order1, order2, chamfer, B, N, M, dev, problems=0, counts=None, L=0):
     """opts for a call that takes order1= / order2= / chamfer=True as keywords (or a ready make_opts object).
-    problems = Bt > 0: a multi-pose evaluation of B instances (include/rrl.h rrl_opts.problems); the orders then have Bt rows."""
+    problems = Bt > 0: a multi-pose evaluation of B instances (include/rrl.h rrl_opts.problems); the orders then have Bt rows.
+    counts = (counts1, counts2, nlines) of a ragged batch (any of them None), L = the lines' capacity."""
+    ragged = counts is not None and any(c is not None for c in counts)
     if opts is not None:
         if chamfer and getattr(opts, "ride", None) is None:
             raise ValueError("chamfer=True with ready-made opts: build them with make_opts(chamfer=ChamferRide(...))")
+        if ragged:
+            raise ValueError("counts1= / counts2= / nlines= with ready-made opts: hand them to make_opts instead")
         return opts
     ride = ChamferRide(B, N, M, dev) if chamfer else None
-    if ride is None and order1 is None and order2 is None and not problems:
+    if ride is None and order1 is None and order2 is None and not problems and not ragged:
         return None
     # the kernels read an order as int32 [B][64 ceil(n / 64)] on the op's GPU: anything else would be read out of bounds
     Bo = problems or B
+    c1, c2, nl = counts if ragged else (None, None, None)
     return make_opts(order1=_check_order(order1, Bo, N, dev, "order1"), order2=_check_order(order2, Bo, M, dev, "order2"),
-                     chamfer=ride, problems=problems)
+                     chamfer=ride, problems=problems, counts1=check_counts(c1, B, N, dev, "counts1"),
+                     counts2=check_counts(c2, B, M, dev, "counts2"), nlines=check_counts(nl, B, L, dev, "nlines"))
+
+
+def _ragged_gate(ragged, *, pool=False, chamfer=False, target_from=None, wide=False, problems=0):
+    """What a ragged batch (counts1 / counts2 / nlines) is refused with, before anything is launched; each message names
+    the alternative."""
+    if not ragged:
+        return
+    if pool:
+        raise ValueError(_ragged_refusal("pool=True (the reference's pooled B > 1 call has one size per batch)",
+                                         "call with pool=False: every sample is its own loss"))
+    if chamfer:
+        raise ValueError(_ragged_refusal("chamfer=True (a ragged Chamfer mean has a denominator of its own)",
+                                         "evaluate the monitor per sample with ops.chamfer on the truncated clouds"))
+    if target_from is not None:
+        raise ValueError(_ragged_refusal("target_from (a carried-over target scan)", "let the call scan its target itself"))
+    if wide:
+        raise ValueError(_ragged_refusal("a wide bucket range (more than 4 hits per line)",
+                                         "use a range within 1..4 (e_m, e_n <= 5), or B = 1 calls on the truncated tensors"))
+    if problems:
+        raise ValueError(_ragged_refusal("a multi-pose evaluation (several poses per problem)",
+                                         "evaluate the poses one call after the other"))
 
 
 def intersection_loss(points1, points2, line, rng=(1, 1, 5, 5), pool=False, mode="cull", chunk=0,
-                      target_from=None, order1=None, order2=None, opts=None, chamfer=False, _force_wide=False):
+                      target_from=None, order1=None, order2=None, opts=None, chamfer=False, _force_wide=False,
+                      counts1=None, counts2=None, nlines=None):
     """Batched loss: returns (loss[G], info[G,4] = (nbuckets, nselected, nvalues, NaN flag), status[4])
     on the GPU, G = 1 if pool else B.  Each sample is an independent loss (what every reference
     caller obtains by looping B=1 calls); pool=True reproduces the reference's own B>1 behaviour
@@ -917,12 +999,22 @@ def intersection_loss(points1, points2, line, rng=(1, 1, 5, 5), pool=False, mode
     Bucket ranges: within 1..4 hits per line (e_m, e_n <= 5) the narrow path above; up to 8 (e_m, e_n <= 9) the wide
     pipeline (include/rrl.h rrl_loss_forward_wide) -- gradients to points1 and points2, pool, mode, order1 / order2 as
     above; it synchronises once (its hit-recovery check) and takes neither target_from, chamfer=True nor the
-    deterministic-gradient mode.  _force_wide (tests): run a range within 1..4 through the wide pipeline."""
+    deterministic-gradient mode.  _force_wide (tests): run a range within 1..4 through the wide pipeline.
+    counts1 / counts2 / nlines: a RAGGED batch (include/rrl.h rrl_opts.count1): int32 (B,) -- on the GPU (read by the
+    kernels: no synchronisation), or a list / CPU tensor (validated, uploaded) -- with the rows each sample really has;
+    points1 (B, N, 9), points2 (B, M, 9), line (B, L, 6) are capacities.  Sample b gives what a B = 1 call on
+    points1[b, :counts1[b]], points2[b, :counts2[b]], line[b, :nlines[b]] gives, bit for bit; the rows beyond a count are
+    never read as data (they may hold NaN) and their gradient rows are zero.  Not with pool, chamfer=True, target_from or
+    a wide range (ValueError).  Orders of ragged clouds: cloud_order(tri, counts=)."""
     if (_force_wide or _is_wide(rng)) and chamfer:
         raise ValueError(_wide_refusal("chamfer=True (the Chamfer walk riding in the scan launch)"))
-    if opts is None and (chamfer or order1 is not None or order2 is not None):
+    ragged = counts1 is not None or counts2 is not None or nlines is not None or bool(getattr(opts, "ragged", False))
+    _ragged_gate(ragged, pool=pool, chamfer=chamfer, target_from=target_from, wide=_force_wide or _is_wide(rng))
+    if opts is None and (chamfer or order1 is not None or order2 is not None or ragged):
         opts = _with_ride(None, order1, order2, chamfer and not pool, points1.shape[0], points1.shape[1], points2.shape[1],
-                          _home(points1, points2, line))
+                          _home(points1, points2, line), counts=(counts1, counts2, nlines), L=line.shape[1])
+    elif ragged and (counts1 is not None or counts2 is not None or nlines is not None):
+        raise ValueError("counts1= / counts2= / nlines= with ready-made opts: hand them to make_opts instead")
     return _IntersectionLoss.apply(points1, points2, line, tuple(rng), pool, mode, chunk, target_from, opts, bool(_force_wide))
 
 
@@ -974,6 +1066,7 @@ class _RegistrationLoss(torch.autograd.Function):
             return out
         s_m, s_n, e_m, e_n = _check_range(rng, "registration_loss")
         st = LossState(B, N, M, L, B, src.device)
+        st.ragged = bool(getattr(opts, "ragged", False))
         ride = _arm_ride(opts)
         with _guard(dev):
             check(_lib.load().rrl_registration_forward_ex(
@@ -1022,7 +1115,7 @@ class _RegistrationLoss(torch.autograd.Function):
 
 def registration_loss(src_tri, R, t, tar_tri, line, rng=(1, 1, 5, 5), transpose_r=True,
                       mode="cull", chunk=0, want_payload=False, target_from=None, order1=None, order2=None, opts=None,
-                      chamfer=False):
+                      chamfer=False, counts1=None, counts2=None, nlines=None):
     """loss[b] of `src_tri[b]` moved by (R[b], t[b]) against `tar_tri[b]` along `line[b]` -- the
     rigid transform of the training call sites fused with the loss.  transpose_r=True is
     x R^T + t (R x + t per point: RPM / DCP / FMR), False is x R + t (Reconstruction_point).
@@ -1034,7 +1127,9 @@ def registration_loss(src_tri, R, t, tar_tri, line, rng=(1, 1, 5, 5), transpose_
     order1 / order2: ops.cloud_order of src_tri (in its own frame: a rigid motion keeps the order) and tar_tri -- the
     per-call cell sort is skipped, same results.
     chamfer=True: the trainers' Chamfer monitor (moved source's first points vs the target's; chamfer_from_state) is issued
-    inside this evaluation's scan launch (ChamferRide) -- chamfer_from_state(last_state()) then costs no launch."""
+    inside this evaluation's scan launch (ChamferRide) -- chamfer_from_state(last_state()) then costs no launch.
+    counts1 / counts2 / nlines: a ragged batch, as ops.intersection_loss; the gradient of src_tri has zero rows beyond
+    counts1.  Not with chamfer=True, target_from or several poses per problem."""
     # MULTI-POSE (round 5; include/rrl.h rrl_opts.problems): R / t may hold k poses for each of the B_t problems
     # (instance s = pose s // B_t of problem s % B_t -- torch.cat of the per-iteration (B_t, 3, 3) estimates): all k * B_t
     # losses come out of ONE evaluation, the target scanned once per problem; loss (k * B_t,), bit-identical per instance to
@@ -1044,9 +1139,14 @@ def registration_loss(src_tri, R, t, tar_tri, line, rng=(1, 1, 5, 5), transpose_
     problems = Bt if (Binst != Bt and Bt > 0 and Binst % Bt == 0) else 0
     if problems and (target_from is not None or mode != "cull"):
         raise ValueError("a multi-pose evaluation scans its target itself, in scan mode cull")
-    if opts is None and (chamfer or order1 is not None or order2 is not None or problems):
+    ragged = counts1 is not None or counts2 is not None or nlines is not None or bool(getattr(opts, "ragged", False))
+    _ragged_gate(ragged, chamfer=chamfer, target_from=target_from, problems=problems)
+    if opts is None and (chamfer or order1 is not None or order2 is not None or problems or ragged):
         opts = _with_ride(None, order1, order2, chamfer, Binst, src_tri.reshape(Bt, -1, 9).shape[1],
-                          tar_tri.reshape(tar_tri.shape[0], -1, 9).shape[1], _home(src_tri, tar_tri, line, R, t), problems)
+                          tar_tri.reshape(tar_tri.shape[0], -1, 9).shape[1], _home(src_tri, tar_tri, line, R, t), problems,
+                          counts=(counts1, counts2, nlines), L=line.shape[1])
+    elif ragged and (counts1 is not None or counts2 is not None or nlines is not None):
+        raise ValueError("counts1= / counts2= / nlines= with ready-made opts: hand them to make_opts instead")
     return _RegistrationLoss.apply(src_tri, R, t, tar_tri, line, tuple(rng), transpose_r, mode,
                                    chunk, want_payload, target_from, opts)
 
@@ -1058,7 +1158,7 @@ class _Step:
     before it calls _set_opts(), and keeps its own outputs, argument tuples and C calls."""
 
     def __init__(self, what, src_tri, tar_tri, n_lines, rng, transpose_r, mode, chunk, prepared, src_order, tar_order,
-                 chamfer, poses, chain):
+                 chamfer, poses, chain, counts1=None, counts2=None, nlines=None):
         dev = _home(src_tri, tar_tri)
         self.dev = dev
         self.src = _prep(src_tri, "src_tri", 9, dev)
@@ -1078,10 +1178,19 @@ class _Step:
         self.rng = _check_range(rng, what)
         self.tr, self.mode, self.chunk = int(bool(transpose_r)), _MODES[mode], int(chunk)
         self.st = LossState(B, N, M, L, B, dev)
+        # a RAGGED batch (include/rrl.h rrl_opts.count1 / count2 / nlines): the step keeps pointing at these GPU tensors like it
+        # does at its clouds -- their CONTENT is read by the kernels of every call (update counts1 / nlines in place, also
+        # between the replays of a captured step; counts2 belongs to the kept target: see set_counts)
+        self.counts1 = check_counts(counts1, Bt, N, dev, "counts1")
+        self.counts2 = check_counts(counts2, Bt, M, dev, "counts2")
+        self.nlines = check_counts(nlines, Bt, L, dev, "nlines")
+        self.ragged = self.counts1 is not None or self.counts2 is not None or self.nlines is not None
+        _ragged_gate(self.ragged, chamfer=chamfer, problems=self.poses > 1)
         # the Chamfer monitor of every step, issued inside its scan launch (ChamferRide): .chamfer_value after each call
         self.ride = ChamferRide(B, N, M, dev) if chamfer else None
         self.chamfer_value = None
-        self._extra = dict(chamfer=self.ride, problems=Bt if self.poses > 1 else None)
+        self._extra = dict(chamfer=self.ride, problems=Bt if self.poses > 1 else None, counts1=self.counts1,
+                           counts2=self.counts2, nlines=self.nlines)
         self.ones = torch.ones(B, dtype=torch.float32, device=dev)
         if prepared is None:  # default: on (RRL_PREPARED=0 turns the default off: A/B runs of unmodified callers)
             prepared = os.environ.get("RRL_PREPARED", "1") != "0"
@@ -1098,9 +1207,37 @@ class _Step:
         self.fused = False
         self.order1 = self.order2 = None
         if self.prepared:
-            self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src)
-            self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar)
+            self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src, self.counts1)
+            self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar, self.counts2)
         self._lib = _lib.load()
+
+    def set_counts(self, counts1=None, counts2=None, nlines=None, src_order=None, tar_order=None):
+        """New count TENSORS for a ragged step (None keeps the current one; writing new values INTO the current tensors needs
+        no call at all -- the kernels read them).  A prepared step's orders must match the counts (every row's first
+        counts[b] entries a permutation of [0, counts[b])): they come along (src_order / tar_order), or are taken here from
+        the step's clouds; after an in-place write to counts1 write the new order into step.order1 in place as well.  A new
+        counts2 is a new target: its records are rebuilt by the next call (an in-place write to counts2 needs
+        invalidate_target(), like any write to the target the step cannot see)."""
+        Bt, (B, N, M, L) = self.Bt, self.dims
+        if counts1 is not None:
+            self.counts1 = check_counts(counts1, Bt, N, self.dev, "counts1")
+        if counts2 is not None:
+            self.counts2 = check_counts(counts2, Bt, M, self.dev, "counts2")
+            self._kept_key = None
+        if nlines is not None:
+            self.nlines = check_counts(nlines, Bt, L, self.dev, "nlines")
+        self.ragged = self.counts1 is not None or self.counts2 is not None or self.nlines is not None
+        _ragged_gate(self.ragged, chamfer=self.ride is not None, problems=self.poses > 1)
+        self._extra.update(counts1=self.counts1, counts2=self.counts2, nlines=self.nlines)
+        if self.prepared:
+            if counts1 is not None or src_order is not None:
+                self.order1 = _check_order(src_order, Bt, N, self.dev, "src_order") if src_order is not None \
+                    else cloud_order(self.src, self.counts1)
+            if counts2 is not None or tar_order is not None:
+                self.order2 = _check_order(tar_order, Bt, M, self.dev, "tar_order") if tar_order is not None \
+                    else cloud_order(self.tar, self.counts2)
+                self._kept_key = None
+        self._set_opts()
 
     def invalidate_target(self):
         """Forget the kept target: the next call rebuilds cloud 2's records and tree.  The step notices a changed target by
@@ -1130,6 +1267,8 @@ class _Step:
         op, key = self._optr, None
         if self.prepared:
             key = _write_key(self.tar) if (self.keep_target and target_from is None) else None
+            if key is not None and self.counts2 is not None:  # the target's row counts belong to its records
+                key = key + _write_key(self.counts2)
             kept = key is not None and key == self._kept_key
             if chain:
                 op = self._optr_c[2 if (kept and self._chain_ready) else (1 if kept else 0)]
@@ -1147,6 +1286,7 @@ class _Step:
         self._chain_ready = self.prepared and bool(self._chain_left.value & 1)
         self.fused = bool(self._chain_left.value & 2)  # THIS call's records + scans ran as one launch
         self.st.counts_cleared = self._chain_ready
+        self.st.ragged = self.ragged
         _IntersectionLoss.last_state = self.st
         if self.ride is not None:  # .chamfer_value: this step's monitor (it rode in the scan's launch, or one launch now)
             _keep_ride(self.st, self.ride)
@@ -1182,8 +1322,10 @@ class RegistrationStep(_Step):
 
     def __init__(self, src_tri, tar_tri, n_lines, rng=(1, 1, 5, 5), transpose_r=True, mode="cull", chunk=0,
                  want_payload=False, prepared=None, src_order=None, tar_order=None, reduce_mode=None, deterministic=None,
-                 sort_parts=None, chamfer=False, poses=1, chain=False):
-        """reduce_mode / deterministic / sort_parts: per-call options of THIS step object (include/rrl.h rrl_opts; None =
+                 sort_parts=None, chamfer=False, poses=1, chain=False, counts1=None, counts2=None, nlines=None):
+        """counts1 / counts2 / nlines: a ragged batch (ops.intersection_loss; _Step.set_counts) -- not with chamfer=True,
+        poses > 1 or target_from=.
+        reduce_mode / deterministic / sort_parts: per-call options of THIS step object (include/rrl.h rrl_opts; None =
         the library default) -- they travel with every call, so two steps with different options can run from two
         threads on two streams at the same time (tests/test_gpu_threads.py).
         poses = k > 1 (round 5): a MULTI-POSE step (rrl_opts.problems) -- every call takes R (k * B, 3, 3), t (k * B, 3): k
@@ -1193,7 +1335,7 @@ class RegistrationStep(_Step):
         chain: OFF by default here (see _Step): a chained step clears its hit counts on exit, and this step's state is
         what callers hand on as target_from= (RPM / FMR)."""
         super().__init__("RegistrationStep", src_tri, tar_tri, n_lines, rng, transpose_r, mode, chunk, prepared, src_order,
-                         tar_order, chamfer, poses, chain)
+                         tar_order, chamfer, poses, chain, counts1, counts2, nlines)
         self._extra.update(reduce_mode=reduce_mode, deterministic=deterministic, sort_parts=sort_parts)
         B, N, M, L = self.dims
         gacc = self.st.gacc
@@ -1227,11 +1369,12 @@ class RegistrationStep(_Step):
             raise ValueError(f"src_tri {(Bt, N, 9)} / tar_tri {(Bt, M, 9)} expected")
         if self.poses > 1 and target_from is not None:
             raise ValueError("a multi-pose step scans its target itself")
+        _ragged_gate(self.ragged, target_from=target_from)
         if self.prepared and (src_tri is not None or src_order is not None or tar_tri is not None or tar_order is not None):
             if src_tri is not None or src_order is not None:  # a new source: its order comes along, or is taken now
-                self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src)
+                self.order1 = _check_order(src_order, Bt, N, dev, "src_order") if src_order is not None else cloud_order(self.src, self.counts1)
             if tar_tri is not None or tar_order is not None:
-                self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar)
+                self.order2 = _check_order(tar_order, Bt, M, dev, "tar_order") if tar_order is not None else cloud_order(self.tar, self.counts2)
                 self._kept_key = None
             self._set_opts()
         op, key = self._pick(self.chain and RegistrationStep.ONE_CALL and target_from is None, target_from)
@@ -1275,8 +1418,10 @@ class LossStep(_Step):
 
     def __init__(self, src_tri, tar_tri, n_lines, rng=(1, 1, 5, 5), transpose_r=True, mode="cull", chunk=0,
                  prepared=None, src_order=None, tar_order=None, chamfer=False, want_payload=False, poses=1, chain=True,
-                 deterministic=None):
-        """deterministic=True (round 6; include/rrl.h rrl_set_deterministic): points1.grad accumulates in 64-bit fixed point and
+                 deterministic=None, counts1=None, counts2=None, nlines=None):
+        """counts1 / counts2 / nlines: a ragged batch (ops.intersection_loss; _Step.set_counts): the gradient rows beyond
+        counts1 are zero; a chained ragged step takes the plain four-launch build (same bits).  Not with chamfer=True or poses > 1.
+        deterministic=True (round 6; include/rrl.h rrl_set_deterministic): points1.grad accumulates in 64-bit fixed point and
         reproduces BIT FOR BIT from call to call (the float atomics of the default scatter agree only to their rounding order);
         the step then runs forward + scatter + a conversion launch (no chain, no riding backward).  None: the library default.
         chain=True (default; round 6, include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED): from its second call on, while the target is
@@ -1291,7 +1436,7 @@ class LossStep(_Step):
         poses = k > 1: a multi-pose step as RegistrationStep's -- R (k * B, 3, 3), t (k * B, 3) (required), loss (k * B,),
         grad (k * B, N, 9) = dL/d(moved triangles) of every instance."""
         super().__init__("LossStep", src_tri, tar_tri, n_lines, rng, transpose_r, mode, chunk, prepared, src_order,
-                         tar_order, chamfer, poses, chain)
+                         tar_order, chamfer, poses, chain, counts1, counts2, nlines)
         B, N, M, L = self.dims
         self.grad = torch.empty(B, N, 9, dtype=torch.float32, device=self.dev)
         # (in the workspace's accumulator field: the step's first launch clears it, as for RegistrationStep)
@@ -1599,6 +1744,7 @@ def chamfer_from_state(state=None, keys=False):
     st = state or _IntersectionLoss.last_state
     if st is None:
         raise ValueError("no loss evaluation to take the clouds from")
+    _refuse_ragged_state(st, "chamfer_from_state", _RAGGED_CHAMFER)
     ride = getattr(st, "cham_ride", None)
     if ride is not None:  # the walk rode in this evaluation's own scan launch (ChamferRide): nothing left to launch
         return (ride.val.reshape(()), ride.bx, ride.by) if keys else ride.val.reshape(())
@@ -1606,9 +1752,13 @@ def chamfer_from_state(state=None, keys=False):
     return (val.reshape(()), bx, by) if keys else val.reshape(())
 
 
+_RAGGED_CHAMFER = "evaluate the monitor per sample with ops.chamfer on the truncated clouds"
+
+
 def _chamfer_from_loss(st):
     """(ws, bx, by, val): rrl_chamfer_from_loss on the workspace of evaluation `st` (and of the state holding its
     target), into fresh buffers."""
+    _refuse_ragged_state(st, "the Chamfer monitor of a loss evaluation", _RAGGED_CHAMFER)
     B, N, M, L, _ = st.dims
     dev = st.ws.device
     tar = getattr(st, "target_state", None) or st
@@ -1632,6 +1782,7 @@ def chamfer_group_means(state=None, groups=1):
     st = state or _IntersectionLoss.last_state
     if st is None:
         raise ValueError("no loss evaluation to take the clouds from")
+    _refuse_ragged_state(st, "chamfer_group_means", _RAGGED_CHAMFER)
     B, N, M, L, _ = st.dims
     if B % groups:
         raise ValueError("groups must divide the evaluation's instances")
@@ -1658,11 +1809,15 @@ def dense_scan(tri, line):
     return norm_d, label.view(torch.bool), status
 
 
-def aabb(v):
-    """(B, n, 3) -> (B, 6) = min xyz, max xyz on the GPU."""
+def aabb(v, counts=None):
+    """(B, n, 3) -> (B, 6) = min xyz, max xyz on the GPU.  counts (ragged clouds; int32 (B,) on the GPU, or a list / CPU
+    tensor): over v[b, :counts[b]] only -- the other rows are not read; a zero count gives (+inf, -inf)."""
     vs = _prep(v, "vertices", 3)
     B, n, _ = vs.shape
     out = torch.empty(B, 6, device=vs.device)
+    if counts is not None:
+        _run(vs.device, "rrl_aabb_counted", _p(vs), _p(check_counts(counts, B, n, vs.device, "counts")), _p(out), B, n)
+        return out
     _run(vs.device, "rrl_aabb", _p(vs), _p(out), B, n)
     return out
 
@@ -1729,7 +1884,10 @@ def sample_lines(rands, r, centers, aabb1, aabb2, out=None, rng_shape=None):
     """rands (rounds, 4, B, n) uniform draws -> lines (B, n, 6), filled (B,) int32.
     rands=None with rng_shape=(rounds, B, n): the uniforms are drawn inside the kernels by the library's generator
     (sampler_rng) -- no (rounds, 4, B, n) tensor exists at all.
-    out: a contiguous fp32 (B, n, 6) GPU tensor to write the lines into (no extra copy)."""
+    out: a contiguous fp32 (B, n, 6) GPU tensor to write the lines into (no extra copy).
+    filled[b] = rows of sample b that hold a sampled line; the rest stays all-zero, and the reference evaluates those
+    all-zero rows as lines (so does every call here by default).  Passing `filled` as nlines= to intersection_loss /
+    registration_loss / the step objects drops them -- a deliberate deviation from the reference, hence opt-in."""
     dev = _home(out, rands, aabb1, aabb2, r)
     if rands is not None:
         rd = _prep(rands, "rands", None, dev)

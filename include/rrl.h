@@ -280,6 +280,24 @@ typedef struct rrl_opts {
      * otherwise. */
     int32_t problems;
     int32_t *chain_left;     /* NULL, or a HOST int32 that receives the two bits above at issue time (RRL_F_CHAIN) */
+    /* RAGGED batches: NULL (all rows), or DEVICE int32 [B] -- the number of source triangles, target triangles and lines
+     * sample b really has.  tri1 [B][N][9], tri2 [B][M][9], line [B][L][6] keep their meaning as capacities and strides;
+     * sample b is evaluated as if the call were B = 1 on tri1[b][0 .. count1[b]), tri2[b][0 .. count2[b]),
+     * line[b][0 .. nlines[b]): same loss bits, INFO row, median and hit lists.  Rows beyond a count are never interpreted
+     * (they may hold NaN, inf, anything): no hit, no tree node, no partial box, no line maximum, no NaN flag, gradient rows
+     * exactly zero.  A sample with a zero count has no populated bucket: loss 0, INFO[b][0] = 0.  The counts are read by
+     * the kernels (a workgroup-uniform load), never on the host -- a ragged call does not synchronise and can be captured
+     * in a graph; a kernel clamps a count to [0, capacity] (memory safety only).  A prepared order of a ragged cloud is
+     * [B][64 ceil(N / 64)] whose first count[b] entries are a permutation of [0, count[b]); the rest is not read.  With
+     * RRL_F_TARGET_KEPT count2 must hold what it held when the target was built.  A staged entry reads the counts of its
+     * OWN call's opts: the build count1 / count2, the scan all three -- the SAME values: the builds write nothing beyond a
+     * sample's last supergroup, so a scan with larger counts (or none) walks unwritten records --, the later stages none.
+     * For the same reason rrl_chamfer_from_loss must not be run on the workspace of a ragged call.  Workgroups of the builds and
+     * scans whose rows, supergroups or lines lie wholly beyond their sample's counts leave before their first load.
+     * A call with counts takes the plain four-launch step where a chained one was asked for (same bits), and is refused
+     * (RRL_E_ARG, before any launch) together with: pool != 0, problems (multi-pose), the Chamfer rider, target_ws, the
+     * wide entries, clouds beyond the sort capacity.  DESIGN.md "Ragged batches". */
+    const int32_t *count1, *count2, *nlines;
 } rrl_opts;
 
 size_t rrl_workspace_bytes(int B, int N, int M, int L);
@@ -393,6 +411,11 @@ int rrl_cloud_order(const float *tri, int32_t *order, void *ws, size_t ws_bytes,
 /* the same for point clouds pts [B][n][3] (the Chamfer monitor's inputs: rrl_chamfer_tree_fwd_ex); a cloud of
  * pseudo-triangles and the cloud of their first points have the same order */
 int rrl_cloud_order_points(const float *pts, int32_t *order, void *ws, size_t ws_bytes, int B, int n, void *stream);
+/* rrl_cloud_order for RAGGED clouds tri [B][n][9] (n = capacity): counts [B] device int32 (clamped to [0, n]); the first
+ * counts[b] entries of row b are a permutation of [0, counts[b]) -- rows beyond the count are not read --, the rest 0.
+ * counts == NULL: rrl_cloud_order. */
+int rrl_cloud_order_counted(const float *tri, const int32_t *counts, int32_t *order, void *ws, size_t ws_bytes, int B, int n,
+                            void *stream);
 
 /* The fused entries with per-call options (rrl_opts above; NULL = defaults = the plain entries). */
 int rrl_loss_forward_ex(const float *tri1, const float *tri2, const float *line, void *ws, size_t ws_bytes,
@@ -724,6 +747,10 @@ int rrl_dense_scan(const float *tri, const float *line, float *norm_d, uint8_t *
  *   tile_counts: scratch, 8-byte aligned, int32 [B * rounds * ceil(n/1024) * 32] (one 64-bit accept
  *     ballot per wavefront of every tile of 1024 candidates) */
 int rrl_aabb(const float *v, float *aabb, int B, int n, void *stream);
+/* ... over the first counts[b] points of sample b only (device int32 [B], clamped to [0, n]; n = capacity and stride):
+ * min / max are exact, so the box equals the one of a B = 1 call on the truncated cloud; a zero count gives (+inf, -inf).
+ * counts == NULL: every point. */
+int rrl_aabb_counted(const float *v, const int32_t *counts, float *aabb, int B, int n, void *stream);
 /* y = x R + t (rrl_rigid_apply_fwd, row layout) and aabb [B][6] of y (rrl_aabb) in one launch, one workgroup per
  * sample: for loops whose clouds are small enough that either is launch latency (the demo's epoch). */
 int rrl_rigid_apply_aabb(const float *x, const float *R, const float *t, float *y, float *aabb, int B, int n,
