@@ -51,8 +51,8 @@ static inline int rrl_fill(void *p, uint32_t word, size_t nbytes, hipStream_t s)
     size_t nb = (n + 255) / 256;
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(rrl_fill_words_kernel, dim3((unsigned)nb), dim3(256), 0, s, (uint32_t *)p, word, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    RRL_LAUNCH_CHECK();
+    return 0;
 }
 static inline int rrl_copy(void *d, const void *src, size_t nbytes, hipStream_t s) {
     const size_t n = nbytes / 4;
@@ -61,8 +61,8 @@ static inline int rrl_copy(void *d, const void *src, size_t nbytes, hipStream_t 
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(rrl_copy_words_kernel, dim3((unsigned)nb), dim3(256), 0, s, (uint32_t *)d,
                        (const uint32_t *)src, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    RRL_LAUNCH_CHECK();
+    return 0;
 }
 
 // Ragged batches (include/rrl.h rrl_opts.count1 / count2 / nlines): the rows sample b really has -- its entry of the call's

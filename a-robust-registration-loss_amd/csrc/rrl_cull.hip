@@ -902,8 +902,12 @@ __global__ __launch_bounds__(256) void big_sphere_kernel(const BuildArgs a) {
 typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load
 typedef const int __attribute__((address_space(4))) * kiptr;
 
-static BuildArgs make_build_args(const float *tri1, const float *tri2, void *ws, const WsLayout &w, int B, int N, int M,
-                                 int clouds, const RrlXform *xf, const float *line, int L, const RrlCall &o, bool chunked);
+static BuildArgs make_build_args(const RrlCall &o, const float *tri1, const float *tri2, int clouds, const float *line, bool chunked);
+// The grid of a culled scan: wavefronts per workgroup, supergroups per slice, the variant, line tiles, slices.
+struct CullGeom {
+    int waves, spw, tiles, slices;
+    bool fat, may_ride;
+};
 // polls (~1 us each) before a source-cloud workgroup of the chained step's launch gives up waiting for its records (RRL_CHAIN_SPIN)
 static unsigned rrl_chain_spin_limit(void) {
     static long v = -1;
@@ -945,12 +949,8 @@ namespace scan16 {
 }
 static_assert(scan8::kWPB == scan16::kWPB && scan8::kLPW == scan16::kLPW, "one line tiling for both variants");
 
-// The grid of a culled scan: wavefronts per workgroup, supergroups per slice, the variant, line tiles, slices.
-struct CullGeom {
-    int waves, spw, tiles, slices;
-    bool fat, may_ride;
-};
-static CullGeom cull_geometry(int B, int N, int M, int L, int clouds, const RrlCall &o) {
+static CullGeom cull_geometry(const RrlCall &o, int clouds) {
+    const int B = o.B, N = o.N, M = o.M, L = o.L;
     // a workgroup = (cloud and sample, tile of <= WPB x 128 lines, slice of spw supergroups).  With
     // few lines or small clouds the slices get thinner, so that the launch still has ~1000
     // workgroups for the 256 CUs (measured with tools/attic/geom_sweep.sh: thinner slices cost little,
@@ -988,14 +988,15 @@ static CullGeom cull_geometry(int B, int N, int M, int L, int clouds, const RrlC
 // Can the chained step's ONE launch (source records + target scan + source scan: cull_scan_build_kernel) serve this call?
 // Both clouds scanned here with full 512-lane workgroups, no rider, no counters; the caller (rrl_plan) checks the
 // rest (prepared orders, kept target, the per-line stage + tail kernel behind it).
-int rrl_cull_scan_can_fuse(int B, int N, int M, int L, const RrlCall &o) {
+int rrl_cull_scan_can_fuse(const RrlCall &o) {
+    const int B = o.B, N = o.N, M = o.M, L = o.L;
     if (B <= 0 || N <= 0 || M <= 0 || L <= 0 || (N > M ? N : M) > SORT_CAP) return 0;
     if (o.rider || o.counters || o.problems || o.tar_ws) return 0;
     // a ragged batch (rrl_opts.count1 / count2 / nlines): the ready count a source workgroup waits for is derived from the
     // capacity, and a records piece / source workgroup beyond its sample's rows leaves early -- the plain build serves (same bits)
     if (o.ragged()) return 0;
     if (const char *e = getenv("RRL_CHAIN")) if (e[0] == '0') return 0;  // (A/B runs)
-    const CullGeom g = cull_geometry(B, N, M, L, 2, o);
+    const CullGeom g = cull_geometry(o, 2);
     if (g.waves != scan8::kWPB) return 0;
     // Where the ONE launch pays (measured, profiles/r06_experiments.txt 2; us per step chained / plain): C2 45.8 / 49.8, B = 4
     // 40.9 / 42.9, B = 12 .. 32 at C2's shape 59.0 / 62.7 .. 110.8 / 116.5, the demo's shape 36.1 / 38.1, C4's 46.2 / 49.4 --
@@ -1015,21 +1016,19 @@ int rrl_cull_scan_can_fuse(int B, int N, int M, int L, const RrlCall &o) {
     return 1;
 }
 
-int rrl_launch_cull_scan(const float *line, void *ws, const WsLayout &w, int B, int N, int M, int L,
-                         int clouds, int lmax_ready, const RrlCall &o, hipStream_t s) {
-    const CullGeom g = cull_geometry(B, N, M, L, clouds, o);
-    if (o.plan.fused_build && (clouds != 2 || g.waves != scan8::kWPB)) return RRL_E_ARG;  // (rrl_cull_scan_can_fuse said otherwise)
-    if (!lmax_ready && !o.plan.fused_build)  // the triangles were prepared without the lines: their partial maxima first (a tiny launch)
-        hipLaunchKernelGGL(line_max_kernel, dim3(LMAX_CHUNKS, (unsigned)B), dim3(REC_BLK), 0, s, line, L,
-                           (float2 *)w.f32(ws, RRL_WS_LMAX), o.problems, o.nlines);
+int rrl_launch_cull_scan(const RrlCall &o, const float *line) {
+    const CullGeom g = cull_geometry(o, o.plan.clouds);
+    if (o.plan.fused_build && (o.plan.clouds != 2 || g.waves != scan8::kWPB)) return RRL_E_ARG;  // (rrl_cull_scan_can_fuse said otherwise)
+    if (!o.plan.lmax_ready && !o.plan.fused_build)  // the triangles were prepared without the lines: their partial maxima first (a tiny launch)
+        hipLaunchKernelGGL(line_max_kernel, dim3(LMAX_CHUNKS, (unsigned)o.B), dim3(REC_BLK), 0, o.s, line, o.L,
+                           (float2 *)o.f32(RRL_WS_LMAX), o.problems, o.nlines);
     // (A PERSISTENT variant -- as many workgroups as fit on the chip, each keeping one line tile staged and pulling
     // (cloud, slice) items from per-tile work queues, the next slice's records prefetched during the walk -- was built
     // and measured in round 3: exact, but 40.7 us against 30.4 at C2 and 29.0 against 13.8 at the demo's shape.  A slot
     // is held for the SLOWEST of a workgroup's eight wavefronts either way (16.5 us per item against a mean wavefront
     // lifetime of 12.4), so queueing the items removed no waiting, and the item barriers added some;
     // profiles/r03_scan_experiments.txt.)
-    return g.fat ? scan16::launch_variant(line, ws, w, B, N, M, L, clouds, o, s, g.waves, g.spw, g.tiles, g.slices, g.may_ride)
-                 : scan8::launch_variant(line, ws, w, B, N, M, L, clouds, o, s, g.waves, g.spw, g.tiles, g.slices, g.may_ride);
+    return g.fat ? scan16::launch_variant(o, line, g) : scan8::launch_variant(o, line, g);
 }
 // Executed-work counters (profiling; include/rrl.h rrl_scan_counters): while a buffer is set,
 // culled scans launch the COUNT instantiation and add to it.
@@ -1080,71 +1079,64 @@ static size_t sort_lds_bytes(int nsg, int parts, int raw_points) {
 
 // Launchers used by rrl_tri_prepare / rrl_line_tri_scan (rrl_scan.hip)
 // The arguments of a records launch (rrl_launch_tri_build; the chained step's fused launch, launch_variant).
-static BuildArgs make_build_args(const float *tri1, const float *tri2, void *ws, const WsLayout &w, int B, int N, int M,
-                                 int clouds, const RrlXform *xf, const float *line, int L, const RrlCall &o, bool chunked) {
+// clouds: the clouds this launch builds; line != NULL: it also reduces the lines' maxima
+static BuildArgs make_build_args(const RrlCall &o, const float *tri1, const float *tri2, int clouds, const float *line, bool chunked) {
+    const int B = o.B, N = o.N, M = o.M, L = o.L;
+    const RrlXform *xf = o.xf;
     const int nmax = clouds == 2 && M > N ? M : N;
     BuildArgs a;
     a.tri1 = xf ? xf->src : tri1;
     a.tri2 = tri2;
     a.R = xf ? xf->R : nullptr;
     a.t = xf ? xf->t : nullptr;
-    a.tri1_out = xf ? w.f32(ws, RRL_WS_TRI1) : nullptr;
-    a.ptri1 = w.f32(ws, RRL_WS_PTRI1);
-    a.ptri2 = w.f32(ws, RRL_WS_PTRI2);
-    a.crec1 = (float4 *)w.f32(ws, RRL_WS_CREC1);
-    a.crec2 = (float4 *)w.f32(ws, RRL_WS_CREC2);
-    a.apart = w.f32(ws, RRL_WS_APART);
-    a.p0s1 = (float4 *)w.f32(ws, RRL_WS_P0S1);
-    a.p0s2 = (float4 *)w.f32(ws, RRL_WS_P0S2);
-    a.idx1 = w.i32(ws, RRL_WS_IDX1);
-    a.idx2 = w.i32(ws, RRL_WS_IDX2);
-    a.grp1 = (float4 *)w.f32(ws, RRL_WS_GRP1);
-    a.grp2 = (float4 *)w.f32(ws, RRL_WS_GRP2);
-    a.pmax = (uint32_t *)w.i32(ws, RRL_WS_PMAX);
-    a.zero_base = (uint4 *)((char *)ws + w.off[RRL_WS_STATUS]);
-    a.zero_vec4 = w.zero_bytes / 16;
-    a.g1 = xf && xf->zero_g1 ? (uint4 *)((char *)ws + w.off[RRL_WS_GACC]) : nullptr;  // small: 12 B + 16 floats
-    a.g1_vec4 = a.g1 ? (w.off[RRL_WS_KJC] - w.off[RRL_WS_GACC]) / 16 : 0;
-    a.z2 = nmax > 4096 && !chunked ? (uint4 *)((char *)ws + w.off[RRL_WS_HISTG]) : nullptr;
+    a.tri1_out = xf ? o.f32(RRL_WS_TRI1) : nullptr;
+    a.ptri1 = o.f32(RRL_WS_PTRI1);
+    a.ptri2 = o.f32(RRL_WS_PTRI2);
+    a.crec1 = (float4 *)o.f32(RRL_WS_CREC1);
+    a.crec2 = (float4 *)o.f32(RRL_WS_CREC2);
+    a.apart = o.f32(RRL_WS_APART);
+    a.p0s1 = (float4 *)o.f32(RRL_WS_P0S1);
+    a.p0s2 = (float4 *)o.f32(RRL_WS_P0S2);
+    a.idx1 = o.i32(RRL_WS_IDX1);
+    a.idx2 = o.i32(RRL_WS_IDX2);
+    a.grp1 = (float4 *)o.f32(RRL_WS_GRP1);
+    a.grp2 = (float4 *)o.f32(RRL_WS_GRP2);
+    a.pmax = o.u32(RRL_WS_PMAX);
+    a.zero_base = (uint4 *)o.i32(RRL_WS_STATUS);
+    a.zero_vec4 = o.w.zero_bytes / 16;
+    a.g1 = xf && xf->zero_g1 ? (uint4 *)o.f32(RRL_WS_GACC) : nullptr;  // small: 12 B + 16 floats
+    a.g1_vec4 = a.g1 ? (o.w.off[RRL_WS_KJC] - o.w.off[RRL_WS_GACC]) / 16 : 0;
+    a.z2 = nmax > 4096 && !chunked ? (uint4 *)o.u32(RRL_WS_HISTG) : nullptr;
     a.z2_vec4 = a.z2 ? (size_t)2 * B * 2 * SORT_CELLS * sizeof(unsigned) / 16 : 0;
-    a.z3 = (uint4 *)((char *)ws + w.state_off);
-    a.z3_vec4 = w.state_bytes / 16;
+    a.z3 = (uint4 *)((char *)o.ws + o.w.state_off);
+    a.z3_vec4 = o.w.state_bytes / 16;
     a.z4 = (uint32_t *)o.clear_ptr;
     a.z4_words = o.clear_ptr ? o.clear_bytes / 4 : 0;
-    a.z5 = w.u32(ws, RRL_WS_CHAIN);
+    a.z5 = o.u32(RRL_WS_CHAIN);
     a.z5_words = (size_t)4 * B;
-    a.del1 = w.f32(ws, RRL_WS_DEL1);
-    a.del2 = w.f32(ws, RRL_WS_DEL2);
+    a.del1 = o.f32(RRL_WS_DEL1);
+    a.del2 = o.f32(RRL_WS_DEL2);
     a.zwords = nullptr; a.nzwords = 0;
     a.line = line;
-    a.lmax = line && L > 0 ? (float2 *)w.f32(ws, RRL_WS_LMAX) : nullptr;
+    a.lmax = line && L > 0 ? (float2 *)o.f32(RRL_WS_LMAX) : nullptr;
     a.L = L;
     a.B = B; a.N = N; a.M = M; a.clouds = clouds;
     a.transpose_r = xf ? xf->transpose_r : 0;
     a.Bt = o.problems;
     a.cnt1 = o.count1; a.cnt2 = o.count2; a.nlines = o.nlines;
-    a.xcd_align = 0;
+    // producer and consumer of a cloud's records on the same XCD (round 5: -0.7 us on the records launch, -0.5 us on the scan
+    // at C2; RRL_XCD_ALIGN=0 turns it off)
+    a.xcd_align = xcd_align_on() && (clouds * B) % 8 == 0 ? 1 : 0;
     const int nall = N > M ? N : M;  // APART is laid out for the larger cloud
     a.nblk = (nall + REC_BLK - 1) / REC_BLK;
     a.nchunk = chunked ? (nmax + 4095) / 4096 : 1;
     a.nblk_tri = (nmax + REC_BLK - 1) / REC_BLK;
-    {   // producer and consumer of a cloud's records on the same XCD (round 5: -0.7 us on the records launch, -0.5 us on the
-        // scan at C2; RRL_XCD_ALIGN=0 turns it off)
-        static int xa = -1;
-        if (xa < 0) {
-            xa = 1;
-#ifdef RRL_EXPERIMENT  // (A/B runs of the placement, experimental builds only)
-            if (const char *e = getenv("RRL_XCD_ALIGN")) xa = e[0] == '0' ? 0 : 1;
-#endif
-        }
-        a.xcd_align = xa && (clouds * B) % 8 == 0 ? 1 : 0;
-    }
     return a;
 }
 
-int rrl_launch_tri_build(const float *tri1, const float *tri2, void *ws, const WsLayout &w, int B,
-                         int N, int M, int clouds, const RrlXform *xf, const float *line, int L, const RrlCall &o,
-                         hipStream_t s) {
+int rrl_launch_tri_build(const RrlCall &o, const float *tri1, const float *tri2, const float *line) {
+    const int B = o.B, N = o.N, M = o.M, clouds = o.plan.build_clouds;
+    const hipStream_t s = o.s;
     const int nmax = clouds == 2 && M > N ? M : N;
     const size_t ngpmax = (size_t)(nmax + SGT - 1) / SGT * SGG;  // groups, padded to whole supergroups
     // Clouds of more than 4096 triangles: ONE launch of the single-workgroup sort per chunk of 4096 records
@@ -1160,38 +1152,38 @@ int rrl_launch_tri_build(const float *tri1, const float *tri2, void *ws, const W
     const size_t ngps = nmax <= 4096 ? ngpmax : (size_t)(4096 / GRP);
     const int parts = sort_parts((int)(ngps / SGG), o.sort_parts);
     const size_t lds = nmax <= 4096 || chunked ? sort_lds_bytes((int)(ngps / SGG), parts, 0) : 16;
-    BuildArgs a = make_build_args(tri1, tri2, ws, w, B, N, M, clouds, xf, line, L, o, chunked);
+    BuildArgs a = make_build_args(o, tri1, tri2, clouds, line, chunked);
     if (o.prepared()) {  // the order is known: ONE launch (records at their sorted positions + tree refit), no sort
         a.z2 = nullptr; a.z2_vec4 = 0;
         a.nblk_tri = (int)(((size_t)(nmax + SGT - 1) / SGT * SGT + REC_BLK - 1) / REC_BLK);
         hipLaunchKernelGGL(tri_records_sorted_kernel, dim3((unsigned)(a.nblk_tri * B * clouds + (a.lmax ? LMAX_CHUNKS * B : 0))),
                            dim3(REC_BLK), 0, s, a, o.order1, o.order2);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : (int)e;
+        RRL_LAUNCH_CHECK();
+        return 0;
     }
     hipLaunchKernelGGL(tri_records_kernel, dim3((unsigned)(a.nblk_tri * B * clouds + (a.lmax ? LMAX_CHUNKS * B : 0))),
                        dim3(REC_BLK), 0, s, a);
     if (nmax <= 4096 || chunked) {
         hipLaunchKernelGGL((tri_sort_kernel<4, false>), dim3((unsigned)(clouds * B * a.nchunk), (unsigned)parts), dim3(1024), lds, s, a);
     } else {  // wide three-launch sort (HISTG was cleared by tri_records_kernel)
-        unsigned *histg = (unsigned *)w.i32(ws, RRL_WS_HISTG);
+        unsigned *histg = o.u32(RRL_WS_HISTG);
         const dim3 gt((unsigned)((nmax + 255) / 256), (unsigned)B, (unsigned)clouds);
         hipLaunchKernelGGL(big_hist_kernel, gt, dim3(256), 0, s, a, histg);
         hipLaunchKernelGGL(big_scatter_kernel, gt, dim3(256), 0, s, a, histg);
         const dim3 gs((unsigned)((2 * ngpmax + 255) / 256), (unsigned)B, (unsigned)clouds);
         hipLaunchKernelGGL(big_sphere_kernel, gs, dim3(256), 0, s, a);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    RRL_LAUNCH_CHECK();
+    return 0;
 }
 
 // PMAX of a prepared build for consumers other than the culled scan (include/rrl.h rrl_tri_prepare_ex)
-int rrl_launch_pmax_from_partials(void *ws, const WsLayout &w, int B, int N, int M, int clouds, const RrlCall &o, hipStream_t s) {
-    const int nall = N > M ? N : M;
-    hipLaunchKernelGGL(pmax_from_partials_kernel, dim3((unsigned)(clouds * B)), dim3(64), 0, s, w.f32(ws, RRL_WS_APART),
-                       (uint32_t *)w.i32(ws, RRL_WS_PMAX), B, N, M, (nall + REC_BLK - 1) / REC_BLK, o.count1, o.count2);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+int rrl_launch_pmax_from_partials(const RrlCall &o, int clouds) {
+    const int nall = o.N > o.M ? o.N : o.M;
+    hipLaunchKernelGGL(pmax_from_partials_kernel, dim3((unsigned)(clouds * o.B)), dim3(64), 0, o.s, o.f32(RRL_WS_APART),
+                       o.u32(RRL_WS_PMAX), o.B, o.N, o.M, (nall + REC_BLK - 1) / REC_BLK, o.count1, o.count2);
+    RRL_LAUNCH_CHECK();
+    return 0;
 }
 
 // Sort + sphere tree for callers outside the loss workspace (the Chamfer path, rrl_chamfer.hip): the same
@@ -1230,8 +1222,8 @@ int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, f
         const dim3 gs((unsigned)((2 * ngpmax + 255) / 256), (unsigned)B, 2u);
         hipLaunchKernelGGL(big_sphere_kernel, gs, dim3(256), 0, s, a);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    RRL_LAUNCH_CHECK();
+    return 0;
 }
 
 int rrl_sort_capacity(void) { return SORT_CAP; }

@@ -994,49 +994,47 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
     STAMPR(6);
 }
 
+// The arguments of a culled scan over o.plan.clouds clouds; tws: the workspace that holds cloud 2's records (this call's, or
+// the one a riding walk takes a carried-over target from)
+static CullKArgs cull_args(const RrlCall &o, const float *line, const CullGeom &g, const void *tws) {
+    CullKArgs a;
+    a.ptri1 = o.f32(RRL_WS_PTRI1); a.ptri2 = o.w.f32(tws, RRL_WS_PTRI2);
+    a.p0s1 = (const float4 *)o.f32(RRL_WS_P0S1); a.p0s2 = (const float4 *)o.w.f32(tws, RRL_WS_P0S2);
+    a.idx1 = o.i32(RRL_WS_IDX1); a.idx2 = o.w.i32(tws, RRL_WS_IDX2);
+    a.tree1 = (const float4 *)o.f32(RRL_WS_GRP1); a.tree2 = (const float4 *)o.w.f32(tws, RRL_WS_GRP2);
+    a.line = line;
+    a.count1 = o.i32(RRL_WS_COUNT1); a.hit1 = o.i32(RRL_WS_HIT1);
+    a.count2 = o.i32(RRL_WS_COUNT2); a.hit2 = o.i32(RRL_WS_HIT2);
+    a.status = o.i32(RRL_WS_STATUS); a.pmax = o.u32(RRL_WS_PMAX);
+    a.del1 = o.f32(RRL_WS_DEL1); a.del2 = o.f32(RRL_WS_DEL2);
+    a.lmax = (const float2 *)o.f32(RRL_WS_LMAX);
+    a.apart = o.prepared() ? o.f32(RRL_WS_APART) : nullptr;  // prepared build: PMAX comes from the partial rows
+    a.aflag = o.f32(RRL_WS_APART); a.aflag_tar = o.w.f32(tws, RRL_WS_APART);
+    a.nblk_apart = ((o.N > o.M ? o.N : o.M) + REC_BLK - 1) / REC_BLK;
+    a.B = o.B; a.N = o.N; a.M = o.M; a.L = o.L; a.spw = g.spw;
+    a.gx = o.plan.clouds * o.B; a.gy = g.tiles; a.Bt = o.problems;
+    return a;
+}
+
 // The launch of THIS variant for a geometry chosen by rrl_launch_cull_scan: (waves per workgroup, supergroups per slice,
-// line tiles, slices); may_ride: the evaluation's Chamfer walk may be carried (full 512-lane workgroups).
-static int launch_variant(const float *line, void *ws, const WsLayout &w, int B, int N, int M, int L, int clouds,
-                          const RrlCall &o, hipStream_t s, int waves, int spw, int tiles, int zslices, bool may_ride) {
-#define RRL_CULL_LAUNCH(COUNT)                                                                              \
-    hipLaunchKernelGGL(cull_scan_kernel<COUNT>, dim3((unsigned)(clouds * B), (unsigned)tiles, (unsigned)zslices),   \
-                       dim3(64 * waves), 0, s, w.f32(ws, RRL_WS_PTRI1), w.f32(ws, RRL_WS_PTRI2),             \
-                       (const float4 *)w.f32(ws, RRL_WS_P0S1), (const float4 *)w.f32(ws, RRL_WS_P0S2),       \
-                       w.i32(ws, RRL_WS_IDX1), w.i32(ws, RRL_WS_IDX2), (const float4 *)w.f32(ws, RRL_WS_GRP1), \
-                       (const float4 *)w.f32(ws, RRL_WS_GRP2), line, w.i32(ws, RRL_WS_COUNT1),               \
-                       w.i32(ws, RRL_WS_HIT1), w.i32(ws, RRL_WS_COUNT2), w.i32(ws, RRL_WS_HIT2),             \
-                       w.i32(ws, RRL_WS_STATUS), (uint32_t *)w.i32(ws, RRL_WS_PMAX),                         \
-                       w.f32(ws, RRL_WS_DEL1), w.f32(ws, RRL_WS_DEL2), (const float2 *)w.f32(ws, RRL_WS_LMAX),   \
-                       apart, w.f32(ws, RRL_WS_APART), nblk_apart, B, N, M, L, spw,                          \
-                       o.counters, o.counter_rows, o.problems, o.count1, o.count2, o.nlines)
-    const float *apart = o.prepared() ? w.f32(ws, RRL_WS_APART) : nullptr;  // prepared build: PMAX comes from the partial rows
-    const int nblk_apart = ((N > M ? N : M) + REC_BLK - 1) / REC_BLK;
+// line tiles, slices); g.may_ride: the evaluation's Chamfer walk may be carried (full 512-lane workgroups).
+static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g) {
+    const int B = o.B, N = o.N, M = o.M, clouds = o.plan.clouds, waves = g.waves, spw = g.spw, tiles = g.tiles;
     if (o.plan.fused_build) {  // the chained step: source records + target scan + source scan as ONE launch (cull_scan_build_kernel)
         if (waves != WPB || clouds != 2 || !o.prepared()) return RRL_E_ARG;
-        CullKArgs a;
-        a.ptri1 = w.f32(ws, RRL_WS_PTRI1); a.ptri2 = w.f32(ws, RRL_WS_PTRI2);
-        a.p0s1 = (const float4 *)w.f32(ws, RRL_WS_P0S1); a.p0s2 = (const float4 *)w.f32(ws, RRL_WS_P0S2);
-        a.idx1 = w.i32(ws, RRL_WS_IDX1); a.idx2 = w.i32(ws, RRL_WS_IDX2);
-        a.tree1 = (const float4 *)w.f32(ws, RRL_WS_GRP1); a.tree2 = (const float4 *)w.f32(ws, RRL_WS_GRP2);
-        a.line = line;
-        a.count1 = w.i32(ws, RRL_WS_COUNT1); a.hit1 = w.i32(ws, RRL_WS_HIT1);
-        a.count2 = w.i32(ws, RRL_WS_COUNT2); a.hit2 = w.i32(ws, RRL_WS_HIT2);
-        a.status = nullptr; a.pmax = (uint32_t *)w.i32(ws, RRL_WS_PMAX);
-        a.del1 = w.f32(ws, RRL_WS_DEL1); a.del2 = w.f32(ws, RRL_WS_DEL2);
-        a.lmax = (const float2 *)w.f32(ws, RRL_WS_LMAX);  // (not read: the tile's own maxima)
-        a.apart = apart; a.aflag = w.f32(ws, RRL_WS_APART); a.aflag_tar = a.aflag;
-        a.nblk_apart = nblk_apart; a.B = B; a.N = N; a.M = M; a.L = L; a.spw = spw;
-        a.gx = 2 * B; a.gy = tiles; a.Bt = 0;
+        CullKArgs a = cull_args(o, line, g, o.ws);  // (lmax is not read: the tile's own maxima; no multi-pose: rrl_cull_scan_can_fuse)
+        a.status = nullptr;
         // the source's records body: the arguments of a records launch of cloud 1 alone, in 512-lane pieces; it clears what
         // no scan workgroup of this launch touches: NSEL (+ NVALS), the reduce's state, the accumulators, the gradient target
-        BuildArgs bld = ::make_build_args(o.tri1_in, nullptr, ws, w, B, N, M, 1, o.xf, nullptr, 0, o, false);
+        BuildArgs bld = ::make_build_args(o, o.tri1_in, nullptr, 1, nullptr, false);
+        bld.L = 0;
         bld.nblk_tri = (int)(((size_t)(N + SGT - 1) / SGT * SGT + 64 * WPB - 1) / (64 * WPB));
-        bld.zero_base = (uint4 *)((char *)ws + w.off[RRL_WS_NVALS]);
-        bld.zero_vec4 = (w.off[RRL_WS_PMAX] - w.off[RRL_WS_NVALS]) / 16;
+        bld.zero_base = (uint4 *)o.i32(RRL_WS_NVALS);
+        bld.zero_vec4 = (o.w.off[RRL_WS_PMAX] - o.w.off[RRL_WS_NVALS]) / 16;
         bld.z2 = nullptr; bld.z2_vec4 = 0;
         bld.z5 = nullptr; bld.z5_words = 0;
         ChainKArgs ch;
-        ch.chain = w.u32(ws, RRL_WS_CHAIN);
+        ch.chain = o.u32(RRL_WS_CHAIN);
         ch.nrec_b = bld.nblk_tri;
         ch.zrec = (bld.nblk_tri + tiles - 1) / tiles;
         const int nsg1 = (N + SGT - 1) / SGT, nsg2 = (M + SGT - 1) / SGT;
@@ -1048,50 +1046,42 @@ static int launch_variant(const float *line, void *ws, const WsLayout &w, int B,
         if (const char *e = getenv("RRL_CHAIN_EXP")) ch.exp = atoi(e);
 #endif
         hipLaunchKernelGGL(cull_scan_build_kernel, dim3((unsigned)B, (unsigned)tiles, (unsigned)(ch.zrec + ch.z2 + z1)), dim3(64 * WPB), 0,
-                           s, a.ptri1, a.ptri2, a.p0s1, a.p0s2, a.idx1, a.idx2, a.tree1, a.tree2, a.line, a.count1, a.hit1, a.count2,
-                           a.hit2, a.pmax, a.del1, a.del2, a.apart, a.nblk_apart, B, N, M, L, spw, bld, o.order1, ch);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : (int)e;
+                           o.s, a.ptri1, a.ptri2, a.p0s1, a.p0s2, a.idx1, a.idx2, a.tree1, a.tree2, a.line, a.count1, a.hit1, a.count2,
+                           a.hit2, a.pmax, a.del1, a.del2, a.apart, a.nblk_apart, a.B, a.N, a.M, a.L, a.spw, bld, o.order1, ch);
+        RRL_LAUNCH_CHECK();
+        return 0;
     }
-    if (may_ride && waves == WPB) {
+    if (g.may_ride && waves == WPB) {
         // the evaluation's Chamfer walk rides along (cull_scan_chamfer_kernel): ONE launch for both.  A carried-over target
         // (clouds == 1: only the source is scanned here) is walked in the workspace that holds its records.
-        const void *tws = clouds == 2 ? ws : o.tar_ws;
         const ChamLayout C(B, N, M);
         if (o.rider->ws && o.rider->ws_bytes >= C.total && o.rider->best_x && o.rider->best_y && o.rider->value) {
-            CullKArgs a;
-            a.ptri1 = w.f32(ws, RRL_WS_PTRI1); a.ptri2 = w.f32(tws, RRL_WS_PTRI2);
-            a.p0s1 = (const float4 *)w.f32(ws, RRL_WS_P0S1); a.p0s2 = (const float4 *)w.f32(tws, RRL_WS_P0S2);
-            a.idx1 = w.i32(ws, RRL_WS_IDX1); a.idx2 = w.i32(tws, RRL_WS_IDX2);
-            a.tree1 = (const float4 *)w.f32(ws, RRL_WS_GRP1); a.tree2 = (const float4 *)w.f32(tws, RRL_WS_GRP2);
-            a.line = line;
-            a.count1 = w.i32(ws, RRL_WS_COUNT1); a.hit1 = w.i32(ws, RRL_WS_HIT1);
-            a.count2 = w.i32(ws, RRL_WS_COUNT2); a.hit2 = w.i32(ws, RRL_WS_HIT2);
-            a.status = w.i32(ws, RRL_WS_STATUS); a.pmax = (uint32_t *)w.i32(ws, RRL_WS_PMAX);
-            a.del1 = w.f32(ws, RRL_WS_DEL1); a.del2 = w.f32(ws, RRL_WS_DEL2);
-            a.lmax = (const float2 *)w.f32(ws, RRL_WS_LMAX);
-            a.apart = apart; a.aflag = w.f32(ws, RRL_WS_APART); a.aflag_tar = w.f32(tws, RRL_WS_APART);
-            a.nblk_apart = nblk_apart; a.B = B; a.N = N; a.M = M; a.L = L; a.spw = spw;
-            a.gx = clouds * B; a.gy = tiles; a.Bt = o.problems;
+            const CullKArgs a = cull_args(o, line, g, clouds == 2 ? o.ws : o.tar_ws);
             ChamKArgs c;
             char *cw = (char *)o.rider->ws;
             c.best_x = (unsigned long long *)o.rider->best_x; c.best_y = (unsigned long long *)o.rider->best_y;
             c.partial = (double *)(cw + C.partial); c.gpart = (double *)(cw + C.gpart);
             c.value = o.rider->value;
             c.denom = (double)B * (double)(N + M);
-            uint32_t *mctl = w.u32(ws, RRL_WS_MCTL);  // arrival counters of the walk's mean (rrl_chamfer_from_loss_ex)
+            uint32_t *mctl = o.u32(RRL_WS_MCTL);  // arrival counters of the walk's mean (rrl_chamfer_from_loss_ex)
             c.tick = ChamTick{mctl + 32, mctl + 30, 64, 1};
             c.gx = 2 * B; c.gy = ((N > M ? N : M) + SGT - 1) / SGT;  // patches of the larger cloud (either direction)
-            const unsigned nwg = (unsigned)(c.gx * c.gy) + (unsigned)(a.gx * a.gy * zslices);
-            hipLaunchKernelGGL(cull_scan_chamfer_kernel, dim3(nwg), dim3(64 * WPB), 0, s, a, c);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) o.rider->done = 1;
-            return e == hipSuccess ? 0 : (int)e;
+            const unsigned nwg = (unsigned)(c.gx * c.gy) + (unsigned)(a.gx * a.gy * g.slices);
+            hipLaunchKernelGGL(cull_scan_chamfer_kernel, dim3(nwg), dim3(64 * WPB), 0, o.s, a, c);
+            RRL_LAUNCH_CHECK();
+            o.rider->done = 1;
+            return 0;
         }
     }
+    const CullKArgs a = cull_args(o, line, g, o.ws);
+#define RRL_CULL_LAUNCH(COUNT)                                                                                          \
+    hipLaunchKernelGGL(cull_scan_kernel<COUNT>, dim3((unsigned)a.gx, (unsigned)a.gy, (unsigned)g.slices), dim3(64 * waves), 0,  \
+                       o.s, a.ptri1, a.ptri2, a.p0s1, a.p0s2, a.idx1, a.idx2, a.tree1, a.tree2, a.line, a.count1, a.hit1,     \
+                       a.count2, a.hit2, a.status, a.pmax, a.del1, a.del2, a.lmax, a.apart, a.aflag, a.nblk_apart, a.B, a.N,  \
+                       a.M, a.L, a.spw, o.counters, o.counter_rows, a.Bt, o.count1, o.count2, o.nlines)
     if (o.counters) RRL_CULL_LAUNCH(true);
     else RRL_CULL_LAUNCH(false);
 #undef RRL_CULL_LAUNCH
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    RRL_LAUNCH_CHECK();
+    return 0;
 }

@@ -17,12 +17,36 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
     if (!a || a->struct_bytes < (int32_t)offsetof(rrl_demo_epoch_args, pipeline)) return RRL_E_ARG;  // (pipeline: appended in round 4b)
     const int N = a->N, M = a->M, L = a->L;
     if (N <= 0 || M <= 0 || L <= 0 || a->rounds <= 0) return RRL_E_ARG;
-    if (rrl_resolve_opts(a->opts).ragged()) return RRL_E_ARG;  // (one sample, the sampler's own line set: no counts)
+    // the record of the epoch's fused step: one sample, the reference's bucket range, scan mode cull
+    RrlCall o = rrl_begin_call(a->opts, 1, N, M, L, a->ws, a->ws_bytes, stream);
+    if (o.ragged()) return RRL_E_ARG;  // (one sample, the sampler's own line set: no counts)
     const char *env = getenv("RRL_DEMO_RIDE");  // (read per call: tests switch it between epochs) 0: no launch carries another's work
     const bool rides = !(env && env[0] == '0');
     int32_t *pipe = a->struct_bytes >= (int32_t)sizeof(rrl_demo_epoch_args) && rides ? a->pipeline : nullptr;
     if (pipe && ((long)((L + 1023) / 1024) * a->rounds >= 512 || L <= 1024)) pipe = nullptr;  // (the rider's limits: rrl_plan)
-    int rc;
+    // The Chamfer monitor needs the step's records launch only (the sorted moved source + the kept target), and launches of
+    // one stream never overlap on this stack: its walk RIDES in the culled scan's launch (rrl_ws.h RrlChamRider; same
+    // arithmetic, same value) -- one launch and ~12 us per epoch less.  RRL_DEMO_RIDE=0: the separate launch, as before.
+    RrlChamRider rider = {a->cham_ws, a->cham_ws_bytes, a->best_x, a->best_y, a->cham_value, 0};
+    o.rider = rides ? &rider : nullptr;
+    // ... and so does the NEXT epoch's count pass, in the per-line launch (RrlCountRider): it samples against the moved source
+    // of THIS epoch (code/test_demo_optimized_Lie_Algebra.py:46-51), whose box is in the records launch's partial rows
+    const float *rows = o.f32(RRL_WS_APART);  // cloud 1, sample 0: the moved first points' partial boxes
+    RrlCountRider counter = {(const unsigned long long *)a->rng_state, a->radius, a->centers, a->box2, rows,
+                             (N + 255) / 256, (unsigned long long *)a->tile_counts, L, a->rounds, 0};
+    // ... and its WRITE pass in the direct backward's launch (RrlWriteRider): the ballots are there by then (the per-line
+    // launch precedes it), and nothing after the per-line stage reads the line buffer it overwrites
+    RrlWriteRider writer = {(unsigned long long *)a->rng_state, a->radius, a->centers, (const unsigned long long *)a->tile_counts,
+                            a->lines, a->filled, L, a->rounds, 0};
+    if (pipe && (((uintptr_t)a->tile_counts) & 7) == 0) {
+        o.count_rider = &counter;
+        o.write_rider = &writer;
+    }
+    // the step's refusals before the epoch's first launch (the sampler's)
+    const RrlXform xf = {a->src_tri, a->R, a->T, a->transpose_r, 1};
+    const bool pointers = a->src_tri && a->R && a->T && a->tar_tri && a->lines && a->loss && a->grad_loss && a->gR && a->gt;
+    int rc = rrl_check_call(o, pointers, RRL_WANT_DIRECT, nullptr, &xf);
+    if (rc) return rc;
     if (pipe && *pipe == 3) {  // ... and its backward launch the write pass too: this epoch's lines are in place
         rc = 0;
     } else if (pipe && (*pipe & 1)) {  // the previous epoch's per-line launch carried this epoch's count pass: the write pass remains
@@ -33,29 +57,7 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
     }
     if (a->pipeline && a->struct_bytes >= (int32_t)sizeof(rrl_demo_epoch_args)) *a->pipeline = 0;
     if (rc) return rc;
-    // The Chamfer monitor needs the step's records launch only (the sorted moved source + the kept target), and launches of
-    // one stream never overlap on this stack: its walk RIDES in the culled scan's launch (rrl_ws.h RrlChamRider; same
-    // arithmetic, same value) -- one launch and ~12 us per epoch less.  RRL_DEMO_RIDE=0: the separate launch, as before.
-    RrlCall o = rrl_resolve_opts(a->opts);
-    RrlChamRider rider = {a->cham_ws, a->cham_ws_bytes, a->best_x, a->best_y, a->cham_value, 0};
-    o.rider = rides ? &rider : nullptr;
-    // ... and so does the NEXT epoch's count pass, in the per-line launch (RrlCountRider): it samples against the moved source
-    // of THIS epoch (code/test_demo_optimized_Lie_Algebra.py:46-51), whose box is in the records launch's partial rows
-    const WsLayout wl(1, N, M, L);
-    if (a->ws_bytes < wl.total) return RRL_E_WS;
-    RrlCountRider counter = {(const unsigned long long *)a->rng_state, a->radius, a->centers, a->box2, wl.f32(a->ws, RRL_WS_APART),
-                             (N + 255) / 256, (unsigned long long *)a->tile_counts, L, a->rounds, 0};
-    // ... and its WRITE pass in the direct backward's launch (RrlWriteRider): the ballots are there by then (the per-line
-    // launch precedes it), and nothing after the per-line stage reads the line buffer it overwrites
-    RrlWriteRider writer = {(unsigned long long *)a->rng_state, a->radius, a->centers, (const unsigned long long *)a->tile_counts,
-                            a->lines, a->filled, L, a->rounds, 0};
-    if (pipe && (((uintptr_t)a->tile_counts) & 7) == 0) {
-        o.count_rider = &counter;
-        o.write_rider = &writer;
-    }
-    rc = rrl_registration_step_call(a->src_tri, a->R, a->T, a->tar_tri, a->lines, a->ws, a->ws_bytes, a->loss, a->grad_loss,
-                                    a->gR, a->gt, nullptr, 1, N, M, L, a->transpose_r, 1, 1, 5, 5, RRL_SCAN_CULL, 0, nullptr, o,
-                                    stream);
+    rc = rrl_registration_step_call(o, xf, a->tar_tri, a->lines, a->loss, a->grad_loss, a->gR, a->gt, nullptr);
     if (rc) return rc;
     if (pipe) *pipe = counter.done ? (writer.done ? 3 : 1) : 0;  // (a write pass without its count pass cannot have ridden)
     if (!rider.done) {
@@ -63,10 +65,7 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
                                    a->cham_value, stream);
         if (rc) return rc;
     }
-    const WsLayout w(1, N, M, L);
-    if (a->ws_bytes < w.total) return RRL_E_WS;
-    const int32_t *info = w.i32(a->ws, RRL_WS_INFO);        // gate: the loss's bucket count (`if loss_di is not None`)
-    const float *rows = w.f32(a->ws, RRL_WS_APART);         // cloud 1, sample 0: the moved first points' partial boxes
+    const int32_t *info = o.i32(RRL_WS_INFO);  // gate: the loss's bucket count (`if loss_di is not None`)
     return rrl_se3_adam_step(a->xi, a->gR, a->gt, a->m, a->v, a->adam_state, a->lr, info, a->b1, a->b2, a->eps, a->R, a->T,
                              nullptr, a->loss, a->cham_value, a->table, a->cursor, a->table_rows, a->row, rows,
                              (N + 255) / 256, a->box1, stream);

@@ -314,13 +314,12 @@ __global__ __launch_bounds__(256) void reg_bwd_kernel(const float *__restrict__ 
 // G1 in the forward)
 int rrl_fused_backward(int B, int N, int M) { return B > 0 && N > 0 && (N > M ? N : M) <= rrl_sort_capacity(); }
 
-int rrl_launch_reg_bwd(const float *src, const float *R, float *g1, float *grad_src, float *partial,
-                       float *gR, float *gt, float *payload, const float *loss, const int32_t *info,
-                       int32_t *done, int B, int N, int transpose_r, const int32_t *count1, hipStream_t s) {
-    const int n = 3 * N;
-    hipLaunchKernelGGL(reg_bwd_kernel, dim3((unsigned)((n + REG_BWD_PTS - 1) / REG_BWD_PTS), (unsigned)B),
-                       dim3(256), 0, s, src, R, g1, grad_src, partial, gR, gt, payload, loss, info, done, n,
-                       B, transpose_r, count1);
+int rrl_launch_reg_bwd(const RrlCall &o, const float *src, const float *R, float *grad_src, float *gR, float *gt,
+                       float *payload, const float *loss, int transpose_r) {
+    const int n = 3 * o.N;
+    hipLaunchKernelGGL(reg_bwd_kernel, dim3((unsigned)((n + REG_BWD_PTS - 1) / REG_BWD_PTS), (unsigned)o.B), dim3(256), 0, o.s,
+                       src, R, o.f32(RRL_WS_G1), grad_src, o.f32(RRL_WS_RPART), gR, gt, payload, loss, o.i32(RRL_WS_INFO),
+                       o.i32(RRL_WS_STATUS) + 3, n, o.B, transpose_r, o.count1);
     RRL_LAUNCH_CHECK();
     return 0;
 }

@@ -316,8 +316,8 @@ static int cloud_order_impl(const float *tri, int stride, int32_t *order, void *
     }
     const int W = P < KD_WIN ? P : KD_WIN;
     hipLaunchKernelGGL(kd_window_kernel, dim3((unsigned)(P / W), (unsigned)B), dim3(KD_THREADS), 0, s, tri, idx_g, order, n, npad, P, W, W, stride);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    RRL_LAUNCH_CHECK();
+    return 0;
 }
 extern "C" int rrl_cloud_order(const float *tri, int32_t *order, void *ws, size_t ws_bytes, int B, int n, void *stream) {
     return cloud_order_impl(tri, 9, order, ws, ws_bytes, B, n, stream);

@@ -124,68 +124,56 @@ __global__ __launch_bounds__(64) void tri_prepare_kernel(const float *__restrict
     }
 }
 
-int rrl_launch_pmax_from_partials(void *ws, const WsLayout &w, int B, int N, int M, int clouds, const RrlCall &o, hipStream_t s);
-int rrl_launch_tri_build(const float *tri1, const float *tri2, void *ws, const WsLayout &w, int B,
-                         int N, int M, int clouds, const RrlXform *xf, const float *line, int L, const RrlCall &o,
-                         hipStream_t s);
-int rrl_launch_cull_scan(const float *line, void *ws, const WsLayout &w, int B, int N, int M, int L,
-                         int clouds, int lmax_ready, const RrlCall &o, hipStream_t s);
-
-// clouds = 2: both clouds; clouds = 1: the source only (the target's scan results are carried
-// over from an earlier call with the same target and lines, see rrl_loss_forward_cached).  The
-// sorted/legacy decision always looks at both sizes so that a cached call takes the same path.
-// xf != NULL: the source is xf->src moved by (xf->R, xf->t); the moved triangles land in TRI1
+// The build of a checked call.  o.plan.build_clouds = 2: both clouds; 1: the source only (the target's scan results are
+// carried over from an earlier call with the same target and lines, see rrl_loss_forward_cached, or its records are kept).
+// The sorted/legacy decision always looks at both sizes so that a cached call takes the same path.
+// o.xf != NULL: the source is xf->src moved by (xf->R, xf->t); the moved triangles land in TRI1
 // (`tri1` is ignored).  Sorted path: ONE launch (tri_build_kernel) does transform + records +
-// state clearing + sort + spheres.  Legacy path (a cloud > 65536 triangles): rigid apply,
+// state clearing + sort + spheres.  Legacy path (a cloud beyond the sort capacity): rigid apply,
 // memset, tri_prepare_kernel<LEGACY>.
 // line != NULL: the records kernel also reduces the samples' lines to the partial maxima the culled scan derives its
 // slacks from (the fused forwards); NULL: the scan entry does that itself (rrl_tri_prepare + rrl_line_tri_scan).
-int rrl_tri_prepare_clouds(const float *tri1, const float *tri2, void *ws, size_t ws_bytes, int B,
-                           int N, int M, int L, int clouds, const RrlXform *xf, const float *line, const RrlCall &o,
-                           void *stream) {
-    if ((!tri1 && !xf) || !tri2 || !ws || B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
-    hipStream_t s = (hipStream_t)stream;
+int rrl_tri_prepare_clouds(const RrlCall &o, const float *tri1, const float *tri2, const float *line) {
+    const int B = o.B, N = o.N, M = o.M, clouds = o.plan.build_clouds;
+    const RrlXform *xf = o.xf;
     const bool sorted = rrl_sorted_layout(N, M);
     const int nmax = clouds == 2 && M > N ? M : N;
-    uint4 *zb = (uint4 *)((char *)ws + w.off[RRL_WS_STATUS]);
+    uint4 *zb = (uint4 *)o.i32(RRL_WS_STATUS);
     if (!sorted || B == 0 || nmax == 0) {
         // one fill clears status, nvals, nsel, pmax, count1, count2 (contiguous by construction)
-        int rc = rrl_fill(zb, 0u, w.zero_bytes, s);
+        int rc = rrl_fill(zb, 0u, o.w.zero_bytes, o.s);
         if (rc) return rc;
         // ... and one more the tiled reduce's state (MHIST, MCTL, MSUM)
-        if ((rc = rrl_fill((char *)ws + w.state_off, 0u, w.state_bytes, s))) return rc;
-        if (o.clear_ptr && (rc = rrl_fill(o.clear_ptr, 0u, o.clear_bytes, s))) return rc;
+        if ((rc = rrl_fill((char *)o.ws + o.w.state_off, 0u, o.w.state_bytes, o.s))) return rc;
+        if (o.clear_ptr && (rc = rrl_fill(o.clear_ptr, 0u, o.clear_bytes, o.s))) return rc;
     }
     if (B == 0 || nmax == 0) return 0;
-    if (sorted) return rrl_launch_tri_build(tri1, tri2, ws, w, B, N, M, clouds, xf, line, L, o, s);
+    if (sorted) return rrl_launch_tri_build(o, tri1, tri2, line);
     if (xf) {
         if (xf->zero_g1) {
-            int rc = rrl_fill(w.f32(ws, RRL_WS_GACC), 0u, w.off[RRL_WS_KJC] - w.off[RRL_WS_GACC], s);
+            int rc = rrl_fill(o.f32(RRL_WS_GACC), 0u, o.w.off[RRL_WS_KJC] - o.w.off[RRL_WS_GACC], o.s);
             if (rc) return rc;
         }
-        tri1 = w.f32(ws, RRL_WS_TRI1);
-        int rc = rrl_rigid_apply_fwd(xf->src, xf->R, xf->t, w.f32(ws, RRL_WS_TRI1), B, 3 * N,
-                                     xf->transpose_r, 0, stream);
+        tri1 = o.f32(RRL_WS_TRI1);
+        int rc = rrl_rigid_apply_fwd(xf->src, xf->R, xf->t, o.f32(RRL_WS_TRI1), B, 3 * N, xf->transpose_r, 0, o.s);
         if (rc) return rc;
     }
     dim3 grid((unsigned)((nmax + 63) / 64), (unsigned)B, (unsigned)clouds);
-    hipLaunchKernelGGL(tri_prepare_kernel<true>, grid, dim3(64), 0, s, tri1, tri2,
-                       w.f32(ws, RRL_WS_PTRI1), w.f32(ws, RRL_WS_PTRI2),
-                       (uint32_t *)w.i32(ws, RRL_WS_PMAX), zb, (size_t)0, (size_t)0, (size_t)0, B, N, M);
+    hipLaunchKernelGGL(tri_prepare_kernel<true>, grid, dim3(64), 0, o.s, tri1, tri2,
+                       o.f32(RRL_WS_PTRI1), o.f32(RRL_WS_PTRI2),
+                       (uint32_t *)o.i32(RRL_WS_PMAX), zb, (size_t)0, (size_t)0, (size_t)0, B, N, M);
     RRL_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int rrl_tri_prepare_ex(const float *tri1, const float *tri2, void *ws, size_t ws_bytes,
                                   int B, int N, int M, int L, const rrl_opts *opts, void *stream) {
-    RrlCall o = rrl_resolve_opts(opts);
-    if (const int prc = rrl_plan(o, B, N, M, L, 0, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE)) return prc;  // (prepared orders: both, sorted layout)
-    int rc = rrl_tri_prepare_clouds(tri1, tri2, ws, ws_bytes, B, N, M, L, 2, nullptr, nullptr, o, stream);
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    if (const int rc = rrl_check_call(o, tri1 && tri2, RRL_WANT_STAGE)) return rc;  // (prepared orders: both, sorted layout)
+    const int rc = rrl_tri_prepare_clouds(o, tri1, tri2, nullptr);
     if (rc || !o.prepared() || B <= 0 || (N <= 0 && M <= 0)) return rc;
     // prepared build: PMAX is normally reduced by the culled scan's prologue; a stage call leaves it complete itself
-    return rrl_launch_pmax_from_partials(ws, WsLayout(B, N, M, L), B, N, M, 2, o, (hipStream_t)stream);
+    return rrl_launch_pmax_from_partials(o, 2);
 }
 extern "C" int rrl_tri_prepare(const float *tri1, const float *tri2, void *ws, size_t ws_bytes,
                                int B, int N, int M, int L, void *stream) {
@@ -431,23 +419,17 @@ extern "C" int rrl_scan_timing_collect(float *ms, int max_n) {
     return n;
 }
 
-int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B, int N, int M, int L,
-                             int mode, int chunk, int clouds, int lmax_ready, const RrlCall &o, void *stream) {
-    if (!line || !ws || B < 0 || N < 0 || M < 0 || L < 0 || chunk < 0) return RRL_E_ARG;
-    if (mode != RRL_SCAN_STRICT && mode != RRL_SCAN_LAZY && mode != RRL_SCAN_AUTO &&
-        mode != RRL_SCAN_CULL)
-        return RRL_E_ARG;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
+// The scan of a checked call: o.plan.scan_mode over o.plan.clouds clouds (1: the target's scan is carried over);
+// o.plan.lmax_ready: the records launch reduced the lines' maxima
+int rrl_line_tri_scan_clouds(const RrlCall &o, const float *line) {
+    const int B = o.B, N = o.N, M = o.M, L = o.L, mode = o.plan.scan_mode, clouds = o.plan.clouds;
     if (B == 0 || L == 0 || (N == 0 && (M == 0 || clouds == 1))) return 0;
-    if (mode == RRL_SCAN_CULL && !rrl_sorted_layout(N, M)) mode = RRL_SCAN_AUTO;  // (the wide pipeline's calls: no plan)
-    hipStream_t s = (hipStream_t)stream;
     const bool timed = g_timing_on && (g_timing_seen++ % g_timing_on) == 0 && g_timing_n < TIMING_RING;
     if (mode == RRL_SCAN_CULL) {  // one launch: sphere-culled scan with an inline strict fallback
-        if (timed) (void)hipEventRecord(g_ev[g_timing_n][0], s);
-        int rc = rrl_launch_cull_scan(line, ws, w, B, N, M, L, clouds, lmax_ready, o, s);
+        if (timed) (void)hipEventRecord(g_ev[g_timing_n][0], o.s);
+        int rc = rrl_launch_cull_scan(o, line);
         if (rc) return rc;
-        if (timed) (void)hipEventRecord(g_ev[g_timing_n++][1], s);
+        if (timed) (void)hipEventRecord(g_ev[g_timing_n++][1], o.s);
         return 0;
     }
     int R = o.scan_variant;
@@ -459,6 +441,7 @@ int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B
         R = v ? atoi(v) : 0;
         if (R != 1 && R != 2 && R != 4 && R != 8) R = 4;  // measured best for every mode (profiles/r02_scan_sweep.jsonl)
     }
+    int chunk = o.chunk;
     if (chunk == 0) {
         const char *c = nullptr;
 #ifdef RRL_EXPERIMENT
@@ -470,28 +453,30 @@ int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B
     const int nmax = clouds == 2 && M > N ? M : N;
     dim3 grid((unsigned)((L + 256 * R - 1) / (256 * R)), (unsigned)((nmax + chunk - 1) / chunk),
               (unsigned)(clouds * B));
-    if (timed) (void)hipEventRecord(g_ev[g_timing_n][0], s);
+    if (timed) (void)hipEventRecord(g_ev[g_timing_n][0], o.s);
 #define RRL_SCAN_LAUNCH(T, NP)                                                                   \
-    hipLaunchKernelGGL((scan_kernel<T, NP>), grid, dim3(256), 0, s, w.f32(ws, RRL_WS_PTRI1),     \
-                       w.f32(ws, RRL_WS_PTRI2), line, w.i32(ws, RRL_WS_COUNT1),                  \
-                       w.i32(ws, RRL_WS_HIT1), w.i32(ws, RRL_WS_COUNT2), w.i32(ws, RRL_WS_HIT2), \
-                       w.i32(ws, RRL_WS_STATUS), (const uint32_t *)w.i32(ws, RRL_WS_PMAX), B, N, \
-                       M, L, chunk, mode, o.count1, o.count2, o.nlines)
+    hipLaunchKernelGGL((scan_kernel<T, NP>), grid, dim3(256), 0, o.s, o.f32(RRL_WS_PTRI1),       \
+                       o.f32(RRL_WS_PTRI2), line, o.i32(RRL_WS_COUNT1), o.i32(RRL_WS_HIT1),      \
+                       o.i32(RRL_WS_COUNT2), o.i32(RRL_WS_HIT2), o.i32(RRL_WS_STATUS),           \
+                       (const uint32_t *)o.i32(RRL_WS_PMAX), B, N, M, L, chunk, mode, o.count1,  \
+                       o.count2, o.nlines)
     if (R == 1) RRL_SCAN_LAUNCH(float, 1);
     else if (R == 2) RRL_SCAN_LAUNCH(v2f, 1);
     else if (R == 4) RRL_SCAN_LAUNCH(v2f, 2);
     else RRL_SCAN_LAUNCH(v2f, 4);
 #undef RRL_SCAN_LAUNCH
-    if (timed) (void)hipEventRecord(g_ev[g_timing_n++][1], s);
+    if (timed) (void)hipEventRecord(g_ev[g_timing_n++][1], o.s);
     RRL_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int rrl_line_tri_scan_ex(const float *line, void *ws, size_t ws_bytes, int B, int N, int M,
                                     int L, int mode, int chunk, const rrl_opts *opts, void *stream) {
-    RrlCall o = rrl_resolve_opts(opts);
-    if (const int rc = rrl_plan(o, B, N, M, L, 0, mode, nullptr, nullptr, RRL_WANT_STAGE)) return rc;
-    return rrl_line_tri_scan_clouds(line, ws, ws_bytes, B, N, M, L, o.plan.scan_mode, chunk, o.plan.clouds, o.plan.lmax_ready, o, stream);
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    o.mode = mode;
+    o.chunk = chunk;
+    if (const int rc = rrl_check_call(o, line != nullptr, RRL_WANT_STAGE)) return rc;
+    return rrl_line_tri_scan_clouds(o, line);
 }
 extern "C" int rrl_line_tri_scan(const float *line, void *ws, size_t ws_bytes, int B, int N, int M,
                                  int L, int mode, int chunk, void *stream) {

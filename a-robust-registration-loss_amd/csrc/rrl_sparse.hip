@@ -45,48 +45,41 @@ extern "C" int rrl_debug_pstamps(unsigned long long *out, int clear) {
 
 #include "rrl_stage_pair.inc"    // K2: the per-line stage
 
-// tar_ws != NULL: cloud 2's hit counts / hit lists are read where its scan left them -- the workspace of the evaluation the
-// target was carried over from (round 4b: they used to be copied into this workspace first, two launches per evaluation).
-static PairArgs pair_args(const float *tri1, const float *tri2, const float *line, void *ws, const WsLayout &w, int B, int N,
-                          int M, int L, int s_m, int s_n, int e_m, int e_n, bool tally = true, const void *tar_ws = nullptr,
-                          int Bt = 0) {
+// Cloud 2's hit counts / hit lists are read where its scan left them (RrlCall::tar_i32) -- with a carried-over target the
+// workspace of the evaluation it was carried over from (round 4b: they used to be copied into this workspace first, two
+// launches per evaluation).  tally: the launch feeds the tiled reduces' histogram (not the single-tile kernels).
+static PairArgs pair_args(const RrlCall &o, const float *tri1, const float *tri2, const float *line, bool tally) {
     PairArgs a;
-    a.mhist = tally ? w.u32(ws, RRL_WS_MHIST) : nullptr;
-    a.mctl = tally ? w.u32(ws, RRL_WS_MCTL) : nullptr;
+    a.mhist = tally ? o.u32(RRL_WS_MHIST) : nullptr;
+    a.mctl = tally ? o.u32(RRL_WS_MCTL) : nullptr;
     a.tri1 = tri1;
     a.tri2 = tri2;
     a.line = line;
-    a.count1 = w.i32(ws, RRL_WS_COUNT1); a.hit1 = w.i32(ws, RRL_WS_HIT1);
-    a.count2 = tar_ws ? w.i32(tar_ws, RRL_WS_COUNT2) : w.i32(ws, RRL_WS_COUNT2);
-    a.hit2 = tar_ws ? w.i32(tar_ws, RRL_WS_HIT2) : w.i32(ws, RRL_WS_HIT2);
-    a.kj = w.u8(ws, RRL_WS_KJ);
-    a.sel_out = w.i32(ws, RRL_WS_SEL); a.nsel = w.i32(ws, RRL_WS_NSEL);
-    a.hs1 = w.i32(ws, RRL_WS_HS1); a.hs2 = w.i32(ws, RRL_WS_HS2);
-    a.w1 = w.f32(ws, RRL_WS_W1); a.w2 = w.f32(ws, RRL_WS_W2);
-    a.Q1 = (float4 *)w.f32(ws, RRL_WS_Q1); a.Q2 = (float4 *)w.f32(ws, RRL_WS_Q2);
-    a.D = w.f32(ws, RRL_WS_D); a.dc = w.f32(ws, RRL_WS_VALS);
-    a.kjc = w.u8(ws, RRL_WS_KJC); a.blkcnt = w.i32(ws, RRL_WS_BLKCNT);
-    a.lidc = w.u32(ws, RRL_WS_LIDC);
-    a.vlist = w.f32(ws, RRL_WS_VLIST); a.vlcnt = w.i32(ws, RRL_WS_VLCNT);
-    a.B = B; a.N = N; a.M = M; a.L = L;
-    a.s_m = s_m; a.s_n = s_n; a.e_m = e_m; a.e_n = e_n;
+    a.count1 = o.i32(RRL_WS_COUNT1); a.hit1 = o.i32(RRL_WS_HIT1);
+    a.count2 = o.tar_i32(RRL_WS_COUNT2); a.hit2 = o.tar_i32(RRL_WS_HIT2);
+    a.kj = o.u8(RRL_WS_KJ);
+    a.sel_out = o.i32(RRL_WS_SEL); a.nsel = o.i32(RRL_WS_NSEL);
+    a.hs1 = o.i32(RRL_WS_HS1); a.hs2 = o.i32(RRL_WS_HS2);
+    a.w1 = o.f32(RRL_WS_W1); a.w2 = o.f32(RRL_WS_W2);
+    a.Q1 = (float4 *)o.f32(RRL_WS_Q1); a.Q2 = (float4 *)o.f32(RRL_WS_Q2);
+    a.D = o.f32(RRL_WS_D); a.dc = o.f32(RRL_WS_VALS);
+    a.kjc = o.u8(RRL_WS_KJC); a.blkcnt = o.i32(RRL_WS_BLKCNT);
+    a.lidc = o.u32(RRL_WS_LIDC);
+    a.vlist = o.f32(RRL_WS_VLIST); a.vlcnt = o.i32(RRL_WS_VLCNT);
+    a.B = o.B; a.N = o.N; a.M = o.M; a.L = o.L;
+    a.s_m = o.s_m; a.s_n = o.s_n; a.e_m = o.e_m; a.e_n = o.e_n;
     a.st1 = 9; a.st2 = 9;
-    a.Bt = Bt;  // multi-pose (RrlCall::problems)
-    a.xcd_align = B % 8 == 0 && xcd_align_on();
+    a.Bt = o.problems;  // multi-pose (RrlCall::problems)
+    a.xcd_align = o.B % 8 == 0 && xcd_align_on();
     a.zc1 = a.zc2 = nullptr;
     return a;
 }
 
-static int line_pair_dist_impl(const float *tri1, const float *tri2, const float *line, void *ws, size_t ws_bytes, int B,
-                               int N, int M, int L, int s_m, int s_n, int e_m, int e_n, const RrlCall &o, void *stream) {
-    if (!tri1 || !tri2 || !line || !ws || B < 0 || N < 0 || M < 0 || L < 0 || L >= (1 << 24)) return RRL_E_ARG;  // 24-bit line ids in LDS
-    if (s_m < 1 || s_n < 1 || e_m > RRL_MAX_HITS + 1 || e_n > RRL_MAX_HITS + 1) return RRL_E_RANGE;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
+static int line_pair_dist_impl(const RrlCall &o, const float *tri1, const float *tri2, const float *line) {
+    const int B = o.B, L = o.L;
     if (B == 0 || L == 0) return 0;
-    PairArgs pa = pair_args(tri1, tri2, line, ws, w, B, N, M, L, s_m, s_n, e_m, e_n, true, o.tar_ws);
-    pa.Bt = o.problems;
-    if (o.plan.leave_clean) { pa.zc1 = w.i32(ws, RRL_WS_COUNT1); pa.zc2 = w.i32(ws, RRL_WS_COUNT2); }
+    PairArgs pa = pair_args(o, tri1, tri2, line, true);
+    if (o.plan.leave_clean) { pa.zc1 = o.i32(RRL_WS_COUNT1); pa.zc2 = o.i32(RRL_WS_COUNT2); }
     if (o.plan.reduce != RRL_RED_TAIL) pa.vlist = nullptr;  // only the tail kernel reads VLIST
     if (o.plan.count_rides) {  // the next epoch's count pass rides along (pair_count_kernel)
         RrlCountRider *cr = o.count_rider;
@@ -94,14 +87,12 @@ static int line_pair_dist_impl(const float *tri1, const float *tri2, const float
         const CountKArgs c = {cr->rng_state, cr->r, cr->centers, cr->aabb2, cr->rows, cr->accept, cr->n_rows, cr->n,
                               cr->rounds, rrl_sample_prefilter(), ctiles, cr->rounds};
         const int pgx = (L + 1023) / 1024;
-        hipLaunchKernelGGL(pair_count_kernel, dim3((unsigned)(ctiles * cr->rounds + pgx * B)), dim3(1024), 0,
-                           (hipStream_t)stream, pa, c, pgx);
+        hipLaunchKernelGGL(pair_count_kernel, dim3((unsigned)(ctiles * cr->rounds + pgx * B)), dim3(1024), 0, o.s, pa, c, pgx);
         RRL_LAUNCH_CHECK();
         cr->done = 1;
         return 0;
     }
-    hipLaunchKernelGGL(line_pair_dist_kernel, dim3((unsigned)((L + 1023) / 1024), (unsigned)B), dim3(1024), 0,
-                       (hipStream_t)stream, pa);
+    hipLaunchKernelGGL(line_pair_dist_kernel, dim3((unsigned)((L + 1023) / 1024), (unsigned)B), dim3(1024), 0, o.s, pa);
     RRL_LAUNCH_CHECK();
     return 0;
 }
@@ -109,9 +100,10 @@ static int line_pair_dist_impl(const float *tri1, const float *tri2, const float
 extern "C" int rrl_line_pair_dist_ex(const float *tri1, const float *tri2, const float *line,
                                      void *ws, size_t ws_bytes, int B, int N, int M, int L, int s_m,
                                      int s_n, int e_m, int e_n, int pool, const rrl_opts *opts, void *stream) {
-    RrlCall o = rrl_resolve_opts(opts);
-    if (const int rc = rrl_plan(o, B, N, M, L, pool, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE)) return rc;
-    return line_pair_dist_impl(tri1, tri2, line, ws, ws_bytes, B, N, M, L, s_m, s_n, e_m, e_n, o, stream);
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    o.set(s_m, s_n, e_m, e_n, pool);
+    if (const int rc = rrl_check_call(o, tri1 && tri2 && line, RRL_WANT_STAGE)) return rc;
+    return line_pair_dist_impl(o, tri1, tri2, line);
 }
 extern "C" int rrl_line_pair_dist(const float *tri1, const float *tri2, const float *line,
                                   void *ws, size_t ws_bytes, int B, int N, int M, int L, int s_m,
@@ -139,9 +131,10 @@ static int default_reduce_mode() {
     return g_reduce_mode;
 }
 static bool default_deterministic();
-// include/rrl.h rrl_opts -> the options of one call (csrc/rrl_ws.h RrlCall).  Fields the caller's struct does not
-// reach (struct_bytes), -1 and NULL mean the process-wide default.  The internal fields start zero: an empty plan.
-RrlCall rrl_resolve_opts(const rrl_opts *p) {
+// The record of one call (csrc/rrl_ws.h RrlCall): include/rrl.h rrl_opts -> its options -- fields the caller's struct does
+// not reach (struct_bytes), -1 and NULL mean the process-wide default; the internal fields start zero: an empty plan --,
+// then the shape, the workspace with its layout and the stream.
+RrlCall rrl_begin_call(const rrl_opts *p, int B, int N, int M, int L, void *ws, size_t ws_bytes, void *stream) {
     RrlCall o{};
     rrl_opts v;
     memset(&v, 0, sizeof v);
@@ -162,6 +155,11 @@ RrlCall rrl_resolve_opts(const rrl_opts *p) {
     o.problems = v.problems > 0 ? v.problems : 0;
     o.chain_left = v.chain_left;
     o.count1 = v.count1; o.count2 = v.count2; o.nlines = v.nlines;
+    o.B = B; o.N = N; o.M = M; o.L = L;
+    o.set(1, 1, RRL_MAX_HITS + 1, RRL_MAX_HITS + 1, 0);
+    o.ws = ws; o.ws_bytes = ws_bytes;
+    o.w = WsLayout(B, N, M, L);
+    o.s = (hipStream_t)stream;
     return o;
 }
 // Which reduce kernel (rrl_ws.h RRL_RED_*): one workgroup per sample, tiled with the candidate exchange
@@ -234,12 +232,11 @@ static int reduce_kind(int mode, int B, int nblk, int pool, bool with_bwd) {
     if (mode == 0 && tail_ok && with_bwd && nblk >= 2) return RRL_RED_TAIL;
     return xchg_ok && nblk >= 2 ? RRL_RED_XCHG : RRL_RED_SINGLE;
 }
-int rrl_cull_scan_can_fuse(int B, int N, int M, int L, const RrlCall &o);  // rrl_cull.hip
-
 // The plan of one call (rrl_ws.h RrlPlan).  target_ws != NULL: the target's scan is carried over from it (one cloud scanned);
 // xf != NULL: the call moves the source; want: RRL_WANT_*.  A stage entry (RRL_WANT_STAGE) takes the options as given --
 // no whole forward, so no single-tile kernel, chain, rider or multi-pose check -- and builds both clouds.
-int rrl_plan(RrlCall &o, int B, int N, int M, int L, int pool, int mode, const void *target_ws, const RrlXform *xf, int want) {
+int rrl_plan(RrlCall &o, int want, const void *target_ws, const RrlXform *xf) {
+    const int B = o.B, N = o.N, M = o.M, L = o.L, pool = o.pool, mode = o.mode;
     RrlPlan &p = o.plan;
     p = RrlPlan{};
     const bool stage = want == RRL_WANT_STAGE, sorted = rrl_sorted_layout(N, M);
@@ -283,7 +280,7 @@ int rrl_plan(RrlCall &o, int B, int N, int M, int L, int pool, int mode, const v
     // ... and a step that FINDS them cleared runs source records + target scan + source scan as ONE launch.  Only a step that
     // also leaves them cleared: the reduce of a fused build writes the CHAIN words it clears (else the plain build serves)
     p.fused_build = p.leave_clean && (o.flags & RRL_F_CHAINED) && o.target_kept() && !o.count_rider && !o.write_rider &&
-                    rrl_cull_scan_can_fuse(B, N, M, L, o);
+                    rrl_cull_scan_can_fuse(o);
     // the next epoch's sampler passes (rrl_demo_epoch): the count pass in the per-line launch, the write pass -- with the
     // ballots of THAT count pass -- in the launch that carries the direct backward (nothing after it reads the lines)
     if (const RrlCountRider *cr = o.count_rider)
@@ -306,57 +303,86 @@ struct TailBwd {
     float *grad_tri1;  // scatter target (rrl_loss_step) instead of (gR, gt)
 };
 
-static ReduceArgs reduce_args(void *ws, const WsLayout &w, float *loss, int B, int L, int s_m, int s_n, int e_m, int e_n,
-                              int pool) {
+// The validation of every narrow entry (rrl_ws.h; the order: include/rrl.h "Refusals")
+int rrl_check_call(RrlCall &o, bool pointers, int want, const void *target_ws, const RrlXform *xf) {
+    if (!pointers || !o.ws || o.B < 0 || o.N < 0 || o.M < 0 || o.L < 0 || o.L >= (1 << 24)) return RRL_E_ARG;  // 24-bit line ids in LDS
+    if (o.mode < RRL_SCAN_STRICT || o.mode > RRL_SCAN_CULL || o.chunk < 0 || target_ws == o.ws) return RRL_E_ARG;
+    if (want != RRL_WANT_NONE)
+        if (const int rc = rrl_plan(o, want, target_ws, xf)) return rc;
+    if (o.s_m < 1 || o.s_n < 1 || o.e_m > RRL_MAX_HITS + 1 || o.e_n > RRL_MAX_HITS + 1) return RRL_E_RANGE;
+    return o.ws_bytes < o.w.total ? RRL_E_WS : 0;
+}
+
+static ReduceArgs reduce_args(const RrlCall &o, float *loss) {
     ReduceArgs r;
-    r.kjc = w.u8(ws, RRL_WS_KJC); r.dc = w.f32(ws, RRL_WS_VALS); r.blkcnt = w.i32(ws, RRL_WS_BLKCNT);
-    r.med_out = w.f32(ws, RRL_WS_MED); r.bcnt_out = w.i32(ws, RRL_WS_BCNT); r.bsum_out = w.i64(ws, RRL_WS_BSUM);
-    r.info = w.i32(ws, RRL_WS_INFO); r.loss = loss; r.status = w.i32(ws, RRL_WS_STATUS);
-    r.B = B; r.nblk = (L + 1023) / 1024;
-    r.s_m = s_m; r.s_n = s_n; r.e_m = e_m; r.e_n = e_n; r.pool = pool;
+    r.kjc = o.u8(RRL_WS_KJC); r.dc = o.f32(RRL_WS_VALS); r.blkcnt = o.i32(RRL_WS_BLKCNT);
+    r.med_out = o.f32(RRL_WS_MED); r.bcnt_out = o.i32(RRL_WS_BCNT); r.bsum_out = o.i64(RRL_WS_BSUM);
+    r.info = o.i32(RRL_WS_INFO); r.loss = loss; r.status = o.i32(RRL_WS_STATUS);
+    r.B = o.B; r.nblk = (o.L + 1023) / 1024;
+    r.s_m = o.s_m; r.s_n = o.s_n; r.e_m = o.e_m; r.e_n = o.e_n; r.pool = o.pool;
     return r;
 }
 
+// tb: the backward that rides in the tail kernel's launch (o.plan.bwd_rides), else NULL
+static TailArgs tail_args(const RrlCall &o, float *loss, const TailBwd *tb) {
+    TailArgs t;
+    t.lidc = o.u32(RRL_WS_LIDC); t.dc = o.f32(RRL_WS_VALS); t.blkcnt = o.i32(RRL_WS_BLKCNT);
+    t.vlist = o.f32(RRL_WS_VLIST); t.vlcnt = o.i32(RRL_WS_VLCNT);
+    t.mhist = o.u32(RRL_WS_MHIST); t.mctl = o.u32(RRL_WS_MCTL);
+    t.msum = (unsigned long long *)o.i64(RRL_WS_MSUM);
+    t.med_out = o.f32(RRL_WS_MED); t.bcnt_out = o.i32(RRL_WS_BCNT); t.bsum_out = o.i64(RRL_WS_BSUM);
+    t.info = o.i32(RRL_WS_INFO); t.loss = loss; t.status = o.i32(RRL_WS_STATUS);
+    t.B = o.B; t.nblk = (o.L + 1023) / 1024; t.s_m = o.s_m; t.s_n = o.s_n; t.e_m = o.e_m; t.e_n = o.e_n;
+    const TailBwd none{}, &b = tb ? *tb : none;  // (no riding backward: all NULL)
+    t.do_bwd = tb ? 1 : 0; t.N = o.N; t.L = o.L; t.transpose_r = b.transpose_r;
+    t.hs1 = o.i32(RRL_WS_HS1); t.w1 = o.f32(RRL_WS_W1);
+    t.Q1 = (const float4 *)o.f32(RRL_WS_Q1); t.Q2 = (const float4 *)o.f32(RRL_WS_Q2);
+    t.grad_loss = b.grad_loss; t.src = b.src; t.gR = b.gR; t.gt = b.gt; t.payload = b.payload; t.grad_tri1 = b.grad_tri1;
+    t.Bt = o.problems;
+    t.xcd_align = o.B % 8 == 0 && xcd_align_on();
+    t.chain = o.plan.leave_clean ? o.u32(RRL_WS_CHAIN) : nullptr;
+    t.chain_flags = o.plan.fused_build;
+    return t;
+}
+
+static TiledArgs tiled_args(const RrlCall &o, float *loss) {
+    TiledArgs t;
+    t.kjc = o.u8(RRL_WS_KJC); t.dc = o.f32(RRL_WS_VALS); t.blkcnt = o.i32(RRL_WS_BLKCNT);
+    t.mhist = o.u32(RRL_WS_MHIST); t.mctl = o.u32(RRL_WS_MCTL); t.mcand = o.u32(RRL_WS_MCAND);
+    t.msum = (unsigned long long *)o.i64(RRL_WS_MSUM);
+    t.med_out = o.f32(RRL_WS_MED); t.bcnt_out = o.i32(RRL_WS_BCNT); t.bsum_out = o.i64(RRL_WS_BSUM);
+    t.info = o.i32(RRL_WS_INFO); t.loss = loss; t.status = o.i32(RRL_WS_STATUS);
+    t.B = o.B; t.nblk = (o.L + 1023) / 1024; t.s_m = o.s_m; t.s_n = o.s_n; t.e_m = o.e_m; t.e_n = o.e_n;
+    t.spin_limit = spin_limit();
+    t.xcd_align = o.B % 8 == 0 && xcd_align_on();
+    t.payload = o.plan.payload_in_reduce ? o.payload : nullptr;
+    t.chain = o.plan.leave_clean ? o.u32(RRL_WS_CHAIN) : nullptr;
+    t.chain_flags = o.plan.fused_build;
+    return t;
+}
+
+// the next epoch's sampler write pass, riding in the launch that carries the direct backward (rrl_ws.h RrlWriteRider)
+static WriteKArgs write_args(const RrlWriteRider *wr) {
+    const int wtiles = (wr->n + 1023) / 1024;
+    return WriteKArgs{wr->rng_state, wr->r, wr->centers, wr->accept, wr->lines, wr->filled, wr->n, wr->rounds, wtiles, wr->rounds};
+}
+
 // o.plan: rrl_plan; tb: the backward that rides in the launch (o.plan.bwd_rides), else NULL
-static int loss_reduce_impl(void *ws, size_t ws_bytes, float *loss, int B, int N, int M, int L, int s_m, int s_n, int e_m,
-                            int e_n, int pool, const TailBwd *tb, const RrlCall &o, void *stream) {
-    if (!ws || !loss || B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
-    if (s_m < 1 || s_n < 1 || e_m > RRL_MAX_HITS + 1 || e_n > RRL_MAX_HITS + 1) return RRL_E_RANGE;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
+static int loss_reduce_impl(const RrlCall &o, float *loss, const TailBwd *tb) {
+    const int B = o.B, nblk = (o.L + 1023) / 1024;
     if (B == 0) return 0;
-    const int nblk = (L + 1023) / 1024;
     if (o.plan.reduce == RRL_RED_TAIL) {
-        TailArgs t;
-        t.lidc = w.u32(ws, RRL_WS_LIDC); t.dc = w.f32(ws, RRL_WS_VALS); t.blkcnt = w.i32(ws, RRL_WS_BLKCNT);
-        t.vlist = w.f32(ws, RRL_WS_VLIST); t.vlcnt = w.i32(ws, RRL_WS_VLCNT);
-        t.mhist = w.u32(ws, RRL_WS_MHIST); t.mctl = w.u32(ws, RRL_WS_MCTL);
-        t.msum = (unsigned long long *)w.i64(ws, RRL_WS_MSUM);
-        t.med_out = w.f32(ws, RRL_WS_MED); t.bcnt_out = w.i32(ws, RRL_WS_BCNT); t.bsum_out = w.i64(ws, RRL_WS_BSUM);
-        t.info = w.i32(ws, RRL_WS_INFO); t.loss = loss; t.status = w.i32(ws, RRL_WS_STATUS);
-        t.B = B; t.nblk = nblk; t.s_m = s_m; t.s_n = s_n; t.e_m = e_m; t.e_n = e_n;
-        t.do_bwd = tb ? 1 : 0; t.N = N; t.L = L; t.transpose_r = tb ? tb->transpose_r : 0;
-        t.hs1 = w.i32(ws, RRL_WS_HS1); t.w1 = w.f32(ws, RRL_WS_W1);
-        t.Q1 = (const float4 *)w.f32(ws, RRL_WS_Q1); t.Q2 = (const float4 *)w.f32(ws, RRL_WS_Q2);
-        t.grad_loss = tb ? tb->grad_loss : nullptr; t.src = tb ? tb->src : nullptr;
-        t.gR = tb ? tb->gR : nullptr; t.gt = tb ? tb->gt : nullptr; t.payload = tb ? tb->payload : nullptr;
-        t.grad_tri1 = tb ? tb->grad_tri1 : nullptr;
-        t.Bt = o.problems;
-        t.xcd_align = B % 8 == 0 && xcd_align_on();
-        t.chain = o.plan.leave_clean ? w.u32(ws, RRL_WS_CHAIN) : nullptr;
-        t.chain_flags = o.plan.fused_build;
+        const TailArgs t = tail_args(o, loss, tb);
         if (tb && o.plan.write_rides) {  // the next epoch's sampler write pass rides along (tail_write_kernel; rrl_demo_epoch)
-            RrlWriteRider *wr = o.write_rider;
-            const int wtiles = (wr->n + 1023) / 1024;
-            const WriteKArgs wk = {wr->rng_state, wr->r, wr->centers, wr->accept, wr->lines, wr->filled, wr->n, wr->rounds, wtiles, wr->rounds};
+            const WriteKArgs wk = write_args(o.write_rider);
             const dim3 g((unsigned)(wk.gx * wk.gy + nblk * B * TAIL_SUBS));
             const size_t lds = sizeof(int32_t) * (size_t)wk.rounds * wk.gx;
-            if (t.grad_tri1) hipLaunchKernelGGL(tail_write_kernel<true>, g, dim3(TAIL_LANES), lds, (hipStream_t)stream, t, wk);
-            else hipLaunchKernelGGL(tail_write_kernel<false>, g, dim3(TAIL_LANES), lds, (hipStream_t)stream, t, wk);
-            wr->done = 1;
+            if (t.grad_tri1) hipLaunchKernelGGL(tail_write_kernel<true>, g, dim3(TAIL_LANES), lds, o.s, t, wk);
+            else hipLaunchKernelGGL(tail_write_kernel<false>, g, dim3(TAIL_LANES), lds, o.s, t, wk);
+            o.write_rider->done = 1;
         } else {
             const dim3 g((unsigned)nblk, (unsigned)B, TAIL_SUBS);
-#define RRL_TAIL(S_, R_) hipLaunchKernelGGL((loss_tail_kernel<S_, R_>), g, dim3(TAIL_LANES), 0, (hipStream_t)stream, t)
+#define RRL_TAIL(S_, R_) hipLaunchKernelGGL((loss_tail_kernel<S_, R_>), g, dim3(TAIL_LANES), 0, o.s, t)
             if (t.grad_tri1) { if (o.plan.tail_rpl2) RRL_TAIL(true, 2); else RRL_TAIL(true, TAIL_RPL); }
             else { if (o.plan.tail_rpl2) RRL_TAIL(false, 2); else RRL_TAIL(false, TAIL_RPL); }
 #undef RRL_TAIL
@@ -365,34 +391,23 @@ static int loss_reduce_impl(void *ws, size_t ws_bytes, float *loss, int B, int N
         return 0;
     }
     if (o.plan.reduce == RRL_RED_XCHG) {
-        TiledArgs t;
-        t.kjc = w.u8(ws, RRL_WS_KJC); t.dc = w.f32(ws, RRL_WS_VALS); t.blkcnt = w.i32(ws, RRL_WS_BLKCNT);
-        t.mhist = w.u32(ws, RRL_WS_MHIST); t.mctl = w.u32(ws, RRL_WS_MCTL); t.mcand = w.u32(ws, RRL_WS_MCAND);
-        t.msum = (unsigned long long *)w.i64(ws, RRL_WS_MSUM);
-        t.med_out = w.f32(ws, RRL_WS_MED); t.bcnt_out = w.i32(ws, RRL_WS_BCNT); t.bsum_out = w.i64(ws, RRL_WS_BSUM);
-        t.info = w.i32(ws, RRL_WS_INFO); t.loss = loss; t.status = w.i32(ws, RRL_WS_STATUS);
-        t.B = B; t.nblk = nblk; t.s_m = s_m; t.s_n = s_n; t.e_m = e_m; t.e_n = e_n;
-        t.spin_limit = spin_limit();
-        t.xcd_align = B % 8 == 0 && xcd_align_on();
-        t.payload = o.plan.payload_in_reduce ? o.payload : nullptr;
-        t.chain = o.plan.leave_clean ? w.u32(ws, RRL_WS_CHAIN) : nullptr;
-        t.chain_flags = o.plan.fused_build;
-        hipLaunchKernelGGL(loss_reduce_tiled_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, (hipStream_t)stream, t);
+        hipLaunchKernelGGL(loss_reduce_tiled_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, o.s, tiled_args(o, loss));
         RRL_LAUNCH_CHECK();
         return 0;
     }
     // (RRL_RED_TILE here: the reduce stage of a one-tile call issued stage by stage)
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3((unsigned)(pool ? 1 : B)), dim3(1024), sizeof(int) * (size_t)(nblk + 1),
-                       (hipStream_t)stream, reduce_args(ws, w, loss, B, L, s_m, s_n, e_m, e_n, pool));
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3((unsigned)(o.pool ? 1 : B)), dim3(1024), sizeof(int) * (size_t)(nblk + 1), o.s,
+                       reduce_args(o, loss));
     RRL_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int rrl_loss_reduce_ex(void *ws, size_t ws_bytes, float *loss, int B, int N, int M, int L,
                                   int s_m, int s_n, int e_m, int e_n, int pool, const rrl_opts *opts, void *stream) {
-    RrlCall o = rrl_resolve_opts(opts);
-    if (const int rc = rrl_plan(o, B, N, M, L, pool, RRL_SCAN_CULL, nullptr, nullptr, RRL_WANT_STAGE)) return rc;
-    return loss_reduce_impl(ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, nullptr, o, stream);
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    o.set(s_m, s_n, e_m, e_n, pool);
+    if (const int rc = rrl_check_call(o, loss != nullptr, RRL_WANT_STAGE)) return rc;
+    return loss_reduce_impl(o, loss, nullptr);
 }
 extern "C" int rrl_loss_reduce(void *ws, size_t ws_bytes, float *loss, int B, int N, int M, int L,
                                int s_m, int s_n, int e_m, int e_n, int pool, void *stream) {
@@ -442,14 +457,14 @@ static bool default_deterministic() {
     return g_deterministic == 1;
 }
 
-static ScatArgs scat_args(const void *ws, const WsLayout &w, const float *grad_loss, float *g1, float *g2, int N, int M, int L) {
+static ScatArgs scat_args(const RrlCall &o, const float *grad_loss, float *g1, float *g2) {
     ScatArgs a;
-    a.lidc = w.u32(ws, RRL_WS_LIDC); a.blkcnt = w.i32(ws, RRL_WS_BLKCNT);
-    a.hs1 = w.i32(ws, RRL_WS_HS1); a.hs2 = w.i32(ws, RRL_WS_HS2); a.bcnt = w.i32(ws, RRL_WS_BCNT); a.info = w.i32(ws, RRL_WS_INFO);
-    a.w1 = w.f32(ws, RRL_WS_W1); a.w2 = w.f32(ws, RRL_WS_W2); a.D = w.f32(ws, RRL_WS_D); a.med = w.f32(ws, RRL_WS_MED);
+    a.lidc = o.u32(RRL_WS_LIDC); a.blkcnt = o.i32(RRL_WS_BLKCNT);
+    a.hs1 = o.i32(RRL_WS_HS1); a.hs2 = o.i32(RRL_WS_HS2); a.bcnt = o.i32(RRL_WS_BCNT); a.info = o.i32(RRL_WS_INFO);
+    a.w1 = o.f32(RRL_WS_W1); a.w2 = o.f32(RRL_WS_W2); a.D = o.f32(RRL_WS_D); a.med = o.f32(RRL_WS_MED);
     a.grad_loss = grad_loss;
-    a.Q1 = (const float4 *)w.f32(ws, RRL_WS_Q1); a.Q2 = (const float4 *)w.f32(ws, RRL_WS_Q2);
-    a.g1 = g1; a.g2 = g2; a.N = N; a.M = M; a.L = L;
+    a.Q1 = (const float4 *)o.f32(RRL_WS_Q1); a.Q2 = (const float4 *)o.f32(RRL_WS_Q2);
+    a.g1 = g1; a.g2 = g2; a.N = o.N; a.M = o.M; a.L = o.L;
     a.fx = nullptr; a.fxbits = 0; a.fxB = 0;
     return a;
 }
@@ -463,33 +478,27 @@ static int scat_fx_bits_host(int L) {
 // deterministic: include/rrl.h rrl_set_deterministic -- the scatter accumulates in the workspace's fixed-point field (which this
 // call clears and therefore WRITES: the one entry that touches the workspace of a finished forward) and one more launch
 // converts; grad_tri1 / grad_tri2 are overwritten, not accumulated.
-static int loss_backward_impl(const float *tri1, const float *tri2, const void *ws,
-                              size_t ws_bytes, const float *grad_loss, float *grad_tri1,
-                              float *grad_tri2, int B, int N, int M, int L, int pool, bool zero1,
-                              void *stream, bool deterministic = false) {
-    if (!tri1 || !tri2 || !ws || !grad_loss || !grad_tri1) return RRL_E_ARG;
-    if (B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
-    hipStream_t s = (hipStream_t)stream;
+static int loss_backward_impl(const RrlCall &o, const float *grad_loss, float *grad_tri1, float *grad_tri2, bool zero1,
+                              bool deterministic) {
+    const int B = o.B, N = o.N, M = o.M, L = o.L;
     int rc;
-    if (zero1 && (rc = rrl_fill(grad_tri1, 0u, sizeof(float) * 9 * (size_t)B * N, s))) return rc;
-    if (grad_tri2 && (rc = rrl_fill(grad_tri2, 0u, sizeof(float) * 9 * (size_t)B * M, s))) return rc;
+    if (zero1 && (rc = rrl_fill(grad_tri1, 0u, sizeof(float) * 9 * (size_t)B * N, o.s))) return rc;
+    if (grad_tri2 && (rc = rrl_fill(grad_tri2, 0u, sizeof(float) * 9 * (size_t)B * M, o.s))) return rc;
     if (B == 0 || L == 0) return 0;
-    ScatArgs sa = scat_args(ws, w, grad_loss, grad_tri1, grad_tri2, N, M, L);
+    ScatArgs sa = scat_args(o, grad_loss, grad_tri1, grad_tri2);
     if (deterministic && (N + M) > 0) {
-        sa.fx = (unsigned long long *)((char *)const_cast<void *>(ws) + w.off[RRL_WS_GFIX]);
+        sa.fx = (unsigned long long *)o.i64(RRL_WS_GFIX);
         sa.fxbits = scat_fx_bits_host(L);
         sa.fxB = B;
-        if ((rc = rrl_fill(sa.fx, 0u, 8 * (size_t)B * (N + M) * 9 + 8 * (size_t)B, s))) return rc;
+        if ((rc = rrl_fill(sa.fx, 0u, 8 * (size_t)B * (N + M) * 9 + 8 * (size_t)B, o.s))) return rc;
     }
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)((L + 1023) / 1024), (unsigned)B, BWDS_SUBS), dim3(256), 0, s, sa, B, pool,
+    hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)((L + 1023) / 1024), (unsigned)B, BWDS_SUBS), dim3(256), 0, o.s, sa, B, o.pool,
                        B % 8 == 0 && xcd_align_on() ? 1 : 0);
     RRL_LAUNCH_CHECK();
     if (sa.fx) {
         const int nmax = grad_tri2 && M > N ? M : N;
         hipLaunchKernelGGL(scatter_fix_to_float_kernel, dim3((unsigned)(((size_t)nmax * 9 + 255) / 256), (unsigned)B, grad_tri2 ? 2u : 1u),
-                           dim3(256), 0, s, sa, B, pool);
+                           dim3(256), 0, o.s, sa, B, o.pool);
         RRL_LAUNCH_CHECK();
     }
     return 0;
@@ -499,14 +508,11 @@ extern "C" int rrl_loss_backward(const float *tri1, const float *tri2, const voi
                                  size_t ws_bytes, const float *grad_loss, float *grad_tri1,
                                  float *grad_tri2, int B, int N, int M, int L, int pool,
                                  void *stream) {
-    return loss_backward_impl(tri1, tri2, ws, ws_bytes, grad_loss, grad_tri1, grad_tri2, B, N, M, L,
-                              pool, true, stream, default_deterministic());
+    RrlCall o = rrl_begin_call(nullptr, B, N, M, L, const_cast<void *>(ws), ws_bytes, stream);
+    o.pool = pool;
+    if (const int rc = rrl_check_call(o, tri1 && tri2 && grad_loss && grad_tri1, RRL_WANT_NONE)) return rc;
+    return loss_backward_impl(o, grad_loss, grad_tri1, grad_tri2, true, default_deterministic());
 }
-
-int rrl_fused_backward(int B, int N, int M);
-int rrl_launch_reg_bwd(const float *src, const float *R, float *g1, float *grad_src, float *partial,
-                       float *gR, float *gt, float *payload, const float *loss, const int32_t *info,
-                       int32_t *done, int B, int N, int transpose_r, const int32_t *count1, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // workspace + fused forward
@@ -515,28 +521,31 @@ extern "C" size_t rrl_workspace_bytes(int B, int N, int M, int L) { return WsLay
 
 extern "C" int rrl_workspace_layout(int B, int N, int M, int L, size_t *offsets) {
     if (!offsets || B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
-    WsLayout w(B, N, M, L);
-    for (int i = 0; i < RRL_WS_FIELDS; ++i) offsets[i] = w.off[i];
+    const WsLayout layout(B, N, M, L);
+    for (int i = 0; i < RRL_WS_FIELDS; ++i) offsets[i] = layout.off[i];
     return 0;
 }
 
-int rrl_tri_prepare_clouds(const float *tri1, const float *tri2, void *ws, size_t ws_bytes, int B,
-                           int N, int M, int L, int clouds, const RrlXform *xf, const float *line, const RrlCall &o,
-                           void *stream);
-int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B, int N, int M, int L,
-                             int mode, int chunk, int clouds, int lmax_ready, const RrlCall &o, void *stream);
+// the direct backward that rides in the single-tile kernel's launch (rrl_registration_step)
+static SoloBwd solo_bwd_args(const RrlCall &o, float *loss, const TailBwd *tb) {
+    SoloBwd sb;
+    sb.kj = o.u8(RRL_WS_KJ); sb.sel = o.i32(RRL_WS_SEL); sb.nsel = o.i32(RRL_WS_NSEL);
+    sb.hs1 = o.i32(RRL_WS_HS1); sb.bcnt = o.i32(RRL_WS_BCNT); sb.info = o.i32(RRL_WS_INFO);
+    sb.w1 = o.f32(RRL_WS_W1); sb.D = o.f32(RRL_WS_D); sb.med = o.f32(RRL_WS_MED);
+    sb.grad_loss = tb->grad_loss; sb.src = tb->src; sb.loss = loss;
+    sb.Q1 = (const float4 *)o.f32(RRL_WS_Q1); sb.Q2 = (const float4 *)o.f32(RRL_WS_Q2);
+    sb.gR = tb->gR; sb.gt = tb->gt; sb.payload = tb->payload; sb.mctl = o.u32(RRL_WS_MCTL);
+    sb.B = o.B; sb.N = o.N; sb.L = o.L; sb.transpose_r = tb->transpose_r; sb.Bt = o.problems;
+    return sb;
+}
 
-// The forward of one planned call (o.plan: rrl_plan).  o.tar_ws != NULL: a workspace of the same (B, N, M, L) that already
-// went through a forward with the SAME tri2 and line (RPM / FMR evaluate several source poses against one target and one
-// line set, rpm/Train_RPM.py:204-231): only the source cloud is prepared, sorted and scanned.  o.xf != NULL: tri1 is the
-// workspace field TRI1, filled from o.xf->src.  tb: the backward that rides in the reduce's launch (o.plan.bwd_rides).
-static int loss_forward_impl(const float *tri1, const float *tri2, const float *line, void *ws,
-                             size_t ws_bytes, float *loss, int B, int N, int M, int L, int s_m,
-                             int s_n, int e_m, int e_n, int pool, int chunk, RrlCall o, void *stream,
+// The forward of one checked and planned call (rrl_check_call; o.plan: rrl_plan).  o.tar_ws != NULL: a workspace of the same
+// (B, N, M, L) that already went through a forward with the SAME tri2 and line (RPM / FMR evaluate several source poses
+// against one target and one line set, rpm/Train_RPM.py:204-231): only the source cloud is prepared, sorted and scanned.
+// o.xf != NULL: tri1 is the workspace field TRI1, filled from o.xf->src.  tb: the backward that rides in the reduce's launch
+// (o.plan.bwd_rides).
+static int loss_forward_impl(RrlCall &o, const float *tri1, const float *tri2, const float *line, float *loss,
                              const TailBwd *tb = nullptr) {
-    if (!tri1 || !tri2 || !line || !ws || !loss) return RRL_E_ARG;
-    if (s_m < 1 || s_n < 1 || e_m > RRL_MAX_HITS + 1 || e_n > RRL_MAX_HITS + 1) return RRL_E_RANGE;
-    if (o.tar_ws == ws) return RRL_E_ARG;
     const RrlPlan &p = o.plan;
     if (o.chain_left) *o.chain_left = p.leave_clean | (p.fused_build << 1);  // bit 0: leaves the workspace chain-clean; bit 1: THIS call's build is fused
     o.tri1_in = tri1;
@@ -544,54 +553,50 @@ static int loss_forward_impl(const float *tri1, const float *tri2, const float *
     RrlRange step("rrl forward");
     if (!p.fused_build) {
         RrlRange r("K1' records + sort + tree");
-        if ((rc = rrl_tri_prepare_clouds(tri1, tri2, ws, ws_bytes, B, N, M, L, p.build_clouds, o.xf, line, o, stream))) return rc;
+        if ((rc = rrl_tri_prepare_clouds(o, tri1, tri2, line))) return rc;
     }
     {
         RrlRange r("K1 line<->triangle scan");
-        if ((rc = rrl_line_tri_scan_clouds(line, ws, ws_bytes, B, N, M, L, p.scan_mode, chunk, p.clouds, p.lmax_ready, o, stream)))
-            return rc;
+        if ((rc = rrl_line_tri_scan_clouds(o, line))) return rc;
     }
     if (p.reduce == RRL_RED_TILE) {  // one tile of lines per sample: K2 + K3 + K4 in one launch
         RrlRange r("K2 + K3 + K4 (single tile)");
-        WsLayout w(B, N, M, L);
-        if (ws_bytes < w.total) return RRL_E_WS;
-        const PairArgs pa = pair_args(tri1, tri2, line, ws, w, B, N, M, L, s_m, s_n, e_m, e_n, false, o.tar_ws, o.problems);
-        const ReduceArgs ra = reduce_args(ws, w, loss, B, L, s_m, s_n, e_m, e_n, 0);
-        const hipStream_t s = (hipStream_t)stream;
+        const PairArgs pa = pair_args(o, tri1, tri2, line, false);
+        const ReduceArgs ra = reduce_args(o, loss);
+        const dim3 grid((unsigned)o.B);
         if (tb && tb->grad_tri1) {  // ... and the scatter backward to points1.grad too (rrl_loss_step_ex)
-            hipLaunchKernelGGL(pair_reduce_scatter_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, s, pa, ra,
-                               scat_args(ws, w, tb->grad_loss, tb->grad_tri1, nullptr, N, M, L), tb->payload, w.u32(ws, RRL_WS_MCTL));
+            hipLaunchKernelGGL(pair_reduce_scatter_kernel, grid, dim3(1024), sizeof(int) * 2, o.s, pa, ra,
+                               scat_args(o, tb->grad_loss, tb->grad_tri1, nullptr), tb->payload, o.u32(RRL_WS_MCTL));
         } else if (tb) {  // ... and the direct backward too (rrl_registration_step)
-            SoloBwd sb;
-            sb.kj = w.u8(ws, RRL_WS_KJ); sb.sel = w.i32(ws, RRL_WS_SEL); sb.nsel = w.i32(ws, RRL_WS_NSEL);
-            sb.hs1 = w.i32(ws, RRL_WS_HS1); sb.bcnt = w.i32(ws, RRL_WS_BCNT); sb.info = w.i32(ws, RRL_WS_INFO);
-            sb.w1 = w.f32(ws, RRL_WS_W1); sb.D = w.f32(ws, RRL_WS_D); sb.med = w.f32(ws, RRL_WS_MED);
-            sb.grad_loss = tb->grad_loss; sb.src = tb->src; sb.loss = loss;
-            sb.Q1 = (const float4 *)w.f32(ws, RRL_WS_Q1); sb.Q2 = (const float4 *)w.f32(ws, RRL_WS_Q2);
-            sb.gR = tb->gR; sb.gt = tb->gt; sb.payload = tb->payload; sb.mctl = w.u32(ws, RRL_WS_MCTL);
-            sb.B = B; sb.N = N; sb.L = L; sb.transpose_r = tb->transpose_r; sb.Bt = o.problems;
-            hipLaunchKernelGGL(pair_reduce_bwd_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, s, pa, ra, sb);
+            hipLaunchKernelGGL(pair_reduce_bwd_kernel, grid, dim3(1024), sizeof(int) * 2, o.s, pa, ra, solo_bwd_args(o, loss, tb));
         } else {
-            hipLaunchKernelGGL(pair_reduce_kernel, dim3((unsigned)B), dim3(1024), sizeof(int) * 2, s, pa, ra);
+            hipLaunchKernelGGL(pair_reduce_kernel, grid, dim3(1024), sizeof(int) * 2, o.s, pa, ra);
         }
         RRL_LAUNCH_CHECK();
         return 0;
     }
     {
         RrlRange r("K2 per-line distances");
-        if ((rc = line_pair_dist_impl(tri1, tri2, line, ws, ws_bytes, B, N, M, L, s_m, s_n, e_m, e_n, o, stream))) return rc;
+        if ((rc = line_pair_dist_impl(o, tri1, tri2, line))) return rc;
     }
     RrlRange r("K3+K4 median + Welsch reduce");
-    return loss_reduce_impl(ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, tb, o, stream);
+    return loss_reduce_impl(o, loss, tb);
+}
+
+// rrl_loss_forward_ex on its record (rrl_loss_forward_info reads INFO through the same one)
+static int loss_forward_call(RrlCall &o, const float *tri1, const float *tri2, const float *line, float *loss,
+                             const void *target_ws) {
+    if (const int rc = rrl_check_call(o, tri1 && tri2 && line && loss, RRL_WANT_FORWARD, target_ws)) return rc;
+    return loss_forward_impl(o, tri1, tri2, line, loss);
 }
 
 extern "C" int rrl_loss_forward_ex(const float *tri1, const float *tri2, const float *line,
                                    void *ws, size_t ws_bytes, float *loss, int B, int N, int M,
                                    int L, int s_m, int s_n, int e_m, int e_n, int pool, int mode,
                                    int chunk, const void *target_ws, const rrl_opts *opts, void *stream) {
-    RrlCall o = rrl_resolve_opts(opts);
-    const int rc = rrl_plan(o, B, N, M, L, pool, mode, target_ws, nullptr, RRL_WANT_FORWARD);
-    return rc ? rc : loss_forward_impl(tri1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, chunk, o, stream);
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    o.set(s_m, s_n, e_m, e_n, pool, mode, chunk);
+    return loss_forward_call(o, tri1, tri2, line, loss, target_ws);
 }
 extern "C" int rrl_loss_forward_cached(const float *tri1, const float *tri2, const float *line,
                                        void *ws, size_t ws_bytes, float *loss, int B, int N, int M,
@@ -612,16 +617,14 @@ extern "C" int rrl_loss_forward_info(const float *tri1, const float *tri2, const
                                      int s_n, int e_m, int e_n, int pool, int mode, int chunk,
                                      const void *target_ws, int32_t *host_info, void *stream) {
     if (!host_info) return RRL_E_ARG;
-    int rc = rrl_loss_forward_ex(tri1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, pool, mode, chunk,
-                                 target_ws, nullptr, stream);
-    if (rc) return rc;
+    RrlCall o = rrl_begin_call(nullptr, B, N, M, L, ws, ws_bytes, stream);
+    o.set(s_m, s_n, e_m, e_n, pool, mode, chunk);
+    if (const int rc = loss_forward_call(o, tri1, tri2, line, loss, target_ws)) return rc;
     const int G = pool ? 1 : B;
     if (G <= 0) return 0;
-    WsLayout w(B, N, M, L);
-    hipError_t e = hipMemcpyAsync(host_info, w.i32(ws, RRL_WS_INFO), sizeof(int32_t) * 4 * (size_t)G,
-                                  hipMemcpyDeviceToHost, (hipStream_t)stream);
+    hipError_t e = hipMemcpyAsync(host_info, o.i32(RRL_WS_INFO), sizeof(int32_t) * 4 * (size_t)G, hipMemcpyDeviceToHost, o.s);
     if (e != hipSuccess) return (int)e;
-    e = hipStreamSynchronize((hipStream_t)stream);
+    e = hipStreamSynchronize(o.s);
     return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -642,16 +645,12 @@ extern "C" int rrl_registration_forward_ex(const float *src, const float *R, con
                                            int L, int transpose_r, int s_m, int s_n, int e_m,
                                            int e_n, int mode, int chunk, const void *target_ws,
                                            const rrl_opts *opts, void *stream) {
-    if (!src || !R || !t || !tri2 || !line || !ws || !loss) return RRL_E_ARG;
-    if (B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    o.set(s_m, s_n, e_m, e_n, 0, mode, chunk);
     // the transform runs inside the prepare step
     const RrlXform xf = {src, R, t, transpose_r, 1};  // 1: clear GACC for the backward's atomics
-    RrlCall o = rrl_resolve_opts(opts);
-    const int rc = rrl_plan(o, B, N, M, L, 0, mode, target_ws, &xf, RRL_WANT_FORWARD);
-    return rc ? rc : loss_forward_impl(w.f32(ws, RRL_WS_TRI1), tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0,
-                                       chunk, o, stream);
+    if (const int rc = rrl_check_call(o, src && R && t && tri2 && line && loss, RRL_WANT_FORWARD, target_ws, &xf)) return rc;
+    return loss_forward_impl(o, o.f32(RRL_WS_TRI1), tri2, line, loss);
 }
 extern "C" int rrl_registration_forward_cached(const float *src, const float *R, const float *t,
                                                const float *tri2, const float *line, void *ws,
@@ -673,19 +672,76 @@ extern "C" int rrl_registration_forward(const float *src, const float *R, const 
                                            stream);
 }
 
-static int registration_backward_impl(const float *src, const float *R, const float *tri2,
-                                      void *ws, size_t ws_bytes, const float *loss,
-                                      const float *grad_loss, float *grad_src, float *gR, float *gt,
-                                      float *payload, int B, int N, int M, int L, int transpose_r,
-                                      const RrlCall &o, void *stream);
 // The direct backward accumulates (gR, gt, payload) with atomics: clear them unless they are the workspace's GACC field,
 // which the forward's first launch clears
-static int clear_direct_grads(void *ws, const WsLayout &w, float *gR, float *gt, float *payload, int B, hipStream_t s) {
-    const float *gacc = w.f32(ws, RRL_WS_GACC);
-    if (gR == gacc && gt == gacc + 9 * (size_t)B && (!payload || payload == gacc + 12 * (size_t)B)) return 0;
-    int rc = rrl_fill(gR, 0u, sizeof(float) * 9 * (size_t)B, s);
-    if (!rc) rc = rrl_fill(gt, 0u, sizeof(float) * 3 * (size_t)B, s);
-    if (!rc && payload) rc = rrl_fill(payload, 0u, sizeof(float) * 14, s);
+static int clear_direct_grads(const RrlCall &o, float *gR, float *gt, float *payload) {
+    const float *gacc = o.f32(RRL_WS_GACC);
+    const size_t B = (size_t)o.B;
+    if (gR == gacc && gt == gacc + 9 * B && (!payload || payload == gacc + 12 * B)) return 0;
+    int rc = rrl_fill(gR, 0u, sizeof(float) * 9 * B, o.s);
+    if (!rc) rc = rrl_fill(gt, 0u, sizeof(float) * 3 * B, o.s);
+    if (!rc && payload) rc = rrl_fill(payload, 0u, sizeof(float) * 14, o.s);
+    return rc;
+}
+
+// part: the deterministic variant's partial rows; gx: the backward's workgroups per sample
+static BwdKArgs bwd_args(const RrlCall &o, const float *src, const float *loss, const float *grad_loss, float *gR, float *gt,
+                         float *payload, int transpose_r, float *part, int gx) {
+    return BwdKArgs{o.u8(RRL_WS_KJ), o.i32(RRL_WS_SEL), o.i32(RRL_WS_NSEL), o.i32(RRL_WS_HS1), o.f32(RRL_WS_W1),
+                    (const float4 *)o.f32(RRL_WS_Q1), (const float4 *)o.f32(RRL_WS_Q2), o.f32(RRL_WS_D), o.f32(RRL_WS_MED),
+                    o.i32(RRL_WS_BCNT), o.i32(RRL_WS_INFO), grad_loss, src, gR, gt, payload, loss,
+                    o.B, o.N, o.L, transpose_r, part, gx};
+}
+
+// The backward of a checked call (rrl_check_call), after its forward on this workspace
+static int registration_backward_impl(const RrlCall &o, const float *src, const float *R, const float *loss,
+                                      const float *grad_loss, float *grad_src, float *gR, float *gt, float *payload,
+                                      int transpose_r) {
+    const int B = o.B, N = o.N, M = o.M, L = o.L;
+    float *g1 = o.f32(RRL_WS_G1);
+    RrlRange step("K5 rrl backward");
+    if (!grad_src && B > 0 && L > 0) {
+        // only dL/dR, dL/dt (+ payload): ONE launch, straight from the selected lines
+        const int nblk = o.deterministic ? 16 * ((L + 1023) / 1024) : (L + BWD_LINES - 1) / BWD_LINES;
+        // partials in VALS (the reduce kernel's input tiles: dead after the forward; B * Lp * 16 floats
+        // >= B * 16 ceil(L / 1024) * 12), fixed-order sums by a second launch: nothing to clear
+        float *part = o.deterministic ? o.f32(RRL_WS_VALS) : nullptr;
+        const BwdKArgs a = bwd_args(o, src, loss, grad_loss, gR, gt, payload, transpose_r, part, nblk);
+        // the next epoch's sampler write pass rides along (bwd_write_kernel; rrl_demo_epoch)
+        RrlWriteRider *wr = o.plan.write_rides ? o.write_rider : nullptr;
+        const WriteKArgs wk = wr ? write_args(wr) : WriteKArgs{};
+#define RRL_BWD(DET)                                                                                                            \
+        if (wr) {                                                                                                               \
+            hipLaunchKernelGGL(bwd_write_kernel<DET>, dim3((unsigned)(wk.gx * wk.gy + nblk * B)), dim3(256),                      \
+                               sizeof(int32_t) * (size_t)wk.rounds * wk.gx, o.s, a, wk);                                         \
+            wr->done = 1;                                                                                                       \
+        } else                                                                                                                  \
+            hipLaunchKernelGGL(loss_bwd_rt_kernel<DET>, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, o.s, a.kj, a.sel, a.nsel, \
+                               a.hs1, a.w1, a.Q1, a.Q2, a.D, a.med, a.bcnt, a.info, a.grad_loss, a.src, a.gR, a.gt, a.payload,    \
+                               a.loss, a.B, a.N, a.L, a.transpose_r, a.part, o.problems, B % 8 == 0 && xcd_align_on() ? 1 : 0)
+        if (o.deterministic) {
+            RRL_BWD(true);
+            hipLaunchKernelGGL(loss_bwd_rt_finalize_kernel, dim3(1), dim3(256), 0, o.s, part, o.i32(RRL_WS_INFO), loss,
+                               gR, gt, payload, B, nblk);
+            RRL_LAUNCH_CHECK();
+            return 0;
+        }
+        if (int rc = clear_direct_grads(o, gR, gt, payload)) return rc;
+        RRL_BWD(false);
+#undef RRL_BWD
+        RRL_LAUNCH_CHECK();
+        return 0;
+    }
+    // dL/dsrc wanted too: scatter of the line gradients into G1 (cleared first) ...
+    if (rrl_fused_backward(B, N, M)) {  // ... then rigid backward + payload (reg_bwd_kernel)
+        if (int rc = loss_backward_impl(o, grad_loss, g1, nullptr, true, false)) return rc;
+        return rrl_launch_reg_bwd(o, src, R, grad_src, gR, gt, payload, loss, transpose_r);
+    }
+    int rc = loss_backward_impl(o, grad_loss, g1, nullptr, true, default_deterministic());
+    if (rc) return rc;
+    rc = rrl_rigid_apply_bwd(src, R, g1, grad_src, gR, gt, o.f32(RRL_WS_RPART), B, 3 * N, transpose_r, 0, o.s);
+    if (rc) return rc;
+    if (payload) rc = rrl_shard_payload(loss, o.ws, o.ws_bytes, gR, gt, payload, B, N, M, L, o.s);
     return rc;
 }
 
@@ -699,28 +755,22 @@ extern "C" int rrl_registration_step_ex(const float *src, const float *R, const 
                                         const float *grad_loss, float *gR, float *gt, float *payload, int B, int N,
                                         int M, int L, int transpose_r, int s_m, int s_n, int e_m, int e_n, int mode,
                                         int chunk, const void *target_ws, const rrl_opts *opts, void *stream) {
-    return rrl_registration_step_call(src, R, t, tri2, line, ws, ws_bytes, loss, grad_loss, gR, gt, payload, B, N, M, L,
-                                      transpose_r, s_m, s_n, e_m, e_n, mode, chunk, target_ws, rrl_resolve_opts(opts), stream);
-}
-int rrl_registration_step_call(const float *src, const float *R, const float *t, const float *tri2, const float *line,
-                               void *ws, size_t ws_bytes, float *loss, const float *grad_loss, float *gR, float *gt,
-                               float *payload, int B, int N, int M, int L, int transpose_r, int s_m, int s_n, int e_m, int e_n,
-                               int mode, int chunk, const void *target_ws, RrlCall o, void *stream) {
-    if (!src || !R || !t || !tri2 || !line || !ws || !loss || !grad_loss || !gR || !gt) return RRL_E_ARG;
-    if (B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    o.set(s_m, s_n, e_m, e_n, 0, mode, chunk);
     const RrlXform xf = {src, R, t, transpose_r, 1};
-    int rc = rrl_plan(o, B, N, M, L, 0, mode, target_ws, &xf, RRL_WANT_DIRECT);
-    if (rc) return rc;
+    const bool pointers = src && R && t && tri2 && line && loss && grad_loss && gR && gt;
+    if (const int rc = rrl_check_call(o, pointers, RRL_WANT_DIRECT, target_ws, &xf)) return rc;
+    return rrl_registration_step_call(o, xf, tri2, line, loss, grad_loss, gR, gt, payload);
+}
+int rrl_registration_step_call(RrlCall &o, const RrlXform &xf, const float *tri2, const float *line, float *loss,
+                               const float *grad_loss, float *gR, float *gt, float *payload) {
+    int rc;
     const bool ride = o.plan.bwd_rides;
-    if (ride && (rc = clear_direct_grads(ws, w, gR, gt, payload, B, (hipStream_t)stream))) return rc;
-    const TailBwd tb = {grad_loss, src, gR, gt, payload, transpose_r, nullptr};
-    rc = loss_forward_impl(w.f32(ws, RRL_WS_TRI1), tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0, chunk, o,
-                           stream, ride ? &tb : nullptr);
+    if (ride && (rc = clear_direct_grads(o, gR, gt, payload))) return rc;
+    const TailBwd tb = {grad_loss, xf.src, gR, gt, payload, xf.transpose_r, nullptr};
+    rc = loss_forward_impl(o, o.f32(RRL_WS_TRI1), tri2, line, loss, ride ? &tb : nullptr);
     if (rc || ride) return rc;
-    return registration_backward_impl(src, R, tri2, ws, ws_bytes, loss, grad_loss, nullptr, gR, gt, payload, B, N, M, L,
-                                      transpose_r, o, stream);
+    return registration_backward_impl(o, xf.src, xf.R, loss, grad_loss, nullptr, gR, gt, payload, xf.transpose_r);
 }
 extern "C" int rrl_registration_step(const float *src, const float *R, const float *t, const float *tri2,
                                      const float *line, void *ws, size_t ws_bytes, float *loss,
@@ -740,30 +790,28 @@ extern "C" int rrl_loss_step_ex(const float *tri1, const float *R, const float *
                                 void *ws, size_t ws_bytes, float *loss, const float *grad_loss, float *grad_tri1,
                                 float *grad_tri2, int B, int N, int M, int L, int transpose_r, int s_m, int s_n, int e_m,
                                 int e_n, int mode, int chunk, const void *target_ws, const rrl_opts *opts, void *stream) {
-    if (!tri1 || !tri2 || !line || !ws || !loss || !grad_loss || !grad_tri1 || ((R == nullptr) != (t == nullptr))) return RRL_E_ARG;
-    if (B < 0 || N < 0 || M < 0 || L < 0) return RRL_E_ARG;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
-    RrlCall o = rrl_resolve_opts(opts);
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    o.set(s_m, s_n, e_m, e_n, 0, mode, chunk);
+    RrlXform xf = {tri1, R, t, transpose_r, 0};
+    const bool pointers = tri1 && tri2 && line && loss && grad_loss && grad_tri1 && (R == nullptr) == (t == nullptr);
+    int rc = rrl_check_call(o, pointers, grad_tri2 ? RRL_WANT_SCATTER2 : RRL_WANT_SCATTER, target_ws, R ? &xf : nullptr);
+    if (rc) return rc;
     o.clear_ptr = grad_tri1;
     o.clear_bytes = sizeof(float) * 9 * (size_t)B * N;
     // the shard payload of the step (rrl_opts.payload): in the workspace's GACC field the records launch clears it with the
     // rest of the accumulator (the fused op's convention); any other buffer is cleared here first
     float *payload = o.payload;
-    const bool pay_in_ws = payload && R && payload == w.f32(ws, RRL_WS_GACC) + 12 * (size_t)B;
-    const RrlXform xf = {tri1, R, t, transpose_r, pay_in_ws ? 1 : 0};
-    int rc = rrl_plan(o, B, N, M, L, 0, mode, target_ws, R ? &xf : nullptr, grad_tri2 ? RRL_WANT_SCATTER2 : RRL_WANT_SCATTER);
-    if (rc) return rc;
-    if (payload && !pay_in_ws && (rc = rrl_fill(payload, 0u, sizeof(float) * 14, (hipStream_t)stream))) return rc;
-    const float *p1 = R ? w.f32(ws, RRL_WS_TRI1) : tri1;  // points1: the moved source, or the caller's triangles as given
+    const bool pay_in_ws = payload && R && payload == o.f32(RRL_WS_GACC) + 12 * (size_t)B;
+    xf.zero_g1 = pay_in_ws ? 1 : 0;
+    if (payload && !pay_in_ws && (rc = rrl_fill(payload, 0u, sizeof(float) * 14, o.s))) return rc;
+    const float *p1 = R ? o.f32(RRL_WS_TRI1) : tri1;  // points1: the moved source, or the caller's triangles as given
     const TailBwd tb = {grad_loss, nullptr, nullptr, nullptr, payload, 0, grad_tri1};
-    rc = loss_forward_impl(p1, tri2, line, ws, ws_bytes, loss, B, N, M, L, s_m, s_n, e_m, e_n, 0, chunk, o, stream,
-                           o.plan.bwd_rides ? &tb : nullptr);
+    rc = loss_forward_impl(o, p1, tri2, line, loss, o.plan.bwd_rides ? &tb : nullptr);
     if (rc || o.plan.bwd_rides) return rc;
     // (grad_tri1 was cleared by the build step's first launch -- or by its fill on the unsorted path; an empty batch /
     //  cloud launches nothing: clear here)
-    if (B == 0 || (N == 0 && M == 0)) return rrl_fill(grad_tri1, 0u, o.clear_bytes, (hipStream_t)stream);
-    rc = loss_backward_impl(p1, tri2, ws, ws_bytes, grad_loss, grad_tri1, grad_tri2, B, N, M, L, 0, false, stream, o.deterministic != 0);
+    if (B == 0 || (N == 0 && M == 0)) return rrl_fill(grad_tri1, 0u, o.clear_bytes, o.s);
+    rc = loss_backward_impl(o, grad_loss, grad_tri1, grad_tri2, false, o.deterministic != 0);
     if (rc || !payload || L <= 0 || o.plan.payload_in_reduce) return rc;
     return rrl_shard_payload(loss, ws, ws_bytes, nullptr, nullptr, payload, B, N, M, L, stream);
 }
@@ -773,8 +821,13 @@ extern "C" int rrl_registration_backward_ex(const float *src, const float *R, co
                                             const float *grad_loss, float *grad_src, float *gR, float *gt,
                                             float *payload, int B, int N, int M, int L, int transpose_r,
                                             const rrl_opts *opts, void *stream) {
-    return registration_backward_impl(src, R, tri2, ws, ws_bytes, loss, grad_loss, grad_src, gR, gt, payload, B, N, M, L,
-                                      transpose_r, rrl_resolve_opts(opts), stream);
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    bool ok = src && R && tri2 && grad_loss && gR && gt && (loss || !payload);
+    if (o.problems > 0 && o.problems < B && grad_src) ok = false;  // multi-pose: the direct backward only (dL/dsrc would sum over the poses)
+    // a ragged batch (the counts of the forward, again): the sorted layout's fused tail, which skips the absent source rows
+    if (o.ragged() && (o.problems > 0 || !rrl_sorted_layout(N, M))) ok = false;
+    if (const int rc = rrl_check_call(o, ok, RRL_WANT_NONE)) return rc;
+    return registration_backward_impl(o, src, R, loss, grad_loss, grad_src, gR, gt, payload, transpose_r);
 }
 extern "C" int rrl_registration_backward(const float *src, const float *R, const float *tri2,
                                          void *ws, size_t ws_bytes, const float *loss,
@@ -783,85 +836,4 @@ extern "C" int rrl_registration_backward(const float *src, const float *R, const
                                          void *stream) {
     return rrl_registration_backward_ex(src, R, tri2, ws, ws_bytes, loss, grad_loss, grad_src, gR, gt, payload, B, N, M, L,
                                         transpose_r, nullptr, stream);
-}
-
-static int registration_backward_impl(const float *src, const float *R, const float *tri2,
-                                      void *ws, size_t ws_bytes, const float *loss,
-                                      const float *grad_loss, float *grad_src, float *gR, float *gt,
-                                      float *payload, int B, int N, int M, int L, int transpose_r,
-                                      const RrlCall &o, void *stream) {
-    if (!src || !R || !tri2 || !ws || !grad_loss || !gR || !gt) return RRL_E_ARG;
-    if (payload && !loss) return RRL_E_ARG;
-    if (o.problems > 0 && o.problems < B && grad_src) return RRL_E_ARG;  // multi-pose: the direct backward only (dL/dsrc would sum over the poses)
-    // a ragged batch (the counts of the forward, again): the sorted layout's fused tail, which skips the absent source rows
-    if (o.ragged() && (o.problems > 0 || !rrl_sorted_layout(N, M))) return RRL_E_ARG;
-    WsLayout w(B, N, M, L);
-    if (ws_bytes < w.total) return RRL_E_WS;
-    float *g1 = w.f32(ws, RRL_WS_G1);
-    hipStream_t s = (hipStream_t)stream;
-    RrlRange step("K5 rrl backward");
-    if (!grad_src && B > 0 && L > 0) {
-        // only dL/dR, dL/dt (+ payload): ONE launch, straight from the selected lines
-        const int nblk = o.deterministic ? 16 * ((L + 1023) / 1024) : (L + BWD_LINES - 1) / BWD_LINES;
-#define RRL_BWD_RT(DET, PART)                                                                                  \
-        hipLaunchKernelGGL(loss_bwd_rt_kernel<DET>, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, s,            \
-                           w.u8(ws, RRL_WS_KJ), w.i32(ws, RRL_WS_SEL), w.i32(ws, RRL_WS_NSEL), w.i32(ws, RRL_WS_HS1), \
-                           w.f32(ws, RRL_WS_W1), (const float4 *)w.f32(ws, RRL_WS_Q1),                             \
-                           (const float4 *)w.f32(ws, RRL_WS_Q2), w.f32(ws, RRL_WS_D), w.f32(ws, RRL_WS_MED),       \
-                           w.i32(ws, RRL_WS_BCNT), w.i32(ws, RRL_WS_INFO), grad_loss, src, gR, gt, payload, loss,  \
-                           B, N, L, transpose_r, PART, o.problems, B % 8 == 0 && xcd_align_on() ? 1 : 0)
-        // the next epoch's sampler write pass rides along (bwd_write_kernel; rrl_demo_epoch)
-        RrlWriteRider *wr = o.plan.write_rides ? o.write_rider : nullptr;
-        const int wtiles = wr ? (wr->n + 1023) / 1024 : 0;
-        const WriteKArgs wk = wr ? WriteKArgs{wr->rng_state, wr->r, wr->centers, wr->accept, wr->lines, wr->filled, wr->n,
-                                                wr->rounds, wtiles, wr->rounds}
-                                   : WriteKArgs{};
-#define RRL_BWD_WRITE(DET, PART)                                                                               \
-        do {                                                                                                   \
-            const BwdKArgs ba = {w.u8(ws, RRL_WS_KJ), w.i32(ws, RRL_WS_SEL), w.i32(ws, RRL_WS_NSEL), w.i32(ws, RRL_WS_HS1), \
-                                 w.f32(ws, RRL_WS_W1), (const float4 *)w.f32(ws, RRL_WS_Q1),                    \
-                                 (const float4 *)w.f32(ws, RRL_WS_Q2), w.f32(ws, RRL_WS_D), w.f32(ws, RRL_WS_MED), \
-                                 w.i32(ws, RRL_WS_BCNT), w.i32(ws, RRL_WS_INFO), grad_loss, src, gR, gt, payload, loss, \
-                                 B, N, L, transpose_r, PART, nblk};                                             \
-            hipLaunchKernelGGL(bwd_write_kernel<DET>, dim3((unsigned)(wk.gx * wk.gy + nblk * B)), dim3(256),     \
-                               sizeof(int32_t) * (size_t)wk.rounds * wk.gx, s, ba, wk);                         \
-            wr->done = 1;                                                                                      \
-        } while (0)
-        if (o.deterministic) {
-            // partials in VALS (the reduce kernel's input tiles: dead after the forward; B * Lp * 16 floats
-            // >= B * 16 ceil(L / 1024) * 12), fixed-order sums by a second launch: nothing to clear
-            float *part = w.f32(ws, RRL_WS_VALS);
-            if (wr) RRL_BWD_WRITE(true, part);
-            else RRL_BWD_RT(true, part);
-            hipLaunchKernelGGL(loss_bwd_rt_finalize_kernel, dim3(1), dim3(256), 0, s, part, w.i32(ws, RRL_WS_INFO), loss,
-                               gR, gt, payload, B, nblk);
-            RRL_LAUNCH_CHECK();
-            return 0;
-        }
-        if (int rc = clear_direct_grads(ws, w, gR, gt, payload, B, s)) return rc;
-        if (wr) RRL_BWD_WRITE(false, nullptr);
-        else RRL_BWD_RT(false, nullptr);
-#undef RRL_BWD_RT
-#undef RRL_BWD_WRITE
-        RRL_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rrl_fused_backward(B, N, M)) {
-        // dL/dsrc wanted too: scatter of the line gradients into G1 (cleared first), then rigid
-        // backward + payload (reg_bwd_kernel)
-        int rc = loss_backward_impl(w.f32(ws, RRL_WS_TRI1), tri2, ws, ws_bytes, grad_loss, g1, nullptr,
-                                    B, N, M, L, 0, true, stream);
-        if (rc) return rc;
-        return rrl_launch_reg_bwd(src, R, g1, grad_src, w.f32(ws, RRL_WS_RPART), gR, gt, payload, loss,
-                                  w.i32(ws, RRL_WS_INFO), w.i32(ws, RRL_WS_STATUS) + 3, B, N, transpose_r,
-                                  o.count1, s);
-    }
-    int rc = rrl_loss_backward(w.f32(ws, RRL_WS_TRI1), tri2, ws, ws_bytes, grad_loss, g1, nullptr, B,
-                               N, M, L, 0, stream);
-    if (rc) return rc;
-    rc = rrl_rigid_apply_bwd(src, R, g1, grad_src, gR, gt, w.f32(ws, RRL_WS_RPART), B, 3 * N,
-                             transpose_r, 0, stream);
-    if (rc) return rc;
-    if (payload) rc = rrl_shard_payload(loss, ws, ws_bytes, gR, gt, payload, B, N, M, L, stream);
-    return rc;
 }

@@ -160,16 +160,7 @@ __device__ __forceinline__ void xcd_sample_of(int lin, int gx, int &x, int &b) {
     x = slot % gx;
     b = (lin & 7) + 8 * (slot / gx);
 }
-static int xcd_align_on() {  // RRL_XCD_ALIGN=0 turns it off (experiments)
-    static int v = -1;
-    if (v < 0) {
-        v = 1;
-#ifdef RRL_EXPERIMENT
-        if (const char *e = getenv("RRL_XCD_ALIGN")) v = e[0] == '0' ? 0 : 1;
-#endif
-    }
-    return v;
-}
+// (the host side's switch: rrl_ws.h xcd_align_on)
 
 struct PairArgs {
     const float *tri1, *tri2, *line;  // the triangles of both clouds (raw 36-byte rows: st1 = st2 = 9), the lines

@@ -29,11 +29,6 @@
 
 static_assert(WIDE_HITS == RRL_WIDE_MAX_HITS, "include/rrl.h");
 
-int rrl_tri_prepare_clouds(const float *tri1, const float *tri2, void *ws, size_t ws_bytes, int B, int N, int M, int L,
-                           int clouds, const RrlXform *xf, const float *line, const RrlCall &o, void *stream);  // rrl_scan.hip
-int rrl_line_tri_scan_clouds(const float *line, void *ws, size_t ws_bytes, int B, int N, int M, int L, int mode,
-                             int chunk, int clouds, int lmax_ready, const RrlCall &o, void *stream);         // rrl_scan.hip
-
 // ---- layout of the wide workspace (include/rrl.h RRL_WW_*); every field on a 256-byte boundary, STATUS and NSEL first
 //      (one fill clears both)
 struct WwLayout {
@@ -484,7 +479,10 @@ extern "C" int rrl_wide_workspace_layout(int B, int N, int M, int L, size_t *off
     return 0;
 }
 
-static WideArgs wide_args(void *wws, const WwLayout &v, int B, int N, int M, int L, int pool) {
+// The fields of the wide workspace; with a record (the forward) also the scan's results in the narrow one, the range and
+// the loss -- the backward (o == NULL) reads none of them
+static WideArgs wide_args(void *wws, const WwLayout &v, int B, int N, int M, int L, int pool, const RrlCall *o = nullptr,
+                          float *loss = nullptr) {
     WideArgs a;
     memset(&a, 0, sizeof a);
     a.status = v.at<int32_t>(wws, RRL_WW_STATUS); a.nsel = v.at<int32_t>(wws, RRL_WW_NSEL);
@@ -496,58 +494,65 @@ static WideArgs wide_args(void *wws, const WwLayout &v, int B, int N, int M, int
     a.bcnt = v.at<int32_t>(wws, RRL_WW_BCNT); a.bsum = v.at<unsigned long long>(wws, RRL_WW_BSUM);
     a.info = v.at<int32_t>(wws, RRL_WW_INFO);
     a.B = B; a.N = N; a.M = M; a.L = L; a.pool = pool ? 1 : 0;
+    if (o) {
+        a.count1 = o->i32(RRL_WS_COUNT1); a.count2 = o->i32(RRL_WS_COUNT2);
+        a.hit1 = o->i32(RRL_WS_HIT1); a.hit2 = o->i32(RRL_WS_HIT2);
+        a.ptri1 = o->f32(RRL_WS_PTRI1); a.ptri2 = o->f32(RRL_WS_PTRI2);
+        a.scan_status = o->i32(RRL_WS_STATUS);
+        a.loss = loss;
+        a.s_m = o->s_m; a.s_n = o->s_n; a.e_m = o->e_m; a.e_n = o->e_n;
+    }
     return a;
 }
 
+// The wide entries refuse in the narrow ones' order (include/rrl.h "Refusals") with their own limits: RRL_E_ARG, then
+// RRL_E_RANGE (1 .. RRL_WIDE_MAX_HITS), then RRL_E_WS (either workspace)
 extern "C" int rrl_loss_forward_wide(const float *tri1, const float *tri2, const float *line, void *ws, size_t ws_bytes,
                                      void *wws, size_t wws_bytes, float *loss, int B, int N, int M, int L, int s_m,
                                      int s_n, int e_m, int e_n, int pool, int mode, int chunk, const rrl_opts *opts,
                                      void *stream) {
     if (!tri1 || !tri2 || !line || !ws || !wws || !loss) return RRL_E_ARG;
     if (B < 0 || N < 0 || M < 0 || L < 0 || L >= (1 << 24) || (long long)B * L >= (1ll << 31) || mode < RRL_SCAN_STRICT ||
-        mode > RRL_SCAN_CULL)
+        mode > RRL_SCAN_CULL || chunk < 0)
         return RRL_E_ARG;
+    // the scan, as the narrow forward runs it (rrl_sparse.hip loss_forward_impl): prepared orders and the scan knobs of the
+    // options are honoured; target carry-over, chains, riders, multi-pose and the payload are not (narrow-only features)
+    RrlCall o = rrl_begin_call(opts, B, N, M, L, ws, ws_bytes, stream);
+    o.set(s_m, s_n, e_m, e_n, pool, mode, chunk);
+    if (o.ragged()) return RRL_E_ARG;  // (rrl_opts.count1 / count2 / nlines: the narrow entries only)
     if (s_m < 1 || s_n < 1 || e_m > RRL_WIDE_MAX_HITS + 1 || e_n > RRL_WIDE_MAX_HITS + 1) return RRL_E_RANGE;
-    if (rrl_resolve_opts(opts).ragged()) return RRL_E_ARG;  // (rrl_opts.count1 / count2 / nlines: the narrow entries only)
-    const WsLayout w(B, N, M, L);
     const WwLayout v(B, N, M, L);
-    if (ws_bytes < w.total || wws_bytes < v.total) return RRL_E_WS;
+    if (ws_bytes < o.w.total || wws_bytes < v.total) return RRL_E_WS;
     if (B == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = o.s;
     const int G = pool ? 1 : B;
-    WideArgs a = wide_args(wws, v, B, N, M, L, pool);
+    WideArgs a = wide_args(wws, v, B, N, M, L, pool, &o, loss);
+    a.tri1 = tri1; a.tri2 = tri2; a.line = line;
     int rc;
     if (L == 0) {  // no line: no bucket (INFO, loss zero)
         if ((rc = rrl_fill(a.info, 0u, sizeof(int32_t) * 4 * (size_t)G, s))) return rc;
         return rrl_fill(loss, 0u, sizeof(float) * (size_t)G, s);
     }
-    // the scan, as the narrow forward runs it (rrl_sparse.hip loss_forward_impl): prepared orders and the scan knobs of the
-    // options are honoured; target carry-over, chains, riders, multi-pose and the payload are not (narrow-only features)
-    RrlCall o = rrl_resolve_opts(opts);
     o.flags = 0;
     o.problems = 0;
     o.rider = nullptr;
     o.payload = nullptr;
     o.chain_left = nullptr;
-    if (o.prepared() && (mode != RRL_SCAN_CULL || (N > M ? N : M) > rrl_sort_capacity() || !o.order2))
-        o.order1 = o.order2 = nullptr;
+    const bool sorted = rrl_sorted_layout(N, M);
+    if (o.prepared() && (mode != RRL_SCAN_CULL || !sorted || !o.order2)) o.order1 = o.order2 = nullptr;
     o.tri1_in = tri1;
+    // (no rrl_plan: what the build and the scan read of it)
+    o.plan.scan_mode = mode == RRL_SCAN_CULL && !sorted ? RRL_SCAN_AUTO : mode;
+    o.plan.clouds = o.plan.build_clouds = 2;
+    o.plan.lmax_ready = sorted && (M > N ? M : N) > 0;
     {
         RrlRange r("K1' records + sort + tree");
-        if ((rc = rrl_tri_prepare_clouds(tri1, tri2, ws, ws_bytes, B, N, M, L, 2, nullptr, line, o, stream))) return rc;
+        if ((rc = rrl_tri_prepare_clouds(o, tri1, tri2, line))) return rc;
     }
     {
         RrlRange r("K1 line<->triangle scan");
-        const int lmax_ready = (N > M ? N : M) <= rrl_sort_capacity() && (M > N ? M : N) > 0;
-        if ((rc = rrl_line_tri_scan_clouds(line, ws, ws_bytes, B, N, M, L, mode, chunk, 2, lmax_ready, o, stream))) return rc;
+        if ((rc = rrl_line_tri_scan_clouds(o, line))) return rc;
     }
-    a.tri1 = tri1; a.tri2 = tri2; a.line = line;
-    a.count1 = w.i32(ws, RRL_WS_COUNT1); a.count2 = w.i32(ws, RRL_WS_COUNT2);
-    a.hit1 = w.i32(ws, RRL_WS_HIT1); a.hit2 = w.i32(ws, RRL_WS_HIT2);
-    a.ptri1 = w.f32(ws, RRL_WS_PTRI1); a.ptri2 = w.f32(ws, RRL_WS_PTRI2);
-    a.scan_status = w.i32(ws, RRL_WS_STATUS);
-    a.loss = loss;
-    a.s_m = s_m; a.s_n = s_n; a.e_m = e_m; a.e_n = e_n;
     RrlRange r("W1..W4 wide stages");
     if ((rc = rrl_fill(wws, 0u, v.zero_bytes, s))) return rc;  // STATUS, NSEL
     const dim3 lines((unsigned)((L + 255) / 256), (unsigned)B);

@@ -1,7 +1,12 @@
-// rrl_ws.h -- layout of the caller-allocated workspace (fields: include/rrl.h RRL_WS_*).
-// The first six fields (status, nvals, nsel, pmax, count1, count2) are contiguous so that one
+// rrl_ws.h -- the host layer's shared types: the layout of the caller-allocated workspace (WsLayout; fields: include/rrl.h
+// RRL_WS_*), the record of ONE call (RrlCall: options, plan, shape, bucket range, workspace + layout, stream -- set once at
+// the top of an extern "C" entry by rrl_begin_call, validated once by rrl_check_call, then handed to every host function
+// below the entry), and the prototypes of the host functions that cross translation units.
+// The first six workspace fields (status, nvals, nsel, pmax, count1, count2) are contiguous so that one
 // hipMemsetAsync clears all per-call state.  Every field starts on a 256-byte boundary.
 #pragma once
+#include <stdlib.h>
+
 #include "rrl_common.h"
 
 struct WsLayout {
@@ -9,6 +14,7 @@ struct WsLayout {
     size_t total, zero_bytes;
     size_t state_off, state_bytes;  // MHIST .. MSUM: per-call state of the tiled reduce (cleared by the records kernel)
 
+    __host__ WsLayout() : off{}, total(0), zero_bytes(0), state_off(0), state_bytes(0) {}  // (a record before rrl_begin_call)
     __host__ WsLayout(int B, int N, int M, int L) {
         const size_t b = (size_t)(B > 0 ? B : 0), n = (size_t)(N > 0 ? N : 0),
                      m = (size_t)(M > 0 ? M : 0), l = (size_t)(L > 0 ? L : 0);
@@ -119,10 +125,10 @@ struct RrlWriteRider {
 struct RrlXform;
 // What an entry runs besides the forward (STAGE: one stage entry on its own, no whole forward; SCATTER2: grad_tri2 too);
 // the reduce that serves a call (TILE: one tile of lines per sample, per-line stage + reduce + a backward in one launch).
-enum { RRL_WANT_STAGE, RRL_WANT_FORWARD, RRL_WANT_SCATTER, RRL_WANT_SCATTER2, RRL_WANT_DIRECT };
+enum { RRL_WANT_NONE = -1, RRL_WANT_STAGE, RRL_WANT_FORWARD, RRL_WANT_SCATTER, RRL_WANT_SCATTER2, RRL_WANT_DIRECT };
 enum { RRL_RED_SINGLE, RRL_RED_XCHG, RRL_RED_TAIL, RRL_RED_TILE };
 // Which kernels serve ONE call of the narrow pipeline, decided by rrl_plan (rrl_sparse.hip) before its first launch; the
-// launchers read it and derive none of it again.  All zero (rrl_resolve_opts): nothing rides, nothing chains.
+// launchers read it and derive none of it again.  All zero (rrl_begin_call): nothing rides, nothing chains.
 struct RrlPlan {
     int scan_mode;          // cull demoted to auto beyond the sort capacity
     int clouds, build_clouds;  // clouds scanned (1: the target's scan carried over) / built (1: a kept target)
@@ -159,14 +165,40 @@ struct RrlCall {
     const RrlXform *xf;   // (internal) the source's transform, for the fused build's records body (plan.fused_build) ...
     const float *tri1_in; //   ... and the caller's source rows when there is no transform
     RrlPlan plan;
+    // The call itself (rrl_begin_call): shape, bucket range, pool / scan mode / chunk as the entry received them, the
+    // workspace with its layout -- built ONCE per call -- and the stream.  No host function below an entry takes any of
+    // these as a parameter of its own.
+    int B, N, M, L;
+    int s_m, s_n, e_m, e_n;
+    int pool, mode, chunk;
+    void *ws;
+    size_t ws_bytes;
+    WsLayout w;
+    hipStream_t s;
+    __host__ float *f32(int f) const { return w.f32(ws, f); }
+    __host__ int32_t *i32(int f) const { return w.i32(ws, f); }
+    __host__ uint8_t *u8(int f) const { return w.u8(ws, f); }
+    __host__ int64_t *i64(int f) const { return w.i64(ws, f); }
+    __host__ uint32_t *u32(int f) const { return w.u32(ws, f); }
+    // ... and a field of cloud 2 where its scan left it: the carried-over target's workspace (tar_ws), else this one
+    __host__ const int32_t *tar_i32(int f) const { return w.i32(tar_ws ? tar_ws : (const void *)ws, f); }
+    __host__ void set(int sm, int sn, int em, int en, int pool_, int mode_ = RRL_SCAN_CULL, int chunk_ = 0) {
+        s_m = sm; s_n = sn; e_m = em; e_n = en; pool = pool_; mode = mode_; chunk = chunk_;
+    }
     __host__ bool prepared() const { return order1 != nullptr; }
     __host__ bool target_kept() const { return order1 != nullptr && (flags & RRL_F_TARGET_KEPT); }
     __host__ bool ragged() const { return count1 != nullptr || count2 != nullptr || nlines != nullptr; }
 };
-RrlCall rrl_resolve_opts(const rrl_opts *o);  // rrl_sparse.hip
+// The record of one call (rrl_sparse.hip): rrl_opts resolved + the shape, the workspace with its layout, the stream; bucket
+// range 1 .. 4, pool 0, scan mode cull, chunk 0 until the entry sets what it was given (RrlCall::set)
+RrlCall rrl_begin_call(const rrl_opts *opts, int B, int N, int M, int L, void *ws, size_t ws_bytes, void *stream);
+// THE validation of a narrow entry, before its first launch, in the order of include/rrl.h ("Refusals"): RRL_E_ARG --
+// !pointers (the entry's own null pointers and illegal combinations), the shape, the mode, the plan's refusals
+// (rrl_plan(o, want, target_ws, xf); RRL_WANT_NONE: an entry without a forward, no plan) --, RRL_E_RANGE, RRL_E_WS
+int rrl_check_call(RrlCall &o, bool pointers, int want, const void *target_ws = nullptr, const RrlXform *xf = nullptr);
 // the plan of one call (o.plan; also settles o.problems, the orders, o.tar_ws, o.xf); RRL_E_ARG: an illegal multi-pose call,
 // or a ragged one (counts) combined with what does not serve it (include/rrl.h rrl_opts.count1)
-int rrl_plan(RrlCall &o, int B, int N, int M, int L, int pool, int mode, const void *target_ws, const RrlXform *xf, int want);
+int rrl_plan(RrlCall &o, int want, const void *target_ws, const RrlXform *xf);
 // include/rrl.h rrl_sort_capacity (rrl_cull.hip): the sorted layout (records kernel, sphere tree, culled scan) serves up to it
 inline bool rrl_sorted_layout(int N, int M) { return (N > M ? N : M) <= rrl_sort_capacity(); }
 // the sampler's two passes on their own (rrl_geom.hip; rrl_sample_lines_rng = both): rrl_demo_epoch pipelines them
@@ -175,11 +207,38 @@ int rrl_sample_count_pass(const uint64_t *rng_state, const float *r, const float
 int rrl_sample_write_pass(uint64_t *rng_state, const float *r, const float *centers, float *lines, int32_t *filled,
                           int32_t *tile_counts, int B, int n, int rounds, void *stream);
 int rrl_sample_prefilter(void);
-// rrl_registration_step_ex with the call's options already resolved (rrl_sparse.hip; rrl_epoch.hip adds a rider)
-int rrl_registration_step_call(const float *src, const float *R, const float *t, const float *tri2, const float *line,
-                               void *ws, size_t ws_bytes, float *loss, const float *grad_loss, float *gR, float *gt,
-                               float *payload, int B, int N, int M, int L, int transpose_r, int s_m, int s_n, int e_m, int e_n,
-                               int mode, int chunk, const void *target_ws, RrlCall o, void *stream);
+// rrl_registration_step_ex on a record that went through rrl_check_call(o, .., RRL_WANT_DIRECT, target_ws, &xf)
+// (rrl_sparse.hip; rrl_epoch.hip adds its riders before the check)
+int rrl_registration_step_call(RrlCall &o, const RrlXform &xf, const float *tri2, const float *line, float *loss,
+                               const float *grad_loss, float *gR, float *gt, float *payload);
+// The build and the scan of a planned call (rrl_scan.hip; the plan says which clouds and which scan): o.xf != NULL moves the
+// source into TRI1; line != NULL: the records launch also reduces the lines' maxima
+int rrl_tri_prepare_clouds(const RrlCall &o, const float *tri1, const float *tri2, const float *line);
+int rrl_line_tri_scan_clouds(const RrlCall &o, const float *line);
+// their launchers on the sorted layout (rrl_cull.hip)
+int rrl_launch_tri_build(const RrlCall &o, const float *tri1, const float *tri2, const float *line);
+int rrl_launch_cull_scan(const RrlCall &o, const float *line);
+int rrl_launch_pmax_from_partials(const RrlCall &o, int clouds);
+int rrl_cull_scan_can_fuse(const RrlCall &o);
+int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, float4 *crec2, float *apart, int nblk,
+                          float4 *p0s1, float4 *p0s2, int32_t *idx1, int32_t *idx2, float4 *grp1, float4 *grp2,
+                          uint32_t *pmax, unsigned *histg, uint32_t *zwords, int nzwords, int B, int N, int M, hipStream_t s);
+// the rigid backward behind the scatter (rrl_geom.hip)
+int rrl_fused_backward(int B, int N, int M);
+int rrl_launch_reg_bwd(const RrlCall &o, const float *src, const float *R, float *grad_src, float *gR, float *gt,
+                       float *payload, const float *loss, int transpose_r);  // (G1 -> grad_src, gR, gt; RPART, INFO, STATUS[3])
+// Sample b's workgroups on XCD b % 8 (rrl_stage_pair.inc xcd_sample_of; the records launch places (cloud, sample) pairs the
+// same way).  RRL_XCD_ALIGN=0 turns it off (experimental builds): the one reader of that knob, for every launcher
+inline int xcd_align_on() {
+    static int v = -1;
+    if (v < 0) {
+        v = 1;
+#ifdef RRL_EXPERIMENT
+        if (const char *e = getenv("RRL_XCD_ALIGN")) v = e[0] == '0' ? 0 : 1;
+#endif
+    }
+    return v;
+}
 // the process-wide defaults, one accessor per translation unit that owns one
 int rrl_default_sort_parts(void);                                           // rrl_cull.hip
 void rrl_default_scan_counters(unsigned long long **buf, long long *rows);  // rrl_cull.hip

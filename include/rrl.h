@@ -16,6 +16,14 @@
  *     scan-timing hook owns a few hipEvents);
  *   - `stream` is a hipStream_t (pass torch's current stream);
  *   - return value: 0 ok, <0 argument error (RRL_E_*), >0 a hipError_t;
+ *   - Refusals.  Every entry of the loss pipeline (rrl_tri_prepare .. rrl_loss_step_ex, rrl_demo_epoch's step) validates its
+ *     call ONCE, on the host, before its first launch, and reports what it finds in this order: (1) RRL_E_ARG -- a null
+ *     pointer, a negative size, L >= 2^24 (line ids have 24 bits), an unknown scan mode, a negative chunk, target_ws == ws,
+ *     and every combination of options the entry does not serve (rrl_opts below: multi-pose, ragged batches); (2)
+ *     RRL_E_RANGE -- a bucket range outside 1..RRL_MAX_HITS; (3) RRL_E_WS -- a workspace smaller than
+ *     rrl_workspace_bytes(B, N, M, L).  A call that is invalid in several ways reports the first of these.  The wide
+ *     entries follow the same order with their own limits (B L < 2^31, 1..RRL_WIDE_MAX_HITS, both workspaces).  An empty
+ *     batch or line set (B == 0, L == 0) is valid and returns 0 after the checks;
  *   - all floating-point data is fp32, dense and contiguous;
  *   - re-entrant and thread-safe per stream AND per workspace: no entry keeps state between calls except what the
  *     caller's buffers hold, the options of a call are resolved once at its top (rrl_opts below), and two host threads
