@@ -732,7 +732,9 @@ extern "C" int rrl_chamfer_bwd(const float *x, const float *y, const uint64_t *b
                                const uint64_t *best_y, const float *grad_value, float *gx, float *gy,
                                int B, int N, int M, void *stream) {
     if (!x || !y || !best_x || !best_y || !grad_value || B < 0 || N < 0 || M < 0) return RRL_E_ARG;
-    if (B == 0 || N + M == 0) return 0;
+    if (B == 0) return 0;
+    // an empty cloud has no minima: the forward refuses it, so no keys exist whose index the kernel could follow
+    if (N == 0 || M == 0) return RRL_E_ARG;
     hipLaunchKernelGGL(chamfer_bwd_kernel, dim3((unsigned)((N + M + 255) / 256), (unsigned)B), dim3(256),
                        0, (hipStream_t)stream, x, y, (const unsigned long long *)best_x,
                        (const unsigned long long *)best_y, grad_value, gx, gy, B, N, M);

@@ -733,6 +733,8 @@ int rrl_chamfer_tree_fwd_ex(const float *x, const float *y, void *ws, size_t ws_
 int rrl_chamfer_from_loss_ex(void *ws_src, const void *ws_tar, size_t loss_ws_bytes, int B, int N, int M,
                              int L, void *ws, size_t ws_bytes, uint64_t *best_x, uint64_t *best_y, float *value,
                              uint64_t *counters, long long counter_rows, void *stream);
+/* Backward of either forward from the keys it left: gx [B][N][3], gy [B][M][3] are ACCUMULATED into (zero them first);
+ * either may be NULL.  Like the forwards it refuses an empty cloud (N == 0 or M == 0 with B > 0: RRL_E_ARG, no launch). */
 int rrl_chamfer_bwd(const float *x, const float *y, const uint64_t *best_x,
                     const uint64_t *best_y, const float *grad_value, float *gx, float *gy, int B,
                     int N, int M, void *stream);
