@@ -95,17 +95,31 @@ __device__ __forceinline__ T dist_sq(float px, float py, float pz, T ux, T uy, T
 //      its CU's L1 (no acquire fence).  16-byte accesses go through a buffer descriptor built from wave-uniform values
 //      (base: kernel argument + blockIdx-derived offset; bytes < 2^31), 4-byte ones are relaxed agent-scope atomics.
 typedef unsigned int rrl_v4u __attribute__((ext_vector_type(4)));
+constexpr int RRL_RSRC_FLAGS = 0x00020000;  // word 3 of a raw buffer descriptor (gfx9: DATA_FORMAT = 32, no swizzle)
+constexpr int RRL_POLICY_SC1 = 16;          // cache-policy operand of the raw buffer accesses: sc1 (0: the default policy)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rrl_rsrc(const void *base, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)(bytes > 0x7ffffff0u ? 0x7ffffff0u : bytes), 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)(bytes > 0x7ffffff0u ? 0x7ffffff0u : bytes), RRL_RSRC_FLAGS);
+}
+// ... with a size the caller knows to fit 31 bits: no 64-bit clamp (VALU work on this target); bytes = 0: every access is out of
+// range and reads zeros
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rrl_rsrc32(const void *base, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, bytes, RRL_RSRC_FLAGS);
 }
 __device__ __forceinline__ void st16_sc1(__amdgpu_buffer_rsrc_t r, unsigned byte_off, float4 v) {
     const rrl_v4u u = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-    __builtin_amdgcn_raw_buffer_store_b128(u, r, (int)byte_off, 0, 16);
+    __builtin_amdgcn_raw_buffer_store_b128(u, r, (int)byte_off, 0, RRL_POLICY_SC1);
 }
-__device__ __forceinline__ float4 ld16_sc1(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    const rrl_v4u u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 16);
+// range-checked loads through a descriptor (a lane past the descriptor's size reads zeros), POLICY = 0 or RRL_POLICY_SC1
+template <int POLICY>
+__device__ __forceinline__ float4 ld16_buf(__amdgpu_buffer_rsrc_t r, int byte_off) {
+    const rrl_v4u u = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, POLICY);
     return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
 }
+template <int POLICY>
+__device__ __forceinline__ float ld4_buf(__amdgpu_buffer_rsrc_t r, int byte_off) {
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, POLICY));
+}
+__device__ __forceinline__ float4 ld16_sc1(__amdgpu_buffer_rsrc_t r, unsigned byte_off) { return ld16_buf<RRL_POLICY_SC1>(r, (int)byte_off); }
 __device__ __forceinline__ void st4_sc1(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float ld4_sc1(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 

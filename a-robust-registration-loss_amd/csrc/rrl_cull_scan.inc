@@ -491,6 +491,10 @@ __device__ __forceinline__ void cull_scan_body(
     const int bx, const int by, const int bz, const int gx, const int gy, const int Bt,
     const int32_t *__restrict__ cnt1, const int32_t *__restrict__ cnt2, const int32_t *__restrict__ nlines,
     Wait wait_ready = Wait()) {
+    // the chained launch (TILEMAX) always runs 64 * WPB lanes: blockDim.x is a HIDDEN kernel argument, a cache line of its own
+    // far behind the explicit ones and one more dependent scalar round in front of the line loads
+    auto bdim = []() { if constexpr (TILEMAX) return 64u * WPB; else return blockDim.x; };
+    auto nwv = []() { if constexpr (TILEMAX) return (int)WPB; else return (int)(blockDim.x >> 6); };
 #if !CULL_REGLINES
     float2 (&line_lds)[WPB][LPW * 3] = lds_.line_lds;
 #endif
@@ -524,7 +528,7 @@ __device__ __forceinline__ void cull_scan_body(
     const int sg0 = bz * spw;
     if (sg0 >= nsg) return;  // uniform: the smaller cloud (or sample) has fewer slices
     const int nl = rrl_rows(nlines, input_of(b, Bt), L);
-    if (by * (int)(blockDim.x >> 6) * LPW >= nl) return;  // uniform: a tile of lines the sample does not have (nl < L only)
+    if (by * nwv() * LPW >= nl) return;  // uniform: a tile of lines the sample does not have (nl < L only)
     // multi-pose evaluation (rrl_opts.problems): instance b has the target and lines of problem b % Bt -- the target's scan
     // is the same for every pose, so only the first Bt instances scan cloud 2 (the per-line stage reads it there)
     if (cloud && Bt > 0 && b >= Bt) return;  // uniform
@@ -537,7 +541,7 @@ __device__ __forceinline__ void cull_scan_body(
     //      wavefront's 128 lines
     constexpr int RPT = (SPW * SGT + 64 * WPB - 1) / (64 * WPB);  // records per lane of a full workgroup
     static_assert(SPW * NODE <= 64 * WPB, "one node per lane");
-    const bool one_each = (int)blockDim.x == 64 * WPB;
+    const bool one_each = (int)bdim() == 64 * WPB;
     const int32_t *idx = (cloud ? idx2 : idx1) + (size_t)b * nsgc * SGT;
     float4 rec0[RPT], nd0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     static_assert(LMAX_CHUNKS == 64, "one partial row per lane");
@@ -553,27 +557,64 @@ __device__ __forceinline__ void cull_scan_body(
     // max |P|^2 of the cloud: from the sort kernel (PMAX), or -- prepared clouds, whose build has no single-workgroup stage
     // -- from the records kernel's per-workgroup partial rows, reduced here next to the line maxima (one more independent
     // load of the prologue; one workgroup per cloud and sample leaves PMAX for the later consumers)
+    // TILEMAX (the chained launch; measured there, profiles/prologue_rounds.txt): the three requests -- partial rows, records,
+    // nodes -- are BUFFER loads whose descriptors span exactly the rows this workgroup may read: a lane past the end gets
+    // zeros from the range check instead of sitting out behind an exec mask.  Their lane offsets are computed here, ahead
+    // of everything; what remains per request is scalar work and the instruction itself, so no vector register is written
+    // between two requests and nothing makes the compiler wait for one of them before the next leaves (it used to put a
+    // full wait between the record and the node request of a source workgroup, and one behind the partial rows' loop).
+    // The values are only TAKEN here; pmv is folded where the slack needs it.  The plain kernel keeps the loop and the
+    // predicated loads: its steps (cold, unkept, ragged) have no measurement of the other form.
     float pmv = 0.0f;
+    const int off16 = tid * 16, off32 = lane * 32;
+    int offk[RPT];  // (in the vector offset: the range check does not see a scalar offset)
+#pragma unroll
+    for (int k = 0; k < RPT; ++k) offk[k] = off16 + 64 * WPB * 16 * k;
     auto issue_records = [&]() {
-        if (apart != nullptr) {  // uniform
+        if constexpr (TILEMAX) {
+            const bool pub = cloud == 0;  // (uniform; sc1: the source's rows were written by this launch's records workgroups)
             const int nb = (n + REC_BLK - 1) / REC_BLK;
-            const float *ap = apart + (size_t)(cloud * B + b) * nblk_apart * 8 + 6;
-            for (int j = lane; j < nb; j += 64) pmv = fmaxf(pmv, TILEMAX && cloud == 0 ? ld4_sc1(ap + (size_t)j * 8) : ap[(size_t)j * 8]);
-        } else {
-            pmv = __uint_as_float(pmax[cloud * B + b]);
-        }
-        if (one_each) {
-            if (TILEMAX && cloud == 0) {  // (uniform; sc1: the source's records and nodes were written by this launch's records workgroups)
-                const __amdgpu_buffer_rsrc_t prs = rrl_rsrc(p0s, (size_t)nsg * SGT * 16), trs = rrl_rsrc(tree, (size_t)nsg * NODE * 16);
-    #pragma unroll
-                for (int k = 0; k < RPT; ++k)
-                    if (tid + 64 * WPB * k < nsl * SGT) rec0[k] = ld16_sc1(prs, (unsigned)(sg0 * SGT + tid + 64 * WPB * k) * 16u);
-                if (tid < nsl * NODE) nd0 = ld16_sc1(trs, (unsigned)(sg0 * NODE + tid) * 16u);
+            const float *ap = apart != nullptr ? apart + (size_t)(cloud * B + b) * nblk_apart * 8 + 6 : nullptr;
+            // (sizes in 32 bits: at most SORT_CAP records of 16 bytes)
+            // (ars: row j's word lies at byte 32 j and is 4 bytes long -> the last one ends at 32 (nb - 1) + 4 = 32 nb - 28)
+            const __amdgpu_buffer_rsrc_t ars = rrl_rsrc32(ap, apart != nullptr ? nb * 32 - 28 : 0);
+            const __amdgpu_buffer_rsrc_t prs = rrl_rsrc32(p0s + (size_t)sg0 * SGT, nsl * (SGT * 16));
+            const __amdgpu_buffer_rsrc_t trs = rrl_rsrc32(tree + (size_t)sg0 * NODE, nsl * (NODE * 16));
+            // (pmv is DEFINED by exactly one of the three sources -- a value merged with an earlier one would be a register copy,
+            //  and a copy waits for every load in flight)
+            if (apart == nullptr) {  // uniform
+                pmv = __uint_as_float(pmax[cloud * B + b]);
+            } else if (nb > 64) {  // uniform; clouds beyond 16384 records: more than one partial row per lane
+                float m = 0.0f;
+                for (int j = lane; j < nb; j += 64) m = fmaxf(m, pub ? ld4_sc1(ap + (size_t)j * 8) : ap[(size_t)j * 8]);
+                pmv = m;
+            } else if (pub) {
+                pmv = ld4_buf<RRL_POLICY_SC1>(ars, off32);
             } else {
-    #pragma unroll
-            for (int k = 0; k < RPT; ++k)
-                if (tid + 64 * WPB * k < nsl * SGT) rec0[k] = p0s[(size_t)sg0 * SGT + tid + 64 * WPB * k];
-            if (tid < nsl * NODE) nd0 = tree[(size_t)sg0 * NODE + tid];
+                pmv = ld4_buf<0>(ars, off32);
+            }
+            if (pub) {
+#pragma unroll
+                for (int k = 0; k < RPT; ++k) rec0[k] = ld16_buf<RRL_POLICY_SC1>(prs, offk[k]);
+                nd0 = ld16_buf<RRL_POLICY_SC1>(trs, off16);
+            } else {
+#pragma unroll
+                for (int k = 0; k < RPT; ++k) rec0[k] = ld16_buf<0>(prs, offk[k]);
+                nd0 = ld16_buf<0>(trs, off16);
+            }
+        } else {
+            if (apart != nullptr) {  // uniform
+                const int nb = (n + REC_BLK - 1) / REC_BLK;
+                const float *ap = apart + (size_t)(cloud * B + b) * nblk_apart * 8 + 6;
+                for (int j = lane; j < nb; j += 64) pmv = fmaxf(pmv, ap[(size_t)j * 8]);
+            } else {
+                pmv = __uint_as_float(pmax[cloud * B + b]);
+            }
+            if (one_each) {
+#pragma unroll
+                for (int k = 0; k < RPT; ++k)
+                    if (tid + 64 * WPB * k < nsl * SGT) rec0[k] = p0s[(size_t)sg0 * SGT + tid + 64 * WPB * k];
+                if (tid < nsl * NODE) nd0 = tree[(size_t)sg0 * NODE + tid];
             }
         }
     };
@@ -584,7 +625,7 @@ __device__ __forceinline__ void cull_scan_body(
     // this wave's 128 lines: a full, 16-byte aligned tile arrives as three coalesced 16-byte loads per lane straight
     // into its LDS rows; the lanes then pick up their own two lines from there
     const float *ln = line + (size_t)input_of(b, Bt) * L * 6;
-    const int lw0 = (by * (int)(blockDim.x >> 6) + wave) * LPW;
+    const int lw0 = (by * nwv() + wave) * LPW;
     const int l0 = lw0 + lane, l1 = l0 + 64;
     const bool live0 = l0 < nl, live1 = l1 < nl;
     const bool has_lines = lw0 < nl;  // a wave without lines (the last tile of the line set) still stages records
@@ -613,7 +654,7 @@ __device__ __forceinline__ void cull_scan_body(
     // ---- slack of this (cloud, sample): the same values in every wavefront and workgroup (no exchange, no barrier)
     float pm = pmv;
     if (apart != nullptr) {  // uniform
-        pm = wave_max_nonneg(pmv);
+        pm = wave_max_nonneg(TILEMAX ? fmaxf(0.0f, pmv) : pmv);  // (fmaxf(0, row): what the loop computes for a lane with one row)
         if (by == 0 && bz == 0 && tid == 0) pmax[cloud * B + b] = __float_as_uint(pm);
     }
     // ---- this wavefront's lines into LDS / registers, the lane's own two lines, their norms
@@ -654,7 +695,7 @@ __device__ __forceinline__ void cull_scan_body(
         if (lane == 0) *(float2 *)&qa_lds[wave][0] = make_float2(sm, om);
         __syncthreads();
         smax = 0.0f; o2max = 0.0f;
-        const int nw = (int)(blockDim.x >> 6);
+        const int nw = nwv();
         for (int w_ = 0; w_ < nw; ++w_) {
             const float2 t = *(const float2 *)&qa_lds[w_][0];
             smax = fmaxf(smax, t.x); o2max = fmaxf(o2max, t.y);
@@ -706,7 +747,7 @@ __device__ __forceinline__ void cull_scan_body(
                 if (tid + 64 * WPB * k < nsl * SGT) dl[tid + 64 * WPB * k] = dv[k];
         } else {
             const float *del = (cloud ? del2 : del1) + (size_t)b * ncap;
-            for (int i = tid; i < nsl * SGT; i += blockDim.x) {
+            for (int i = tid; i < nsl * SGT; i += bdim()) {
                 const int sp = sg0 * SGT + i;
                 dl[i] = sp < n ? del[psorted ? sp : idx[sp]] : 0.0f;
             }
@@ -748,8 +789,8 @@ __device__ __forceinline__ void cull_scan_body(
             if (tid + 64 * WPB * k < nsl * SGT) stage_rec(tid + 64 * WPB * k, rec0[k], nanwide ? dv[k] : 0.0f);
         if (tid < nsl * NODE) stage_node(tid, nd0);
     } else {
-        for (int i = tid; i < nsl * SGT; i += blockDim.x) stage_rec(i, p0s[(size_t)sg0 * SGT + i], nanwide ? dl[i] : 0.0f);
-        for (int i = tid; i < nsl * NODE; i += blockDim.x) stage_node(i, tree[(size_t)sg0 * NODE + i]);
+        for (int i = tid; i < nsl * SGT; i += bdim()) stage_rec(i, p0s[(size_t)sg0 * SGT + i], nanwide ? dl[i] : 0.0f);
+        for (int i = tid; i < nsl * NODE; i += bdim()) stage_node(i, tree[(size_t)sg0 * NODE + i]);
     }
     if constexpr (COUNT) wall_prebar = wall_clock64();  // this wavefront's own share is staged: what follows is the wait for the others
     __syncthreads();  // the one barrier of the (usual) prologue
@@ -910,11 +951,19 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 8))
 // CHAIN arrive cleared.  The scan's NaN flag / fallback count of this launch are per sample (CHAIN[b][1], [2]): STATUS could not
 // be cleared under the target workgroups' feet.
 // ---------------------------------------------------------------------------------------
+// (the head: what a scan workgroup needs for its place in the grid, its line loads and -- one round of scalar loads at kernel
+//  entry -- its record loads; the first members are the candidates for kernel-argument preload)
 struct ChainKArgs {
-    uint32_t *chain;       // CHAIN words [B][4]
     int zrec;              // grid planes [0, zrec): the records pieces
-    int nrec_b;            // records pieces (workgroups) per sample: the ready count a source workgroup waits for
     int z2;                // grid planes [zrec, zrec + z2): the target cloud's slices; the source cloud's follow
+    int B, N, M, L, spw, nblk_apart;
+    const float *line;
+    uint32_t *chain;       // CHAIN words [B][4]
+    const float *apart;
+    const float4 *p0s1, *p0s2, *tree1, *tree2;
+    uint32_t *pmax;
+    int nrec_b;            // records pieces (workgroups) per sample: the ready count a source workgroup waits for
+    int gy;                // line tiles: the grid's second extent (gridDim is a hidden argument)
     unsigned spin_limit;   // polls before a waiter gives up
     int exp;               // (experimental builds, -DRRL_CHAIN_EXP: RRL_CHAIN_EXP = 1 nobody waits | 2 the records workgroups return at once
                            //  -- timing only, results invalid)
@@ -925,22 +974,24 @@ struct ChainKArgs {
 // cloud's slices, the rest the source cloud's -- dispatch goes plane by plane, so the order is records, target, source,
 // and a workgroup's place needs no division.
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))) void cull_scan_build_kernel(
-    const float *__restrict__ ptri1, const float *__restrict__ ptri2, const float4 *__restrict__ p0s1,
-    const float4 *__restrict__ p0s2, const int32_t *__restrict__ idx1, const int32_t *__restrict__ idx2,
-    const float4 *__restrict__ tree1, const float4 *__restrict__ tree2, const float *__restrict__ line,
-    int32_t *__restrict__ count1, int32_t *__restrict__ hit1, int32_t *__restrict__ count2,
-    int32_t *__restrict__ hit2, uint32_t *pmax, const float *__restrict__ del1, const float *__restrict__ del2,
-    const float *__restrict__ apart, int nblk_apart, int B, int N, int M, int L, int spw, const BuildArgs bld,
-    const int32_t *__restrict__ order1, const ChainKArgs ch) {
+    const ChainKArgs ch, const float *__restrict__ ptri1, const float *__restrict__ ptri2,
+    const int32_t *__restrict__ idx1, const int32_t *__restrict__ idx2, int32_t *__restrict__ count1,
+    int32_t *__restrict__ hit1, int32_t *__restrict__ count2, int32_t *__restrict__ hit2,
+    const float *__restrict__ del1, const float *__restrict__ del2, const BuildArgs bld,
+    const int32_t *__restrict__ order1) {
     __shared__ union {
         CullLds scan;
         float red[WPB][8];
     } lds_;
+    asm volatile("" ::"s"(ch.zrec), "s"(ch.z2), "s"(ch.B), "s"(ch.N), "s"(ch.M), "s"(ch.L), "s"(ch.spw), "s"(ch.nblk_apart),
+                 "s"(ch.line), "s"(ch.chain), "s"(ch.apart), "s"(ch.p0s1), "s"(ch.p0s2), "s"(ch.tree1), "s"(ch.tree2), "s"(ch.pmax),
+                 "s"(ch.nrec_b), "s"(ch.gy), "s"(ch.spin_limit));
+    const int B = ch.B;
     const int b = (int)blockIdx.x, by = (int)blockIdx.y, z = (int)blockIdx.z;
     STAMPR(0);
     if (z < ch.zrec) {  // uniform per workgroup: one 512-lane piece of the source's records (+ tree refit, partial rows)
         RecPlace pl;
-        pl.cloud = 0; pl.b = b; pl.bxr = z * (int)gridDim.y + by; pl.lch = -1;
+        pl.cloud = 0; pl.b = b; pl.bxr = z * ch.gy + by; pl.lch = -1;
         if (pl.bxr >= ch.nrec_b) return;
 #ifdef RRL_CHAIN_EXP
         if (ch.exp & 2) return;
@@ -961,7 +1012,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
 #ifndef RRL_NO_LATE
         rec_late_stores(bld, pl, late);
 #endif
-        build_clear_state(bld, ((size_t)(pl.bxr * B + b)) * blockDim.x + threadIdx.x, (size_t)ch.nrec_b * B * blockDim.x);
+        build_clear_state(bld, ((size_t)(pl.bxr * B + b)) * (64 * WPB) + threadIdx.x, (size_t)ch.nrec_b * B * (64 * WPB));
         STAMPR(4);
         return;
     }
@@ -987,10 +1038,10 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
             STAMPR(5);
         }
     };
-    cull_scan_body<false, true>(lds_.scan, ptri1, ptri2, p0s1, p0s2, idx1, idx2, tree1, tree2, line, count1, hit1, count2, hit2,
-                                (int32_t *)(ch.chain + 4 * b + 1), pmax, del1, del2, nullptr, apart, apart, nblk_apart, B, N, M, L,
-                                spw, nullptr, 0, cloud * B + b, by, bz, 2 * B, (int)gridDim.y, 0, nullptr, nullptr, nullptr,
-                                wait_ready);  // (no counts: rrl_cull_scan_can_fuse declines ragged calls)
+    cull_scan_body<false, true>(lds_.scan, ptri1, ptri2, ch.p0s1, ch.p0s2, idx1, idx2, ch.tree1, ch.tree2, ch.line, count1, hit1,
+                                count2, hit2, (int32_t *)(ch.chain + 4 * b + 1), ch.pmax, del1, del2, nullptr, ch.apart, ch.apart,
+                                ch.nblk_apart, B, ch.N, ch.M, ch.L, ch.spw, nullptr, 0, cloud * B + b, by, bz, 2 * B, ch.gy, 0,
+                                nullptr, nullptr, nullptr, wait_ready);  // (no counts: rrl_cull_scan_can_fuse declines ragged calls)
     STAMPR(6);
 }
 
@@ -1034,6 +1085,9 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
         bld.z2 = nullptr; bld.z2_vec4 = 0;
         bld.z5 = nullptr; bld.z5_words = 0;
         ChainKArgs ch;
+        ch.B = a.B; ch.N = a.N; ch.M = a.M; ch.L = a.L; ch.spw = a.spw; ch.nblk_apart = a.nblk_apart;
+        ch.line = a.line; ch.apart = a.apart; ch.p0s1 = a.p0s1; ch.p0s2 = a.p0s2; ch.tree1 = a.tree1; ch.tree2 = a.tree2;
+        ch.pmax = a.pmax; ch.gy = tiles;
         ch.chain = o.u32(RRL_WS_CHAIN);
         ch.nrec_b = bld.nblk_tri;
         ch.zrec = (bld.nblk_tri + tiles - 1) / tiles;
@@ -1046,8 +1100,8 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
         if (const char *e = getenv("RRL_CHAIN_EXP")) ch.exp = atoi(e);
 #endif
         hipLaunchKernelGGL(cull_scan_build_kernel, dim3((unsigned)B, (unsigned)tiles, (unsigned)(ch.zrec + ch.z2 + z1)), dim3(64 * WPB), 0,
-                           o.s, a.ptri1, a.ptri2, a.p0s1, a.p0s2, a.idx1, a.idx2, a.tree1, a.tree2, a.line, a.count1, a.hit1, a.count2,
-                           a.hit2, a.pmax, a.del1, a.del2, a.apart, a.nblk_apart, a.B, a.N, a.M, a.L, a.spw, bld, o.order1, ch);
+                           o.s, ch, a.ptri1, a.ptri2, a.idx1, a.idx2, a.count1, a.hit1, a.count2, a.hit2, a.del1, a.del2, bld,
+                           o.order1);
         RRL_LAUNCH_CHECK();
         return 0;
     }
