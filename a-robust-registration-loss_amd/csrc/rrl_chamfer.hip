@@ -233,12 +233,12 @@ extern "C" int rrl_chamfer_from_loss_ex(void *ws_src, const void *ws_tar, size_t
     const ChamTick tick = {mctl + 32, mctl + 30, 64, 1};
 #define RRL_NN_LAUNCH(COUNT)                                                                                     \
     hipLaunchKernelGGL((chamfer_tree_kernel<COUNT, true>), dim3((unsigned)(2 * B), (unsigned)nsgmax), dim3(64 * NWV), 0, \
-                       s, (const float4 *)lw.f32(ws_src, RRL_WS_P0S1), (const float4 *)lw.f32(ws_tar, RRL_WS_P0S2), \
-                       (const float4 *)lw.f32(ws_src, RRL_WS_GRP1), (const float4 *)lw.f32(ws_tar, RRL_WS_GRP2),  \
+                       s, (const float4 *)lw.at<RRL_WS_P0S1>(ws_src), (const float4 *)lw.at<RRL_WS_P0S2>(ws_tar), \
+                       (const float4 *)lw.at<RRL_WS_GRP1>(ws_src), (const float4 *)lw.at<RRL_WS_GRP2>(ws_tar),  \
                        (const float *)nullptr, 0, (unsigned long long *)best_x, (unsigned long long *)best_y,    \
-                       (double *)(w + C.partial), B, N, M, cnt_buf, cnt_rows, lw.i32(ws_src, RRL_WS_IDX1), \
-                       lw.i32(ws_tar, RRL_WS_IDX2), (const uint32_t *)lw.i32(ws_src, RRL_WS_PMAX),              \
-                       (const uint32_t *)lw.i32(ws_tar, RRL_WS_PMAX) + B, tick, (double *)(w + C.gpart), value,  \
+                       (double *)(w + C.partial), B, N, M, cnt_buf, cnt_rows, lw.at<RRL_WS_IDX1>(ws_src), \
+                       lw.at<RRL_WS_IDX2>(ws_tar), (const uint32_t *)lw.at<RRL_WS_PMAX>(ws_src),              \
+                       (const uint32_t *)lw.at<RRL_WS_PMAX>(ws_tar) + B, tick, (double *)(w + C.gpart), value,  \
                        (double)B * (double)(N + M))
     if (cnt_buf) RRL_NN_LAUNCH(true);
     else RRL_NN_LAUNCH(false);

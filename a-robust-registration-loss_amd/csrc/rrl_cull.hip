@@ -1021,7 +1021,7 @@ int rrl_launch_cull_scan(const RrlCall &o, const float *line) {
     if (o.plan.fused_build && (o.plan.clouds != 2 || g.waves != scan8::kWPB)) return RRL_E_ARG;  // (rrl_cull_scan_can_fuse said otherwise)
     if (!o.plan.lmax_ready && !o.plan.fused_build)  // the triangles were prepared without the lines: their partial maxima first (a tiny launch)
         hipLaunchKernelGGL(line_max_kernel, dim3(LMAX_CHUNKS, (unsigned)o.B), dim3(REC_BLK), 0, o.s, line, o.L,
-                           (float2 *)o.f32(RRL_WS_LMAX), o.problems, o.nlines);
+                           (float2 *)o.at<RRL_WS_LMAX>(), o.problems, o.nlines);
     // (A PERSISTENT variant -- as many workgroups as fit on the chip, each keeping one line tile staged and pulling
     // (cloud, slice) items from per-tile work queues, the next slice's records prefetched during the walk -- was built
     // and measured in round 3: exact, but 40.7 us against 30.4 at C2 and 29.0 against 13.8 at the demo's shape.  A slot
@@ -1089,36 +1089,36 @@ static BuildArgs make_build_args(const RrlCall &o, const float *tri1, const floa
     a.tri2 = tri2;
     a.R = xf ? xf->R : nullptr;
     a.t = xf ? xf->t : nullptr;
-    a.tri1_out = xf ? o.f32(RRL_WS_TRI1) : nullptr;
-    a.ptri1 = o.f32(RRL_WS_PTRI1);
-    a.ptri2 = o.f32(RRL_WS_PTRI2);
-    a.crec1 = (float4 *)o.f32(RRL_WS_CREC1);
-    a.crec2 = (float4 *)o.f32(RRL_WS_CREC2);
-    a.apart = o.f32(RRL_WS_APART);
-    a.p0s1 = (float4 *)o.f32(RRL_WS_P0S1);
-    a.p0s2 = (float4 *)o.f32(RRL_WS_P0S2);
-    a.idx1 = o.i32(RRL_WS_IDX1);
-    a.idx2 = o.i32(RRL_WS_IDX2);
-    a.grp1 = (float4 *)o.f32(RRL_WS_GRP1);
-    a.grp2 = (float4 *)o.f32(RRL_WS_GRP2);
-    a.pmax = o.u32(RRL_WS_PMAX);
-    a.zero_base = (uint4 *)o.i32(RRL_WS_STATUS);
+    a.tri1_out = xf ? o.at<RRL_WS_TRI1>() : nullptr;
+    a.ptri1 = o.at<RRL_WS_PTRI1>();
+    a.ptri2 = o.at<RRL_WS_PTRI2>();
+    a.crec1 = (float4 *)o.at<RRL_WS_CREC1>();
+    a.crec2 = (float4 *)o.at<RRL_WS_CREC2>();
+    a.apart = o.at<RRL_WS_APART>();
+    a.p0s1 = (float4 *)o.at<RRL_WS_P0S1>();
+    a.p0s2 = (float4 *)o.at<RRL_WS_P0S2>();
+    a.idx1 = o.at<RRL_WS_IDX1>();
+    a.idx2 = o.at<RRL_WS_IDX2>();
+    a.grp1 = (float4 *)o.at<RRL_WS_GRP1>();
+    a.grp2 = (float4 *)o.at<RRL_WS_GRP2>();
+    a.pmax = (uint32_t *)o.at<RRL_WS_PMAX>();
+    a.zero_base = (uint4 *)o.at<RRL_WS_STATUS>();
     a.zero_vec4 = o.w.zero_bytes / 16;
-    a.g1 = xf && xf->zero_g1 ? (uint4 *)o.f32(RRL_WS_GACC) : nullptr;  // small: 12 B + 16 floats
+    a.g1 = xf && xf->zero_g1 ? (uint4 *)o.at<RRL_WS_GACC>() : nullptr;  // small: 12 B + 16 floats
     a.g1_vec4 = a.g1 ? (o.w.off[RRL_WS_KJC] - o.w.off[RRL_WS_GACC]) / 16 : 0;
-    a.z2 = nmax > 4096 && !chunked ? (uint4 *)o.u32(RRL_WS_HISTG) : nullptr;
+    a.z2 = nmax > 4096 && !chunked ? (uint4 *)o.at<RRL_WS_HISTG>() : nullptr;
     a.z2_vec4 = a.z2 ? (size_t)2 * B * 2 * SORT_CELLS * sizeof(unsigned) / 16 : 0;
     a.z3 = (uint4 *)((char *)o.ws + o.w.state_off);
     a.z3_vec4 = o.w.state_bytes / 16;
     a.z4 = (uint32_t *)o.clear_ptr;
     a.z4_words = o.clear_ptr ? o.clear_bytes / 4 : 0;
-    a.z5 = o.u32(RRL_WS_CHAIN);
+    a.z5 = (uint32_t *)o.at<RRL_WS_CHAIN>();
     a.z5_words = (size_t)4 * B;
-    a.del1 = o.f32(RRL_WS_DEL1);
-    a.del2 = o.f32(RRL_WS_DEL2);
+    a.del1 = o.at<RRL_WS_DEL1>();
+    a.del2 = o.at<RRL_WS_DEL2>();
     a.zwords = nullptr; a.nzwords = 0;
     a.line = line;
-    a.lmax = line && L > 0 ? (float2 *)o.f32(RRL_WS_LMAX) : nullptr;
+    a.lmax = line && L > 0 ? (float2 *)o.at<RRL_WS_LMAX>() : nullptr;
     a.L = L;
     a.B = B; a.N = N; a.M = M; a.clouds = clouds;
     a.transpose_r = xf ? xf->transpose_r : 0;
@@ -1166,7 +1166,7 @@ int rrl_launch_tri_build(const RrlCall &o, const float *tri1, const float *tri2,
     if (nmax <= 4096 || chunked) {
         hipLaunchKernelGGL((tri_sort_kernel<4, false>), dim3((unsigned)(clouds * B * a.nchunk), (unsigned)parts), dim3(1024), lds, s, a);
     } else {  // wide three-launch sort (HISTG was cleared by tri_records_kernel)
-        unsigned *histg = o.u32(RRL_WS_HISTG);
+        unsigned *histg = (uint32_t *)o.at<RRL_WS_HISTG>();
         const dim3 gt((unsigned)((nmax + 255) / 256), (unsigned)B, (unsigned)clouds);
         hipLaunchKernelGGL(big_hist_kernel, gt, dim3(256), 0, s, a, histg);
         hipLaunchKernelGGL(big_scatter_kernel, gt, dim3(256), 0, s, a, histg);
@@ -1180,8 +1180,8 @@ int rrl_launch_tri_build(const RrlCall &o, const float *tri1, const float *tri2,
 // PMAX of a prepared build for consumers other than the culled scan (include/rrl.h rrl_tri_prepare_ex)
 int rrl_launch_pmax_from_partials(const RrlCall &o, int clouds) {
     const int nall = o.N > o.M ? o.N : o.M;
-    hipLaunchKernelGGL(pmax_from_partials_kernel, dim3((unsigned)(clouds * o.B)), dim3(64), 0, o.s, o.f32(RRL_WS_APART),
-                       o.u32(RRL_WS_PMAX), o.B, o.N, o.M, (nall + REC_BLK - 1) / REC_BLK, o.count1, o.count2);
+    hipLaunchKernelGGL(pmax_from_partials_kernel, dim3((unsigned)(clouds * o.B)), dim3(64), 0, o.s, o.at<RRL_WS_APART>(),
+                       (uint32_t *)o.at<RRL_WS_PMAX>(), o.B, o.N, o.M, (nall + REC_BLK - 1) / REC_BLK, o.count1, o.count2);
     RRL_LAUNCH_CHECK();
     return 0;
 }

@@ -1049,18 +1049,18 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
 // the one a riding walk takes a carried-over target from)
 static CullKArgs cull_args(const RrlCall &o, const float *line, const CullGeom &g, const void *tws) {
     CullKArgs a;
-    a.ptri1 = o.f32(RRL_WS_PTRI1); a.ptri2 = o.w.f32(tws, RRL_WS_PTRI2);
-    a.p0s1 = (const float4 *)o.f32(RRL_WS_P0S1); a.p0s2 = (const float4 *)o.w.f32(tws, RRL_WS_P0S2);
-    a.idx1 = o.i32(RRL_WS_IDX1); a.idx2 = o.w.i32(tws, RRL_WS_IDX2);
-    a.tree1 = (const float4 *)o.f32(RRL_WS_GRP1); a.tree2 = (const float4 *)o.w.f32(tws, RRL_WS_GRP2);
+    a.ptri1 = o.at<RRL_WS_PTRI1>(); a.ptri2 = o.w.at<RRL_WS_PTRI2>(tws);
+    a.p0s1 = (const float4 *)o.at<RRL_WS_P0S1>(); a.p0s2 = (const float4 *)o.w.at<RRL_WS_P0S2>(tws);
+    a.idx1 = o.at<RRL_WS_IDX1>(); a.idx2 = o.w.at<RRL_WS_IDX2>(tws);
+    a.tree1 = (const float4 *)o.at<RRL_WS_GRP1>(); a.tree2 = (const float4 *)o.w.at<RRL_WS_GRP2>(tws);
     a.line = line;
-    a.count1 = o.i32(RRL_WS_COUNT1); a.hit1 = o.i32(RRL_WS_HIT1);
-    a.count2 = o.i32(RRL_WS_COUNT2); a.hit2 = o.i32(RRL_WS_HIT2);
-    a.status = o.i32(RRL_WS_STATUS); a.pmax = o.u32(RRL_WS_PMAX);
-    a.del1 = o.f32(RRL_WS_DEL1); a.del2 = o.f32(RRL_WS_DEL2);
-    a.lmax = (const float2 *)o.f32(RRL_WS_LMAX);
-    a.apart = o.prepared() ? o.f32(RRL_WS_APART) : nullptr;  // prepared build: PMAX comes from the partial rows
-    a.aflag = o.f32(RRL_WS_APART); a.aflag_tar = o.w.f32(tws, RRL_WS_APART);
+    a.count1 = o.at<RRL_WS_COUNT1>(); a.hit1 = o.at<RRL_WS_HIT1>();
+    a.count2 = o.at<RRL_WS_COUNT2>(); a.hit2 = o.at<RRL_WS_HIT2>();
+    a.status = o.at<RRL_WS_STATUS>(); a.pmax = (uint32_t *)o.at<RRL_WS_PMAX>();
+    a.del1 = o.at<RRL_WS_DEL1>(); a.del2 = o.at<RRL_WS_DEL2>();
+    a.lmax = (const float2 *)o.at<RRL_WS_LMAX>();
+    a.apart = o.prepared() ? o.at<RRL_WS_APART>() : nullptr;  // prepared build: PMAX comes from the partial rows
+    a.aflag = o.at<RRL_WS_APART>(); a.aflag_tar = o.w.at<RRL_WS_APART>(tws);
     a.nblk_apart = ((o.N > o.M ? o.N : o.M) + REC_BLK - 1) / REC_BLK;
     a.B = o.B; a.N = o.N; a.M = o.M; a.L = o.L; a.spw = g.spw;
     a.gx = o.plan.clouds * o.B; a.gy = g.tiles; a.Bt = o.problems;
@@ -1080,7 +1080,7 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
         BuildArgs bld = ::make_build_args(o, o.tri1_in, nullptr, 1, nullptr, false);
         bld.L = 0;
         bld.nblk_tri = (int)(((size_t)(N + SGT - 1) / SGT * SGT + 64 * WPB - 1) / (64 * WPB));
-        bld.zero_base = (uint4 *)o.i32(RRL_WS_NVALS);
+        bld.zero_base = (uint4 *)o.at<RRL_WS_NVALS>();
         bld.zero_vec4 = (o.w.off[RRL_WS_PMAX] - o.w.off[RRL_WS_NVALS]) / 16;
         bld.z2 = nullptr; bld.z2_vec4 = 0;
         bld.z5 = nullptr; bld.z5_words = 0;
@@ -1088,7 +1088,7 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
         ch.B = a.B; ch.N = a.N; ch.M = a.M; ch.L = a.L; ch.spw = a.spw; ch.nblk_apart = a.nblk_apart;
         ch.line = a.line; ch.apart = a.apart; ch.p0s1 = a.p0s1; ch.p0s2 = a.p0s2; ch.tree1 = a.tree1; ch.tree2 = a.tree2;
         ch.pmax = a.pmax; ch.gy = tiles;
-        ch.chain = o.u32(RRL_WS_CHAIN);
+        ch.chain = (uint32_t *)o.at<RRL_WS_CHAIN>();
         ch.nrec_b = bld.nblk_tri;
         ch.zrec = (bld.nblk_tri + tiles - 1) / tiles;
         const int nsg1 = (N + SGT - 1) / SGT, nsg2 = (M + SGT - 1) / SGT;
@@ -1117,7 +1117,7 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
             c.partial = (double *)(cw + C.partial); c.gpart = (double *)(cw + C.gpart);
             c.value = o.rider->value;
             c.denom = (double)B * (double)(N + M);
-            uint32_t *mctl = o.u32(RRL_WS_MCTL);  // arrival counters of the walk's mean (rrl_chamfer_from_loss_ex)
+            uint32_t *mctl = (uint32_t *)o.at<RRL_WS_MCTL>();  // arrival counters of the walk's mean (rrl_chamfer_from_loss_ex)
             c.tick = ChamTick{mctl + 32, mctl + 30, 64, 1};
             c.gx = 2 * B; c.gy = ((N > M ? N : M) + SGT - 1) / SGT;  // patches of the larger cloud (either direction)
             const unsigned nwg = (unsigned)(c.gx * c.gy) + (unsigned)(a.gx * a.gy * g.slices);

@@ -31,7 +31,7 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
     o.rider = rides ? &rider : nullptr;
     // ... and so does the NEXT epoch's count pass, in the per-line launch (RrlCountRider): it samples against the moved source
     // of THIS epoch (code/test_demo_optimized_Lie_Algebra.py:46-51), whose box is in the records launch's partial rows
-    const float *rows = o.f32(RRL_WS_APART);  // cloud 1, sample 0: the moved first points' partial boxes
+    const float *rows = o.at<RRL_WS_APART>();  // cloud 1, sample 0: the moved first points' partial boxes
     RrlCountRider counter = {(const unsigned long long *)a->rng_state, a->radius, a->centers, a->box2, rows,
                              (N + 255) / 256, (unsigned long long *)a->tile_counts, L, a->rounds, 0};
     // ... and its WRITE pass in the direct backward's launch (RrlWriteRider): the ballots are there by then (the per-line
@@ -65,7 +65,7 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
                                    a->cham_value, stream);
         if (rc) return rc;
     }
-    const int32_t *info = o.i32(RRL_WS_INFO);  // gate: the loss's bucket count (`if loss_di is not None`)
+    const int32_t *info = o.at<RRL_WS_INFO>();  // gate: the loss's bucket count (`if loss_di is not None`)
     return rrl_se3_adam_step(a->xi, a->gR, a->gt, a->m, a->v, a->adam_state, a->lr, info, a->b1, a->b2, a->eps, a->R, a->T,
                              nullptr, a->loss, a->cham_value, a->table, a->cursor, a->table_rows, a->row, rows,
                              (N + 255) / 256, a->box1, stream);

@@ -318,8 +318,8 @@ int rrl_launch_reg_bwd(const RrlCall &o, const float *src, const float *R, float
                        float *payload, const float *loss, int transpose_r) {
     const int n = 3 * o.N;
     hipLaunchKernelGGL(reg_bwd_kernel, dim3((unsigned)((n + REG_BWD_PTS - 1) / REG_BWD_PTS), (unsigned)o.B), dim3(256), 0, o.s,
-                       src, R, o.f32(RRL_WS_G1), grad_src, o.f32(RRL_WS_RPART), gR, gt, payload, loss, o.i32(RRL_WS_INFO),
-                       o.i32(RRL_WS_STATUS) + 3, n, o.B, transpose_r, o.count1);
+                       src, R, o.at<RRL_WS_G1>(), grad_src, o.at<RRL_WS_RPART>(), gR, gt, payload, loss, o.at<RRL_WS_INFO>(),
+                       o.at<RRL_WS_STATUS>() + 3, n, o.B, transpose_r, o.count1);
     RRL_LAUNCH_CHECK();
     return 0;
 }
@@ -1085,7 +1085,7 @@ extern "C" int rrl_shard_payload(const float *loss, const void *ws, size_t ws_by
     WsLayout w(B, N, M, L);
     if (ws_bytes < w.total) return RRL_E_WS;
     hipLaunchKernelGGL(shard_payload_kernel, dim3(1), dim3(14 * 64), 0, (hipStream_t)stream, loss,
-                       w.i32(ws, RRL_WS_INFO), gR, gt, out, B);
+                       w.at<RRL_WS_INFO>(ws), gR, gt, out, B);
     RRL_LAUNCH_CHECK();
     return 0;
 }

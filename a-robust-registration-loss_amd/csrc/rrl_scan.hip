@@ -138,7 +138,7 @@ int rrl_tri_prepare_clouds(const RrlCall &o, const float *tri1, const float *tri
     const RrlXform *xf = o.xf;
     const bool sorted = rrl_sorted_layout(N, M);
     const int nmax = clouds == 2 && M > N ? M : N;
-    uint4 *zb = (uint4 *)o.i32(RRL_WS_STATUS);
+    uint4 *zb = (uint4 *)o.at<RRL_WS_STATUS>();
     if (!sorted || B == 0 || nmax == 0) {
         // one fill clears status, nvals, nsel, pmax, count1, count2 (contiguous by construction)
         int rc = rrl_fill(zb, 0u, o.w.zero_bytes, o.s);
@@ -151,17 +151,17 @@ int rrl_tri_prepare_clouds(const RrlCall &o, const float *tri1, const float *tri
     if (sorted) return rrl_launch_tri_build(o, tri1, tri2, line);
     if (xf) {
         if (xf->zero_g1) {
-            int rc = rrl_fill(o.f32(RRL_WS_GACC), 0u, o.w.off[RRL_WS_KJC] - o.w.off[RRL_WS_GACC], o.s);
+            int rc = rrl_fill(o.at<RRL_WS_GACC>(), 0u, o.w.off[RRL_WS_KJC] - o.w.off[RRL_WS_GACC], o.s);
             if (rc) return rc;
         }
-        tri1 = o.f32(RRL_WS_TRI1);
-        int rc = rrl_rigid_apply_fwd(xf->src, xf->R, xf->t, o.f32(RRL_WS_TRI1), B, 3 * N, xf->transpose_r, 0, o.s);
+        tri1 = o.at<RRL_WS_TRI1>();
+        int rc = rrl_rigid_apply_fwd(xf->src, xf->R, xf->t, o.at<RRL_WS_TRI1>(), B, 3 * N, xf->transpose_r, 0, o.s);
         if (rc) return rc;
     }
     dim3 grid((unsigned)((nmax + 63) / 64), (unsigned)B, (unsigned)clouds);
     hipLaunchKernelGGL(tri_prepare_kernel<true>, grid, dim3(64), 0, o.s, tri1, tri2,
-                       o.f32(RRL_WS_PTRI1), o.f32(RRL_WS_PTRI2),
-                       (uint32_t *)o.i32(RRL_WS_PMAX), zb, (size_t)0, (size_t)0, (size_t)0, B, N, M);
+                       o.at<RRL_WS_PTRI1>(), o.at<RRL_WS_PTRI2>(),
+                       (uint32_t *)o.at<RRL_WS_PMAX>(), zb, (size_t)0, (size_t)0, (size_t)0, B, N, M);
     RRL_LAUNCH_CHECK();
     return 0;
 }
@@ -455,10 +455,10 @@ int rrl_line_tri_scan_clouds(const RrlCall &o, const float *line) {
               (unsigned)(clouds * B));
     if (timed) (void)hipEventRecord(g_ev[g_timing_n][0], o.s);
 #define RRL_SCAN_LAUNCH(T, NP)                                                                   \
-    hipLaunchKernelGGL((scan_kernel<T, NP>), grid, dim3(256), 0, o.s, o.f32(RRL_WS_PTRI1),       \
-                       o.f32(RRL_WS_PTRI2), line, o.i32(RRL_WS_COUNT1), o.i32(RRL_WS_HIT1),      \
-                       o.i32(RRL_WS_COUNT2), o.i32(RRL_WS_HIT2), o.i32(RRL_WS_STATUS),           \
-                       (const uint32_t *)o.i32(RRL_WS_PMAX), B, N, M, L, chunk, mode, o.count1,  \
+    hipLaunchKernelGGL((scan_kernel<T, NP>), grid, dim3(256), 0, o.s, o.at<RRL_WS_PTRI1>(),       \
+                       o.at<RRL_WS_PTRI2>(), line, o.at<RRL_WS_COUNT1>(), o.at<RRL_WS_HIT1>(),      \
+                       o.at<RRL_WS_COUNT2>(), o.at<RRL_WS_HIT2>(), o.at<RRL_WS_STATUS>(),           \
+                       (const uint32_t *)o.at<RRL_WS_PMAX>(), B, N, M, L, chunk, mode, o.count1,  \
                        o.count2, o.nlines)
     if (R == 1) RRL_SCAN_LAUNCH(float, 1);
     else if (R == 2) RRL_SCAN_LAUNCH(v2f, 1);

@@ -5,6 +5,7 @@
 //   K5 backward         autograd of code/loss.py:170-232
 // About 9 % of the lines are selected; these kernels touch O(L) data and are latency bound
 // (a few microseconds each) next to the O(L*(N+M)) scan.
+#include <ctype.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -50,22 +51,22 @@ extern "C" int rrl_debug_pstamps(unsigned long long *out, int clear) {
 // launches per evaluation).  tally: the launch feeds the tiled reduces' histogram (not the single-tile kernels).
 static PairArgs pair_args(const RrlCall &o, const float *tri1, const float *tri2, const float *line, bool tally) {
     PairArgs a;
-    a.mhist = tally ? o.u32(RRL_WS_MHIST) : nullptr;
-    a.mctl = tally ? o.u32(RRL_WS_MCTL) : nullptr;
+    a.mhist = tally ? (uint32_t *)o.at<RRL_WS_MHIST>() : nullptr;
+    a.mctl = tally ? (uint32_t *)o.at<RRL_WS_MCTL>() : nullptr;
     a.tri1 = tri1;
     a.tri2 = tri2;
     a.line = line;
-    a.count1 = o.i32(RRL_WS_COUNT1); a.hit1 = o.i32(RRL_WS_HIT1);
-    a.count2 = o.tar_i32(RRL_WS_COUNT2); a.hit2 = o.tar_i32(RRL_WS_HIT2);
-    a.kj = o.u8(RRL_WS_KJ);
-    a.sel_out = o.i32(RRL_WS_SEL); a.nsel = o.i32(RRL_WS_NSEL);
-    a.hs1 = o.i32(RRL_WS_HS1); a.hs2 = o.i32(RRL_WS_HS2);
-    a.w1 = o.f32(RRL_WS_W1); a.w2 = o.f32(RRL_WS_W2);
-    a.Q1 = (float4 *)o.f32(RRL_WS_Q1); a.Q2 = (float4 *)o.f32(RRL_WS_Q2);
-    a.D = o.f32(RRL_WS_D); a.dc = o.f32(RRL_WS_VALS);
-    a.kjc = o.u8(RRL_WS_KJC); a.blkcnt = o.i32(RRL_WS_BLKCNT);
-    a.lidc = o.u32(RRL_WS_LIDC);
-    a.vlist = o.f32(RRL_WS_VLIST); a.vlcnt = o.i32(RRL_WS_VLCNT);
+    a.count1 = o.at<RRL_WS_COUNT1>(); a.hit1 = o.at<RRL_WS_HIT1>();
+    a.count2 = o.tar_at<RRL_WS_COUNT2>(); a.hit2 = o.tar_at<RRL_WS_HIT2>();
+    a.kj = o.at<RRL_WS_KJ>();
+    a.sel_out = o.at<RRL_WS_SEL>(); a.nsel = o.at<RRL_WS_NSEL>();
+    a.hs1 = o.at<RRL_WS_HS1>(); a.hs2 = o.at<RRL_WS_HS2>();
+    a.w1 = o.at<RRL_WS_W1>(); a.w2 = o.at<RRL_WS_W2>();
+    a.Q1 = (float4 *)o.at<RRL_WS_Q1>(); a.Q2 = (float4 *)o.at<RRL_WS_Q2>();
+    a.D = o.at<RRL_WS_D>(); a.dc = o.at<RRL_WS_VALS>();
+    a.kjc = o.at<RRL_WS_KJC>(); a.blkcnt = o.at<RRL_WS_BLKCNT>();
+    a.lidc = (uint32_t *)o.at<RRL_WS_LIDC>();
+    a.vlist = o.at<RRL_WS_VLIST>(); a.vlcnt = o.at<RRL_WS_VLCNT>();
     a.B = o.B; a.N = o.N; a.M = o.M; a.L = o.L;
     a.s_m = o.s_m; a.s_n = o.s_n; a.e_m = o.e_m; a.e_n = o.e_n;
     a.st1 = 9; a.st2 = 9;
@@ -79,7 +80,7 @@ static int line_pair_dist_impl(const RrlCall &o, const float *tri1, const float 
     const int B = o.B, L = o.L;
     if (B == 0 || L == 0) return 0;
     PairArgs pa = pair_args(o, tri1, tri2, line, true);
-    if (o.plan.leave_clean) { pa.zc1 = o.i32(RRL_WS_COUNT1); pa.zc2 = o.i32(RRL_WS_COUNT2); }
+    if (o.plan.leave_clean) { pa.zc1 = o.at<RRL_WS_COUNT1>(); pa.zc2 = o.at<RRL_WS_COUNT2>(); }
     if (o.plan.reduce != RRL_RED_TAIL) pa.vlist = nullptr;  // only the tail kernel reads VLIST
     if (o.plan.count_rides) {  // the next epoch's count pass rides along (pair_count_kernel)
         RrlCountRider *cr = o.count_rider;
@@ -315,9 +316,9 @@ int rrl_check_call(RrlCall &o, bool pointers, int want, const void *target_ws, c
 
 static ReduceArgs reduce_args(const RrlCall &o, float *loss) {
     ReduceArgs r;
-    r.kjc = o.u8(RRL_WS_KJC); r.dc = o.f32(RRL_WS_VALS); r.blkcnt = o.i32(RRL_WS_BLKCNT);
-    r.med_out = o.f32(RRL_WS_MED); r.bcnt_out = o.i32(RRL_WS_BCNT); r.bsum_out = o.i64(RRL_WS_BSUM);
-    r.info = o.i32(RRL_WS_INFO); r.loss = loss; r.status = o.i32(RRL_WS_STATUS);
+    r.kjc = o.at<RRL_WS_KJC>(); r.dc = o.at<RRL_WS_VALS>(); r.blkcnt = o.at<RRL_WS_BLKCNT>();
+    r.med_out = o.at<RRL_WS_MED>(); r.bcnt_out = o.at<RRL_WS_BCNT>(); r.bsum_out = o.at<RRL_WS_BSUM>();
+    r.info = o.at<RRL_WS_INFO>(); r.loss = loss; r.status = o.at<RRL_WS_STATUS>();
     r.B = o.B; r.nblk = (o.L + 1023) / 1024;
     r.s_m = o.s_m; r.s_n = o.s_n; r.e_m = o.e_m; r.e_n = o.e_n; r.pool = o.pool;
     return r;
@@ -326,37 +327,37 @@ static ReduceArgs reduce_args(const RrlCall &o, float *loss) {
 // tb: the backward that rides in the tail kernel's launch (o.plan.bwd_rides), else NULL
 static TailArgs tail_args(const RrlCall &o, float *loss, const TailBwd *tb) {
     TailArgs t;
-    t.lidc = o.u32(RRL_WS_LIDC); t.dc = o.f32(RRL_WS_VALS); t.blkcnt = o.i32(RRL_WS_BLKCNT);
-    t.vlist = o.f32(RRL_WS_VLIST); t.vlcnt = o.i32(RRL_WS_VLCNT);
-    t.mhist = o.u32(RRL_WS_MHIST); t.mctl = o.u32(RRL_WS_MCTL);
-    t.msum = (unsigned long long *)o.i64(RRL_WS_MSUM);
-    t.med_out = o.f32(RRL_WS_MED); t.bcnt_out = o.i32(RRL_WS_BCNT); t.bsum_out = o.i64(RRL_WS_BSUM);
-    t.info = o.i32(RRL_WS_INFO); t.loss = loss; t.status = o.i32(RRL_WS_STATUS);
+    t.lidc = (uint32_t *)o.at<RRL_WS_LIDC>(); t.dc = o.at<RRL_WS_VALS>(); t.blkcnt = o.at<RRL_WS_BLKCNT>();
+    t.vlist = o.at<RRL_WS_VLIST>(); t.vlcnt = o.at<RRL_WS_VLCNT>();
+    t.mhist = (uint32_t *)o.at<RRL_WS_MHIST>(); t.mctl = (uint32_t *)o.at<RRL_WS_MCTL>();
+    t.msum = (unsigned long long *)o.at<RRL_WS_MSUM>();
+    t.med_out = o.at<RRL_WS_MED>(); t.bcnt_out = o.at<RRL_WS_BCNT>(); t.bsum_out = o.at<RRL_WS_BSUM>();
+    t.info = o.at<RRL_WS_INFO>(); t.loss = loss; t.status = o.at<RRL_WS_STATUS>();
     t.B = o.B; t.nblk = (o.L + 1023) / 1024; t.s_m = o.s_m; t.s_n = o.s_n; t.e_m = o.e_m; t.e_n = o.e_n;
     const TailBwd none{}, &b = tb ? *tb : none;  // (no riding backward: all NULL)
     t.do_bwd = tb ? 1 : 0; t.N = o.N; t.L = o.L; t.transpose_r = b.transpose_r;
-    t.hs1 = o.i32(RRL_WS_HS1); t.w1 = o.f32(RRL_WS_W1);
-    t.Q1 = (const float4 *)o.f32(RRL_WS_Q1); t.Q2 = (const float4 *)o.f32(RRL_WS_Q2);
+    t.hs1 = o.at<RRL_WS_HS1>(); t.w1 = o.at<RRL_WS_W1>();
+    t.Q1 = (const float4 *)o.at<RRL_WS_Q1>(); t.Q2 = (const float4 *)o.at<RRL_WS_Q2>();
     t.grad_loss = b.grad_loss; t.src = b.src; t.gR = b.gR; t.gt = b.gt; t.payload = b.payload; t.grad_tri1 = b.grad_tri1;
     t.Bt = o.problems;
     t.xcd_align = o.B % 8 == 0 && xcd_align_on();
-    t.chain = o.plan.leave_clean ? o.u32(RRL_WS_CHAIN) : nullptr;
+    t.chain = o.plan.leave_clean ? (uint32_t *)o.at<RRL_WS_CHAIN>() : nullptr;
     t.chain_flags = o.plan.fused_build;
     return t;
 }
 
 static TiledArgs tiled_args(const RrlCall &o, float *loss) {
     TiledArgs t;
-    t.kjc = o.u8(RRL_WS_KJC); t.dc = o.f32(RRL_WS_VALS); t.blkcnt = o.i32(RRL_WS_BLKCNT);
-    t.mhist = o.u32(RRL_WS_MHIST); t.mctl = o.u32(RRL_WS_MCTL); t.mcand = o.u32(RRL_WS_MCAND);
-    t.msum = (unsigned long long *)o.i64(RRL_WS_MSUM);
-    t.med_out = o.f32(RRL_WS_MED); t.bcnt_out = o.i32(RRL_WS_BCNT); t.bsum_out = o.i64(RRL_WS_BSUM);
-    t.info = o.i32(RRL_WS_INFO); t.loss = loss; t.status = o.i32(RRL_WS_STATUS);
+    t.kjc = o.at<RRL_WS_KJC>(); t.dc = o.at<RRL_WS_VALS>(); t.blkcnt = o.at<RRL_WS_BLKCNT>();
+    t.mhist = (uint32_t *)o.at<RRL_WS_MHIST>(); t.mctl = (uint32_t *)o.at<RRL_WS_MCTL>(); t.mcand = (uint32_t *)o.at<RRL_WS_MCAND>();
+    t.msum = (unsigned long long *)o.at<RRL_WS_MSUM>();
+    t.med_out = o.at<RRL_WS_MED>(); t.bcnt_out = o.at<RRL_WS_BCNT>(); t.bsum_out = o.at<RRL_WS_BSUM>();
+    t.info = o.at<RRL_WS_INFO>(); t.loss = loss; t.status = o.at<RRL_WS_STATUS>();
     t.B = o.B; t.nblk = (o.L + 1023) / 1024; t.s_m = o.s_m; t.s_n = o.s_n; t.e_m = o.e_m; t.e_n = o.e_n;
     t.spin_limit = spin_limit();
     t.xcd_align = o.B % 8 == 0 && xcd_align_on();
     t.payload = o.plan.payload_in_reduce ? o.payload : nullptr;
-    t.chain = o.plan.leave_clean ? o.u32(RRL_WS_CHAIN) : nullptr;
+    t.chain = o.plan.leave_clean ? (uint32_t *)o.at<RRL_WS_CHAIN>() : nullptr;
     t.chain_flags = o.plan.fused_build;
     return t;
 }
@@ -459,11 +460,11 @@ static bool default_deterministic() {
 
 static ScatArgs scat_args(const RrlCall &o, const float *grad_loss, float *g1, float *g2) {
     ScatArgs a;
-    a.lidc = o.u32(RRL_WS_LIDC); a.blkcnt = o.i32(RRL_WS_BLKCNT);
-    a.hs1 = o.i32(RRL_WS_HS1); a.hs2 = o.i32(RRL_WS_HS2); a.bcnt = o.i32(RRL_WS_BCNT); a.info = o.i32(RRL_WS_INFO);
-    a.w1 = o.f32(RRL_WS_W1); a.w2 = o.f32(RRL_WS_W2); a.D = o.f32(RRL_WS_D); a.med = o.f32(RRL_WS_MED);
+    a.lidc = (uint32_t *)o.at<RRL_WS_LIDC>(); a.blkcnt = o.at<RRL_WS_BLKCNT>();
+    a.hs1 = o.at<RRL_WS_HS1>(); a.hs2 = o.at<RRL_WS_HS2>(); a.bcnt = o.at<RRL_WS_BCNT>(); a.info = o.at<RRL_WS_INFO>();
+    a.w1 = o.at<RRL_WS_W1>(); a.w2 = o.at<RRL_WS_W2>(); a.D = o.at<RRL_WS_D>(); a.med = o.at<RRL_WS_MED>();
     a.grad_loss = grad_loss;
-    a.Q1 = (const float4 *)o.f32(RRL_WS_Q1); a.Q2 = (const float4 *)o.f32(RRL_WS_Q2);
+    a.Q1 = (const float4 *)o.at<RRL_WS_Q1>(); a.Q2 = (const float4 *)o.at<RRL_WS_Q2>();
     a.g1 = g1; a.g2 = g2; a.N = o.N; a.M = o.M; a.L = o.L;
     a.fx = nullptr; a.fxbits = 0; a.fxB = 0;
     return a;
@@ -487,7 +488,7 @@ static int loss_backward_impl(const RrlCall &o, const float *grad_loss, float *g
     if (B == 0 || L == 0) return 0;
     ScatArgs sa = scat_args(o, grad_loss, grad_tri1, grad_tri2);
     if (deterministic && (N + M) > 0) {
-        sa.fx = (unsigned long long *)o.i64(RRL_WS_GFIX);
+        sa.fx = (unsigned long long *)o.at<RRL_WS_GFIX>();
         sa.fxbits = scat_fx_bits_host(L);
         sa.fxB = B;
         if ((rc = rrl_fill(sa.fx, 0u, 8 * (size_t)B * (N + M) * 9 + 8 * (size_t)B, o.s))) return rc;
@@ -526,15 +527,58 @@ extern "C" int rrl_workspace_layout(int B, int N, int M, int L, size_t *offsets)
     return 0;
 }
 
+// include/rrl.h rrl_workspace_field: a row of the two tables (row = field, + RRL_WS_FIELDS for the wide ones), described
+template <class T> struct RrlTypeCode;
+template <> struct RrlTypeCode<uint8_t> { static const int v = RRL_T_U8; };
+template <> struct RrlTypeCode<int32_t> { static const int v = RRL_T_I32; };
+template <> struct RrlTypeCode<float> { static const int v = RRL_T_F32; };
+template <> struct RrlTypeCode<int64_t> { static const int v = RRL_T_I64; };
+struct RrlFieldNames {  // the enumerators' names in lower case
+    char s[RRL_WS_FIELDS + RRL_WW_FIELDS][8];
+    RrlFieldNames() {
+        int i = 0;
+#define RRL_ROW_NAME_(name, type, ...)                          \
+    static_assert(sizeof(#name) <= sizeof s[0], #name);         \
+    for (int k = 0; k < (int)sizeof(#name); ++k) s[i][k] = (char)tolower(#name[k]); \
+    ++i;
+        RRL_WS_TABLE(RRL_ROW_NAME_)
+        RRL_WW_TABLE(RRL_ROW_NAME_)
+    }
+};
+extern "C" int rrl_workspace_field(int kind, int field, int B, int N, int M, int L, int G, const char **name, int *dtype,
+                                   long long dims[4]) {
+    static const RrlFieldNames names;
+    if (kind < 0 || kind > 1) return RRL_E_ARG;
+    const int fields = kind ? RRL_WW_FIELDS : RRL_WS_FIELDS;
+    if (field == -1) return fields;
+    if (field < 0 || field >= fields) return RRL_E_ARG;
+    const size_t b = (size_t)(B > 0 ? B : 0), n = (size_t)(N > 0 ? N : 0), m = (size_t)(M > 0 ? M : 0),
+                 l = (size_t)(L > 0 ? L : 0), g = (size_t)(G > 0 ? G : 0);
+    const int row = field + (kind ? RRL_WS_FIELDS : 0);
+    int i = 0, rank = 0;
+#define RRL_ROW_DESCRIBE_(name, type, ...)                                \
+    if (i++ == row) {                                                     \
+        const size_t e[] = {__VA_ARGS__};                                 \
+        static_assert(sizeof e / sizeof *e <= 4, #name);                  \
+        rank = (int)(sizeof e / sizeof *e);                               \
+        for (int k = 0; dims && k < rank; ++k) dims[k] = (long long)e[k]; \
+        if (dtype) *dtype = RrlTypeCode<type>::v;                         \
+    }
+    RRL_WS_TABLE(RRL_ROW_DESCRIBE_)
+    RRL_WW_TABLE(RRL_ROW_DESCRIBE_)
+    if (name) *name = names.s[row];
+    return rank;
+}
+
 // the direct backward that rides in the single-tile kernel's launch (rrl_registration_step)
 static SoloBwd solo_bwd_args(const RrlCall &o, float *loss, const TailBwd *tb) {
     SoloBwd sb;
-    sb.kj = o.u8(RRL_WS_KJ); sb.sel = o.i32(RRL_WS_SEL); sb.nsel = o.i32(RRL_WS_NSEL);
-    sb.hs1 = o.i32(RRL_WS_HS1); sb.bcnt = o.i32(RRL_WS_BCNT); sb.info = o.i32(RRL_WS_INFO);
-    sb.w1 = o.f32(RRL_WS_W1); sb.D = o.f32(RRL_WS_D); sb.med = o.f32(RRL_WS_MED);
+    sb.kj = o.at<RRL_WS_KJ>(); sb.sel = o.at<RRL_WS_SEL>(); sb.nsel = o.at<RRL_WS_NSEL>();
+    sb.hs1 = o.at<RRL_WS_HS1>(); sb.bcnt = o.at<RRL_WS_BCNT>(); sb.info = o.at<RRL_WS_INFO>();
+    sb.w1 = o.at<RRL_WS_W1>(); sb.D = o.at<RRL_WS_D>(); sb.med = o.at<RRL_WS_MED>();
     sb.grad_loss = tb->grad_loss; sb.src = tb->src; sb.loss = loss;
-    sb.Q1 = (const float4 *)o.f32(RRL_WS_Q1); sb.Q2 = (const float4 *)o.f32(RRL_WS_Q2);
-    sb.gR = tb->gR; sb.gt = tb->gt; sb.payload = tb->payload; sb.mctl = o.u32(RRL_WS_MCTL);
+    sb.Q1 = (const float4 *)o.at<RRL_WS_Q1>(); sb.Q2 = (const float4 *)o.at<RRL_WS_Q2>();
+    sb.gR = tb->gR; sb.gt = tb->gt; sb.payload = tb->payload; sb.mctl = (uint32_t *)o.at<RRL_WS_MCTL>();
     sb.B = o.B; sb.N = o.N; sb.L = o.L; sb.transpose_r = tb->transpose_r; sb.Bt = o.problems;
     return sb;
 }
@@ -566,7 +610,7 @@ static int loss_forward_impl(RrlCall &o, const float *tri1, const float *tri2, c
         const dim3 grid((unsigned)o.B);
         if (tb && tb->grad_tri1) {  // ... and the scatter backward to points1.grad too (rrl_loss_step_ex)
             hipLaunchKernelGGL(pair_reduce_scatter_kernel, grid, dim3(1024), sizeof(int) * 2, o.s, pa, ra,
-                               scat_args(o, tb->grad_loss, tb->grad_tri1, nullptr), tb->payload, o.u32(RRL_WS_MCTL));
+                               scat_args(o, tb->grad_loss, tb->grad_tri1, nullptr), tb->payload, (uint32_t *)o.at<RRL_WS_MCTL>());
         } else if (tb) {  // ... and the direct backward too (rrl_registration_step)
             hipLaunchKernelGGL(pair_reduce_bwd_kernel, grid, dim3(1024), sizeof(int) * 2, o.s, pa, ra, solo_bwd_args(o, loss, tb));
         } else {
@@ -622,7 +666,7 @@ extern "C" int rrl_loss_forward_info(const float *tri1, const float *tri2, const
     if (const int rc = loss_forward_call(o, tri1, tri2, line, loss, target_ws)) return rc;
     const int G = pool ? 1 : B;
     if (G <= 0) return 0;
-    hipError_t e = hipMemcpyAsync(host_info, o.i32(RRL_WS_INFO), sizeof(int32_t) * 4 * (size_t)G, hipMemcpyDeviceToHost, o.s);
+    hipError_t e = hipMemcpyAsync(host_info, o.at<RRL_WS_INFO>(), sizeof(int32_t) * 4 * (size_t)G, hipMemcpyDeviceToHost, o.s);
     if (e != hipSuccess) return (int)e;
     e = hipStreamSynchronize(o.s);
     return e == hipSuccess ? 0 : (int)e;
@@ -650,7 +694,7 @@ extern "C" int rrl_registration_forward_ex(const float *src, const float *R, con
     // the transform runs inside the prepare step
     const RrlXform xf = {src, R, t, transpose_r, 1};  // 1: clear GACC for the backward's atomics
     if (const int rc = rrl_check_call(o, src && R && t && tri2 && line && loss, RRL_WANT_FORWARD, target_ws, &xf)) return rc;
-    return loss_forward_impl(o, o.f32(RRL_WS_TRI1), tri2, line, loss);
+    return loss_forward_impl(o, o.at<RRL_WS_TRI1>(), tri2, line, loss);
 }
 extern "C" int rrl_registration_forward_cached(const float *src, const float *R, const float *t,
                                                const float *tri2, const float *line, void *ws,
@@ -675,7 +719,7 @@ extern "C" int rrl_registration_forward(const float *src, const float *R, const 
 // The direct backward accumulates (gR, gt, payload) with atomics: clear them unless they are the workspace's GACC field,
 // which the forward's first launch clears
 static int clear_direct_grads(const RrlCall &o, float *gR, float *gt, float *payload) {
-    const float *gacc = o.f32(RRL_WS_GACC);
+    const float *gacc = o.at<RRL_WS_GACC>();
     const size_t B = (size_t)o.B;
     if (gR == gacc && gt == gacc + 9 * B && (!payload || payload == gacc + 12 * B)) return 0;
     int rc = rrl_fill(gR, 0u, sizeof(float) * 9 * B, o.s);
@@ -687,9 +731,9 @@ static int clear_direct_grads(const RrlCall &o, float *gR, float *gt, float *pay
 // part: the deterministic variant's partial rows; gx: the backward's workgroups per sample
 static BwdKArgs bwd_args(const RrlCall &o, const float *src, const float *loss, const float *grad_loss, float *gR, float *gt,
                          float *payload, int transpose_r, float *part, int gx) {
-    return BwdKArgs{o.u8(RRL_WS_KJ), o.i32(RRL_WS_SEL), o.i32(RRL_WS_NSEL), o.i32(RRL_WS_HS1), o.f32(RRL_WS_W1),
-                    (const float4 *)o.f32(RRL_WS_Q1), (const float4 *)o.f32(RRL_WS_Q2), o.f32(RRL_WS_D), o.f32(RRL_WS_MED),
-                    o.i32(RRL_WS_BCNT), o.i32(RRL_WS_INFO), grad_loss, src, gR, gt, payload, loss,
+    return BwdKArgs{o.at<RRL_WS_KJ>(), o.at<RRL_WS_SEL>(), o.at<RRL_WS_NSEL>(), o.at<RRL_WS_HS1>(), o.at<RRL_WS_W1>(),
+                    (const float4 *)o.at<RRL_WS_Q1>(), (const float4 *)o.at<RRL_WS_Q2>(), o.at<RRL_WS_D>(), o.at<RRL_WS_MED>(),
+                    o.at<RRL_WS_BCNT>(), o.at<RRL_WS_INFO>(), grad_loss, src, gR, gt, payload, loss,
                     o.B, o.N, o.L, transpose_r, part, gx};
 }
 
@@ -698,14 +742,14 @@ static int registration_backward_impl(const RrlCall &o, const float *src, const 
                                       const float *grad_loss, float *grad_src, float *gR, float *gt, float *payload,
                                       int transpose_r) {
     const int B = o.B, N = o.N, M = o.M, L = o.L;
-    float *g1 = o.f32(RRL_WS_G1);
+    float *g1 = o.at<RRL_WS_G1>();
     RrlRange step("K5 rrl backward");
     if (!grad_src && B > 0 && L > 0) {
         // only dL/dR, dL/dt (+ payload): ONE launch, straight from the selected lines
         const int nblk = o.deterministic ? 16 * ((L + 1023) / 1024) : (L + BWD_LINES - 1) / BWD_LINES;
         // partials in VALS (the reduce kernel's input tiles: dead after the forward; B * Lp * 16 floats
         // >= B * 16 ceil(L / 1024) * 12), fixed-order sums by a second launch: nothing to clear
-        float *part = o.deterministic ? o.f32(RRL_WS_VALS) : nullptr;
+        float *part = o.deterministic ? o.at<RRL_WS_VALS>() : nullptr;
         const BwdKArgs a = bwd_args(o, src, loss, grad_loss, gR, gt, payload, transpose_r, part, nblk);
         // the next epoch's sampler write pass rides along (bwd_write_kernel; rrl_demo_epoch)
         RrlWriteRider *wr = o.plan.write_rides ? o.write_rider : nullptr;
@@ -721,7 +765,7 @@ static int registration_backward_impl(const RrlCall &o, const float *src, const 
                                a.loss, a.B, a.N, a.L, a.transpose_r, a.part, o.problems, B % 8 == 0 && xcd_align_on() ? 1 : 0)
         if (o.deterministic) {
             RRL_BWD(true);
-            hipLaunchKernelGGL(loss_bwd_rt_finalize_kernel, dim3(1), dim3(256), 0, o.s, part, o.i32(RRL_WS_INFO), loss,
+            hipLaunchKernelGGL(loss_bwd_rt_finalize_kernel, dim3(1), dim3(256), 0, o.s, part, o.at<RRL_WS_INFO>(), loss,
                                gR, gt, payload, B, nblk);
             RRL_LAUNCH_CHECK();
             return 0;
@@ -739,7 +783,7 @@ static int registration_backward_impl(const RrlCall &o, const float *src, const 
     }
     int rc = loss_backward_impl(o, grad_loss, g1, nullptr, true, default_deterministic());
     if (rc) return rc;
-    rc = rrl_rigid_apply_bwd(src, R, g1, grad_src, gR, gt, o.f32(RRL_WS_RPART), B, 3 * N, transpose_r, 0, o.s);
+    rc = rrl_rigid_apply_bwd(src, R, g1, grad_src, gR, gt, o.at<RRL_WS_RPART>(), B, 3 * N, transpose_r, 0, o.s);
     if (rc) return rc;
     if (payload) rc = rrl_shard_payload(loss, o.ws, o.ws_bytes, gR, gt, payload, B, N, M, L, o.s);
     return rc;
@@ -768,7 +812,7 @@ int rrl_registration_step_call(RrlCall &o, const RrlXform &xf, const float *tri2
     const bool ride = o.plan.bwd_rides;
     if (ride && (rc = clear_direct_grads(o, gR, gt, payload))) return rc;
     const TailBwd tb = {grad_loss, xf.src, gR, gt, payload, xf.transpose_r, nullptr};
-    rc = loss_forward_impl(o, o.f32(RRL_WS_TRI1), tri2, line, loss, ride ? &tb : nullptr);
+    rc = loss_forward_impl(o, o.at<RRL_WS_TRI1>(), tri2, line, loss, ride ? &tb : nullptr);
     if (rc || ride) return rc;
     return registration_backward_impl(o, xf.src, xf.R, loss, grad_loss, nullptr, gR, gt, payload, xf.transpose_r);
 }
@@ -801,10 +845,10 @@ extern "C" int rrl_loss_step_ex(const float *tri1, const float *R, const float *
     // the shard payload of the step (rrl_opts.payload): in the workspace's GACC field the records launch clears it with the
     // rest of the accumulator (the fused op's convention); any other buffer is cleared here first
     float *payload = o.payload;
-    const bool pay_in_ws = payload && R && payload == o.f32(RRL_WS_GACC) + 12 * (size_t)B;
+    const bool pay_in_ws = payload && R && payload == o.at<RRL_WS_GACC>() + 12 * (size_t)B;
     xf.zero_g1 = pay_in_ws ? 1 : 0;
     if (payload && !pay_in_ws && (rc = rrl_fill(payload, 0u, sizeof(float) * 14, o.s))) return rc;
-    const float *p1 = R ? o.f32(RRL_WS_TRI1) : tri1;  // points1: the moved source, or the caller's triangles as given
+    const float *p1 = R ? o.at<RRL_WS_TRI1>() : tri1;  // points1: the moved source, or the caller's triangles as given
     const TailBwd tb = {grad_loss, nullptr, nullptr, nullptr, payload, 0, grad_tri1};
     rc = loss_forward_impl(o, p1, tri2, line, loss, o.plan.bwd_rides ? &tb : nullptr);
     if (rc || o.plan.bwd_rides) return rc;

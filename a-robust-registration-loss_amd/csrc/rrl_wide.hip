@@ -29,44 +29,6 @@
 
 static_assert(WIDE_HITS == RRL_WIDE_MAX_HITS, "include/rrl.h");
 
-// ---- layout of the wide workspace (include/rrl.h RRL_WW_*); every field on a 256-byte boundary, STATUS and NSEL first
-//      (one fill clears both)
-struct WwLayout {
-    size_t off[RRL_WW_FIELDS];
-    size_t total, zero_bytes;
-    __host__ WwLayout(int B, int N, int M, int L) {
-        (void)N; (void)M;
-        const size_t b = (size_t)(B > 0 ? B : 0), l = (size_t)(L > 0 ? L : 0), H = WIDE_HITS;
-        const size_t bytes[RRL_WW_FIELDS] = {
-            4 * 4,                 // STATUS
-            4 * b,                 // NSEL
-            4 * 2 * b * l,         // REC
-            4 * b * l,             // SEL
-            b * l,                 // KJ
-            4 * b * l * H,         // HS1
-            4 * b * l * H,         // HS2
-            4 * b * l * H * 3,     // W1
-            4 * b * l * H * 3,     // W2
-            16 * b * l * H,        // Q1
-            16 * b * l * H,        // Q2
-            4 * b * l * H * H,     // D
-            4 * b,                 // MED
-            4 * b * H * H,         // BCNT
-            8 * b * H * H * 2,     // BSUM
-            4 * b * 4,             // INFO
-        };
-        size_t o = 0;
-        for (int i = 0; i < RRL_WW_FIELDS; ++i) {
-            off[i] = o;
-            o += (bytes[i] + 255) & ~(size_t)255;
-            if (i == RRL_WW_NSEL) zero_bytes = o;
-        }
-        total = o;
-    }
-    template <class T>
-    __host__ T *at(void *ws, int f) const { return (T *)((char *)ws + off[f]); }
-};
-
 struct WideArgs {
     const float *tri1, *tri2, *line;                 // raw 36-byte rows (what the narrow per-line stage reads), lines
     const int32_t *count1, *count2, *hit1, *hit2;    // the scan's results (loss workspace)
@@ -485,20 +447,20 @@ static WideArgs wide_args(void *wws, const WwLayout &v, int B, int N, int M, int
                           float *loss = nullptr) {
     WideArgs a;
     memset(&a, 0, sizeof a);
-    a.status = v.at<int32_t>(wws, RRL_WW_STATUS); a.nsel = v.at<int32_t>(wws, RRL_WW_NSEL);
-    a.rec = v.at<int32_t>(wws, RRL_WW_REC); a.sel = v.at<int32_t>(wws, RRL_WW_SEL); a.kj = v.at<uint8_t>(wws, RRL_WW_KJ);
-    a.hs1 = v.at<int32_t>(wws, RRL_WW_HS1); a.hs2 = v.at<int32_t>(wws, RRL_WW_HS2);
-    a.w1 = v.at<float>(wws, RRL_WW_W1); a.w2 = v.at<float>(wws, RRL_WW_W2);
-    a.Q1 = v.at<float4>(wws, RRL_WW_Q1); a.Q2 = v.at<float4>(wws, RRL_WW_Q2);
-    a.D = v.at<float>(wws, RRL_WW_D); a.med = v.at<float>(wws, RRL_WW_MED);
-    a.bcnt = v.at<int32_t>(wws, RRL_WW_BCNT); a.bsum = v.at<unsigned long long>(wws, RRL_WW_BSUM);
-    a.info = v.at<int32_t>(wws, RRL_WW_INFO);
+    a.status = v.at<RRL_WW_STATUS>(wws); a.nsel = v.at<RRL_WW_NSEL>(wws);
+    a.rec = v.at<RRL_WW_REC>(wws); a.sel = v.at<RRL_WW_SEL>(wws); a.kj = v.at<RRL_WW_KJ>(wws);
+    a.hs1 = v.at<RRL_WW_HS1>(wws); a.hs2 = v.at<RRL_WW_HS2>(wws);
+    a.w1 = v.at<RRL_WW_W1>(wws); a.w2 = v.at<RRL_WW_W2>(wws);
+    a.Q1 = (float4 *)v.at<RRL_WW_Q1>(wws); a.Q2 = (float4 *)v.at<RRL_WW_Q2>(wws);
+    a.D = v.at<RRL_WW_D>(wws); a.med = v.at<RRL_WW_MED>(wws);
+    a.bcnt = v.at<RRL_WW_BCNT>(wws); a.bsum = (unsigned long long *)v.at<RRL_WW_BSUM>(wws);
+    a.info = v.at<RRL_WW_INFO>(wws);
     a.B = B; a.N = N; a.M = M; a.L = L; a.pool = pool ? 1 : 0;
     if (o) {
-        a.count1 = o->i32(RRL_WS_COUNT1); a.count2 = o->i32(RRL_WS_COUNT2);
-        a.hit1 = o->i32(RRL_WS_HIT1); a.hit2 = o->i32(RRL_WS_HIT2);
-        a.ptri1 = o->f32(RRL_WS_PTRI1); a.ptri2 = o->f32(RRL_WS_PTRI2);
-        a.scan_status = o->i32(RRL_WS_STATUS);
+        a.count1 = o->at<RRL_WS_COUNT1>(); a.count2 = o->at<RRL_WS_COUNT2>();
+        a.hit1 = o->at<RRL_WS_HIT1>(); a.hit2 = o->at<RRL_WS_HIT2>();
+        a.ptri1 = o->at<RRL_WS_PTRI1>(); a.ptri2 = o->at<RRL_WS_PTRI2>();
+        a.scan_status = o->at<RRL_WS_STATUS>();
         a.loss = loss;
         a.s_m = o->s_m; a.s_n = o->s_n; a.e_m = o->e_m; a.e_n = o->e_n;
     }

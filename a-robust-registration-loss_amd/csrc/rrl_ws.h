@@ -1,95 +1,63 @@
-// rrl_ws.h -- the host layer's shared types: the layout of the caller-allocated workspace (WsLayout; fields: include/rrl.h
-// RRL_WS_*), the record of ONE call (RrlCall: options, plan, shape, bucket range, workspace + layout, stream -- set once at
+// rrl_ws.h -- the host layer's shared types: the layouts of the caller-allocated workspaces (WsLayout, WwLayout: generated from
+// the field tables of include/rrl.h), the record of ONE call (RrlCall: options, plan, shape, bucket range, workspace + layout, stream -- set once at
 // the top of an extern "C" entry by rrl_begin_call, validated once by rrl_check_call, then handed to every host function
 // below the entry), and the prototypes of the host functions that cross translation units.
-// The first six workspace fields (status, nvals, nsel, pmax, count1, count2) are contiguous so that one
-// hipMemsetAsync clears all per-call state.  Every field starts on a 256-byte boundary.
+// Every field starts on a 256-byte boundary, the fields follow each other in table order.
 #pragma once
 #include <stdlib.h>
 
 #include "rrl_common.h"
 
-struct WsLayout {
-    size_t off[RRL_WS_FIELDS];
-    size_t total, zero_bytes;
-    size_t state_off, state_bytes;  // MHIST .. MSUM: per-call state of the tiled reduce (cleared by the records kernel)
+// ---- layouts, generated from include/rrl.h's tables (kind 0: RRL_WS_TABLE, 1: RRL_WW_TABLE) ----
+template <class T, class... D>
+constexpr size_t rrl_field_bytes(D... d) { return ((sizeof(T) * ... * (size_t)d) + 255) & ~(size_t)255; }
+#define RRL_ROW_END_(name, type, ...) *end++ = o += rrl_field_bytes<type>(__VA_ARGS__);
+// end[0] = 0, end[i + 1] = where field i ends and field i + 1 starts (g = b: room for every grouping)
+template <int KIND>
+inline void rrl_place_fields(size_t *end, int B, int N, int M, int L) {
+    const size_t b = (size_t)(B > 0 ? B : 0), n = (size_t)(N > 0 ? N : 0), m = (size_t)(M > 0 ? M : 0),
+                 l = (size_t)(L > 0 ? L : 0), g = b;
+    size_t o = *end++ = 0;
+    if constexpr (KIND == 0) { RRL_WS_TABLE(RRL_ROW_END_) } else { (void)n; (void)m; RRL_WW_TABLE(RRL_ROW_END_) }
+}
+template <int KIND, int F> struct RrlFieldType;  // ::T, the field's element type
+#define RRL_WS_TYPE_(name, type, ...) template <> struct RrlFieldType<0, RRL_WS_##name> { typedef type T; };
+#define RRL_WW_TYPE_(name, type, ...) template <> struct RrlFieldType<1, RRL_WW_##name> { typedef type T; };
+RRL_WS_TABLE(RRL_WS_TYPE_)
+RRL_WW_TABLE(RRL_WW_TYPE_)
 
-    __host__ WsLayout() : off{}, total(0), zero_bytes(0), state_off(0), state_bytes(0) {}  // (a record before rrl_begin_call)
-    __host__ WsLayout(int B, int N, int M, int L) {
-        const size_t b = (size_t)(B > 0 ? B : 0), n = (size_t)(N > 0 ? N : 0),
-                     m = (size_t)(M > 0 ? M : 0), l = (size_t)(L > 0 ? L : 0);
-        const size_t bytes[RRL_WS_FIELDS] = {
-            4 * 4,               // STATUS
-            4 * b,               // NVALS
-            4 * b,               // NSEL
-            4 * 2 * b,           // PMAX
-            4 * b * l,           // COUNT1
-            4 * b * l,           // COUNT2
-            4 * b * l * 4,       // HIT1
-            4 * b * l * 4,       // HIT2
-            4 * b * n * 12,      // PTRI1
-            4 * b * m * 12,      // PTRI2
-            16 * b * ((n + 63) / 64) * 64,  // P0S1 (padded to whole supergroups of 64)
-            16 * b * ((m + 63) / 64) * 64,  // P0S2
-            4 * b * ((n + 63) / 64) * 64,   // IDX1
-            4 * b * ((m + 63) / 64) * 64,   // IDX2
-            16 * b * ((n + 63) / 64) * 13,  // GRP1 (sphere tree: 13 float4 per supergroup)
-            16 * b * ((m + 63) / 64) * 13,  // GRP2
-            16 * b * ((n + 15) / 16) * 16,  // CREC1
-            16 * b * ((m + 15) / 16) * 16,  // CREC2
-            4 * 2 * b * 8 * (((n > m ? n : m) + 255) / 256),  // APART
-            b * l,               // KJ
-            4 * b * l,           // SEL
-            4 * b * l * 4,       // HS1
-            4 * b * l * 4,       // HS2
-            4 * b * l * 12,      // W1
-            4 * b * l * 12,      // W2
-            4 * b * l * 16,      // Q1
-            4 * b * l * 16,      // Q2
-            4 * b * l * 16,      // D
-            4 * b * ((l + 1023) / 1024) * 1024 * 16,  // VALS (canonical D tiles by compact slot)
-            4 * b,               // MED   (G <= B)
-            4 * b * 16,          // BCNT
-            8 * b * 32,          // BSUM
-            4 * b * 4,           // INFO
-            4 * b * n * 9,       // TRI1
-            4 * b * n * 9,       // G1
-            4 * b * 12 * ((3 * n + 1023) / 1024 + 1),    // RPART
-            4 * (b * 12 + 16),                           // GACC (followed by KJC: see rrl_launch_tri_build)
-            b * ((l + 1023) / 1024) * 1024,              // KJC
-            4 * b * ((l + 1023) / 1024 + 1),             // BLKCNT
-            (n > 4096 || m > 4096) ? 4 * 2 * b * 2 * 4096 : 16,  // HISTG (wide sort of large clouds)
-            4 * b * n,           // DEL1
-            4 * b * m,           // DEL2
-            4 * b * 2048,        // MHIST  (MHIST .. MSUM: contiguous, cleared per call: state_bytes)
-            4 * b * 64,          // MCTL
-            8 * b * 32,          // MSUM
-            4 * b * 2048,        // MCAND
-            4 * b * 64 * 2,      // LMAX
-            4 * b * ((l + 1023) / 1024) * 1024,  // LIDC
-            4 * b * ((l + 1023) / 1024) * 16384, // VLIST
-            4 * b * ((l + 1023) / 1024 + 1),     // VLCNT
-            4 * b * 4,                           // CHAIN (chained steps: include/rrl.h RRL_F_CHAIN)
-            8 * b * (n + m) * 9 + 4 * 2 * b,     // GFIX (deterministic scatter backward)
-        };
-        size_t o = 0;
-        for (int i = 0; i < RRL_WS_FIELDS; ++i) {
-            off[i] = o;
-            o += (bytes[i] + 255) & ~(size_t)255;
-            if (i == RRL_WS_COUNT2) zero_bytes = o;
-            if (i == RRL_WS_MSUM) { state_off = off[RRL_WS_MHIST]; state_bytes = o - state_off; }
-        }
-        total = o;
+template <int KIND, int FIELDS>
+struct RrlLayout {
+    size_t off[FIELDS + 1];  // off[FIELDS] = total
+    size_t total;
+    RrlLayout() : off{}, total(0) {}  // (a record before rrl_begin_call)
+    RrlLayout(int B, int N, int M, int L) { rrl_place_fields<KIND>(off, B, N, M, L); total = off[FIELDS]; }
+    // field F of a workspace, as a pointer to the table's element type
+    template <int F> typename RrlFieldType<KIND, F>::T *at(void *ws) const {
+        return (typename RrlFieldType<KIND, F>::T *)((char *)ws + off[F]);
     }
-    __host__ float *f32(void *ws, int f) const { return (float *)((char *)ws + off[f]); }
-    __host__ int32_t *i32(void *ws, int f) const { return (int32_t *)((char *)ws + off[f]); }
-    __host__ uint8_t *u8(void *ws, int f) const { return (uint8_t *)((char *)ws + off[f]); }
-    __host__ int64_t *i64(void *ws, int f) const { return (int64_t *)((char *)ws + off[f]); }
-    __host__ uint32_t *u32(void *ws, int f) const { return (uint32_t *)((char *)ws + off[f]); }
-    __host__ const float *f32(const void *ws, int f) const { return (const float *)((const char *)ws + off[f]); }
-    __host__ const int32_t *i32(const void *ws, int f) const { return (const int32_t *)((const char *)ws + off[f]); }
-    __host__ const uint8_t *u8(const void *ws, int f) const { return (const uint8_t *)((const char *)ws + off[f]); }
-    __host__ const uint32_t *u32(const void *ws, int f) const { return (const uint32_t *)((const char *)ws + off[f]); }
+    template <int F> const typename RrlFieldType<KIND, F>::T *at(const void *ws) const {
+        return (const typename RrlFieldType<KIND, F>::T *)((const char *)ws + off[F]);
+    }
+};
+
+// What the host code knows about the order of the narrow fields beyond their sizes:
+static_assert(RRL_WS_STATUS == 0 && RRL_WS_NVALS == 1 && RRL_WS_NSEL == 2 && RRL_WS_PMAX == 3 && RRL_WS_COUNT1 == 4 &&
+                  RRL_WS_COUNT2 == 5, "zero_bytes: one fill clears the per-call state, the first six fields");
+static_assert(RRL_WS_MCTL == RRL_WS_MHIST + 1 && RRL_WS_MSUM == RRL_WS_MHIST + 2, "state_off / state_bytes span MHIST .. MSUM");
+static_assert(RRL_WS_KJC == RRL_WS_GACC + 1, "GACC is cleared up to KJC's offset (rrl_launch_tri_build)");
+struct WsLayout : RrlLayout<0, RRL_WS_FIELDS> {
+    size_t zero_bytes;
+    size_t state_off, state_bytes;  // MHIST .. MSUM: per-call state of the tiled reduce (cleared by the records kernel)
+    WsLayout() : zero_bytes(0), state_off(0), state_bytes(0) {}
+    WsLayout(int B, int N, int M, int L)
+        : RrlLayout(B, N, M, L), zero_bytes(off[RRL_WS_COUNT2 + 1]), state_off(off[RRL_WS_MHIST]),
+          state_bytes(off[RRL_WS_MSUM + 1] - off[RRL_WS_MHIST]) {}
+};
+static_assert(RRL_WW_STATUS == 0 && RRL_WW_NSEL == 1, "zero_bytes: one fill clears STATUS and NSEL");
+struct WwLayout : RrlLayout<1, RRL_WW_FIELDS> {
+    size_t zero_bytes;
+    WwLayout(int B, int N, int M, int L) : RrlLayout(B, N, M, L), zero_bytes(off[RRL_WW_NSEL + 1]) {}
 };
 
 // The options of ONE call, resolved once at its top (include/rrl.h rrl_opts; defaults = what the rrl_set_* setters /
@@ -175,13 +143,9 @@ struct RrlCall {
     size_t ws_bytes;
     WsLayout w;
     hipStream_t s;
-    __host__ float *f32(int f) const { return w.f32(ws, f); }
-    __host__ int32_t *i32(int f) const { return w.i32(ws, f); }
-    __host__ uint8_t *u8(int f) const { return w.u8(ws, f); }
-    __host__ int64_t *i64(int f) const { return w.i64(ws, f); }
-    __host__ uint32_t *u32(int f) const { return w.u32(ws, f); }
+    template <int F> auto at() const { return w.at<F>(ws); }  // field F (RRL_WS_*) of this call's workspace
     // ... and a field of cloud 2 where its scan left it: the carried-over target's workspace (tar_ws), else this one
-    __host__ const int32_t *tar_i32(int f) const { return w.i32(tar_ws ? tar_ws : (const void *)ws, f); }
+    template <int F> auto tar_at() const { return w.at<F>(tar_ws ? tar_ws : (const void *)ws); }
     __host__ void set(int sm, int sn, int em, int en, int pool_, int mode_ = RRL_SCAN_CULL, int chunk_ = 0) {
         s_m = sm; s_n = sn; e_m = em; e_n = en; pool = pool_; mode = mode_; chunk = chunk_;
     }

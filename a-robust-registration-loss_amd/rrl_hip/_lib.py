@@ -19,6 +19,7 @@ _Z = _c.c_size_t
 _SIGS = {
     "rrl_workspace_layout": [_I, _I, _I, _I, _P],
     "rrl_wide_workspace_layout": [_I, _I, _I, _I, _P],
+    "rrl_workspace_field": [_I] * 7 + [_P, _P, _P],
     "rrl_loss_forward_wide": [_P, _P, _P, _P, _Z, _P, _Z, _P] + [_I] * 11 + [_P, _P],
     "rrl_loss_backward_wide": [_P, _Z, _P, _P, _P] + [_I] * 5 + [_P],
     "rrl_loss_forward": [_P, _P, _P, _P, _Z, _P] + [_I] * 11 + [_P],

@@ -14,63 +14,6 @@ from ._lib import RRLError, check
 SCAN_STRICT, SCAN_LAZY, SCAN_AUTO, SCAN_CULL = 0, 1, 2, 3
 _MODES = {"strict": SCAN_STRICT, "lazy": SCAN_LAZY, "auto": SCAN_AUTO, "cull": SCAN_CULL}
 
-# workspace fields, in the order of include/rrl.h's RRL_WS_* enum: (name, dtype, shape)
-_WS_FIELDS = [
-    ("status", torch.int32, lambda B, N, M, L, G: (4,)),
-    ("nvals", torch.int32, lambda B, N, M, L, G: (B,)),
-    ("nsel", torch.int32, lambda B, N, M, L, G: (B,)),
-    ("pmax", torch.float32, lambda B, N, M, L, G: (2, B)),
-    ("count1", torch.int32, lambda B, N, M, L, G: (B, L)),
-    ("count2", torch.int32, lambda B, N, M, L, G: (B, L)),
-    ("hit1", torch.int32, lambda B, N, M, L, G: (B, L, 4)),
-    ("hit2", torch.int32, lambda B, N, M, L, G: (B, L, 4)),
-    ("ptri1", torch.float32, lambda B, N, M, L, G: (B, N, 12)),
-    ("ptri2", torch.float32, lambda B, N, M, L, G: (B, M, 12)),
-    ("p0s1", torch.float32, lambda B, N, M, L, G: (B, (N + 63) // 64 * 64, 4)),
-    ("p0s2", torch.float32, lambda B, N, M, L, G: (B, (M + 63) // 64 * 64, 4)),
-    ("idx1", torch.int32, lambda B, N, M, L, G: (B, (N + 63) // 64 * 64)),
-    ("idx2", torch.int32, lambda B, N, M, L, G: (B, (M + 63) // 64 * 64)),
-    ("grp1", torch.float32, lambda B, N, M, L, G: (B, (N + 63) // 64, 13, 4)),  # sphere tree
-    ("grp2", torch.float32, lambda B, N, M, L, G: (B, (M + 63) // 64, 13, 4)),
-    ("crec1", torch.float32, lambda B, N, M, L, G: (B, (N + 15) // 16 * 16, 4)),
-    ("crec2", torch.float32, lambda B, N, M, L, G: (B, (M + 15) // 16 * 16, 4)),
-    ("apart", torch.float32, lambda B, N, M, L, G: (2, B, (max(N, M) + 255) // 256, 8)),
-    ("kj", torch.uint8, lambda B, N, M, L, G: (B, L)),
-    ("sel", torch.int32, lambda B, N, M, L, G: (B, L)),
-    ("hs1", torch.int32, lambda B, N, M, L, G: (B, L, 4)),
-    ("hs2", torch.int32, lambda B, N, M, L, G: (B, L, 4)),
-    ("w1", torch.float32, lambda B, N, M, L, G: (B, L, 4, 3)),
-    ("w2", torch.float32, lambda B, N, M, L, G: (B, L, 4, 3)),
-    ("Q1", torch.float32, lambda B, N, M, L, G: (B, L, 4, 4)),
-    ("Q2", torch.float32, lambda B, N, M, L, G: (B, L, 4, 4)),
-    ("D", torch.float32, lambda B, N, M, L, G: (B, L, 16)),
-    ("vals", torch.float32, lambda B, N, M, L, G: (B, (L + 1023) // 1024 * 1024, 16)),
-    ("med", torch.float32, lambda B, N, M, L, G: (G,)),
-    ("bcnt", torch.int32, lambda B, N, M, L, G: (G, 16)),
-    ("bsum", torch.int64, lambda B, N, M, L, G: (G, 16, 2)),
-    ("info", torch.int32, lambda B, N, M, L, G: (G, 4)),
-    ("tri1t", torch.float32, lambda B, N, M, L, G: (B, N, 9)),
-    ("g1", torch.float32, lambda B, N, M, L, G: (B, N, 9)),
-    ("rpart", torch.float32, lambda B, N, M, L, G: (B, (3 * N + 1023) // 1024 + 1, 12)),
-    ("gacc", torch.float32, lambda B, N, M, L, G: (12 * B + 16,)),
-    ("kjc", torch.uint8, lambda B, N, M, L, G: (B, (L + 1023) // 1024 * 1024)),
-    ("blkcnt", torch.int32, lambda B, N, M, L, G: (B * ((L + 1023) // 1024 + 1),)),
-    ("histg", torch.int32, lambda B, N, M, L, G: (2 * B * 2 * 4096 if max(N, M) > 4096 else 4,)),
-    ("del1", torch.float32, lambda B, N, M, L, G: (B, N)),
-    ("del2", torch.float32, lambda B, N, M, L, G: (B, M)),
-    ("mhist", torch.int32, lambda B, N, M, L, G: (B, 2048)),
-    ("mctl", torch.int32, lambda B, N, M, L, G: (B, 64)),
-    ("msum", torch.int64, lambda B, N, M, L, G: (B, 32)),
-    ("mcand", torch.int32, lambda B, N, M, L, G: (B, 2048)),
-    ("lmax", torch.float32, lambda B, N, M, L, G: (B, 64, 2)),
-    ("lidc", torch.int32, lambda B, N, M, L, G: (B, (L + 1023) // 1024 * 1024)),
-    ("vlist", torch.float32, lambda B, N, M, L, G: (B, (L + 1023) // 1024, 16384)),
-    ("vlcnt", torch.int32, lambda B, N, M, L, G: (B * ((L + 1023) // 1024 + 1),)),
-    ("chain", torch.int32, lambda B, N, M, L, G: (B, 4)),
-    ("gfix", torch.int64, lambda B, N, M, L, G: (B * (N + M) * 9 + B,)),
-]
-_ITEMSIZE = {torch.int32: 4, torch.float32: 4, torch.uint8: 1, torch.int64: 8}
-
 
 _gpu_ok = False
 _deterministic = [os.environ.get("RRL_DETERMINISTIC", "")[:1] == "1"]  # mirrors the library's default (rrl_set_deterministic)
@@ -206,49 +149,75 @@ def _prep(t, name, last=None, dev=None):
     return t.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
-class _Workspace:
-    """One kind of device workspace: its field table (name, dtype, shape), the library's layout entry for it
-    (`<entry>_layout` / `<entry>_bytes`, include/rrl.h) and the attribute of a state that holds its bytes.  Layouts and
-    per-shape view specs are cached here; states call view() from their __getattr__ (nothing here refers to a state)."""
+_DTYPES = (torch.uint8, torch.int32, torch.float32, torch.int64)  # include/rrl.h RRL_T_*
+_PY_NAMES = {"q1": "Q1", "q2": "Q2", "d": "D", "tri1": "tri1t"}    # the attributes that differ from the table's lower-case names
 
-    def __init__(self, fields, entry, attr):
-        self.fields, self.entry, self.attr = fields, entry, attr
-        self.index = {name: i for i, (name, _, _) in enumerate(fields)}
+
+class _Workspace:
+    """One kind of device workspace (include/rrl.h: 0 RRL_WS_TABLE, 1 RRL_WW_TABLE): the library describes its fields
+    (rrl_workspace_field) and lays them out (`<entry>_layout` / `<entry>_bytes`); `attr` is the attribute of a state that
+    holds its bytes.  Names, layouts and per-shape view specs are cached here; states call view() from their __getattr__
+    (nothing here refers to a state)."""
+
+    def __init__(self, kind, entry, attr):
+        self.kind, self.entry, self.attr = kind, entry, attr
+        self.names = None  # asked of the library at first use
         self.layouts = {}  # (B, N, M, L) -> (bytes, [offset of each field])
         self.specs = {}    # (B, N, M, L, G) -> {field: (offset, nbytes, dtype, shape)}
+
+    def _field(self, i, dims=(0, 0, 0, 0, 0)):
+        """(name, dtype, shape) of field i at `dims`, from the library."""
+        name, code, ext = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_longlong * 4)()
+        rank = _lib.load().rrl_workspace_field(self.kind, i, *dims, ctypes.byref(name), ctypes.byref(code), ext)
+        check(min(rank, 0), "rrl_workspace_field")
+        name = name.value.decode()
+        return _PY_NAMES.get(name, name), _DTYPES[code.value], tuple(ext[:rank])
+
+    @property
+    def index(self):
+        if self.names is None:
+            n = _lib.load().rrl_workspace_field(self.kind, -1, 0, 0, 0, 0, 0, None, None, None)
+            self.names = {self._field(i)[0]: i for i in range(n)}
+        return self.names
 
     def layout(self, B, N, M, L):
         key = (B, N, M, L)
         if key not in self.layouts:
             lib = _lib.load()
-            offs = (ctypes.c_size_t * len(self.fields))()
+            offs = (ctypes.c_size_t * len(self.index))()
             check(getattr(lib, self.entry + "_layout")(B, N, M, L, offs), self.entry + "_layout")
             self.layouts[key] = (int(getattr(lib, self.entry + "_bytes")(B, N, M, L)), [int(o) for o in offs])
         return self.layouts[key]
 
-    def view(self, st, name):
-        """Field `name` of state `st`'s workspace as a typed view (a fresh one per access); AttributeError for any
-        other name."""
+    def spec(self, dims, name):
+        """(offset, nbytes, dtype, shape) of field `name` at dims = (B, N, M, L, G); AttributeError for any other name."""
         i = self.index.get(name)
         if i is None:
             raise AttributeError(name)
-        dims = st.dims
         specs = self.specs.get(dims)
         if specs is None:
             specs = self.specs[dims] = {}
         spec = specs.get(name)
         if spec is None:
-            _, dtype, shape = self.fields[i]
-            shp = shape(*dims)
-            n = 1
+            off = self.layout(*dims[:4])[1][i]
+            _, dtype, shp = self._field(i, dims)
+            n = dtype.itemsize
             for d in shp:
                 n *= d
-            spec = specs[name] = (self.layout(*dims[:4])[1][i], n * _ITEMSIZE[dtype], dtype, shp)
-        off, nb, dtype, shp = spec
+            spec = specs[name] = (off, n, dtype, shp)
+        return spec
+
+    def view(self, st, name):
+        """Field `name` of state `st`'s workspace as a typed view (a fresh one per access); AttributeError for any
+        other name (before anything of `st` is read: a state that is still being built has no dims)."""
+        if name not in self.index:
+            raise AttributeError(name)
+        off, nb, dtype, shp = self.spec(st.dims, name)
         return st.__dict__[self.attr][off:off + nb].view(dtype).reshape(shp)
 
 
-_WS = _Workspace(_WS_FIELDS, "rrl_workspace", "ws")
+_WS = _Workspace(0, "rrl_workspace", "ws")
+_WW = _Workspace(1, "rrl_wide_workspace", "wws")
 
 
 class LossState:
@@ -272,28 +241,6 @@ class LossState:
     @property
     def nbuckets(self):
         return self.info[:, 0]
-
-
-# wide workspace fields, in the order of include/rrl.h's RRL_WW_* enum: (name, dtype, shape)
-_WW_FIELDS = [
-    ("status", torch.int32, lambda B, N, M, L, G: (4,)),
-    ("nsel", torch.int32, lambda B, N, M, L, G: (B,)),
-    ("rec", torch.int32, lambda B, N, M, L, G: (2 * B * L,)),
-    ("sel", torch.int32, lambda B, N, M, L, G: (B, L)),
-    ("kj", torch.uint8, lambda B, N, M, L, G: (B, L)),
-    ("hs1", torch.int32, lambda B, N, M, L, G: (B, L, 8)),
-    ("hs2", torch.int32, lambda B, N, M, L, G: (B, L, 8)),
-    ("w1", torch.float32, lambda B, N, M, L, G: (B, L, 8, 3)),
-    ("w2", torch.float32, lambda B, N, M, L, G: (B, L, 8, 3)),
-    ("Q1", torch.float32, lambda B, N, M, L, G: (B, L, 8, 4)),
-    ("Q2", torch.float32, lambda B, N, M, L, G: (B, L, 8, 4)),
-    ("D", torch.float32, lambda B, N, M, L, G: (B, L, 8, 8)),
-    ("med", torch.float32, lambda B, N, M, L, G: (G,)),
-    ("bcnt", torch.int32, lambda B, N, M, L, G: (G, 64)),
-    ("bsum", torch.int64, lambda B, N, M, L, G: (G, 64, 2)),
-    ("info", torch.int32, lambda B, N, M, L, G: (G, 4)),
-]
-_WW = _Workspace(_WW_FIELDS, "rrl_wide_workspace", "wws")
 
 
 class WideState:

@@ -79,82 +79,93 @@ extern "C" {
                              argument is evaluated exactly (csrc/rrl_cull.hip, "NaN").
                              Needs N, M <= rrl_sort_capacity() (2^20), else behaves like AUTO. */
 
-/* workspace fields (indices into rrl_workspace_layout's offset array) */
-enum {
-    RRL_WS_STATUS = 0, /* int32[4]   [0] = NaN seen (reference exit(0), loss.py:89-91); [1] = wavefronts of the
+/* ---- workspace fields ---------------------------------------------------------------------------
+ * ONE table per workspace: a row X(NAME, element type, extents...) per field, in the order of the field's index.  The
+ * extents (one to four, outermost first) are expressions in b, n, m, l -- the call's B, N, M, L, a negative one taken
+ * as 0 -- and g, the number of groups (G = 1 pooled, else B; g <= b).  Generated from the table: the enumerators
+ * RRL_WS_<NAME> (indices into rrl_workspace_layout's offset array), the layout (a field occupies sizeof(element) x the
+ * product of its extents at g = b, rounded up to 256 bytes; fields follow each other in table order), what
+ * rrl_workspace_field reports (and the Python views made from it) and the host accessors' pointer types
+ * (csrc/rrl_ws.h).  Adding a field is adding one row. */
+#define RRL_T_U8 0 /* element types as rrl_workspace_field reports them: uint8_t */
+#define RRL_T_I32 1 /* int32_t */
+#define RRL_T_F32 2 /* float */
+#define RRL_T_I64 3 /* int64_t */
+
+#define RRL_WS_TABLE(X)                                                                                                           \
+    X(STATUS, int32_t, 4) /* [0] = NaN seen (reference exit(0), loss.py:89-91); [1] = wavefronts of the
                           culled scan that fell back to the strict loop; [2] = samples whose exchange reduce was repaired
-                          by their last workgroup after a hand-off time-out (rrl_set_spin_limit); [3] = internal ticket */
-    RRL_WS_NVALS,      /* int32[B]   (unused since the compact-slot layout; kept for ABI stability) */
-    RRL_WS_NSEL,       /* int32[B]   selected lines per sample (length of SEL[b])           */
-    RRL_WS_PMAX,       /* uint32[2][B] bits of max |P|^2 per cloud and sample                */
-    RRL_WS_COUNT1,     /* int32[B][L] hit count, cloud 1 (loss.py:185)                      */
-    RRL_WS_COUNT2,     /* int32[B][L]                                                      */
-    RRL_WS_HIT1,       /* int32[B][L][4] unordered hit indices                              */
-    RRL_WS_HIT2,
-    RRL_WS_PTRI1,      /* float[B][N][12] 9 coords, thr2, thr, original triangle index (int): the scans' records.  Rows in
+                          by their last workgroup after a hand-off time-out (rrl_set_spin_limit); [3] = internal ticket */        \
+    X(NVALS, int32_t, b)  /* (unused since the compact-slot layout; kept for ABI stability) */                                    \
+    X(NSEL, int32_t, b)   /* selected lines per sample (length of SEL[b]) */                                                      \
+    X(PMAX, float, 2, b)  /* max |P|^2 per cloud and sample (maintained as uint32 bit patterns) */                                \
+    X(COUNT1, int32_t, b, l) /* hit count, cloud 1 (loss.py:185) */                                                               \
+    X(COUNT2, int32_t, b, l)                                                                                                      \
+    X(HIT1, int32_t, b, l, 4) /* unordered hit indices */                                                                         \
+    X(HIT2, int32_t, b, l, 4)                                                                                                     \
+    X(PTRI1, float, b, n, 12) /* 9 coords, thr2, thr, original triangle index (int): the scans' records.  Rows in
                           original order after a cold build, at the triangles' SORTED positions after a prepared build
-                          (rrl_opts.order1 / order2) -- slot 7 of the cloud's first APART row says which (0 / 1)  */
-    RRL_WS_PTRI2,      /* float[B][M][12]                                                   */
-    RRL_WS_P0S1,       /* float[B][64*NSG1][4] P0 + thr2 in grid-cell (Hilbert curve) order -- clouds of more than 4096
-                          triangles: each chunk of 4096 (by original index) in its own order; NSG = ceil(N/64)   */
-    RRL_WS_P0S2,       /*   supergroups of 64 sorted triangles; pad records have thr2 = 0 (never hit)           */
-    RRL_WS_IDX1,       /* int32[B][64*NSG1]  original triangle index of each sorted position     */
-    RRL_WS_IDX2,
-    RRL_WS_GRP1,       /* float[B][NSG1][13][4] sphere tree (centre, conservative radius; NaN = empty): per   */
-    RRL_WS_GRP2,       /*   supergroup [0] its own sphere, [1..4] its groups of 16, [5..12] their halves of 8   */
-    RRL_WS_CREC1,      /* float[B][16*NG1][4] P0 + thr2 in original order (input of the sort)   */
-    RRL_WS_CREC2,
-    RRL_WS_APART,      /* float[2][B][ceil(max(N,M)/256)][8] per-workgroup AABB / max |P|^2 partials (slot 7: PTRI layout) */
-    RRL_WS_KJ,         /* uint8[B][L]  k | j<<4, 0 = line not selected                      */
-    RRL_WS_SEL,        /* int32[B][L]  indices of the selected lines, compacted (any order)  */
-    RRL_WS_HS1,        /* int32[B][L][4] ascending hit indices (nonzero() order)            */
-    RRL_WS_HS2,
-    RRL_WS_W1,         /* float[B][L][4][3] weights d / sum d (loss.py:92)                  */
-    RRL_WS_W2,
-    RRL_WS_Q1,         /* float[B][L][4][4] intersection points q (xyz, 0) (loss.py:155-163)  */
-    RRL_WS_Q2,
-    RRL_WS_D,          /* float[B][L][16] k x j block of |q1-q2|^2 (loss.py:165-166)        */
-    RRL_WS_VALS,       /* float[B][Lp][16] canonical 4x4 D tiles (+inf padded) of the selected lines
-                          at compact slots: slot = 1024 * x + rank for the x-th 1024-line tile,
-                          Lp = 1024 * ceil(L/1024) (input of the reduce kernel)                */
-    RRL_WS_MED,        /* float[G]  lower median (loss.py:223-224)                          */
-    RRL_WS_BCNT,       /* int32[G][16] lines per (k,j) bucket                               */
-    RRL_WS_BSUM,       /* int64[G][16][2] bucket sums of row / column minima, 2^-40 fixed pt */
-    RRL_WS_INFO,       /* int32[G][4] nbuckets, nselected, nvalues, STATUS[0] (the scan's NaN flag; after a CHAINED step's fused
-                          launch: the sample's OWN flag, CHAIN[b][1])  */
-    RRL_WS_TRI1,       /* float[B][N][9] transformed source triangles (rrl_registration_*)   */
-    RRL_WS_G1,         /* float[B][N][9] gradient w.r.t. TRI1 (rrl_registration_backward)    */
-    RRL_WS_RPART,      /* float[B][nblk][12] rigid-apply backward partial sums              */
-    RRL_WS_GACC,       /* float[12 B + 16]  dL/dR [B][9], dL/dt [B][3], shard payload [14]: zeroed by
-                          rrl_registration_forward, accumulated by rrl_registration_backward     */
-    RRL_WS_KJC,        /* uint8[B][Lp]  k | j<<4 at the compact slots                            */
-    RRL_WS_BLKCNT,     /* int32[B][ceil(L/1024)] selected lines per 1024-line tile               */
-    RRL_WS_HISTG,      /* uint32[2 B][2][4096] cell counts and cursors of the wide sort (clouds > 4096) */
-    RRL_WS_DEL1,       /* float[B][N]  NaN reach of a triangle: max(|P1-P0|, |P2-P0|) - thr, clamped at 0, rounded up: how   */
-    RRL_WS_DEL2,       /* float[B][M]  much farther than thr points 1, 2 can sit from point 0 (culled scan, NaN detection);
-                          rows laid out like PTRI's (original order / sorted positions)                                  */
-    RRL_WS_MHIST,      /* uint32[B][2048] histogram of the D values' bits 30..20, accumulated by the per-line stage (the
-                          median's first radix pass); MHIST, MCTL, MSUM are contiguous and cleared per call                 */
-    RRL_WS_MCTL,       /* uint32[B][64]  [0..15] lines per (k,j) bucket (per-line stage); [16] candidate cursor, [17] / [18]
-                          arrival counters of the tiled reduce, [19] its error flag (spin time-out)                          */
-    RRL_WS_MSUM,       /* uint64[B][32]  bucket sums of the tiled reduce (2^-40 fixed point, device atomics)                */
-    RRL_WS_MCAND,      /* uint32[B][2048] D values (bit patterns) of the median's bin, gathered by the tiled reduce          */
-    RRL_WS_LMAX,       /* float[B][64][2] (max |dir|^2, max |x0|^2) over 1/64 of a sample's cullable lines: the culled scan's
-                          slacks come from their maxima (written by the records kernel, or by the scan entry itself)       */
-    RRL_WS_LIDC,       /* uint32[B][Lp]  line index | (k | j<<4) << 24 at the compact slots (the tail kernel's way from a
-                          compact slot back to the per-line arrays)                                                        */
-    RRL_WS_VLIST,      /* float[B][ceil(L/1024)][16384]  the valid D values of each 1024-line tile as a dense list (arbitrary order,
-                          padded with -1 to a multiple of 4): what the tail kernel streams to find the median                */
-    RRL_WS_VLCNT,      /* int32[B][ceil(L/1024)]  their number per tile                                                     */
-    RRL_WS_CHAIN,      /* uint32[B][4]  per-sample words of a CHAINED step (RRL_F_CHAIN / RRL_F_CHAINED, round 6): [0] records
+                          (rrl_opts.order1 / order2) -- slot 7 of the cloud's first APART row says which (0 / 1)  */              \
+    X(PTRI2, float, b, m, 12)                                                                                                     \
+    X(P0S1, float, b, (n + 63) / 64 * 64, 4) /* P0 + thr2 in grid-cell (Hilbert curve) order -- clouds of more than 4096
+                          triangles: each chunk of 4096 (by original index) in its own order; padded to whole              */     \
+    X(P0S2, float, b, (m + 63) / 64 * 64, 4) /* supergroups of 64 sorted triangles; pad records have thr2 = 0 (never hit) */      \
+    X(IDX1, int32_t, b, (n + 63) / 64 * 64) /* original triangle index of each sorted position */                                 \
+    X(IDX2, int32_t, b, (m + 63) / 64 * 64)                                                                                       \
+    X(GRP1, float, b, (n + 63) / 64, 13, 4) /* sphere tree (centre, conservative radius; NaN = empty): per   */                   \
+    X(GRP2, float, b, (m + 63) / 64, 13, 4) /* supergroup [0] its own sphere, [1..4] its groups of 16, [5..12] their halves of 8 */ \
+    X(CREC1, float, b, (n + 15) / 16 * 16, 4) /* P0 + thr2 in original order (input of the sort) */                               \
+    X(CREC2, float, b, (m + 15) / 16 * 16, 4)                                                                                     \
+    X(APART, float, 2, b, ((n > m ? n : m) + 255) / 256, 8) /* per-workgroup AABB / max |P|^2 partials (slot 7: PTRI layout) */   \
+    X(KJ, uint8_t, b, l)   /* k | j<<4, 0 = line not selected */                                                                  \
+    X(SEL, int32_t, b, l)  /* indices of the selected lines, compacted (any order) */                                             \
+    X(HS1, int32_t, b, l, 4) /* ascending hit indices (nonzero() order) */                                                        \
+    X(HS2, int32_t, b, l, 4)                                                                                                      \
+    X(W1, float, b, l, 4, 3) /* weights d / sum d (loss.py:92) */                                                                 \
+    X(W2, float, b, l, 4, 3)                                                                                                      \
+    X(Q1, float, b, l, 4, 4) /* intersection points q (xyz, 0) (loss.py:155-163) */                                               \
+    X(Q2, float, b, l, 4, 4)                                                                                                      \
+    X(D, float, b, l, 16)  /* k x j block of |q1-q2|^2 (loss.py:165-166) */                                                       \
+    X(VALS, float, b, (l + 1023) / 1024 * 1024, 16) /* canonical 4x4 D tiles (+inf padded) of the selected lines
+                          at compact slots: slot = 1024 * x + rank for the x-th 1024-line tile (input of the reduce kernel) */    \
+    X(MED, float, g)         /* lower median (loss.py:223-224) */                                                                 \
+    X(BCNT, int32_t, g, 16)  /* lines per (k,j) bucket */                                                                         \
+    X(BSUM, int64_t, g, 16, 2) /* bucket sums of row / column minima, 2^-40 fixed pt */                                           \
+    X(INFO, int32_t, g, 4) /* nbuckets, nselected, nvalues, STATUS[0] (the scan's NaN flag; after a CHAINED step's fused
+                          launch: the sample's OWN flag, CHAIN[b][1])  */                                                         \
+    X(TRI1, float, b, n, 9) /* transformed source triangles (rrl_registration_*) */                                               \
+    X(G1, float, b, n, 9)   /* gradient w.r.t. TRI1 (rrl_registration_backward) */                                                \
+    X(RPART, float, b, (3 * n + 1023) / 1024 + 1, 12) /* rigid-apply backward partial sums */                                     \
+    X(GACC, float, 12 * b + 16) /* dL/dR [B][9], dL/dt [B][3], shard payload [14]: zeroed by
+                          rrl_registration_forward, accumulated by rrl_registration_backward     */                               \
+    X(KJC, uint8_t, b, (l + 1023) / 1024 * 1024) /* k | j<<4 at the compact slots */                                              \
+    X(BLKCNT, int32_t, b * ((l + 1023) / 1024 + 1)) /* selected lines per 1024-line tile */                                       \
+    X(HISTG, int32_t, (n > 4096 || m > 4096) ? 2 * b * 2 * 4096 : 4) /* cell counts and cursors of the wide sort (clouds > 4096) */ \
+    X(DEL1, float, b, n) /* NaN reach of a triangle: max(|P1-P0|, |P2-P0|) - thr, clamped at 0, rounded up: how   */              \
+    X(DEL2, float, b, m) /* much farther than thr points 1, 2 can sit from point 0 (culled scan, NaN detection);
+                          rows laid out like PTRI's (original order / sorted positions)                                  */       \
+    X(MHIST, int32_t, b, 2048) /* histogram of the D values' bits 30..20, accumulated by the per-line stage (the
+                          median's first radix pass); MHIST, MCTL, MSUM are contiguous and cleared per call                 */    \
+    X(MCTL, int32_t, b, 64) /* [0..15] lines per (k,j) bucket (per-line stage); [16] candidate cursor, [17] / [18]
+                          arrival counters of the tiled reduce, [19] its error flag (spin time-out)                          */   \
+    X(MSUM, int64_t, b, 32) /* bucket sums of the tiled reduce (2^-40 fixed point, device atomics) */                             \
+    X(MCAND, int32_t, b, 2048) /* D values (bit patterns) of the median's bin, gathered by the tiled reduce */                    \
+    X(LMAX, float, b, 64, 2) /* (max |dir|^2, max |x0|^2) over 1/64 of a sample's cullable lines: the culled scan's
+                          slacks come from their maxima (written by the records kernel, or by the scan entry itself)       */     \
+    X(LIDC, int32_t, b, (l + 1023) / 1024 * 1024) /* line index | (k | j<<4) << 24 at the compact slots (the tail kernel's way
+                          from a compact slot back to the per-line arrays)                                                 */     \
+    X(VLIST, float, b, (l + 1023) / 1024, 16384) /* the valid D values of each 1024-line tile as a dense list (arbitrary order,
+                          padded with -1 to a multiple of 4): what the tail kernel streams to find the median                */   \
+    X(VLCNT, int32_t, b * ((l + 1023) / 1024 + 1)) /* their number per tile */                                                    \
+    X(CHAIN, int32_t, b, 4) /* per-sample words of a CHAINED step (RRL_F_CHAIN / RRL_F_CHAINED, round 6): [0] records
                           workgroups of the sample that have finished in the step's build + scan launch, [1] the scan's NaN
                           flag of the sample, [2] its wavefronts that fell back to the strict loop, [3] wait time-outs; all
-                          zero between calls (cleared on exit by the sample's last tail workgroup)                          */
-    RRL_WS_GFIX,       /* int64[B][N + M][9] + int32[2 B]  deterministic scatter backward (rrl_opts.deterministic with rrl_loss_step_ex /
-                          rrl_loss_backward): fixed-point accumulators of dL/dpoints1 (and dL/dpoints2), order-independent like MSUM;
-                          behind them one non-finite flag per sample and cloud                                              */
-    RRL_WS_FIELDS
-};
+                          zero between calls (cleared on exit by the sample's last tail workgroup)                          */    \
+    X(GFIX, int64_t, b * (n + m) * 9 + b) /* deterministic scatter backward (rrl_opts.deterministic with rrl_loss_step_ex /
+                          rrl_loss_backward): fixed-point accumulators of dL/dpoints1 (and dL/dpoints2), order-independent like
+                          MSUM; behind them one non-finite int32 flag per sample and cloud                                  */
+#define RRL_WS_ENUM_(name, type, ...) RRL_WS_##name,
+enum { RRL_WS_TABLE(RRL_WS_ENUM_) RRL_WS_FIELDS };
 
 /* ---- wide bucket ranges -----------------------------------------------------------------------
  * Every entry above serves bucket ranges within 1..RRL_MAX_HITS (e_m, e_n <= 5: every reference caller's
@@ -170,26 +181,26 @@ enum {
  * (the forward is deterministic); for a range within 1..4 it gives the narrow entries' loss bits.  Not served by the
  * wide entries: carried-over targets, chained steps, riders, multi-pose evaluation, deterministic gradients, the fused
  * registration steps.  DESIGN.md "Wide bucket ranges". */
-enum {
-    RRL_WW_STATUS = 0, /* int32[4]   [0] lines whose recovered hits disagree with the scan's count (must be 0); [1] hit-recovery
-                          entries (selected line, cloud with > 4 hits); [2], [3] zero */
-    RRL_WW_NSEL,       /* int32[B]   selected lines per sample                                                   */
-    RRL_WW_REC,        /* int32[2 B L] hit-recovery entries: slot | cloud << 31                                    */
-    RRL_WW_SEL,        /* int32[B][L] line index of each selected line, compacted (any order): the SLOT of a line  */
-    RRL_WW_KJ,         /* uint8[B][L] k | j << 4 by slot                                                          */
-    RRL_WW_HS1,        /* int32[B][L][8] ascending hit indices by slot (nonzero() order)                           */
-    RRL_WW_HS2,
-    RRL_WW_W1,         /* float[B][L][8][3] weights d / sum d (loss.py:92)                                         */
-    RRL_WW_W2,
-    RRL_WW_Q1,         /* float[B][L][8][4] intersection points (xyz, 0)                                           */
-    RRL_WW_Q2,
-    RRL_WW_D,          /* float[B][L][8][8] the k x j block of |q1 - q2|^2 by slot (entries outside it undefined)    */
-    RRL_WW_MED,        /* float[G]  lower median                                                                   */
-    RRL_WW_BCNT,       /* int32[G][64] lines per (k, j) bucket, index (k - 1) 8 + (j - 1)                           */
-    RRL_WW_BSUM,       /* int64[G][64][2] bucket sums of row / column minima, 2^-40 fixed point                    */
-    RRL_WW_INFO,       /* int32[G][4] nbuckets, nselected, nvalues, the scan's NaN flag (STATUS[0] of ws)            */
-    RRL_WW_FIELDS
-};
+#define RRL_WW_TABLE(X) /* rows as in RRL_WS_TABLE */                                                                             \
+    X(STATUS, int32_t, 4) /* [0] lines whose recovered hits disagree with the scan's count (must be 0); [1] hit-recovery
+                          entries (selected line, cloud with > 4 hits); [2], [3] zero */                                          \
+    X(NSEL, int32_t, b)          /* selected lines per sample */                                                                  \
+    X(REC, int32_t, 2 * b * l)   /* hit-recovery entries: slot | cloud << 31 */                                                   \
+    X(SEL, int32_t, b, l)        /* line index of each selected line, compacted (any order): the SLOT of a line */                \
+    X(KJ, uint8_t, b, l)         /* k | j << 4 by slot */                                                                         \
+    X(HS1, int32_t, b, l, RRL_WIDE_MAX_HITS) /* ascending hit indices by slot (nonzero() order) */                                \
+    X(HS2, int32_t, b, l, RRL_WIDE_MAX_HITS)                                                                                      \
+    X(W1, float, b, l, RRL_WIDE_MAX_HITS, 3)     /* weights d / sum d (loss.py:92) */                                             \
+    X(W2, float, b, l, RRL_WIDE_MAX_HITS, 3)                                                                                      \
+    X(Q1, float, b, l, RRL_WIDE_MAX_HITS, 4)     /* intersection points (xyz, 0) */                                               \
+    X(Q2, float, b, l, RRL_WIDE_MAX_HITS, 4)                                                                                      \
+    X(D, float, b, l, RRL_WIDE_MAX_HITS, RRL_WIDE_MAX_HITS) /* the k x j block of |q1 - q2|^2 by slot (entries outside it undefined) */ \
+    X(MED, float, g)             /* lower median */                                                                               \
+    X(BCNT, int32_t, g, RRL_WIDE_MAX_HITS * RRL_WIDE_MAX_HITS) /* lines per (k, j) bucket, index (k - 1) 8 + (j - 1) */           \
+    X(BSUM, int64_t, g, RRL_WIDE_MAX_HITS * RRL_WIDE_MAX_HITS, 2) /* bucket sums of row / column minima, 2^-40 fixed point */     \
+    X(INFO, int32_t, g, 4)       /* nbuckets, nselected, nvalues, the scan's NaN flag (STATUS[0] of ws) */
+#define RRL_WW_ENUM_(name, type, ...) RRL_WW_##name,
+enum { RRL_WW_TABLE(RRL_WW_ENUM_) RRL_WW_FIELDS };
 
 const char *rrl_version(void);
 /* Largest cloud (triangles of either cloud) that the SORTED layout serves: the per-step cell sort and sphere tree, the
@@ -311,6 +322,12 @@ typedef struct rrl_opts {
 size_t rrl_workspace_bytes(int B, int N, int M, int L);
 /* offsets[RRL_WS_FIELDS] in bytes from the workspace base */
 int rrl_workspace_layout(int B, int N, int M, int L, size_t *offsets);
+/* field `field` of workspace `kind` (0: RRL_WS_*, 1: RRL_WW_*) at shape (B, N, M, L, G): its lower-case name (static
+ * string), element type (RRL_T_U8 / RRL_T_I32 / RRL_T_F32 / RRL_T_I64) and extents; returns the number of extents
+ * (1..4), or RRL_E_ARG for an unknown kind / field.  field == -1: returns the number of fields of that kind.  Any output
+ * pointer may be NULL. */
+int rrl_workspace_field(int kind, int field, int B, int N, int M, int L, int G, const char **name, int *dtype,
+                        long long dims[4]);
 
 /* ---- fused entry points (what loss.py calls) ------------------------------------------ */
 

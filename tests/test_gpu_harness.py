@@ -731,3 +731,56 @@ def test_bench_two_ranks_sharing_one_gpu():
     assert s["scaling"] == "strong" and s["config"]["global_batch"] == 8 and s["extras"]["valid"] == 8.0
     assert s["extras"]["loss_sum"] > 0 and w["extras"]["loss_sum"] > 0
     print("two ranks on one GPU (gloo):", {k: round(v["ms_per_step"], 4) for k, v in out.items()})
+
+
+def test_named_views_sit_at_the_librarys_offsets(oracle):
+    """(B, N, M, L) = (2, 70, 130, 1030) -- N != M, a padded supergroup, two line tiles: every named view of a LossState and
+    a WideState starts at the library's offset of its field, has the dtype and shape the library's field table gives
+    (rrl_workspace_field) and lies inside the allocation; after a forward + backward at (1, 1, 5, 5) and at (1, 1, 9, 9)
+    the state's info, status and loss views hold what ops.intersection_loss returned (info as the oracle counts it; the
+    second sample has a line with more than 4 hits)."""
+    from rrl_hip import ops
+    B, N, M, Ll = 2, 70, 130, 1030
+    g = load_golden("loss_synth_s0.npz")
+    tri1, tri2 = np.stack([g["tri1"][:N]] * B), np.stack([g["tri2"][:M]] * B)
+    lines = np.stack([g["lines"][:Ll], g["lines"][-Ll:]])
+    tri2, lines = cu(tri2), cu(lines)
+
+    def views_ok(st, W, ws, offsets, nbytes):
+        assert len(offsets) == len(W.index)
+        assert ws.numel() == nbytes == W.layout(B, N, M, Ll)[0] and offsets == W.layout(B, N, M, Ll)[1]
+        for name, i in W.index.items():
+            v = getattr(st, name)
+            _, dtype, shape = W._field(i, st.dims)
+            assert v.data_ptr() == ws.data_ptr() + offsets[i] and v.dtype == dtype and tuple(v.shape) == shape, name
+            assert v.is_contiguous() and offsets[i] + v.numel() * v.element_size() <= nbytes, name
+        with pytest.raises(AttributeError):
+            st.no_such_field
+
+    def is_(v, dtype, *shape):
+        return v.dtype == dtype and tuple(v.shape) == shape
+
+    for rng, kind in (((1, 1, 5, 5), ops.LossState), ((1, 1, 9, 9), ops.WideState)):
+        p1 = cu(tri1, grad=True)
+        loss, info, status = ops.intersection_loss(p1, tri2, lines, rng)
+        st = ops.last_state()
+        assert type(st) is kind and st.dims == (B, N, M, Ll, B)
+        loss.sum().backward()
+        assert torch.isfinite(p1.grad).all() and p1.grad.abs().sum() > 0 and int(status[0]) == 0
+        for b in range(B):
+            ref = oracle.loss(tri1[b], g["tri2"][:M], lines[b].cpu().numpy(), rng)
+            assert info[b].tolist() == [ref["n_buckets"], ref["n_selected"], ref["n_values"], 0], (rng, b)
+            assert abs(loss[b].item() - float(ref["loss"])) <= 1e-5 * abs(float(ref["loss"])), (rng, b)
+        scan = st.scan if kind is ops.WideState else st
+        views_ok(scan, ops._WS, scan.ws, scan.offsets, scan.nbytes)
+        assert is_(scan.p0s1, torch.float32, B, 128, 4) and is_(scan.grp2, torch.float32, B, 3, 13, 4) and is_(scan.kj, torch.uint8, B, Ll)
+        assert is_(scan.blkcnt, torch.int32, B * 3) and is_(scan.bsum, torch.int64, B, 16, 2) and is_(scan.vals, torch.float32, B, 2048, 16)
+        assert is_(scan.gfix, torch.int64, B * (N + M) * 9 + B) and is_(scan.tri1t, torch.float32, B, N, 9)
+        if kind is ops.WideState:
+            views_ok(st, ops._WW, st.wws, st.woffsets, st.wnbytes)
+            assert is_(st.D, torch.float32, B, Ll, 8, 8) and is_(st.rec, torch.int32, 2 * B * Ll) and is_(st.bsum, torch.int64, B, 64, 2)
+        assert torch.equal(st.info, info) and torch.equal(scan.status, status) and torch.equal(st.loss, loss.detach())
+        assert torch.equal(st.nbuckets, info[:, 0]) and tuple(st.info.shape) == (B, 4) and tuple(st.med.shape) == (B,)
+        # ... and the same call again returns the same bits
+        loss2, info2, status2 = ops.intersection_loss(p1.detach(), tri2, lines, rng)
+        assert torch.equal(loss2, loss.detach()) and torch.equal(info2, info) and torch.equal(status2, status)

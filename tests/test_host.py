@@ -41,16 +41,80 @@ def test_abi_argument_errors(libpath):
     # workspace layout: 256-byte aligned, monotone, inside the reported size
     import ctypes as C
     from rrl_hip import ops
-    header = open(os.path.join(ROOT, "include", "rrl.h")).read()
-    enum = header[header.index("RRL_WS_STATUS = 0"):header.index("RRL_WS_FIELDS")]
-    n_fields = len(re.findall(r"RRL_WS_[A-Z0-9]+", enum))
-    assert n_fields == len(ops._WS_FIELDS) == 52  # python view table matches the C enum
+    names = table_names("WS")
+    assert [n.upper() for n in field_names(lib, 0)] == names  # the library describes the header's table, in order
+    assert [n.upper() for n in field_names(lib, 1)] == table_names("WW")
+    assert len(names) == len(ops._WS.index) == 52 and len(ops._WW.index) == 16
+    n_fields = len(names)
     offs = (C.c_size_t * n_fields)()
     assert lib.rrl_workspace_layout(8, 4096, 4096, 10000, offs) == 0
     total = lib.rrl_workspace_bytes(8, 4096, 4096, 10000)
     o = [int(v) for v in offs]
     assert o[0] == 0 and o == sorted(o) and all(v % 256 == 0 for v in o) and o[-1] < total
     assert total < 64 << 20
+    # rrl_workspace_field: unknown kind / field refused, every output optional
+    shape = (8, 4096, 4096, 10000, 8)
+    name, code, dims = C.c_char_p(), C.c_int(), (C.c_longlong * 4)()
+    for kind, field in ((2, 0), (-1, 0), (0, -2), (0, 52), (1, 16), (1, -2)):
+        assert lib.rrl_workspace_field(kind, field, *shape, C.byref(name), C.byref(code), dims) == -1, (kind, field)
+    assert lib.rrl_workspace_field(0, -1, *shape, None, None, None) == 52
+    assert lib.rrl_workspace_field(1, -1, *shape, None, None, None) == 16
+    assert lib.rrl_workspace_field(0, 6, *shape, None, None, None) == 3  # HIT1 [B][L][4]
+    assert lib.rrl_workspace_field(0, 6, *shape, C.byref(name), C.byref(code), dims) == 3
+    assert (name.value, code.value, list(dims)[:3]) == (b"hit1", 1, [8, 10000, 4])
+
+
+def table_names(kind):
+    """The field names of include/rrl.h's RRL_<kind>_TABLE, in order."""
+    header = open(os.path.join(ROOT, "include", "rrl.h")).read()
+    table = header[header.index(f"#define RRL_{kind}_TABLE(X)"):header.index(f"#define RRL_{kind}_ENUM_")]
+    return re.findall(r"\bX\(([A-Z0-9]+),", table)
+
+
+def field_names(lib, kind):
+    import ctypes as C
+    out = []
+    for i in range(lib.rrl_workspace_field(kind, -1, 0, 0, 0, 0, 0, None, None, None)):
+        name = C.c_char_p()
+        assert 1 <= lib.rrl_workspace_field(kind, i, 0, 0, 0, 0, 0, C.byref(name), None, None) <= 4
+        out.append(name.value.decode())
+    return out
+
+
+def test_layout_and_views_reproduce_the_recorded_fixture(libpath):
+    """tests/golden/ws_layout.json was recorded from the hand-written size and view tables that the field tables of
+    include/rrl.h replaced (its "generator" key holds the script): totals, offsets, and every view's name, dtype and shape
+    at G = 1 and G = B are reproduced exactly by the library and rrl_hip.ops at all twelve shapes, and every view ends at
+    or before the next field's offset.  (B = 0 has G = 0 only: G <= B.  A negative extent: the layout entries refuse, so
+    no state exists; the fixture pins the refusal and the clamped total.)"""
+    import ctypes as C
+    import json
+    from rrl_hip import RRLError, _lib, ops
+    lib = _lib.load()
+    fixture = json.load(open(os.path.join(ROOT, "tests", "golden", "ws_layout.json")))
+    assert len(fixture["cases"]) == 12
+    for case in fixture["cases"]:
+        shape = tuple(case["shape"])
+        for key, W in (("ws", ops._WS), ("wws", ops._WW)):
+            want, names = case[key], list(W.index)
+            offs = (C.c_size_t * len(names))()
+            assert getattr(lib, W.entry + "_layout")(*shape, offs) == want["layout_rc"], (shape, key)
+            total = int(getattr(lib, W.entry + "_bytes")(*shape))
+            assert total == want["total"], (shape, key)
+            if want["layout_rc"]:
+                with pytest.raises(RRLError):
+                    W.spec(shape + (1,), names[0])
+                continue
+            assert [int(o) for o in offs] == want["offsets"] == W.layout(*shape)[1] and W.layout(*shape)[0] == total, (shape, key)
+            ends = want["offsets"][1:] + [total]
+            groups = sorted({min(1, shape[0]), shape[0]})
+            assert sorted(k for k in want if k.startswith("views_G")) == sorted(f"views_G{G}" for G in groups)
+            for G in groups:
+                specs = [W.spec(shape + (G,), n) for n in names]
+                got = [[n, str(dt).split(".")[1], list(shp)] for n, (_, _, dt, shp) in zip(names, specs)]
+                assert got == want[f"views_G{G}"], (shape, key, G)
+                for i, (off, nbytes, _, _) in enumerate(specs):
+                    assert off == want["offsets"][i] and off + nbytes <= ends[i], (shape, key, G, names[i])
 
 
 def test_no_gpu_fails_loudly():

@@ -237,9 +237,7 @@ def call(lib, entry, over):
     if entry.startswith("rrl_registration_step") and min(v[k] for k in SHAPE) >= 0:
         # (dL/dR, dL/dt in the workspace's GACC field, the fused op's convention: the records launch clears them, no fill here)
         from rrl_hip import ops
-        off = (ctypes.c_size_t * len(ops._WS_FIELDS))()
-        assert lib.rrl_workspace_layout(*[v[k] for k in SHAPE], off) == 0
-        gacc = FAKE.value + off[[f[0] for f in ops._WS_FIELDS].index("gacc")]
+        gacc = FAKE.value + ops._WS.layout(*[v[k] for k in SHAPE])[1][ops._WS.index["gacc"]]
         v["gR"] = v["gR"] and ctypes.c_void_p(gacc)
         v["gt"] = v["gt"] and ctypes.c_void_p(gacc + 4 * 9 * v["B"])
     return getattr(lib, entry)(*[v[name] for name in ARGS[entry]], None)

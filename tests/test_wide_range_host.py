@@ -25,19 +25,20 @@ def test_wide_symbols_exported_and_enum_matches_view_table(lib):
     header = open(os.path.join(ROOT, "include", "rrl.h")).read()
     for name in WIDE_ENTRIES:
         assert hasattr(lib, name) and name in _lib.EXPORTS and re.search(r"\b" + name + r"\s*\(", header), name
-    enum = header[header.index("RRL_WW_STATUS = 0"):header.index("RRL_WW_FIELDS")]
-    names = re.findall(r"RRL_WW_([A-Z0-9]+)", enum)
-    assert [n.upper() for n, _, _ in ops._WW_FIELDS] == names
+    table = header[header.index("#define RRL_WW_TABLE(X)"):header.index("#define RRL_WW_ENUM_")]
+    names = re.findall(r"\bX\(([A-Z0-9]+),", table)
+    assert len(names) == 16 and [n.upper() for n in ops._WW.index] == names  # the library-derived view table, in order
     offs = (ctypes.c_size_t * len(names))()
     assert lib.rrl_wide_workspace_layout(8, 4096, 4096, 10000, offs) == 0
     total = lib.rrl_wide_workspace_bytes(8, 4096, 4096, 10000)
     o = [int(v) for v in offs]
     assert o[0] == 0 and o == sorted(o) and all(v % 256 == 0 for v in o) and o[-1] < total
-    # every field holds its view (the Python table's sizes fit between the C offsets)
-    B, N, M, L, G = 8, 4096, 4096, 10000, 8
-    for i, (_, dt, shape) in enumerate(ops._WW_FIELDS):
-        n = int(np.prod(shape(B, N, M, L, G))) * ops._ITEMSIZE[dt]
-        assert o[i] + n <= (o[i + 1] if i + 1 < len(o) else total)
+    # every field holds its view (the view table's sizes fit between the C offsets)
+    dims = (8, 4096, 4096, 10000, 8)
+    for i, name in enumerate(ops._WW.index):
+        off, nbytes, dtype, shape = ops._WW.spec(dims, name)
+        assert off == o[i] and nbytes == int(np.prod(shape)) * dtype.itemsize > 0
+        assert o[i] + nbytes <= (o[i + 1] if i + 1 < len(o) else total)
 
 
 def test_wide_entries_validate_on_the_host(lib):
