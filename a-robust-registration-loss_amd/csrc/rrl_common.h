@@ -90,7 +90,7 @@ __device__ __forceinline__ T dist_sq(float px, float py, float pz, T ux, T uy, T
 }
 
 // ---- agent-coherent (sc1) accesses for data handed from one workgroup to another INSIDE a launch (the chained step's build +
-//      scan launch, rrl_cull_scan.inc; cdna_hip_programming.md Guideline 16 R1): the producer's 16-byte stores are
+//      scan launch, rrl_cull_scan.h; cdna_hip_programming.md Guideline 16 R1): the producer's 16-byte stores are
 //      WRITE-THROUGH (no release fence: every storing wave drains, barrier, one relaxed ticket), the consumer's loads bypass
 //      its CU's L1 (no acquire fence).  16-byte accesses go through a buffer descriptor built from wave-uniform values
 //      (base: kernel argument + blockIdx-derived offset; bytes < 2^31), 4-byte ones are relaxed agent-scope atomics.

@@ -12,7 +12,8 @@
 //     triangles one node of 13 float4 = its own sphere, the spheres of its 4 groups of 16 and of
 //     their 8 halves of 8.  Every sphere bounds the P0s of its records: centre c, rho = max |P0-c|
 //     and the conservative squared radius R2 = ((rho + max thr)^2)(1 + 1e-4) + 1e-7.
-//   cull_scan_kernel: a workgroup = one slice of <= SPW supergroups of one cloud (records and
+//   cull_scan_kernel (rrl_cull_scan.h: one template for the two geometry variants Scan8 / Scan16, included once below):
+//   a workgroup = one slice of <= V::kSPW supergroups of one cloud (records and
 //   tree nodes staged in LDS once, ~10 KiB) x WPB wavefronts of 128 lines each.  Every wavefront
 //   walks the tree level by level through private LDS queues, with no workgroup synchronisation
 //   after the staging barrier:
@@ -915,39 +916,8 @@ static unsigned rrl_chain_spin_limit(void) {
     return (unsigned)v;
 }
 
-// The two geometry variants of the culled scan (rrl_cull_scan.inc): same source, two sets of compile-time knobs.
-namespace scan8 {
-#include "rrl_cull_scan.inc"
-}
-#undef SPW
-#undef SG_BITS
-#undef HF_BITS
-#undef WPB
-#undef LPW
-#undef ROWS
-#undef WCCAP
-#undef QA_CAP
-#undef QC_CAP
-#undef CULL_REGLINES
-// (experiments: the fat variant's knobs have names of their own -- -DSCAN16_QA_CAP=... -- the plain names configure scan8)
-#ifndef SCAN16_QA_CAP
-#define SCAN16_QA_CAP 384
-#endif
-#ifndef SCAN16_QC_CAP
-#define SCAN16_QC_CAP 256
-#endif
-#ifndef SCAN16_WCCAP
-#define SCAN16_WCCAP 128
-#endif
-namespace scan16 {
-#define SPW 16
-#define CULL_REGLINES 1
-#define QA_CAP SCAN16_QA_CAP
-#define QC_CAP SCAN16_QC_CAP
-#define WCCAP SCAN16_WCCAP
-#include "rrl_cull_scan.inc"
-}
-static_assert(scan8::kWPB == scan16::kWPB && scan8::kLPW == scan16::kLPW, "one line tiling for both variants");
+// The culled scan: its two geometry variants (Scan8, Scan16), its kernels and launch_variant<V>.
+#include "rrl_cull_scan.h"
 
 static CullGeom cull_geometry(const RrlCall &o, int clouds) {
     const int B = o.B, N = o.N, M = o.M, L = o.L;
@@ -955,27 +925,26 @@ static CullGeom cull_geometry(const RrlCall &o, int clouds) {
     // few lines or small clouds the slices get thinner, so that the launch still has ~1000
     // workgroups for the 256 CUs (measured with tools/attic/geom_sweep.sh: thinner slices cost little,
     // fewer wavefronts per workgroup cost more -- they are only reduced as a last resort)
-    constexpr int WPB_ = scan8::kWPB, LPW_ = scan8::kLPW;
     const int nmax = clouds == 2 && M > N ? M : N;
     const int nsgmax = (nmax + SGT - 1) / SGT;
-    const int lw = (L + LPW_ - 1) / LPW_;  // wavefronts' worth of lines
-    int waves = lw < WPB_ ? lw : WPB_, spw = scan8::kSPW;
+    const int lw = (L + LPW - 1) / LPW;  // wavefronts' worth of lines
+    int waves = lw < WPB ? lw : WPB, spw = Scan8::kSPW;
     auto wgs = [&]() { return (long)clouds * B * ((lw + waves - 1) / waves) * ((nsgmax + spw - 1) / spw); };
-    // FAT slices (scan16: 16 supergroups per workgroup, lines in registers, 4 workgroups per CU) as soon as the grid stays
+    // FAT slices (Scan16: 16 supergroups per workgroup, lines in registers, 4 workgroups per CU) as soon as the grid stays
     // deep with them -- measured (tools/attic/spw_exp2.sh, profiles/r05_experiments.txt): >= 960 fat workgroups win 6 .. 20 %
     // (B = 12 .. 64 at C2's shape, N = 8192, L = 20000), <= 640 lose 7 .. 55 % (C2 itself, C4, the demo).  RRL_CULL_FAT=0 / 1 forces.
-    bool fat = (long)clouds * B * ((lw + waves - 1) / waves) * ((nsgmax + 15) / 16) >= 896 && lw >= WPB_;
+    bool fat = (long)clouds * B * ((lw + waves - 1) / waves) * ((nsgmax + 15) / 16) >= 896 && lw >= WPB;
     if (const char *e = getenv("RRL_CULL_FAT")) fat = e[0] == '1' ? (nsgmax > 8) : (e[0] == '0' ? false : fat);
-    if (fat) spw = scan16::kSPW;
+    if (fat) spw = Scan16::kSPW;
     while (!fat && wgs() < 768 && spw > 1) spw >>= 1;
     // (a riding Chamfer walk needs the scan's full 512-lane workgroups -- and brings workgroups of its own: no thinning then)
-    const bool may_ride = o.rider && !o.counters && (clouds == 2 || o.tar_ws) && lw >= WPB_ && B <= 32767 && N > 0 && M > 0;
+    const bool may_ride = o.rider && !o.counters && (clouds == 2 || o.tar_ws) && lw >= WPB && B <= 32767 && N > 0 && M > 0;
     while (!fat && !may_ride && wgs() < 256 && waves > 2) waves >>= 1;
 #ifdef RRL_EXPERIMENT  // (experimental builds only, RRL_HIPCC_FLAGS=-DRRL_EXPERIMENT -> lib_exp: geometry sweeps)
     if (const char *e = getenv("RRL_CULL_GEOM")) {  // "waves,spw" (spw > 8: the fat variant)
         int w_ = 0, s_ = 0;
-        if (sscanf(e, "%d,%d", &w_, &s_) == 2 && w_ >= 1 && w_ <= WPB_ && s_ >= 1 && s_ <= scan16::kSPW) {
-            waves = w_ < lw ? w_ : lw; spw = s_; fat = s_ > scan8::kSPW;
+        if (sscanf(e, "%d,%d", &w_, &s_) == 2 && w_ >= 1 && w_ <= WPB && s_ >= 1 && s_ <= Scan16::kSPW) {
+            waves = w_ < lw ? w_ : lw; spw = s_; fat = s_ > Scan8::kSPW;
         }
     }
 #endif
@@ -997,7 +966,7 @@ int rrl_cull_scan_can_fuse(const RrlCall &o) {
     if (o.ragged()) return 0;
     if (const char *e = getenv("RRL_CHAIN")) if (e[0] == '0') return 0;  // (A/B runs)
     const CullGeom g = cull_geometry(o, 2);
-    if (g.waves != scan8::kWPB) return 0;
+    if (g.waves != WPB) return 0;
     // Where the ONE launch pays (measured, profiles/r06_experiments.txt 2; us per step chained / plain): C2 45.8 / 49.8, B = 4
     // 40.9 / 42.9, B = 12 .. 32 at C2's shape 59.0 / 62.7 .. 110.8 / 116.5, the demo's shape 36.1 / 38.1, C4's 46.2 / 49.4 --
     // and where it does not: B = 64 (5632 workgroups, ten generations deep: the 512 records workgroups are a small share and
@@ -1009,7 +978,7 @@ int rrl_cull_scan_can_fuse(const RrlCall &o) {
     // that wait hides behind target-cloud work: clouds up to 4096 triangles (<= 8 records pieces per sample) on any grid
     // measured, larger clouds only on grids several generations deep.
     const int spw = g.spw, nsg1 = (N + SGT - 1) / SGT, nsg2 = (M + SGT - 1) / SGT;
-    const int nrec_b = (int)(((size_t)nsg1 * SGT + 64 * scan8::kWPB - 1) / (64 * scan8::kWPB));
+    const int nrec_b = (int)(((size_t)nsg1 * SGT + 64 * WPB - 1) / (64 * WPB));
     const long total = (long)B * (nrec_b + (long)g.tiles * ((nsg1 + spw - 1) / spw + (nsg2 + spw - 1) / spw));
     if (g.fat && total > 4000) return 0;
     if (nrec_b > 8 && total < 2048) return 0;
@@ -1018,7 +987,7 @@ int rrl_cull_scan_can_fuse(const RrlCall &o) {
 
 int rrl_launch_cull_scan(const RrlCall &o, const float *line) {
     const CullGeom g = cull_geometry(o, o.plan.clouds);
-    if (o.plan.fused_build && (o.plan.clouds != 2 || g.waves != scan8::kWPB)) return RRL_E_ARG;  // (rrl_cull_scan_can_fuse said otherwise)
+    if (o.plan.fused_build && (o.plan.clouds != 2 || g.waves != WPB)) return RRL_E_ARG;  // (rrl_cull_scan_can_fuse said otherwise)
     if (!o.plan.lmax_ready && !o.plan.fused_build)  // the triangles were prepared without the lines: their partial maxima first (a tiny launch)
         hipLaunchKernelGGL(line_max_kernel, dim3(LMAX_CHUNKS, (unsigned)o.B), dim3(REC_BLK), 0, o.s, line, o.L,
                            (float2 *)o.at<RRL_WS_LMAX>(), o.problems, o.nlines);
@@ -1028,7 +997,7 @@ int rrl_launch_cull_scan(const RrlCall &o, const float *line) {
     // is held for the SLOWEST of a workgroup's eight wavefronts either way (16.5 us per item against a mean wavefront
     // lifetime of 12.4), so queueing the items removed no waiting, and the item barriers added some;
     // profiles/r03_scan_experiments.txt.)
-    return g.fat ? scan16::launch_variant(o, line, g) : scan8::launch_variant(o, line, g);
+    return g.fat ? launch_variant<Scan16>(o, line, g) : launch_variant<Scan8>(o, line, g);
 }
 // Executed-work counters (profiling; include/rrl.h rrl_scan_counters): while a buffer is set,
 // culled scans launch the COUNT instantiation and add to it.

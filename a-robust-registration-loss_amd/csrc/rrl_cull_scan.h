@@ -1,22 +1,16 @@
-// rrl_cull_scan.inc -- the culled scan (cull_scan_kernel, cull_scan_chamfer_kernel) and the launch of ONE geometry variant.
-// Included TWICE by rrl_cull.hip, inside two namespaces with two sets of the compile-time knobs below (round 5):
-//   scan8   SPW = 8,  the wavefront's lines in LDS            -- 47 KB of LDS, 3 workgroups per CU: the latency-bound grids
-//   scan16  SPW = 16, the lines in registers (CULL_REGLINES)   -- 33 KB, 4 workgroups per CU: half as many workgroups with
+// rrl_cull_scan.h -- the culled scan (cull_scan_kernel, cull_scan_chamfer_kernel, cull_scan_build_kernel) and its launch.
+// Included ONCE by rrl_cull.hip.  The scan has two geometry variants (round 5), the trait structs Scan8 and Scan16 below;
+// everything that depends on a variant's knobs takes the trait as its template parameter V:
+//   Scan8   kSPW = 8,  the wavefront's lines in LDS             -- 47 KB of LDS, 3 workgroups per CU: the latency-bound grids
+//   Scan16  kSPW = 16, the lines in registers (kRegLines)       -- 34 KB, 4 workgroups per CU: half as many workgroups with
 //           twice the slice each -- one prologue per 16 supergroups instead of two, more wavefronts resident; pays as soon
 //           as the grid is several generations deep (B = 64 at C2's shape: 152 -> 121 us; B = 8: 26.4 -> 28.2, so not there)
 // rrl_launch_cull_scan (rrl_cull.hip) picks the variant per call from the grid size.  Same arithmetic, same labels.
+// Experiment builds override the knobs with -D; every override is read HERE and nowhere else: SPW, WCCAP, QA_CAP, QC_CAP
+// (the lean variant), SCAN16_QA_CAP, SCAN16_QC_CAP, SCAN16_WCCAP (the fat one), WPB, ROWS (both).
+#pragma once
 #ifndef SPW
 #define SPW 8      // supergroups per slice (<= 16: SG_BITS); staged once per workgroup
-#endif
-#define SG_BITS 4              // queue entries: line << SG_BITS | supergroup of the slice,
-#define HF_BITS (SG_BITS + 3)  //                line << HF_BITS | half of the slice (7 + 7 bits: 16-bit entries)
-static_assert(SPW <= (1 << SG_BITS), "slot bits of the queue entries");
-#ifndef WPB
-#define WPB 8      // wavefronts per workgroup: same slice, LPW lines each
-#endif
-#define LPW 128    // lines per wavefront (two per lane in level A)
-#ifndef ROWS
-#define ROWS 17    // float4 per staged group row: 16 records + 16 bytes of padding (bank spread)
 #endif
 #ifndef WCCAP
 #define WCCAP 128  // parked point-0 candidates per wave
@@ -30,27 +24,55 @@ static_assert(SPW <= (1 << SG_BITS), "slot bits of the queue entries");
 #ifndef QC_CAP
 #define QC_CAP 256
 #endif
-
-#ifndef CULL_REGLINES
-#define CULL_REGLINES 0  // 1 (experiment, round 4; exact on the whole suite, NOT shipped): the wavefront's 128 lines stay in
-#endif                   // REGISTERS (two per lane) and travel between lanes by ds_bpermute instead of 24 KB of LDS per
-//                          workgroup -> 22.6 KB, 62 VGPRs, 4 workgroups = 32 wavefronts per compute unit instead of 3 / 24.
-//                          Measured slower: 28.3 us against 26.8-27.4 at C2, 13.9 against 12.9 at C1, even at B = 64 --
-//                          twelve cross-lane reads per pass cost more than the extra residency returns; the launch is
-//                          paced by each wavefront's own chain of dependent steps, not by the number of resident ones.
-constexpr int kSPW = SPW, kWPB = WPB, kLPW = LPW;  // (for the launcher: the macros are redefined per variant)
+#ifndef SCAN16_QA_CAP
+#define SCAN16_QA_CAP 384
+#endif
+#ifndef SCAN16_QC_CAP
+#define SCAN16_QC_CAP 256
+#endif
+#ifndef SCAN16_WCCAP
+#define SCAN16_WCCAP 128
+#endif
+struct Scan8 {
+    static constexpr int kSPW = SPW, kQaCap = QA_CAP, kQcCap = QC_CAP, kWcCap = WCCAP;
+    static constexpr bool kRegLines = false;
+};
+// kRegLines: the wavefront's 128 lines stay in REGISTERS (two per lane) and travel between lanes by ds_bpermute instead of
+// 24 KB of LDS per workgroup -> 62 VGPRs, 4 workgroups = 32 wavefronts per compute unit instead of 3 / 24.  With 8
+// supergroups per slice that measured slower (round 4: 28.3 us against 26.8-27.4 at C2, 13.9 against 12.9 at C1 -- twelve
+// cross-lane reads per pass cost more than the extra residency returns); it pays with the fat slice.
+struct Scan16 {
+    static constexpr int kSPW = 16, kQaCap = SCAN16_QA_CAP, kQcCap = SCAN16_QC_CAP, kWcCap = SCAN16_WCCAP;
+    static constexpr bool kRegLines = true;
+};
+// common to both variants (a -DWPB=n / -DROWS=n of an experiment build stands in for the constant itself)
+#ifndef WPB
+constexpr int WPB = 8;     // wavefronts per workgroup: same slice, LPW lines each
+#endif
+#ifndef ROWS
+constexpr int ROWS = 17;   // float4 per staged group row: 16 records + 16 bytes of padding (bank spread)
+#endif
+constexpr int LPW = 128;   // lines per wavefront (two per lane in level A)
+constexpr int SG_BITS = 4;            // queue entries: line << SG_BITS | supergroup of the slice,
+constexpr int HF_BITS = SG_BITS + 3;  //                line << HF_BITS | half of the slice (7 + 7 bits: 16-bit entries)
+static_assert(Scan8::kSPW <= (1 << SG_BITS) && Scan16::kSPW <= (1 << SG_BITS), "slot bits of the queue entries");
 static_assert(LPW <= (1 << (32 - CAND_POS_BITS)), "line-in-wave bits of the candidates (rrl_tree.h CAND_POS_BITS)");
 
-struct WaveCtx {
-#if CULL_REGLINES
+// the wavefront's 128 lines during the walk: in registers, or in LDS
+template <bool REGLINES> struct WaveLines;
+template <> struct WaveLines<true> {
     float v0[6], v1[6];           // this lane's two lines (dir, x0): line `lane` and line `64 + lane` of the wavefront
-#else
+};
+template <> struct WaveLines<false> {
     const float2 *lr;             // this wave's lines in LDS as they lie in memory: 3 float2 per line (dir.xy | dir.z x0.x | x0.yz)
-#endif
+};
+template <class V>
+struct WaveCtx {
+    WaveLines<V::kRegLines> ln;
     const float4 *recs;           // LDS: staged records of the slice, [group][ROWS]
     const float4 *nodes;          // LDS: staged tree nodes of the slice, [supergroup][NODE]
     unsigned short *qa, *qc;      // LDS queues: line << SG_BITS | sg, line << HF_BITS | half (slice-local)
-    unsigned *cands;              // LDS [WCCAP]
+    unsigned *cands;              // LDS [V::kWcCap]
     const int32_t *idx;           // sorted position -> original triangle index
     const float *ptri;            // prepared triangles: rows in original order, or -- psorted -- at their sorted positions
     __amdgpu_buffer_rsrc_t ptri_rs;  // SC1 (the chained step's launch): the same rows through a buffer descriptor, for sc1 loads
@@ -76,12 +98,11 @@ __device__ __forceinline__ LineRow line_row(const float2 *lr, int ll) {
     const float2 a = p[0], b = p[1], c = p[2];
     return {make_float4(a.x, a.y, b.x, b.y), c};
 }
-#if CULL_REGLINES
 // Line ll (0 .. 127) of the wavefront from the registers of the lane that holds it: EVERY lane of the wavefront must
 // call (a ds_bpermute reads the registers of active lanes only); lanes without work pass any ll.  Twelve cross-lane
 // reads + six selects instead of three 8-byte LDS reads -- and 24 KB of LDS per workgroup less: 22.3 KB instead of 47.2,
 // so the wavefront limit (8 per SIMD), not LDS, bounds the residency: 4 workgroups per compute unit instead of 3.
-__device__ __forceinline__ LineRow line_get(const WaveCtx &c, int ll) {
+__device__ __forceinline__ LineRow line_get(const WaveLines<true> &c, int ll) {
     const int src = (ll & 63) << 2;
     const bool hi = ll >= 64;
     float r[6];
@@ -93,14 +114,13 @@ __device__ __forceinline__ LineRow line_get(const WaveCtx &c, int ll) {
     }
     return {make_float4(r[0], r[1], r[2], r[3]), make_float2(r[4], r[5])};
 }
-#endif
 
 // cand = line_in_wave << CAND_POS_BITS | sorted triangle position: a triangle whose point 0 passed the conservative
 // prefilter of level D.  The reference's own arithmetic (dist_sq, bit-identical to the strict scan) decides
 // on all three points here.
 // SC1: the rows may have been written by another workgroup of THIS launch (write-through): loads that bypass the CU's L1.
-template <bool SC1 = false>
-__device__ __forceinline__ void resolve_candidate(const WaveCtx &c, unsigned cand, const LineRow &lrw) {
+template <class V, bool SC1 = false>
+__device__ __forceinline__ void resolve_candidate(const WaveCtx<V> &c, unsigned cand, const LineRow &lrw) {
     const int ll = cand >> CAND_POS_BITS, spos = cand & CAND_POS_MASK;
     const float4 la = lrw.la;
     const float2 lb = lrw.lb;
@@ -191,25 +211,28 @@ __device__ __forceinline__ float sphere_margin(const float4 nd, const float4 la,
     return fmaf(dot, dot, fmaf(-q, 0.999996f, nd.w));
 }
 
-template <bool COUNT, bool SC1 = false>
-__device__ __forceinline__ void flush_cands(WaveCtx &c) {
+template <class V, bool COUNT, bool SC1 = false>
+__device__ __forceinline__ void flush_cands(WaveCtx<V> &c) {
 #ifdef CULL_NO_RESOLVE
     c.ncand = 0;
     return;
 #endif
     wave_lds_fence();
-    const int nc = min(c.ncand, WCCAP);
-    if constexpr (COUNT) c.tcand += (unsigned)c.ncand;  // entries past WCCAP were resolved inline: counted here too
-#if CULL_REGLINES
-    for (int i0 = 0; i0 < nc; i0 += 64) {  // uniform trip count: every lane fetches (line_get), the live ones resolve
-        const int i = i0 + c.lane;
-        const unsigned cand = i < nc ? c.cands[i] : 0u;
-        const LineRow lrw = line_get(c, (int)(cand >> CAND_POS_BITS));
-        if (i < nc) resolve_candidate<SC1>(c, cand, lrw);
+    const int nc = min(c.ncand, V::kWcCap);
+    if constexpr (COUNT) c.tcand += (unsigned)c.ncand;  // entries past kWcCap were resolved inline: counted here too
+    if constexpr (V::kRegLines) {
+        for (int i0 = 0; i0 < nc; i0 += 64) {  // uniform trip count: every lane fetches (line_get), the live ones resolve
+            const int i = i0 + c.lane;
+            const unsigned cand = i < nc ? c.cands[i] : 0u;
+            const LineRow lrw = line_get(c.ln, (int)(cand >> CAND_POS_BITS));
+            if (i < nc) resolve_candidate<V, SC1>(c, cand, lrw);
+        }
+    } else {
+        for (int i = c.lane; i < nc; i += 64) {
+            const unsigned cand = c.cands[i];
+            resolve_candidate<V, SC1>(c, cand, line_row(c.ln.lr, (int)(cand >> CAND_POS_BITS)));
+        }
     }
-#else
-    for (int i = c.lane; i < nc; i += 64) { const unsigned cand = c.cands[i]; resolve_candidate<SC1>(c, cand, line_row(c.lr, (int)(cand >> CAND_POS_BITS))); }
-#endif
     c.ncand = 0;
 }
 
@@ -220,8 +243,8 @@ __device__ __forceinline__ void flush_cands(WaveCtx &c) {
 // (see "Point-0 prefilter" above): 10 operations and one v_alignbit per record instead of the 16 + 3 of
 // the reference's unfused arithmetic.  e < 0 (sign bit) parks the triangle as a candidate; the exact test of
 // all three points happens there (resolve_candidate), on ~3 % of the records.
-template <bool COUNT, bool SC1 = false>
-__device__ __forceinline__ void proc_c(WaveCtx &c, bool all) {
+template <class V, bool COUNT, bool SC1 = false>
+__device__ __forceinline__ void proc_c(WaveCtx<V> &c, bool all) {
 #ifdef CULL_STOP_C  // timing experiments only (tools/attic/knob_sweep.sh): the level is formed but not run
     c.nc = 0;
     return;
@@ -233,17 +256,19 @@ __device__ __forceinline__ void proc_c(WaveCtx &c, bool all) {
         wave_lds_fence();
         uint32_t passbits = 0;
         unsigned lh = 0;  // line << CAND_POS_BITS | first sorted position of the half
-#if CULL_REGLINES
-        const unsigned e = c.lane < take ? c.qc[base + c.lane] : 0u;
-        const int ll = e >> HF_BITS, h = e & ((1 << HF_BITS) - 1);
-        const LineRow lrw = line_get(c, ll);  // (every lane)
+        // (registers: every lane takes part in line_get, so entry and line are fetched in front of the branch; LDS: behind it)
+        unsigned e = 0u;
+        LineRow lrw;
+        if constexpr (V::kRegLines) {
+            e = c.lane < take ? c.qc[base + c.lane] : 0u;
+            lrw = line_get(c.ln, (int)(e >> HF_BITS));
+        }
         if (c.lane < take) {
-#else
-        if (c.lane < take) {
-            const unsigned e = c.qc[base + c.lane];
+            if constexpr (!V::kRegLines) {
+                e = c.qc[base + c.lane];
+                lrw = line_row(c.ln.lr, (int)(e >> HF_BITS));
+            }
             const int ll = e >> HF_BITS, h = e & ((1 << HF_BITS) - 1);
-            const LineRow lrw = line_row(c.lr, ll);
-#endif
             const float4 la = lrw.la;
             const float2 lb = lrw.lb;
             const float4 *row = c.recs + (h >> 1) * ROWS + (h & 1) * 8;
@@ -259,9 +284,8 @@ __device__ __forceinline__ void proc_c(WaveCtx &c, bool all) {
             lh = ((unsigned)ll << CAND_POS_BITS) | (unsigned)(c.pos0 + h * 8);
         }
         while (__any(passbits != 0)) {
-#if CULL_REGLINES
-            if (c.ncand > WCCAP - 64) flush_cands<COUNT, SC1>(c);  // uniform: room for this round's <= 64 candidates (no inline resolve)
-#endif
+            if constexpr (V::kRegLines)  // uniform: room for this round's <= 64 candidates (no inline resolve)
+                if (c.ncand > V::kWcCap - 64) flush_cands<V, COUNT, SC1>(c);
             const bool has = passbits != 0;
             const unsigned long long m = __ballot(has);
             const int t = has ? __ffs(passbits) - 1 : 0;
@@ -269,16 +293,13 @@ __device__ __forceinline__ void proc_c(WaveCtx &c, bool all) {
             const int pos = c.ncand + lane_rank(m);
             const unsigned cand = lh + (unsigned)t;
             if (has) {
-#if CULL_REGLINES
-                c.cands[pos] = cand;
-#else
-                if (pos < WCCAP) c.cands[pos] = cand;
-                else resolve_candidate<SC1>(c, cand, line_row(c.lr, (int)(cand >> CAND_POS_BITS)));
-#endif
+                if constexpr (V::kRegLines) c.cands[pos] = cand;
+                else if (pos < V::kWcCap) c.cands[pos] = cand;
+                else resolve_candidate<V, SC1>(c, cand, line_row(c.ln.lr, (int)(cand >> CAND_POS_BITS)));
             }
             c.ncand += __popcll(m);
         }
-        if (c.ncand > WCCAP - 64) flush_cands<COUNT, SC1>(c);  // uniform: keep room for the next pass
+        if (c.ncand > V::kWcCap - 64) flush_cands<V, COUNT, SC1>(c);  // uniform: keep room for the next pass
     }
 }
 
@@ -286,20 +307,20 @@ __device__ __forceinline__ void proc_c(WaveCtx &c, bool all) {
 // 8 sg) go to queue C.  Usual case: every lane writes its own run of entries behind an exclusive prefix of the
 // counts (one DPP scan instead of eight ballot / rank rounds).  Too many for the queue (dense hits): half by half
 // with drains in between.
-template <bool COUNT, bool SC1 = false>
-__device__ __forceinline__ void push_halves(WaveCtx &c, unsigned pass, unsigned e2) {
+template <class V, bool COUNT, bool SC1 = false>
+__device__ __forceinline__ void push_halves(WaveCtx<V> &c, unsigned pass, unsigned e2) {
     const int cnt = __popc(pass);
     const int incl = wave_incl_scan(cnt);
     const int total = __builtin_amdgcn_readlane(incl, 63);
     if (total == 0) return;  // uniform
     if constexpr (COUNT) c.tc += (unsigned)total;
-    if (c.nc + total > QC_CAP) proc_c<COUNT, SC1>(c, false);  // leaves < 64
-    if (c.nc + total > QC_CAP) {
+    if (c.nc + total > V::kQcCap) proc_c<V, COUNT, SC1>(c, false);  // leaves < 64
+    if (c.nc + total > V::kQcCap) {
         for (int k = 0; k < 8; ++k) {  // uniform
             const bool p = (pass >> k) & 1u;
             const unsigned long long m = __ballot(p);
             if (m == 0ull) continue;
-            if (c.nc > QC_CAP - 64) proc_c<COUNT, SC1>(c, false);
+            if (c.nc > V::kQcCap - 64) proc_c<V, COUNT, SC1>(c, false);
             if (p) c.qc[c.nc + lane_rank(m)] = (unsigned short)(e2 | (unsigned)k);
             c.nc += __popcll(m);
         }
@@ -317,8 +338,8 @@ __device__ __forceinline__ void push_halves(WaveCtx &c, unsigned pass, unsigned 
 // level B: pops (line, supergroup) pairs, one per lane, and tests the supergroup's EIGHT half spheres directly
 // (round 3: the group level in between -- 4 group tests, then 2 half tests per passing group, 9 tests on average
 // -- cost a whole round of queue passes per wavefront for one test less)
-template <bool COUNT, bool SC1 = false>
-__device__ __forceinline__ void proc_a(WaveCtx &c, bool all) {
+template <class V, bool COUNT, bool SC1 = false>
+__device__ __forceinline__ void proc_a(WaveCtx<V> &c, bool all) {
 #ifdef CULL_STOP_A
     c.na = 0;
     return;
@@ -330,17 +351,18 @@ __device__ __forceinline__ void proc_a(WaveCtx &c, bool all) {
         wave_lds_fence();
         unsigned fail = 0xffu;  // bit k: half k cannot be reached (idle lanes: none can)
         unsigned e2 = 0;
-#if CULL_REGLINES
-        const unsigned e = c.lane < take ? c.qa[base + c.lane] : 0u;
-        const int ll = e >> SG_BITS, sg = e & ((1 << SG_BITS) - 1);
-        const LineRow lrw = line_get(c, ll);  // (every lane)
+        unsigned e = 0u;  // (fetched as in proc_c)
+        LineRow lrw;
+        if constexpr (V::kRegLines) {
+            e = c.lane < take ? c.qa[base + c.lane] : 0u;
+            lrw = line_get(c.ln, (int)(e >> SG_BITS));
+        }
         if (c.lane < take) {
-#else
-        if (c.lane < take) {
-            const unsigned e = c.qa[base + c.lane];
+            if constexpr (!V::kRegLines) {
+                e = c.qa[base + c.lane];
+                lrw = line_row(c.ln.lr, (int)(e >> SG_BITS));
+            }
             const int ll = e >> SG_BITS, sg = e & ((1 << SG_BITS) - 1);
-            const LineRow lrw = line_row(c.lr, ll);
-#endif
             const float4 la = lrw.la;
             const float2 lb = lrw.lb;
             const float4 *nd = c.nodes + sg * NODE + 5;
@@ -350,7 +372,7 @@ __device__ __forceinline__ void proc_a(WaveCtx &c, bool all) {
                 fail = __builtin_amdgcn_alignbit(fail, __float_as_uint(sphere_margin(nd[k], la, lb)), 31);
             e2 = ((unsigned)ll << HF_BITS) | (unsigned)(8 * sg);
         }
-        push_halves<COUNT, SC1>(c, ~fail & 0xffu, e2);
+        push_halves<V, COUNT, SC1>(c, ~fail & 0xffu, e2);
     }
 }
 
@@ -390,15 +412,15 @@ __device__ __forceinline__ void strict_slice(const float *ptri, const int32_t *i
 // The culled walk of one wavefront over the STAGED slice (node_lds / ctx.recs): level A on the lane's two lines,
 // level B, level D, candidate resolution.  stamps (COUNT): wall clock after level A, after level B's drain, after
 // level D's drain.
-template <bool COUNT, bool SC1 = false>
-__device__ __forceinline__ void cull_walk(WaveCtx &ctx, const float4 *node_lds, int nsl, int lane, bool live0, bool live1,
+template <class V, bool COUNT, bool SC1 = false>
+__device__ __forceinline__ void cull_walk(WaveCtx<V> &ctx, const float4 *node_lds, int nsl, int lane, bool live0, bool live1,
                                           v2f ux, v2f uy, v2f uz, v2f ox, v2f oy, v2f oz, unsigned long long *stamps) {
     // ---- level A: conservative sphere test of every supergroup of the slice against the lane's two lines
     //      (packed fp32; the staged supergroup nodes come as wave-uniform LDS reads).  No queue traffic inside the
     //      loop: the outcome is one bit per (line, supergroup) in two lane-private masks (sign bits, v_alignbit).
     unsigned f0m = 0u, f1m = 0u;  // bit s: supergroup s cannot be reached by line 0 / line 1 of the lane
 #pragma unroll
-    for (int s = SPW - 1; s >= 0; --s) {  // supergroup s ends up in bit s
+    for (int s = V::kSPW - 1; s >= 0; --s) {  // supergroup s ends up in bit s
         float4 nd = node_lds[(s < nsl ? s : 0) * NODE];
         if (s >= nsl) nd.w = -INFINITY;  // uniform: not part of this slice
         const v2f ax = nd.x - ox, ay = nd.y - oy, az = nd.z - oz;
@@ -409,12 +431,12 @@ __device__ __forceinline__ void cull_walk(WaveCtx &ctx, const float4 *node_lds, 
         f0m = __builtin_amdgcn_alignbit(f0m, __float_as_uint(mg.x), 31);
         f1m = __builtin_amdgcn_alignbit(f1m, __float_as_uint(mg.y), 31);
     }
-    unsigned m0 = live0 ? (~f0m & ((1u << SPW) - 1u)) : 0u, m1 = live1 ? (~f1m & ((1u << SPW) - 1u)) : 0u;
+    unsigned m0 = live0 ? (~f0m & ((1u << V::kSPW) - 1u)) : 0u, m1 = live1 ? (~f1m & ((1u << V::kSPW) - 1u)) : 0u;
     {
         const int cnt_ = __popc(m0) + __popc(m1);
         const int incl = wave_incl_scan(cnt_);
         const int total = __builtin_amdgcn_readlane(incl, 63);
-        if (total <= QA_CAP) {  // the usual case (~128): every lane writes its own run of entries
+        if (total <= V::kQaCap) {  // the usual case (~128): every lane writes its own run of entries
             int at = incl - cnt_;
             while (m0) {
                 const int s = __ffs(m0) - 1;
@@ -432,7 +454,7 @@ __device__ __forceinline__ void cull_walk(WaveCtx &ctx, const float4 *node_lds, 
                 const bool p0 = (m0 >> s) & 1u, p1 = (m1 >> s) & 1u;
                 const unsigned long long b0 = __ballot(p0), b1 = __ballot(p1);
                 if ((b0 | b1) == 0ull) continue;
-                if (ctx.na > QA_CAP - 128) proc_a<COUNT, SC1>(ctx, false);
+                if (ctx.na > V::kQaCap - 128) proc_a<V, COUNT, SC1>(ctx, false);
                 const int c0 = __popcll(b0);
                 if (p0) ctx.qa[ctx.na + lane_rank(b0)] = (unsigned short)((lane << SG_BITS) | s);
                 if (p1) ctx.qa[ctx.na + c0 + lane_rank(b1)] = (unsigned short)(((64 + lane) << SG_BITS) | s);
@@ -441,11 +463,11 @@ __device__ __forceinline__ void cull_walk(WaveCtx &ctx, const float4 *node_lds, 
         }
     }
     if constexpr (COUNT) stamps[0] = wall_clock64();
-    proc_a<COUNT, SC1>(ctx, true);
+    proc_a<V, COUNT, SC1>(ctx, true);
     if constexpr (COUNT) stamps[1] = wall_clock64();
-    proc_c<COUNT, SC1>(ctx, true);
+    proc_c<V, COUNT, SC1>(ctx, true);
     if constexpr (COUNT) stamps[2] = wall_clock64();
-    flush_cands<COUNT, SC1>(ctx);
+    flush_cands<V, COUNT, SC1>(ctx);
 }
 
 // COUNT = true: the same kernel with executed-work counters -- launched instead of the plain one while
@@ -460,15 +482,36 @@ __device__ __forceinline__ void cull_walk(WaveCtx &ctx, const float4 *node_lds, 
 //           slowest wavefront: tools/scan_tail.py prints the spread), [10..14] phase stamps
 // The scan's LDS (47 KiB per 8-wavefront workgroup) as ONE object: cull_scan_chamfer_kernel overlays it with the Chamfer
 // walk's (rrl_chamfer_walk.h ChamLds).
+template <class V>
 struct CullLds {
-#if !CULL_REGLINES
-    __attribute__((aligned(16))) float2 line_lds[WPB][LPW * 3];    // 24 KiB: raw 24-byte line rows
-#endif
-    __attribute__((aligned(16))) float4 rec_lds[SPW * SGG * ROWS]; //  8.5 KiB
-    __attribute__((aligned(16))) float4 node_lds[SPW * NODE];      //  1.6 KiB
-    __attribute__((aligned(16))) unsigned short qa_lds[WPB][QA_CAP];
-    unsigned short qc_lds[WPB][QC_CAP];
-    __attribute__((aligned(16))) unsigned cands_lds[WPB][WCCAP];
+    __attribute__((aligned(16))) float2 line_lds[V::kRegLines ? 0 : WPB][LPW * 3];  // 24 KiB: raw 24-byte line rows (none: lines in registers)
+    __attribute__((aligned(16))) float4 rec_lds[V::kSPW * SGG * ROWS];  //  8.5 KiB (kSPW = 8)
+    __attribute__((aligned(16))) float4 node_lds[V::kSPW * NODE];       //  1.6 KiB
+    __attribute__((aligned(16))) unsigned short qa_lds[WPB][V::kQaCap];
+    unsigned short qc_lds[WPB][V::kQcCap];
+    __attribute__((aligned(16))) unsigned cands_lds[WPB][V::kWcCap];
+};
+
+// What a scan workgroup reads: the kernel arguments of cull_scan_chamfer_kernel (CullKArgs; its gx, gy are that launch's own grid
+// decode) and, beyond them, what only some launches have (ScanArgs).  cull_scan_body takes ONE of these.
+struct CullKArgs {
+    const float *ptri1, *ptri2;
+    const float4 *p0s1, *p0s2;
+    const int32_t *idx1, *idx2;
+    const float4 *tree1, *tree2;
+    const float *line;
+    int32_t *count1, *hit1, *count2, *hit2, *status;
+    uint32_t *pmax;
+    const float *del1, *del2;
+    const float2 *lmax;
+    const float *apart, *aflag;
+    const float *aflag_tar;  // the partial rows of the workspace that holds cloud 2 (== aflag unless the target is carried over)
+    int nblk_apart, B, N, M, L, spw, gx, gy, Bt;
+};
+struct ScanArgs : CullKArgs {                  // (status: the NaN flag / fallback count the body writes)
+    unsigned long long *counters = nullptr;    // COUNT: executed-work rows, see below
+    long long counter_rows = 0;
+    const int32_t *cnt1 = nullptr, *cnt2 = nullptr, *nlines = nullptr;  // a ragged batch's per-sample counts, or null
 };
 
 // One workgroup of the culled scan: (bx, by, bz) = its place in the scan's grid (gx, gy: the grid's first two extents)
@@ -478,32 +521,22 @@ struct CullLds {
 // of the sample-wide LMAX partials, which that launch has no records kernel in front of it to reduce.  Any bound >= the
 // wavefront's own lines is a valid (conservative) slack: same labels, same hit lists.
 struct NoWait { __device__ __forceinline__ void operator()() const {} };
-template <bool COUNT, bool TILEMAX = false, class Wait = NoWait>
-__device__ __forceinline__ void cull_scan_body(
-    CullLds &lds_, const float *__restrict__ ptri1, const float *__restrict__ ptri2, const float4 *__restrict__ p0s1,
-    const float4 *__restrict__ p0s2, const int32_t *__restrict__ idx1, const int32_t *__restrict__ idx2,
-    const float4 *__restrict__ tree1, const float4 *__restrict__ tree2, const float *__restrict__ line,
-    int32_t *__restrict__ count1, int32_t *__restrict__ hit1, int32_t *__restrict__ count2,
-    int32_t *__restrict__ hit2, int32_t *__restrict__ status, uint32_t *pmax,
-    const float *__restrict__ del1, const float *__restrict__ del2, const float2 *__restrict__ lmax,
-    const float *__restrict__ apart, const float *__restrict__ aflag, int nblk_apart, int B,
-    int N, int M, int L, int spw, unsigned long long *__restrict__ counters, long long counter_rows,
-    const int bx, const int by, const int bz, const int gx, const int gy, const int Bt,
-    const int32_t *__restrict__ cnt1, const int32_t *__restrict__ cnt2, const int32_t *__restrict__ nlines,
-    Wait wait_ready = Wait()) {
+template <class V, bool COUNT, bool TILEMAX = false, class Wait = NoWait>
+__device__ __forceinline__ void cull_scan_body(CullLds<V> &lds_, const ScanArgs &args, const int bx, const int by, const int bz, const int gx,
+                                               const int gy, Wait wait_ready = Wait()) {
     // the chained launch (TILEMAX) always runs 64 * WPB lanes: blockDim.x is a HIDDEN kernel argument, a cache line of its own
     // far behind the explicit ones and one more dependent scalar round in front of the line loads
+    // (a copy: its members are plain values to the compiler when it simplifies this function on its own, ahead of inlining it, as
+    //  the members of a record behind a reference are not -- all eight kernels' instruction streams depend on it)
+    const ScanArgs a = args;
     auto bdim = []() { if constexpr (TILEMAX) return 64u * WPB; else return blockDim.x; };
     auto nwv = []() { if constexpr (TILEMAX) return (int)WPB; else return (int)(blockDim.x >> 6); };
-#if !CULL_REGLINES
-    float2 (&line_lds)[WPB][LPW * 3] = lds_.line_lds;
-#endif
-    float4 (&rec_lds)[SPW * SGG * ROWS] = lds_.rec_lds;
-    float4 (&node_lds)[SPW * NODE] = lds_.node_lds;
-    unsigned short (&qa_lds)[WPB][QA_CAP] = lds_.qa_lds;
-    unsigned short (&qc_lds)[WPB][QC_CAP] = lds_.qc_lds;
-    unsigned (&cands_lds)[WPB][WCCAP] = lds_.cands_lds;
-    static_assert(WPB * WCCAP >= SPW * SGT, "the NaN-reach scratch aliases the (still unused) candidate buffers");
+    float4 (&rec_lds)[V::kSPW * SGG * ROWS] = lds_.rec_lds;
+    float4 (&node_lds)[V::kSPW * NODE] = lds_.node_lds;
+    unsigned short (&qa_lds)[WPB][V::kQaCap] = lds_.qa_lds;
+    unsigned short (&qc_lds)[WPB][V::kQcCap] = lds_.qc_lds;
+    unsigned (&cands_lds)[WPB][V::kWcCap] = lds_.cands_lds;
+    static_assert(WPB * V::kWcCap >= V::kSPW * SGT, "the NaN-reach scratch aliases the (still unused) candidate buffers");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform for the compiler
 #ifdef CULL_DELAY_HALF  // experiment: every second workgroup enters ~2 us late -- does "first loads back" of the
@@ -513,47 +546,47 @@ __device__ __forceinline__ void cull_scan_body(
     unsigned long long *crow = nullptr;
     if constexpr (COUNT) {
         const long long wid = (((long long)bz * gy + by) * gx + bx) * (blockDim.x >> 6) + wave;
-        if (wid < counter_rows) crow = counters + 16 * wid;
+        if (wid < a.counter_rows) crow = a.counters + 16 * wid;
     }
     // XCD-aware mapping: workgroups go to the 8 XCDs round-robin by linear id, and x is the fast
     // index -- with (cloud, sample) on x, all workgroups of one cloud land on the same XCD (when
     // 2B is a multiple of 8), so each XCD's L2 holds 1/8 of the records instead of a copy of all
-    const int z = bx, cloud = z >= B ? 1 : 0, b = z - cloud * B;
+    const int z = bx, cloud = z >= a.B ? 1 : 0, b = z - cloud * a.B;
     // N, M, L: the capacities = the strides of every array.  A ragged batch (include/rrl.h rrl_opts.count1 / count2 / nlines)
     // has n <= ncap records of this cloud and sample -- at the sorted positions [0, n), like the pad of any cloud with
     // n % 64 != 0 -- and nl <= L lines: two uniform loads; without counts the capacities themselves
-    const int ncap = cloud ? M : N;
-    const int n = rrl_rows(cloud ? cnt2 : cnt1, b, ncap);
+    const int ncap = cloud ? a.M : a.N;
+    const int n = rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);
     const int nsg = (n + SGT - 1) / SGT, nsgc = (ncap + SGT - 1) / SGT;
-    const int sg0 = bz * spw;
+    const int sg0 = bz * a.spw;
     if (sg0 >= nsg) return;  // uniform: the smaller cloud (or sample) has fewer slices
-    const int nl = rrl_rows(nlines, input_of(b, Bt), L);
+    const int nl = rrl_rows(a.nlines, input_of(b, a.Bt), a.L);
     if (by * nwv() * LPW >= nl) return;  // uniform: a tile of lines the sample does not have (nl < L only)
     // multi-pose evaluation (rrl_opts.problems): instance b has the target and lines of problem b % Bt -- the target's scan
     // is the same for every pose, so only the first Bt instances scan cloud 2 (the per-line stage reads it there)
-    if (cloud && Bt > 0 && b >= Bt) return;  // uniform
-    const int nsl = min(spw, nsg - sg0);
-    const float4 *p0s = (cloud ? p0s2 : p0s1) + (size_t)b * nsgc * SGT;
-    const float4 *tree = (cloud ? tree2 : tree1) + (size_t)b * nsgc * NODE;
+    if (cloud && a.Bt > 0 && b >= a.Bt) return;  // uniform
+    const int nsl = min(a.spw, nsg - sg0);
+    const float4 *p0s = (cloud ? a.p0s2 : a.p0s1) + (size_t)b * nsgc * SGT;
+    const float4 *tree = (cloud ? a.tree2 : a.tree1) + (size_t)b * nsgc * NODE;
 
     // ---- everything the prologue needs is requested up front, in one round of independent loads: the slice's
     //      records and nodes (one per lane in the usual 8-wavefront workgroup), the sample's line maxima, this
     //      wavefront's 128 lines
-    constexpr int RPT = (SPW * SGT + 64 * WPB - 1) / (64 * WPB);  // records per lane of a full workgroup
-    static_assert(SPW * NODE <= 64 * WPB, "one node per lane");
+    constexpr int RPT = (V::kSPW * SGT + 64 * WPB - 1) / (64 * WPB);  // records per lane of a full workgroup
+    static_assert(V::kSPW * NODE <= 64 * WPB, "one node per lane");
     const bool one_each = (int)bdim() == 64 * WPB;
-    const int32_t *idx = (cloud ? idx2 : idx1) + (size_t)b * nsgc * SGT;
+    const int32_t *idx = (cloud ? a.idx2 : a.idx1) + (size_t)b * nsgc * SGT;
     float4 rec0[RPT], nd0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     static_assert(LMAX_CHUNKS == 64, "one partial row per lane");
     // (the line maxima and max |P|^2 are requested FIRST: vector loads return in order, so the slack arithmetic below can
     //  start while the records, nodes and lines requested after them are still in flight)
     float2 lm = make_float2(0.0f, 0.0f);  // (max |dir|^2, max |x0|^2) over 1/64 of the sample's cullable lines
-    if constexpr (!TILEMAX) lm = lmax[(size_t)b * LMAX_CHUNKS + lane];
+    if constexpr (!TILEMAX) lm = a.lmax[(size_t)b * LMAX_CHUNKS + lane];
     // layout of this cloud's PTRI rows, left by the records launch that built it (slot 7 of its first partial row; not
     // needed before the first candidate is resolved)
     // (TILEMAX -- the chained step -- runs on prepared builds only: sorted rows, and no uniform, i.e. scalar-cache, load of a
     //  word another workgroup of this launch has just written)
-    const float play = TILEMAX ? 1.0f : aflag[(size_t)(cloud * B + b) * nblk_apart * 8 + 7];
+    const float play = TILEMAX ? 1.0f : a.aflag[(size_t)(cloud * a.B + b) * a.nblk_apart * 8 + 7];
     // max |P|^2 of the cloud: from the sort kernel (PMAX), or -- prepared clouds, whose build has no single-workgroup stage
     // -- from the records kernel's per-workgroup partial rows, reduced here next to the line maxima (one more independent
     // load of the prologue; one workgroup per cloud and sample leaves PMAX for the later consumers)
@@ -574,16 +607,16 @@ __device__ __forceinline__ void cull_scan_body(
         if constexpr (TILEMAX) {
             const bool pub = cloud == 0;  // (uniform; sc1: the source's rows were written by this launch's records workgroups)
             const int nb = (n + REC_BLK - 1) / REC_BLK;
-            const float *ap = apart != nullptr ? apart + (size_t)(cloud * B + b) * nblk_apart * 8 + 6 : nullptr;
+            const float *ap = a.apart != nullptr ? a.apart + (size_t)(cloud * a.B + b) * a.nblk_apart * 8 + 6 : nullptr;
             // (sizes in 32 bits: at most SORT_CAP records of 16 bytes)
             // (ars: row j's word lies at byte 32 j and is 4 bytes long -> the last one ends at 32 (nb - 1) + 4 = 32 nb - 28)
-            const __amdgpu_buffer_rsrc_t ars = rrl_rsrc32(ap, apart != nullptr ? nb * 32 - 28 : 0);
+            const __amdgpu_buffer_rsrc_t ars = rrl_rsrc32(ap, a.apart != nullptr ? nb * 32 - 28 : 0);
             const __amdgpu_buffer_rsrc_t prs = rrl_rsrc32(p0s + (size_t)sg0 * SGT, nsl * (SGT * 16));
             const __amdgpu_buffer_rsrc_t trs = rrl_rsrc32(tree + (size_t)sg0 * NODE, nsl * (NODE * 16));
             // (pmv is DEFINED by exactly one of the three sources -- a value merged with an earlier one would be a register copy,
             //  and a copy waits for every load in flight)
-            if (apart == nullptr) {  // uniform
-                pmv = __uint_as_float(pmax[cloud * B + b]);
+            if (a.apart == nullptr) {  // uniform
+                pmv = __uint_as_float(a.pmax[cloud * a.B + b]);
             } else if (nb > 64) {  // uniform; clouds beyond 16384 records: more than one partial row per lane
                 float m = 0.0f;
                 for (int j = lane; j < nb; j += 64) m = fmaxf(m, pub ? ld4_sc1(ap + (size_t)j * 8) : ap[(size_t)j * 8]);
@@ -603,12 +636,12 @@ __device__ __forceinline__ void cull_scan_body(
                 nd0 = ld16_buf<0>(trs, off16);
             }
         } else {
-            if (apart != nullptr) {  // uniform
+            if (a.apart != nullptr) {  // uniform
                 const int nb = (n + REC_BLK - 1) / REC_BLK;
-                const float *ap = apart + (size_t)(cloud * B + b) * nblk_apart * 8 + 6;
+                const float *ap = a.apart + (size_t)(cloud * a.B + b) * a.nblk_apart * 8 + 6;
                 for (int j = lane; j < nb; j += 64) pmv = fmaxf(pmv, ap[(size_t)j * 8]);
             } else {
-                pmv = __uint_as_float(pmax[cloud * B + b]);
+                pmv = __uint_as_float(a.pmax[cloud * a.B + b]);
             }
             if (one_each) {
 #pragma unroll
@@ -624,63 +657,61 @@ __device__ __forceinline__ void cull_scan_body(
     if constexpr (!TILEMAX) issue_records();
     // this wave's 128 lines: a full, 16-byte aligned tile arrives as three coalesced 16-byte loads per lane straight
     // into its LDS rows; the lanes then pick up their own two lines from there
-    const float *ln = line + (size_t)input_of(b, Bt) * L * 6;
+    const float *ln = a.line + (size_t)input_of(b, a.Bt) * a.L * 6;
     const int lw0 = (by * nwv() + wave) * LPW;
     const int l0 = lw0 + lane, l1 = l0 + 64;
     const bool live0 = l0 < nl, live1 = l1 < nl;
     const bool has_lines = lw0 < nl;  // a wave without lines (the last tile of the line set) still stages records
-#if CULL_REGLINES
-    // each lane's own two lines straight into registers: three 8-byte loads per line (rows are 24 bytes, 8-byte aligned;
-    // the three instructions of a line cover the wavefront's 1536 contiguous bytes completely); rows past L: zero lines
+    // registers (g0, g1): each lane's own two lines straight into them: three 8-byte loads per line (rows are 24 bytes, 8-byte
+    // aligned; the three instructions of a line cover the wavefront's 1536 contiguous bytes completely); rows past L: zero lines
+    // LDS (lr, t0 .. t2): the wavefront's rows, a full aligned tile as three 16-byte loads per lane.  The variant that does
+    // not use a name never reads it.
     float2 g0[3] = {make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f)}, g1[3] = {g0[0], g0[0], g0[0]};
-    {
-        const float2 *s2 = (const float2 *)ln;
-        if (live0) { g0[0] = s2[3 * (size_t)l0]; g0[1] = s2[3 * (size_t)l0 + 1]; g0[2] = s2[3 * (size_t)l0 + 2]; }
-        if (live1) { g1[0] = s2[3 * (size_t)l1]; g1[1] = s2[3 * (size_t)l1 + 1]; g1[2] = s2[3 * (size_t)l1 + 2]; }
-    }
-#else
-    float2 *lr = line_lds[wave];
+    float2 *const lr = lds_.line_lds[V::kRegLines ? 0 : wave];  // (in front of full_tile: the lean kernels' scalar schedule follows this order)
     const float *lsrc = ln + (size_t)lw0 * 6;
     const bool full_tile = has_lines && lw0 + LPW <= nl && (((uintptr_t)lsrc) & 15) == 0;  // uniform
     float4 t0, t1, t2;
-    if (full_tile) {
+    if constexpr (V::kRegLines) {
+        const float2 *s2 = (const float2 *)ln;
+        if (live0) { g0[0] = s2[3 * (size_t)l0]; g0[1] = s2[3 * (size_t)l0 + 1]; g0[2] = s2[3 * (size_t)l0 + 2]; }
+        if (live1) { g1[0] = s2[3 * (size_t)l1]; g1[1] = s2[3 * (size_t)l1 + 1]; g1[2] = s2[3 * (size_t)l1 + 2]; }
+    } else if (full_tile) {
         const float4 *s4 = (const float4 *)lsrc;
         t0 = s4[lane]; t1 = s4[64 + lane]; t2 = s4[128 + lane];
     }
-#endif
 
     if constexpr (TILEMAX) { wait_ready(); issue_records(); }
 
     // ---- slack of this (cloud, sample): the same values in every wavefront and workgroup (no exchange, no barrier)
     float pm = pmv;
-    if (apart != nullptr) {  // uniform
+    if (a.apart != nullptr) {  // uniform
         pm = wave_max_nonneg(TILEMAX ? fmaxf(0.0f, pmv) : pmv);  // (fmaxf(0, row): what the loop computes for a lane with one row)
-        if (by == 0 && bz == 0 && tid == 0) pmax[cloud * B + b] = __float_as_uint(pm);
+        if (by == 0 && bz == 0 && tid == 0) a.pmax[cloud * a.B + b] = __float_as_uint(pm);
     }
     // ---- this wavefront's lines into LDS / registers, the lane's own two lines, their norms
     float v0[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, v1[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     float sa, oa, sb, ob;
     auto lines_in = [&]() {
-#if CULL_REGLINES
-        v0[0] = g0[0].x; v0[1] = g0[0].y; v0[2] = g0[1].x; v0[3] = g0[1].y; v0[4] = g0[2].x; v0[5] = g0[2].y;
-        v1[0] = g1[0].x; v1[1] = g1[0].y; v1[2] = g1[1].x; v1[3] = g1[1].y; v1[4] = g1[2].x; v1[5] = g1[2].y;
-#else
-        if (full_tile) {
-            float4 *d4 = (float4 *)lr;
-            d4[lane] = t0; d4[64 + lane] = t1; d4[128 + lane] = t2;
-        } else if (has_lines) {  // ragged tail / odd alignment: 8-byte pieces (a row is 24 bytes), zeros past the end
-            const float2 *s2 = (const float2 *)lsrc;
-            const int nf2 = (nl - lw0) * 3;
-            for (int i = lane; i < LPW * 3; i += 64) lr[i] = i < nf2 ? s2[i] : make_float2(0.0f, 0.0f);
-        }
+        if constexpr (V::kRegLines) {
+            v0[0] = g0[0].x; v0[1] = g0[0].y; v0[2] = g0[1].x; v0[3] = g0[1].y; v0[4] = g0[2].x; v0[5] = g0[2].y;
+            v1[0] = g1[0].x; v1[1] = g1[0].y; v1[2] = g1[1].x; v1[3] = g1[1].y; v1[4] = g1[2].x; v1[5] = g1[2].y;
+        } else {
+            if (full_tile) {
+                float4 *d4 = (float4 *)lr;
+                d4[lane] = t0; d4[64 + lane] = t1; d4[128 + lane] = t2;
+            } else if (has_lines) {  // ragged tail / odd alignment: 8-byte pieces (a row is 24 bytes), zeros past the end
+                const float2 *s2 = (const float2 *)lsrc;
+                const int nf2 = (nl - lw0) * 3;
+                for (int i = lane; i < LPW * 3; i += 64) lr[i] = i < nf2 ? s2[i] : make_float2(0.0f, 0.0f);
+            }
 
-        wave_lds_fence();
-        if (has_lines) {
-            const LineRow r0 = line_row(lr, lane), r1 = line_row(lr, 64 + lane);
-            v0[0] = r0.la.x; v0[1] = r0.la.y; v0[2] = r0.la.z; v0[3] = r0.la.w; v0[4] = r0.lb.x; v0[5] = r0.lb.y;
-            v1[0] = r1.la.x; v1[1] = r1.la.y; v1[2] = r1.la.z; v1[3] = r1.la.w; v1[4] = r1.lb.x; v1[5] = r1.lb.y;
+            wave_lds_fence();
+            if (has_lines) {
+                const LineRow r0 = line_row(lr, lane), r1 = line_row(lr, 64 + lane);
+                v0[0] = r0.la.x; v0[1] = r0.la.y; v0[2] = r0.la.z; v0[3] = r0.la.w; v0[4] = r0.lb.x; v0[5] = r0.lb.y;
+                v1[0] = r1.la.x; v1[1] = r1.la.y; v1[2] = r1.la.z; v1[3] = r1.la.w; v1[4] = r1.lb.x; v1[5] = r1.lb.y;
+            }
         }
-#endif
         line_norms(v0[0], v0[1], v0[2], v0[3], v0[4], v0[5], sa, oa);
         line_norms(v1[0], v1[1], v1[2], v1[3], v1[4], v1[5], sb, ob);
     };
@@ -713,7 +744,7 @@ __device__ __forceinline__ void cull_scan_body(
     float dv[RPT];
     const bool psorted = __builtin_amdgcn_readfirstlane(__float_as_int(play)) != 0;  // (1.0f: PTRI / DEL rows at sorted positions)
     if (nanwide && one_each) {
-        const float *del = (cloud ? del2 : del1) + (size_t)b * ncap;
+        const float *del = (cloud ? a.del2 : a.del1) + (size_t)b * ncap;
         if (psorted) {  // uniform: the prepared build left DEL at the sorted positions -- no dependent gather through IDX
 #pragma unroll
             for (int k = 0; k < RPT; ++k)
@@ -733,20 +764,20 @@ __device__ __forceinline__ void cull_scan_body(
     const bool fallback = !cs.ok || !__all(line_cullable(sa, oa) && line_cullable(sb, ob));
     unsigned long long fb_pairs = 0;
 
-    const float *ptri = (cloud ? ptri2 : ptri1) + (size_t)b * ncap * PTRI_STRIDE;
-    int32_t *cnt = (cloud ? count2 : count1) + (size_t)b * L;
-    int32_t *hit = (cloud ? hit2 : hit1) + (size_t)b * L * RRL_MAX_HITS;
+    const float *ptri = (cloud ? a.ptri2 : a.ptri1) + (size_t)b * ncap * PTRI_STRIDE;
+    int32_t *cnt = (cloud ? a.count2 : a.count1) + (size_t)b * a.L;
+    int32_t *hit = (cloud ? a.hit2 : a.hit1) + (size_t)b * a.L * RRL_MAX_HITS;
 
     // nanwide: the slice's del values meet in LDS (a buffer the walk does not use yet) so that every node lane can
     // take the maximum over ITS records -- one more barrier, only on this path
-    float *dl = (float *)&cands_lds[0][0];  // [SPW * SGT]
+    float *dl = (float *)&cands_lds[0][0];  // [kSPW * SGT]
     if (nanwide) {
         if (one_each) {
 #pragma unroll
             for (int k = 0; k < RPT; ++k)
                 if (tid + 64 * WPB * k < nsl * SGT) dl[tid + 64 * WPB * k] = dv[k];
         } else {
-            const float *del = (cloud ? del2 : del1) + (size_t)b * ncap;
+            const float *del = (cloud ? a.del2 : a.del1) + (size_t)b * ncap;
             for (int i = tid; i < nsl * SGT; i += bdim()) {
                 const int sp = sg0 * SGT + i;
                 dl[i] = sp < n ? del[psorted ? sp : idx[sp]] : 0.0f;
@@ -802,13 +833,13 @@ __device__ __forceinline__ void cull_scan_body(
     const unsigned long long wall_staged = COUNT ? wall_clock64() : 0ull;
     unsigned long long wall_a = 0ull, wall_pa = 0ull, wall_pc = 0ull;
 
-    WaveCtx ctx;
-#if CULL_REGLINES
+    WaveCtx<V> ctx;
+    if constexpr (V::kRegLines) {
 #pragma unroll
-    for (int q = 0; q < 6; ++q) { ctx.v0[q] = v0[q]; ctx.v1[q] = v1[q]; }
-#else
-    ctx.lr = lr;
-#endif
+        for (int q = 0; q < 6; ++q) { ctx.ln.v0[q] = v0[q]; ctx.ln.v1[q] = v1[q]; }
+    } else {
+        ctx.ln.lr = lr;
+    }
     ctx.recs = rec_lds;
     ctx.nodes = node_lds;
     ctx.qa = qa_lds[wave];
@@ -825,7 +856,7 @@ __device__ __forceinline__ void cull_scan_body(
     ctx.na = ctx.nc = ctx.ncand = 0;
     ctx.lane = lane;
     ctx.tb = ctx.tc = ctx.td = ctx.tcand = 0;
-    ctx.status = status;
+    ctx.status = a.status;
     ctx.pos0 = sg0 * SGT;
     const v2f ux = {v0[0], v1[0]}, uy = {v0[1], v1[1]}, uz = {v0[2], v1[2]};
     const v2f ox = {v0[3], v1[3]}, oy = {v0[4], v1[4]}, oz = {v0[5], v1[5]};
@@ -833,14 +864,14 @@ __device__ __forceinline__ void cull_scan_body(
 
     if (fallback) {  // rare: kept out of line so that its registers do not count against the culled walk
         const int f0 = sg0 * SGT, f1 = min(n, f0 + nsl * SGT);  // real records sit at sorted positions [0, n)
-        strict_slice(ptri, idx, ctx.psorted, f0, f1, ux, uy, uz, ox, oy, oz, l0, l1, nl, cnt, hit, status);
-        if (lane == 0) atomicAdd(&status[1], 1);  // always on: wavefronts that left the culled path
+        strict_slice(ptri, idx, ctx.psorted, f0, f1, ux, uy, uz, ox, oy, oz, l0, l1, nl, cnt, hit, a.status);
+        if (lane == 0) atomicAdd(&a.status[1], 1);  // always on: wavefronts that left the culled path
         fb_pairs = (unsigned long long)(f1 - f0) * (unsigned long long)min(LPW, nl - lw0);
     } else {
     ta = (unsigned long long)nsl * (unsigned long long)min(LPW, nl - lw0);
 
     unsigned long long stamps[3] = {0ull, 0ull, 0ull};
-    cull_walk<COUNT, TILEMAX>(ctx, node_lds, nsl, lane, live0, live1, ux, uy, uz, ox, oy, oz, stamps);
+    cull_walk<V, COUNT, TILEMAX>(ctx, node_lds, nsl, lane, live0, live1, ux, uy, uz, ox, oy, oz, stamps);
     wall_a = stamps[0]; wall_pa = stamps[1]; wall_pc = stamps[2];
     }
     if constexpr (COUNT) {
@@ -860,7 +891,7 @@ __device__ __forceinline__ void cull_scan_body(
     }
 }
 
-template <bool COUNT>
+template <class V, bool COUNT>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))) void cull_scan_kernel(
     const float *__restrict__ ptri1, const float *__restrict__ ptri2, const float4 *__restrict__ p0s1,
     const float4 *__restrict__ p0s2, const int32_t *__restrict__ idx1, const int32_t *__restrict__ idx2,
@@ -871,10 +902,14 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
     const float *__restrict__ apart, const float *__restrict__ aflag, int nblk_apart, int B,
     int N, int M, int L, int spw, unsigned long long *__restrict__ counters, long long counter_rows, int Bt,
     const int32_t *__restrict__ cnt1, const int32_t *__restrict__ cnt2, const int32_t *__restrict__ nlines) {
-    __shared__ CullLds lds_;
-    cull_scan_body<COUNT>(lds_, ptri1, ptri2, p0s1, p0s2, idx1, idx2, tree1, tree2, line, count1, hit1, count2, hit2, status,
-                          pmax, del1, del2, lmax, apart, aflag, nblk_apart, B, N, M, L, spw, counters, counter_rows,
-                          (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y, Bt, cnt1, cnt2, nlines);
+    __shared__ CullLds<V> lds_;
+    ScanArgs a;
+    a.ptri1 = ptri1; a.ptri2 = ptri2; a.p0s1 = p0s1; a.p0s2 = p0s2; a.idx1 = idx1; a.idx2 = idx2; a.tree1 = tree1; a.tree2 = tree2;
+    a.line = line; a.count1 = count1; a.hit1 = hit1; a.count2 = count2; a.hit2 = hit2; a.status = status; a.pmax = pmax;
+    a.del1 = del1; a.del2 = del2; a.lmax = lmax; a.apart = apart; a.aflag = aflag;
+    a.nblk_apart = nblk_apart; a.B = B; a.N = N; a.M = M; a.L = L; a.spw = spw; a.Bt = Bt;
+    a.counters = counters; a.counter_rows = counter_rows; a.cnt1 = cnt1; a.cnt2 = cnt2; a.nlines = nlines;
+    cull_scan_body<V, COUNT>(lds_, a, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -887,20 +922,6 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
 // the others scan.  Same bodies, same results as the two launches; the LDS of the two is overlaid.  The walk takes
 // max |P|^2 of its target from the partial rows (pm1 == NULL): PMAX is being rebuilt by this launch's scan.
 // ---------------------------------------------------------------------------------------
-struct CullKArgs {
-    const float *ptri1, *ptri2;
-    const float4 *p0s1, *p0s2;
-    const int32_t *idx1, *idx2;
-    const float4 *tree1, *tree2;
-    const float *line;
-    int32_t *count1, *hit1, *count2, *hit2, *status;
-    uint32_t *pmax;
-    const float *del1, *del2;
-    const float2 *lmax;
-    const float *apart, *aflag;
-    const float *aflag_tar;  // the partial rows of the workspace that holds cloud 2 (== aflag unless the target is carried over)
-    int nblk_apart, B, N, M, L, spw, gx, gy, Bt;
-};
 struct ChamKArgs {
     unsigned long long *best_x, *best_y;
     double *partial, *gpart;
@@ -911,10 +932,11 @@ struct ChamKArgs {
 };
 static_assert(NWV == WPB, "the walk and the scan share one launch: the same 512-lane workgroups");
 
+template <class V>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 8))) void cull_scan_chamfer_kernel(
     const CullKArgs a, const ChamKArgs c) {
     __shared__ union {
-        CullLds scan;
+        CullLds<V> scan;
         ChamLds walk;
     } lds_;
     const int ncham = c.gx * c.gy, lin = (int)blockIdx.x;
@@ -925,10 +947,13 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 8))
         return;
     }
     const int l2 = lin - ncham, bx = l2 % a.gx, r = l2 / a.gx;
-    cull_scan_body<false>(lds_.scan, a.ptri1, a.ptri2, a.p0s1, a.p0s2, a.idx1, a.idx2, a.tree1, a.tree2, a.line, a.count1,
-                          a.hit1, a.count2, a.hit2, a.status, a.pmax, a.del1, a.del2, a.lmax, a.apart, a.aflag, a.nblk_apart,
-                          a.B, a.N, a.M, a.L, a.spw, nullptr, 0, bx, r % a.gy, r / a.gy, a.gx, a.gy, a.Bt,
-                          nullptr, nullptr, nullptr);  // (a riding walk and counts exclude each other: rrl_plan)
+    // (no counters, no per-sample counts: a riding walk excludes both, rrl_plan)
+    ScanArgs s;  // (member by member: a block copy of the kernel argument moves this kernel's scalar loads)
+    s.ptri1 = a.ptri1; s.ptri2 = a.ptri2; s.p0s1 = a.p0s1; s.p0s2 = a.p0s2; s.idx1 = a.idx1; s.idx2 = a.idx2; s.tree1 = a.tree1; s.tree2 = a.tree2;
+    s.line = a.line; s.count1 = a.count1; s.hit1 = a.hit1; s.count2 = a.count2; s.hit2 = a.hit2; s.status = a.status; s.pmax = a.pmax;
+    s.del1 = a.del1; s.del2 = a.del2; s.lmax = a.lmax; s.apart = a.apart; s.aflag = a.aflag;
+    s.nblk_apart = a.nblk_apart; s.B = a.B; s.N = a.N; s.M = a.M; s.L = a.L; s.spw = a.spw; s.Bt = a.Bt;
+    cull_scan_body<V, false>(lds_.scan, s, bx, r % a.gy, r / a.gy, a.gx, a.gy);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -973,6 +998,7 @@ struct ChainKArgs {
 // [0, zrec) hold the records pieces (piece z * tiles + y of sample x; the surplus exits), planes [zrec, zrec + z2) the target
 // cloud's slices, the rest the source cloud's -- dispatch goes plane by plane, so the order is records, target, source,
 // and a workgroup's place needs no division.
+template <class V>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))) void cull_scan_build_kernel(
     const ChainKArgs ch, const float *__restrict__ ptri1, const float *__restrict__ ptri2,
     const int32_t *__restrict__ idx1, const int32_t *__restrict__ idx2, int32_t *__restrict__ count1,
@@ -980,7 +1006,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
     const float *__restrict__ del1, const float *__restrict__ del2, const BuildArgs bld,
     const int32_t *__restrict__ order1) {
     __shared__ union {
-        CullLds scan;
+        CullLds<V> scan;
         float red[WPB][8];
     } lds_;
     asm volatile("" ::"s"(ch.zrec), "s"(ch.z2), "s"(ch.B), "s"(ch.N), "s"(ch.M), "s"(ch.L), "s"(ch.spw), "s"(ch.nblk_apart),
@@ -1038,10 +1064,13 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
             STAMPR(5);
         }
     };
-    cull_scan_body<false, true>(lds_.scan, ptri1, ptri2, ch.p0s1, ch.p0s2, idx1, idx2, ch.tree1, ch.tree2, ch.line, count1, hit1,
-                                count2, hit2, (int32_t *)(ch.chain + 4 * b + 1), ch.pmax, del1, del2, nullptr, ch.apart, ch.apart,
-                                ch.nblk_apart, B, ch.N, ch.M, ch.L, ch.spw, nullptr, 0, cloud * B + b, by, bz, 2 * B, ch.gy, 0,
-                                nullptr, nullptr, nullptr, wait_ready);  // (no counts: rrl_cull_scan_can_fuse declines ragged calls)
+    ScanArgs a;  // (no counters, no per-sample counts, one problem: rrl_cull_scan_can_fuse declines the calls that have them)
+    a.ptri1 = ptri1; a.ptri2 = ptri2; a.p0s1 = ch.p0s1; a.p0s2 = ch.p0s2; a.idx1 = idx1; a.idx2 = idx2; a.tree1 = ch.tree1; a.tree2 = ch.tree2;
+    a.line = ch.line; a.count1 = count1; a.hit1 = hit1; a.count2 = count2; a.hit2 = hit2;
+    a.status = (int32_t *)(ch.chain + 4 * b + 1);  // this launch's NaN flag / fallback count are per sample
+    a.pmax = ch.pmax; a.del1 = del1; a.del2 = del2; a.lmax = nullptr; a.apart = ch.apart; a.aflag = ch.apart;
+    a.nblk_apart = ch.nblk_apart; a.B = B; a.N = ch.N; a.M = ch.M; a.L = ch.L; a.spw = ch.spw; a.Bt = 0;
+    cull_scan_body<V, false, true>(lds_.scan, a, cloud * B + b, by, bz, 2 * B, ch.gy, wait_ready);
     STAMPR(6);
 }
 
@@ -1067,8 +1096,9 @@ static CullKArgs cull_args(const RrlCall &o, const float *line, const CullGeom &
     return a;
 }
 
-// The launch of THIS variant for a geometry chosen by rrl_launch_cull_scan: (waves per workgroup, supergroups per slice,
+// The launch of variant V for a geometry chosen by rrl_launch_cull_scan: (waves per workgroup, supergroups per slice,
 // line tiles, slices); g.may_ride: the evaluation's Chamfer walk may be carried (full 512-lane workgroups).
+template <class V>
 static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g) {
     const int B = o.B, N = o.N, M = o.M, clouds = o.plan.clouds, waves = g.waves, spw = g.spw, tiles = g.tiles;
     if (o.plan.fused_build) {  // the chained step: source records + target scan + source scan as ONE launch (cull_scan_build_kernel)
@@ -1077,7 +1107,7 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
         a.status = nullptr;
         // the source's records body: the arguments of a records launch of cloud 1 alone, in 512-lane pieces; it clears what
         // no scan workgroup of this launch touches: NSEL (+ NVALS), the reduce's state, the accumulators, the gradient target
-        BuildArgs bld = ::make_build_args(o, o.tri1_in, nullptr, 1, nullptr, false);
+        BuildArgs bld = make_build_args(o, o.tri1_in, nullptr, 1, nullptr, false);
         bld.L = 0;
         bld.nblk_tri = (int)(((size_t)(N + SGT - 1) / SGT * SGT + 64 * WPB - 1) / (64 * WPB));
         bld.zero_base = (uint4 *)o.at<RRL_WS_NVALS>();
@@ -1094,12 +1124,12 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
         const int nsg1 = (N + SGT - 1) / SGT, nsg2 = (M + SGT - 1) / SGT;
         const int z1 = (nsg1 + spw - 1) / spw;  // slices per cloud: no empty workgroups
         ch.z2 = (nsg2 + spw - 1) / spw;
-        ch.spin_limit = ::rrl_chain_spin_limit();
+        ch.spin_limit = rrl_chain_spin_limit();
         ch.exp = 0;
 #ifdef RRL_CHAIN_EXP
         if (const char *e = getenv("RRL_CHAIN_EXP")) ch.exp = atoi(e);
 #endif
-        hipLaunchKernelGGL(cull_scan_build_kernel, dim3((unsigned)B, (unsigned)tiles, (unsigned)(ch.zrec + ch.z2 + z1)), dim3(64 * WPB), 0,
+        hipLaunchKernelGGL(cull_scan_build_kernel<V>, dim3((unsigned)B, (unsigned)tiles, (unsigned)(ch.zrec + ch.z2 + z1)), dim3(64 * WPB), 0,
                            o.s, ch, a.ptri1, a.ptri2, a.idx1, a.idx2, a.count1, a.hit1, a.count2, a.hit2, a.del1, a.del2, bld,
                            o.order1);
         RRL_LAUNCH_CHECK();
@@ -1121,21 +1151,21 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
             c.tick = ChamTick{mctl + 32, mctl + 30, 64, 1};
             c.gx = 2 * B; c.gy = ((N > M ? N : M) + SGT - 1) / SGT;  // patches of the larger cloud (either direction)
             const unsigned nwg = (unsigned)(c.gx * c.gy) + (unsigned)(a.gx * a.gy * g.slices);
-            hipLaunchKernelGGL(cull_scan_chamfer_kernel, dim3(nwg), dim3(64 * WPB), 0, o.s, a, c);
+            hipLaunchKernelGGL(cull_scan_chamfer_kernel<V>, dim3(nwg), dim3(64 * WPB), 0, o.s, a, c);
             RRL_LAUNCH_CHECK();
             o.rider->done = 1;
             return 0;
         }
     }
     const CullKArgs a = cull_args(o, line, g, o.ws);
-#define RRL_CULL_LAUNCH(COUNT)                                                                                          \
-    hipLaunchKernelGGL(cull_scan_kernel<COUNT>, dim3((unsigned)a.gx, (unsigned)a.gy, (unsigned)g.slices), dim3(64 * waves), 0,  \
-                       o.s, a.ptri1, a.ptri2, a.p0s1, a.p0s2, a.idx1, a.idx2, a.tree1, a.tree2, a.line, a.count1, a.hit1,     \
-                       a.count2, a.hit2, a.status, a.pmax, a.del1, a.del2, a.lmax, a.apart, a.aflag, a.nblk_apart, a.B, a.N,  \
-                       a.M, a.L, a.spw, o.counters, o.counter_rows, a.Bt, o.count1, o.count2, o.nlines)
-    if (o.counters) RRL_CULL_LAUNCH(true);
-    else RRL_CULL_LAUNCH(false);
-#undef RRL_CULL_LAUNCH
+    auto plain = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)a.gx, (unsigned)a.gy, (unsigned)g.slices), dim3(64 * waves), 0, o.s, a.ptri1, a.ptri2,
+                           a.p0s1, a.p0s2, a.idx1, a.idx2, a.tree1, a.tree2, a.line, a.count1, a.hit1, a.count2, a.hit2, a.status, a.pmax,
+                           a.del1, a.del2, a.lmax, a.apart, a.aflag, a.nblk_apart, a.B, a.N, a.M, a.L, a.spw, o.counters, o.counter_rows,
+                           a.Bt, o.count1, o.count2, o.nlines);
+    };
+    if (o.counters) plain(cull_scan_kernel<V, true>);
+    else plain(cull_scan_kernel<V, false>);
     RRL_LAUNCH_CHECK();
     return 0;
 }

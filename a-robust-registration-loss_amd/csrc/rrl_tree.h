@@ -9,7 +9,7 @@
 #define SGT (GRP * SGG)  // triangles per supergroup
 #define NODE 13          // float4 per supergroup in the sphere tree: [0] supergroup, [1..4] groups, [5..12] halves
 #define SORT_CAP (1 << 20)  // largest cloud of the sorted / culled layout (include/rrl.h rrl_sort_capacity)
-// The culled scan's point-0 candidates are 32-bit words  line_in_wave << CAND_POS_BITS | sorted position  (rrl_cull_scan.inc):
+// The culled scan's point-0 candidates are 32-bit words  line_in_wave << CAND_POS_BITS | sorted position  (rrl_cull_scan.h):
 // the top 8 bits hold one of the 128 lines of a wavefront, the low 24 a sorted position (24, not 25: a position below 2^24
 // keeps the row offset a v_mul_u32_u24, and the scan kernels compile to the same instructions as with the 16-bit field of
 // the 65536-triangle layout, only the shift and mask constants differ).  Nothing else in the sorted layout is narrower than

@@ -1,4 +1,4 @@
-"""Chained steps (round 6; include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED, csrc/rrl_cull_scan.inc cull_scan_build_kernel).
+"""Chained steps (round 6; include/rrl.h RRL_F_CHAIN / RRL_F_CHAINED, csrc/rrl_cull_scan.h cull_scan_build_kernel).
 
 A loop that evaluates the loss again and again on one workspace with a kept target (the demo,
 code/test_demo_optimized_Lie_Algebra.py:48-62: new lines and a new pose every step, the target never moves) runs, from its
@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from test_gpu_parity import cu
-from test_gpu_prepared import _lines, _pairs, _rot
+from test_gpu_prepared import _lines, _pairs, _rot, _with_fat
 
 pytestmark = pytest.mark.gpu
 
@@ -101,6 +101,29 @@ def test_chained_steps_equal_unchained_steps(L, B, n, m, nl, scale, fusable):
         assert int(chained.st.chain.abs().max()) == 0
         assert int(plain.st.count1.max()) > 0
     assert fused == (4 if fusable else 0)
+    assert int(b["info"][:, 1].min()) > 0 and int(b["info"][:, 3].max()) == 0
+
+
+def test_fat_variant_chained_at_a_small_size(L):
+    """cull_scan_build_kernel of the fat variant (Scan16), which the automatic choice reaches only at B >= 12 of the full size,
+    forced by RRL_CULL_FAT=1 at B = 2, N = 1200, M = 1000, L = 2500: 19 supergroups > 8, so the forced choice is honoured; 20
+    wavefronts' worth of lines, so the workgroups are full; 3 records pieces per sample, 3 line tiles and 2 + 1 slices, 24
+    workgroups in all, so rrl_cull_scan_can_fuse accepts.  Chained equals unchained under the same setting, three steps."""
+    from rrl_hip import ops
+    B, n, m, nl = 2, 1200, 1000, 2500
+    prs, src, tar = _pairs(960, B, n, m)
+    plain = ops.LossStep(src, tar, nl, want_payload=True)
+    plain.chain = False
+    chained = ops.LossStep(src, tar, nl, want_payload=True)
+    for it in range(3):
+        ln = _new_lines(L, prs, nl, it)
+        R, t = _poses(B, it)
+        a = _with_fat("1", lambda: _snapshot(plain, plain(R, t, ln)))
+        b = _with_fat("1", lambda: _snapshot(chained, chained(R, t, ln)))
+        _assert_same(a, b, it)
+        assert plain.fused is False and chained.fused is (it > 0), it
+        assert int(chained.st.count1.abs().max()) == 0 and int(chained.st.count2.abs().max()) == 0
+        assert int(chained.st.chain.abs().max()) == 0
     assert int(b["info"][:, 1].min()) > 0 and int(b["info"][:, 3].max()) == 0
 
 

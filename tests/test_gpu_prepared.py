@@ -657,7 +657,7 @@ def test_multi_pose_argument_errors(L):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# round 5: the FAT geometry variant of the culled scan (csrc/rrl_cull_scan.inc scan16: slices of 16 supergroups, the lines in
+# round 5: the FAT geometry variant of the culled scan (csrc/rrl_cull_scan.h Scan16: slices of 16 supergroups, the lines in
 # registers) -- chosen automatically for deep grids (B >= 12 at C2's shape), forced here by RRL_CULL_FAT on small ones
 def _with_fat(flag, fn):
     import os

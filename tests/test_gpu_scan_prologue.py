@@ -1,4 +1,4 @@
-"""The culled scan's prologue branches (csrc/rrl_cull_scan.inc cull_scan_body): the scan's arguments arrive in one round of
+"""The culled scan's prologue branches (csrc/rrl_cull_scan.h cull_scan_body): the scan's arguments arrive in one round of
 scalar loads and its partial rows, records and nodes leave as range-checked buffer loads with no wait in between.  None of
 that may change a label, so every case here compares the default (culled) mode against mode="strict" on the same inputs --
 hit counts, ascending hit lists, info, loss bits -- and, for steps that may chain, the chained step against chain=False the
