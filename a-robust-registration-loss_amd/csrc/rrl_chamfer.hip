@@ -56,7 +56,8 @@ extern "C" size_t rrl_chamfer_workspace_bytes(int B, int N, int M) {
 __global__ __launch_bounds__(256) void pts_records_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                           float4 *__restrict__ crec1, float4 *__restrict__ crec2,
                                                           float *__restrict__ apart, uint4 *__restrict__ zero,
-                                                          size_t zero_vec4, int B, int N, int M, int nblk) {
+                                                          size_t zero_vec4, int B, int N, int M, int nblk,
+                                                          const int32_t *__restrict__ cnt1, const int32_t *__restrict__ cnt2) {
     __shared__ float red[4][8];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cloud = blockIdx.z, b = blockIdx.y;
@@ -65,15 +66,16 @@ __global__ __launch_bounds__(256) void pts_records_kernel(const float *__restric
         const size_t me = (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 256 + tid;
         for (size_t i = me; i < zero_vec4; i += nthr) zero[i] = make_uint4(0, 0, 0, 0);
     }
-    const int n = cloud ? M : N;
-    if ((int)blockIdx.x * 256 >= n) return;  // uniform
+    const int ncap = cloud ? M : N;                          // the capacity: the stride of the cloud's arrays
+    const int n = rrl_rows(cloud ? cnt2 : cnt1, b, ncap);    // the sample's own points (a ragged batch; uniform)
+    if ((int)blockIdx.x * 256 >= n) return;  // uniform (the clearing above stays in front of it)
     const int f = blockIdx.x * 256 + tid;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY}, p2 = 0.0f;
     bool bad = false;
     if (f < n) {
-        const float *p = (cloud ? y : x) + ((size_t)b * n + f) * 3;
+        const float *p = (cloud ? y : x) + ((size_t)b * ncap + f) * 3;
         const float c0 = p[0], c1 = p[1], c2 = p[2];
-        const int ng = (n + GRP - 1) / GRP;
+        const int ng = (ncap + GRP - 1) / GRP;
         ((cloud ? crec2 : crec1) + (size_t)b * ng * GRP)[f] = make_float4(c0, c1, c2, __int_as_float(f));
         mn[0] = mx[0] = c0; mn[1] = mx[1] = c1; mn[2] = mx[2] = c2;
         p2 = c0 * c0 + c1 * c1 + c2 * c2;
@@ -109,15 +111,18 @@ __global__ __launch_bounds__(256) void pts_records_sorted_kernel(const float *__
                                                                  int32_t *__restrict__ idx1, int32_t *__restrict__ idx2,
                                                                  float4 *__restrict__ grp1, float4 *__restrict__ grp2,
                                                                  float *__restrict__ apart, uint32_t *__restrict__ zwords, int nzwords,
-                                                                 int B, int N, int M, int nblk) {
+                                                                 int B, int N, int M, int nblk,
+                                                                 const int32_t *__restrict__ cnt1, const int32_t *__restrict__ cnt2) {
     __shared__ float red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cloud = blockIdx.z, b = blockIdx.y;
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
         for (int i = tid; i < nzwords; i += 256) zwords[i] = 0u;
-    const int n = cloud ? M : N;
-    const int npad = (n + SGT - 1) / SGT * SGT;
-    if ((int)blockIdx.x * 256 >= npad) return;  // uniform
+    const int ncap = cloud ? M : N;
+    const int n = rrl_rows(cloud ? cnt2 : cnt1, b, ncap);  // the sample's own points (a ragged batch: the first n entries of its order row)
+    const int npad = (ncap + SGT - 1) / SGT * SGT;         // the stride of the sorted arrays and of the order
+    const int nown = (n + SGT - 1) / SGT * SGT;            // the sample's records end with its last supergroup
+    if ((int)blockIdx.x * 256 >= nown) return;  // uniform
     const int s_ = blockIdx.x * 256 + tid;
     const bool valid = s_ < n;
     float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
@@ -125,10 +130,10 @@ __global__ __launch_bounds__(256) void pts_records_sorted_kernel(const float *__
     if (valid) {
         f = (cloud ? order2 : order1)[(size_t)b * npad + s_];
         f = min(max(f, 0), n - 1);  // memory safety only: the order must be a permutation of [0, n)
-        const float *p = (cloud ? y : x) + ((size_t)b * n + f) * 3;
+        const float *p = (cloud ? y : x) + ((size_t)b * ncap + f) * 3;
         c0 = p[0]; c1 = p[1]; c2 = p[2];
     }
-    if (s_ - lane < npad) {  // wave-uniform: this wavefront holds a supergroup
+    if (s_ - lane < nown) {  // wave-uniform: this wavefront holds a supergroup
         (cloud ? p0s2 : p0s1)[(size_t)b * npad + s_] = valid ? make_float4(c0, c1, c2, __int_as_float(f)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         (cloud ? idx2 : idx1)[(size_t)b * npad + s_] = f;
         wave_tree(c0, c1, c2, __int_as_float(f), valid, lane, (cloud ? grp2 : grp1) + ((size_t)b * (npad / SGT) + (s_ - lane) / SGT) * NODE);
@@ -149,16 +154,26 @@ extern "C" int rrl_chamfer_counters(uint64_t *dev_counters, long long rows) {
     return 0;
 }
 
+// the walk of a ragged batch (rrl_chamfer_tree_fwd_counted): a kernel of its own, so that the uniform ones keep their code
+__global__ __launch_bounds__(64 * NWV) void chamfer_tree_counted_kernel(
+    const float4 *__restrict__ p0s1, const float4 *__restrict__ p0s2, const float4 *__restrict__ grp1,
+    const float4 *__restrict__ grp2, const float *__restrict__ apart, int nblk, unsigned long long *__restrict__ best_x,
+    unsigned long long *__restrict__ best_y, double *__restrict__ partial, int B, int N, int M, const ChamTick tk_,
+    double *__restrict__ gpart, float *__restrict__ values, float *__restrict__ value, const int32_t *__restrict__ cntx,
+    const int32_t *__restrict__ cnty) {
+    __shared__ ChamLds lds_;
+    chamfer_tree_body<false, false, true>(lds_, p0s1, p0s2, grp1, grp2, apart, nblk, best_x, best_y, partial, B, N, M, nullptr, 0,
+                                          nullptr, nullptr, nullptr, nullptr, tk_, gpart, value, 0.0, (int)blockIdx.x,
+                                          (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y, nullptr, cntx, cnty, values);
+}
+
+// The launches of a tree forward on validated arguments.  values == NULL: the uniform walk (today's kernels, today's bits);
+// else the ragged one -- count_x / count_y [B] (or NULL: the capacities) reach every kernel, values [B] is written.
 // best_x [B][N], best_y [B][M]: u64 keys, every entry written exactly once (no initialisation needed).
-extern "C" int rrl_chamfer_tree_fwd_ex(const float *x, const float *y, void *ws, size_t ws_bytes, uint64_t *best_x,
-                                       uint64_t *best_y, float *value, int B, int N, int M, const int32_t *order_x,
-                                       const int32_t *order_y, uint64_t *counters, long long counter_rows, void *stream) {
-    unsigned long long *const cnt_buf = (unsigned long long *)counters;  // per-call counter table (NULL: the plain kernel)
-    const long long cnt_rows = counters ? counter_rows : 0;
-    if (!x || !y || !ws || !best_x || !best_y || !value || B <= 0 || N <= 0 || M <= 0) return RRL_E_ARG;
-    if ((N > M ? N : M) > rrl_sort_capacity() || B > 32767) return RRL_E_ARG;
-    const ChamLayout L(B, N, M);
-    if (ws_bytes < L.total) return RRL_E_WS;
+static int chamfer_tree_launches(const float *x, const float *y, const int32_t *count_x, const int32_t *count_y, void *ws,
+                                 const ChamLayout &L, uint64_t *best_x, uint64_t *best_y, float *values, float *value, int B,
+                                 int N, int M, const int32_t *order_x, const int32_t *order_y, unsigned long long *cnt_buf,
+                                 long long cnt_rows, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     char *w = (char *)ws;
     const int nmax = N > M ? N : M;
@@ -169,22 +184,31 @@ extern "C" int rrl_chamfer_tree_fwd_ex(const float *x, const float *y, void *ws,
         hipLaunchKernelGGL(pts_records_sorted_kernel, dim3((unsigned)((npadmax + 255) / 256), (unsigned)B, 2u), dim3(256), 0, s, x, y,
                            order_x, order_y, (float4 *)(w + L.p0s1), (float4 *)(w + L.p0s2), (int32_t *)(w + L.idx1),
                            (int32_t *)(w + L.idx2), (float4 *)(w + L.grp1), (float4 *)(w + L.grp2), (float *)(w + L.apart),
-                           (uint32_t *)(w + L.ctrl), (int)(L.ctrl_bytes / 4), B, N, M, L.nblk);
+                           (uint32_t *)(w + L.ctrl), (int)(L.ctrl_bytes / 4), B, N, M, L.nblk, count_x, count_y);
     } else {
     if (!small)
         hipLaunchKernelGGL(pts_records_kernel, dim3((unsigned)((nmax + 255) / 256), (unsigned)B, 2u), dim3(256), 0, s, x,
                            y, (float4 *)(w + L.crec1), (float4 *)(w + L.crec2), (float *)(w + L.apart),
-                           (uint4 *)(w + L.histg), (L.total - L.histg) / 16, B, N, M, L.nblk);
+                           (uint4 *)(w + L.histg), (L.total - L.histg) / 16, B, N, M, L.nblk, count_x, count_y);
     rc = rrl_launch_cloud_sort(small ? x : nullptr, small ? y : nullptr, (float4 *)(w + L.crec1), (float4 *)(w + L.crec2), (float *)(w + L.apart), L.nblk,
                                    (float4 *)(w + L.p0s1), (float4 *)(w + L.p0s2), (int32_t *)(w + L.idx1),
                                    (int32_t *)(w + L.idx2), (float4 *)(w + L.grp1), (float4 *)(w + L.grp2),
                                    (uint32_t *)(w + L.pmax), (unsigned *)(w + L.histg),
                                    small ? (uint32_t *)(w + L.ctrl) : nullptr, (int)(L.ctrl_bytes / 4),  // (large clouds: cleared by pts_records_kernel)
-                                   B, N, M, s);
+                                   B, N, M, count_x, count_y, s);
     }
     if (rc) return rc;
     const int nsgmax = (nmax + SGT - 1) / SGT;
     const ChamTick tick = {(uint32_t *)(w + L.ctrl), (uint32_t *)(w + L.ctrl) + 32, 64, 32};
+    if (values) {  // a ragged batch: the grid stays that of the capacities, patches beyond a sample leave through the tickets
+        hipLaunchKernelGGL(chamfer_tree_counted_kernel, dim3((unsigned)(2 * B), (unsigned)nsgmax), dim3(64 * NWV), 0, s,
+                           (const float4 *)(w + L.p0s1), (const float4 *)(w + L.p0s2), (const float4 *)(w + L.grp1),
+                           (const float4 *)(w + L.grp2), (const float *)(w + L.apart), L.nblk, (unsigned long long *)best_x,
+                           (unsigned long long *)best_y, (double *)(w + L.partial), B, N, M, tick, (double *)(w + L.gpart),
+                           values, value, count_x, count_y);
+        RRL_LAUNCH_CHECK();
+        return 0;
+    }
 #define RRL_NN_LAUNCH(COUNT)                                                                                     \
     hipLaunchKernelGGL((chamfer_tree_kernel<COUNT, false>), dim3((unsigned)(2 * B), (unsigned)nsgmax), dim3(64 * NWV), 0, \
                        s, (const float4 *)(w + L.p0s1), (const float4 *)(w + L.p0s2),                            \
@@ -198,6 +222,29 @@ extern "C" int rrl_chamfer_tree_fwd_ex(const float *x, const float *y, void *ws,
 #undef RRL_NN_LAUNCH
     RRL_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int rrl_chamfer_tree_fwd_ex(const float *x, const float *y, void *ws, size_t ws_bytes, uint64_t *best_x,
+                                       uint64_t *best_y, float *value, int B, int N, int M, const int32_t *order_x,
+                                       const int32_t *order_y, uint64_t *counters, long long counter_rows, void *stream) {
+    if (!x || !y || !ws || !best_x || !best_y || !value || B <= 0 || N <= 0 || M <= 0) return RRL_E_ARG;
+    if ((N > M ? N : M) > rrl_sort_capacity() || B > 32767) return RRL_E_ARG;
+    const ChamLayout L(B, N, M);
+    if (ws_bytes < L.total) return RRL_E_WS;
+    return chamfer_tree_launches(x, y, nullptr, nullptr, ws, L, best_x, best_y, nullptr, value, B, N, M, order_x, order_y,
+                                 (unsigned long long *)counters, counters ? counter_rows : 0, stream);  // (NULL: the plain kernel)
+}
+// Ragged batches (include/rrl.h): per-sample counts in one call.  Every refusal on the host, before any launch.
+extern "C" int rrl_chamfer_tree_fwd_counted(const float *x, const float *y, const int32_t *count_x, const int32_t *count_y,
+                                            void *ws, size_t ws_bytes, uint64_t *best_x, uint64_t *best_y, float *values,
+                                            float *value, int B, int N, int M, const int32_t *order_x,
+                                            const int32_t *order_y, void *stream) {
+    if (!x || !y || !ws || !best_x || !best_y || !values || B <= 0 || N <= 0 || M <= 0) return RRL_E_ARG;
+    if ((count_x == nullptr) != (count_y == nullptr) || (order_x == nullptr) != (order_y == nullptr)) return RRL_E_ARG;
+    if ((N > M ? N : M) > rrl_sort_capacity() || B > 32767) return RRL_E_ARG;  // (no counted brute-force kernel)
+    const ChamLayout L(B, N, M);
+    if (ws_bytes < L.total) return RRL_E_WS;
+    return chamfer_tree_launches(x, y, count_x, count_y, ws, L, best_x, best_y, values, value, B, N, M, order_x, order_y,
+                                 nullptr, 0, stream);
 }
 extern "C" int rrl_chamfer_tree_fwd(const float *x, const float *y, void *ws, size_t ws_bytes, uint64_t *best_x,
                                     uint64_t *best_y, float *value, int B, int N, int M, void *stream) {

@@ -144,7 +144,12 @@ struct ChamLds {
 // The walk of one workgroup (bx = 2 sample + direction, by = patch; gx, gy = the walk's grid): the kernel below, and --
 // round 4b -- the rider of the culled scan's launch in the demo epoch (IDX = true with pm1 == NULL: max |P|^2 of the target
 // then comes from the loss workspace's partial rows `apart`, because that launch's scan is still rebuilding PMAX).
-template <bool COUNT, bool IDX>
+// RAG = true (rrl_chamfer_tree_fwd_counted, a ragged batch): cntx / cnty [B] hold the points sample b really has (NULL: the
+// capacity); N, M stay the strides of every array.  A sample with an empty cloud has no minima in either direction.  The
+// patches -- and the lanes of the boundary patch -- beyond a sample's queries write all-ones keys to their own rows of the
+// capacity and take the ticket path with a sum of +0.0; the finishing wavefront also writes values[b] and divides by the
+// denominators it adds up from the counts.  The other instantiations contain none of this.
+template <bool COUNT, bool IDX, bool RAG = false>
 __device__ __forceinline__ void chamfer_tree_body(
     ChamLds &lds_, const float4 *__restrict__ p0s1, const float4 *__restrict__ p0s2, const float4 *__restrict__ grp1,
     const float4 *__restrict__ grp2, const float *__restrict__ apart, int nblk,
@@ -152,7 +157,8 @@ __device__ __forceinline__ void chamfer_tree_body(
     double *__restrict__ partial, int B, int N, int M, unsigned long long *__restrict__ counters, long long counter_rows,
     const int32_t *__restrict__ idx1, const int32_t *__restrict__ idx2, const uint32_t *__restrict__ pm1,
     const uint32_t *__restrict__ pm2, const ChamTick tk_, double *__restrict__ gpart, float *__restrict__ value, double denom,
-    const int bx, const int by, const int gx, const int gy, const float *__restrict__ apart_tar = nullptr) {
+    const int bx, const int by, const int gx, const int gy, const float *__restrict__ apart_tar = nullptr,
+    const int32_t *__restrict__ cntx = nullptr, const int32_t *__restrict__ cnty = nullptr, float *__restrict__ values = nullptr) {
     unsigned long long (&s_best)[64] = lds_.s_best;
     float4 (&s_q)[64] = lds_.s_q;
     float4 (&s_rec)[NWV][CHK * LROW] = lds_.s_rec;
@@ -165,8 +171,16 @@ __device__ __forceinline__ void chamfer_tree_body(
     // XCD-aware: workgroups go to the 8 XCDs round-robin by linear id; with (sample, direction) on the fast
     // index every XCD's L2 holds the records and trees of 2 B / 8 of the (cloud pair, direction) combinations only
     const int b = bx >> 1, dir = bx & 1;
-    const int nq = dir ? M : N, nt = dir ? N : M;
-    const int nsgq = (nq + SGT - 1) / SGT, nsgt = (nt + SGT - 1) / SGT;
+    const int capq = dir ? M : N, capt = dir ? N : M;  // capacities: the strides
+    int nq = capq, nt = capt;                          // the sample's queries and targets (workgroup-uniform)
+    if constexpr (RAG) {  // two scalar loads
+        const int cx = rrl_rows(cntx, b, N), cy = rrl_rows(cnty, b, M);
+        const bool live = cx > 0 && cy > 0;
+        nq = live ? (dir ? cy : cx) : 0;
+        nt = live ? (dir ? cx : cy) : 0;
+    }
+    const int nsgq = (nq + SGT - 1) / SGT, nsgt = (nt + SGT - 1) / SGT;  // extents ...
+    const int ssgq = RAG ? (capq + SGT - 1) / SGT : nsgq, ssgt = RAG ? (capt + SGT - 1) / SGT : nsgt;  // ... and strides, in supergroups
     const int sgq = by;
     double mine = 0.0;
     unsigned c_sg = 0, c_gt = 0, c_ge = 0, c_pairs = 0;
@@ -175,17 +189,17 @@ __device__ __forceinline__ void chamfer_tree_body(
     tk[0] = RRL_NOW();
     const long long wall0 = COUNT ? (long long)wall_clock64() : 0ll;
     if (sgq < nsgq) {  // workgroup-uniform
-        const float4 *Q = (dir ? p0s2 : p0s1) + (size_t)b * nsgq * SGT;
-        const float4 *treeQ = (dir ? grp2 : grp1) + (size_t)b * nsgq * NODE;
+        const float4 *Q = (dir ? p0s2 : p0s1) + (size_t)b * ssgq * SGT;
+        const float4 *treeQ = (dir ? grp2 : grp1) + (size_t)b * ssgq * NODE;
         NNWave w;
-        w.T = (dir ? p0s1 : p0s2) + (size_t)b * nsgt * SGT;
-        w.tree = (dir ? grp1 : grp2) + (size_t)b * nsgt * NODE;
+        w.T = (dir ? p0s1 : p0s2) + (size_t)b * ssgt * SGT;
+        w.tree = (dir ? grp1 : grp2) + (size_t)b * ssgt * NODE;
         w.nt = nt;
         const int qi = sgq * SGT + lane;
         w.valid = qi < nq;
         const float4 qr = Q[qi];  // pad records exist up to the supergroup boundary
-        const int32_t *idxT = IDX ? (dir ? idx1 : idx2) + (size_t)b * nsgt * SGT : nullptr;
-        const int qorig = IDX ? ((dir ? idx2 : idx1) + (size_t)b * nsgq * SGT)[qi] : __float_as_int(qr.w);
+        const int32_t *idxT = IDX ? (dir ? idx1 : idx2) + (size_t)b * ssgt * SGT : nullptr;
+        const int qorig = IDX ? ((dir ? idx2 : idx1) + (size_t)b * ssgq * SGT)[qi] : __float_as_int(qr.w);
         // a staged target record carries its original index in .w
         auto target = [&](int pos) {
             float4 r = w.T[pos];
@@ -351,8 +365,16 @@ __device__ __forceinline__ void chamfer_tree_body(
             const bool qnan = (w.qx != w.qx) || (w.qy != w.qy) || (w.qz != w.qz);
             if (qnan || tnan)  // torch.min propagates NaN
                 w.best = ((unsigned long long)0x7fc00000u << 32) | (unsigned)(w.best & 0xffffffffu);
-            (dir ? best_y : best_x)[(size_t)b * nq + qorig] = w.best;
+            (dir ? best_y : best_x)[(size_t)b * capq + qorig] = w.best;
             mine = (double)__uint_as_float((unsigned)(w.best >> 32));
+        }
+        if constexpr (RAG) {  // the boundary patch: its lanes beyond the sample's queries own the absent rows of the same index
+            if (wv == 0 && !w.valid && qi < capq) (dir ? best_y : best_x)[(size_t)b * capq + qi] = ~0ull;
+        }
+    } else {
+        if constexpr (RAG) {  // a patch beyond the sample's queries: all-ones keys within the capacity, then the ticket path
+            const int qi = sgq * SGT + lane;
+            if (wv == 0 && qi < capq) (dir ? best_y : best_x)[(size_t)b * capq + qi] = ~0ull;
         }
     }
     if constexpr (COUNT) {
@@ -422,6 +444,23 @@ __device__ __forceinline__ void chamfer_tree_body(
     acc = 0.0;
     for (int i = lane; i < ngrp; i += 64) acc += ld64(&gpart[i]);
     const double tot = wave_total(acc);
+    if constexpr (RAG) {  // per-sample means and the denominators, from the counts: samples lane-strided, fixed order
+        double den = 0.0;
+        for (int i = lane; i < ngrp / 2; i += 64) {
+            const int cx = rrl_rows(cntx, i, N), cy = rrl_rows(cnty, i, M);
+            const bool live = cx > 0 && cy > 0;
+            const double d = live ? (double)(cx + cy) : 0.0;
+            const double s2 = ld64(&gpart[2 * i]) + ld64(&gpart[2 * i + 1]);
+            values[i] = live ? (float)(s2 / d) : 0.0f;
+            den += d;
+        }
+        const double dtot = wave_total(den);  // integers: exact
+        if (lane == 0) {
+            if (value != nullptr) value[0] = dtot > 0.0 ? (float)(tot / dtot) : 0.0f;
+            __hip_atomic_store(tk_.top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return;
+    }
     if (lane == 0) {
         value[0] = (float)(tot / denom);
         __hip_atomic_store(tk_.top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

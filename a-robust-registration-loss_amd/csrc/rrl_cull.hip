@@ -547,8 +547,12 @@ __global__ __launch_bounds__(1024) void tri_sort_kernel(const BuildArgs a) {
     const int chunk = (int)blockIdx.x % nch, cb = (int)blockIdx.x / nch;
     const int cloud = cb >= B ? 1 : 0, b = cb - cloud * B;
     const int ncap = cloud ? a.M : a.N;                  // capacity of the cloud: the stride of its arrays
-    const int nfull = RAW ? ncap : rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);  // records of the whole cloud (a ragged batch: this sample's)
+    const int nfull = rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);  // records of the whole cloud (a ragged batch: this sample's)
     const int base0 = chunk * (1024 * NPT);              // first record of the chunk (multiple of 64)
+    if constexpr (RAW) {  // the Chamfer walk's arrival counters (next launch): in front of the return -- a ragged sample may be empty
+        if (a.zwords != nullptr && blockIdx.x == 0 && blockIdx.y == 0)
+            for (int i = threadIdx.x; i < a.nzwords; i += 1024) a.zwords[i] = 0u;
+    }
     if (base0 >= nfull) return;                          // uniform: the smaller cloud (or sample) has fewer chunks
     const int n = min(1024 * NPT, nfull - base0);        // records of this chunk
     const int ngf = (ncap + GRP - 1) / GRP, nsgf = (ncap + SGT - 1) / SGT;
@@ -566,15 +570,17 @@ __global__ __launch_bounds__(1024) void tri_sort_kernel(const BuildArgs a) {
     __shared__ unsigned s_bw[2][64]; // their records per (pass k, wavefront): exclusive prefix in index order
     if (tid < 64) STAMPR(0);
     if (tid < 2) s_cb[tid] = -1;
-    if (a.zwords != nullptr && blockIdx.x == 0 && blockIdx.y == 0)  // the Chamfer walk's arrival counters (next launch)
-        for (int i = tid; i < a.nzwords; i += 1024) a.zwords[i] = 0u;
+    if constexpr (!RAW) {
+        if (a.zwords != nullptr && blockIdx.x == 0 && blockIdx.y == 0)  // the Chamfer walk's arrival counters (next launch)
+            for (int i = tid; i < a.nzwords; i += 1024) a.zwords[i] = 0u;
+    }
 
     // ---- AABB of the P0s and max |P|^2 from the per-workgroup partials of tri_records_kernel
     float4 rec[NPT];
     float bb[7];
     if constexpr (RAW) {
         __shared__ __attribute__((aligned(16))) float s_bb[16][8];
-        const float *pts = (cloud ? a.tri2 : a.tri1) + (size_t)b * n * 3;
+        const float *pts = (cloud ? a.tri2 : a.tri1) + (size_t)b * ncap * 3;  // (the capacity is the stride; n: this sample's points)
         float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY}, p2 = 0.0f;
         bool bad = false;
         // the 12-byte rows are fetched as one flat, coalesced stream of 16-byte loads into the (still
@@ -842,9 +848,10 @@ __device__ __forceinline__ unsigned grid_cell(const CellGrid &g, const float4 r)
 __global__ __launch_bounds__(256) void big_hist_kernel(const BuildArgs a, unsigned *__restrict__ histg) {
     __shared__ float red[4][8];
     const int cloud = blockIdx.z, b = blockIdx.y;
-    const int n = cloud ? a.M : a.N;
+    const int ncap = cloud ? a.M : a.N;                           // the capacity: the stride of the cloud's arrays
+    const int n = rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);     // the sample's own records (uniform)
     if ((int)blockIdx.x * 256 >= n) return;
-    const int ng = (n + GRP - 1) / GRP;
+    const int ng = (ncap + GRP - 1) / GRP;
     const float4 *crec = (cloud ? a.crec2 : a.crec1) + (size_t)b * ng * GRP;
     const CellGrid g = load_grid(a, cloud, b, n, red);
     if (blockIdx.x == 0 && threadIdx.x == 0) a.pmax[cloud * a.B + b] = __float_as_uint(g.p2);
@@ -857,13 +864,15 @@ __global__ __launch_bounds__(256) void big_scatter_kernel(const BuildArgs a, uns
     __shared__ unsigned base[SORT_CELLS];
     __shared__ unsigned wsum[4];
     const int cloud = blockIdx.z, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = cloud ? a.M : a.N;
+    const int ncap = cloud ? a.M : a.N;
+    const int n = rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);
     if ((int)blockIdx.x * 256 >= n) return;
-    const int ng = (n + GRP - 1) / GRP;
+    const int ng = (ncap + GRP - 1) / GRP;
     const float4 *crec = (cloud ? a.crec2 : a.crec1) + (size_t)b * ng * GRP;
-    const int npad = (n + SGT - 1) / SGT * SGT;
-    float4 *p0s = (cloud ? a.p0s2 : a.p0s1) + (size_t)b * npad;
-    int32_t *idx = (cloud ? a.idx2 : a.idx1) + (size_t)b * npad;
+    const int npad = (n + SGT - 1) / SGT * SGT;                   // the sample's records end with its last supergroup
+    const size_t row = (size_t)b * ((ncap + SGT - 1) / SGT * SGT);
+    float4 *p0s = (cloud ? a.p0s2 : a.p0s1) + row;
+    int32_t *idx = (cloud ? a.idx2 : a.idx1) + row;
     unsigned *cnt = histg + ((size_t)(cloud * a.B + b) * 2) * SORT_CELLS, *cur = cnt + SORT_CELLS;
     const int f = blockIdx.x * 256 + tid;
     const float4 r = f < n ? crec[f] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // in flight during the scan
@@ -892,12 +901,13 @@ __global__ __launch_bounds__(256) void big_scatter_kernel(const BuildArgs a, uns
 
 __global__ __launch_bounds__(256) void big_sphere_kernel(const BuildArgs a) {
     const int cloud = blockIdx.z, b = blockIdx.y;
-    const int n = cloud ? a.M : a.N;
-    const int nsg = (n + SGT - 1) / SGT;
+    const int ncap = cloud ? a.M : a.N;
+    const int n = rrl_rows(cloud ? a.cnt2 : a.cnt1, b, ncap);
+    const int nsg = (n + SGT - 1) / SGT, nsgf = (ncap + SGT - 1) / SGT;  // supergroups with nodes, and the stride
     const int hh = blockIdx.x * 256 + threadIdx.x;  // 256 = 32 whole supergroups
     if (hh >= nsg * 2 * SGG) return;
-    const float4 *r = (cloud ? a.p0s2 : a.p0s1) + (size_t)b * nsg * SGT;
-    half_tree([&](int s_) { return r[s_]; }, hh, n, (cloud ? a.grp2 : a.grp1) + (size_t)b * nsg * NODE);
+    const float4 *r = (cloud ? a.p0s2 : a.p0s1) + (size_t)b * nsgf * SGT;
+    half_tree([&](int s_) { return r[s_]; }, hh, n, (cloud ? a.grp2 : a.grp1) + (size_t)b * nsgf * NODE);
 }
 
 typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load
@@ -1116,7 +1126,8 @@ int rrl_launch_tri_build(const RrlCall &o, const float *tri1, const float *tri2,
     // ~27 triangles per cell at N = 16384, in arbitrary order, so its groups are no tighter).
     // RRL_SORT_WIDE=1 keeps the wide sort (experiments / tests; it still serves the Chamfer path).
     const char *wide_env = getenv("RRL_SORT_WIDE");
-    // (a ragged batch always takes the chunked sort: the wide kernels know one size per call)
+    // (a ragged batch always takes the chunked sort: the wide kernels read counts too -- for the Chamfer path,
+    //  rrl_launch_cloud_sort -- but the loss build's ragged contract was only ever tested on the chunked one)
     const bool chunked = nmax > 4096 && (o.ragged() || !(wide_env && atoi(wide_env) != 0));
     const size_t ngps = nmax <= 4096 ? ngpmax : (size_t)(4096 / GRP);
     const int parts = sort_parts((int)(ngps / SGG), o.sort_parts);
@@ -1159,10 +1170,12 @@ int rrl_launch_pmax_from_partials(const RrlCall &o, int clouds) {
 // kernels as above.  Clouds of <= 4096 points given as raw1 / raw2 ([B][n][3]) are sorted straight from
 // the points (tri_sort_kernel<4, true>: records, AABB and NaN flag built in the kernel); otherwise the
 // (x, y, z, w) records (CREC layout) and per-256-record AABB partials (APART layout, nblk rows per cloud
-// and sample) must already exist and histg (cleared by the caller) is used beyond 4096 records.
+// and sample) must already exist and histg (cleared by the caller) is used beyond 4096 records.  cnt1 / cnt2: NULL, or the
+// points sample b really has (N, M stay the strides; pads sort last, nodes only for a sample's own supergroups).
 int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, float4 *crec2, float *apart, int nblk,
                           float4 *p0s1, float4 *p0s2, int32_t *idx1, int32_t *idx2, float4 *grp1, float4 *grp2,
-                          uint32_t *pmax, unsigned *histg, uint32_t *zwords, int nzwords, int B, int N, int M, hipStream_t s) {
+                          uint32_t *pmax, unsigned *histg, uint32_t *zwords, int nzwords, int B, int N, int M,
+                          const int32_t *cnt1, const int32_t *cnt2, hipStream_t s) {
     const int nmax = M > N ? M : N;
     if (nmax > SORT_CAP || B <= 0 || nmax <= 0) return RRL_E_ARG;
     const size_t ngpmax = (size_t)(nmax + SGT - 1) / SGT * SGG;
@@ -1176,6 +1189,7 @@ int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, f
     a.pmax = pmax;
     a.zwords = zwords; a.nzwords = nzwords;
     a.B = B; a.N = N; a.M = M; a.Bt = 0;
+    a.cnt1 = cnt1; a.cnt2 = cnt2;  // a ragged batch (rrl_chamfer_tree_fwd_counted): the points each sample has, or NULL
     // (the chunked sort of rrl_launch_tri_build was tried here too: a nearest-neighbour walk evaluates twice the
     //  pairs on chunked clouds -- 63.0 -> 64.4 us at N = M = 16384, 188 -> 380 at 65536: whole-cloud order stays)
     if (nmax <= 4096) {

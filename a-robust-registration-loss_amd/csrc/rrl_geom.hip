@@ -704,6 +704,10 @@ extern "C" int rrl_log_row(const float *loss, const float *value, const int32_t 
 }
 
 // d mean / d x_i: every minimum contributes 2 (x_i - y_j) / (B (N + M)) to its two end points
+// RAG = true (rrl_chamfer_bwd_counted, a ragged batch): gval [B] is per sample and sample b's scale is
+// 2 gval[b] / (cx_b + cy_b) with its own counts (cntx / cnty, or NULL: the capacities); the threads of absent rows and of
+// samples with an empty cloud do nothing (their keys are all-ones).
+template <bool RAG>
 __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float *__restrict__ x,
                                                           const float *__restrict__ y,
                                                           const unsigned long long *__restrict__ bx,
@@ -711,14 +715,27 @@ __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float *__restric
                                                           const float *__restrict__ gval,
                                                           float *__restrict__ gx,
                                                           float *__restrict__ gy, int B, int N,
-                                                          int M) {
+                                                          int M, const int32_t *__restrict__ cntx,
+                                                          const int32_t *__restrict__ cnty) {
     const int b = blockIdx.y;
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= N + M) return;
+    int cx = N, cy = M;
+    if constexpr (RAG) {
+        cx = rrl_rows(cntx, b, N); cy = rrl_rows(cnty, b, M);  // uniform
+        if (cx == 0 || cy == 0) return;
+        if (t < N ? t >= cx : t - N >= cy) return;
+    }
     int i, j;
     if (t < N) { i = t; j = (int)(unsigned)bx[(size_t)b * N + i]; }
     else { j = t - N; i = (int)(unsigned)by[(size_t)b * M + j]; }
-    const float sc = 2.0f * gval[0] / ((float)B * (float)(N + M));
+    float sc;
+    if constexpr (RAG) {
+        i = min(max(i, 0), cx - 1); j = min(max(j, 0), cy - 1);  // memory safety only: a present row's key holds a present index
+        sc = 2.0f * gval[b] / (float)(cx + cy);
+    } else {
+        sc = 2.0f * gval[0] / ((float)B * (float)(N + M));
+    }
     const float *xp = x + ((size_t)b * N + i) * 3, *yp = y + ((size_t)b * M + j) * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -735,9 +752,24 @@ extern "C" int rrl_chamfer_bwd(const float *x, const float *y, const uint64_t *b
     if (B == 0) return 0;
     // an empty cloud has no minima: the forward refuses it, so no keys exist whose index the kernel could follow
     if (N == 0 || M == 0) return RRL_E_ARG;
-    hipLaunchKernelGGL(chamfer_bwd_kernel, dim3((unsigned)((N + M + 255) / 256), (unsigned)B), dim3(256),
+    hipLaunchKernelGGL(chamfer_bwd_kernel<false>, dim3((unsigned)((N + M + 255) / 256), (unsigned)B), dim3(256),
                        0, (hipStream_t)stream, x, y, (const unsigned long long *)best_x,
-                       (const unsigned long long *)best_y, grad_value, gx, gy, B, N, M);
+                       (const unsigned long long *)best_y, grad_value, gx, gy, B, N, M, (const int32_t *)nullptr,
+                       (const int32_t *)nullptr);
+    RRL_LAUNCH_CHECK();
+    return 0;
+}
+// Backward of rrl_chamfer_tree_fwd_counted (include/rrl.h): grad_values [B], per-sample scales from the counts
+extern "C" int rrl_chamfer_bwd_counted(const float *x, const float *y, const uint64_t *best_x, const uint64_t *best_y,
+                                       const float *grad_values, const int32_t *count_x, const int32_t *count_y, float *gx,
+                                       float *gy, int B, int N, int M, void *stream) {
+    if (!x || !y || !best_x || !best_y || !grad_values || B < 0 || N < 0 || M < 0) return RRL_E_ARG;
+    if ((count_x == nullptr) != (count_y == nullptr)) return RRL_E_ARG;
+    if (B > 32767 || N == 0 || M == 0 || (N > M ? N : M) > rrl_sort_capacity()) return RRL_E_ARG;  // what the forward refuses
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(chamfer_bwd_kernel<true>, dim3((unsigned)((N + M + 255) / 256), (unsigned)B), dim3(256),
+                       0, (hipStream_t)stream, x, y, (const unsigned long long *)best_x,
+                       (const unsigned long long *)best_y, grad_values, gx, gy, B, N, M, count_x, count_y);
     RRL_LAUNCH_CHECK();
     return 0;
 }

@@ -186,7 +186,8 @@ int rrl_launch_pmax_from_partials(const RrlCall &o, int clouds);
 int rrl_cull_scan_can_fuse(const RrlCall &o);
 int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, float4 *crec2, float *apart, int nblk,
                           float4 *p0s1, float4 *p0s2, int32_t *idx1, int32_t *idx2, float4 *grp1, float4 *grp2,
-                          uint32_t *pmax, unsigned *histg, uint32_t *zwords, int nzwords, int B, int N, int M, hipStream_t s);
+                          uint32_t *pmax, unsigned *histg, uint32_t *zwords, int nzwords, int B, int N, int M,
+                          const int32_t *cnt1, const int32_t *cnt2, hipStream_t s);
 // the rigid backward behind the scatter (rrl_geom.hip)
 int rrl_fused_backward(int B, int N, int M);
 int rrl_launch_reg_bwd(const RrlCall &o, const float *src, const float *R, float *grad_src, float *gR, float *gt,

@@ -134,10 +134,14 @@ def _scan_mode(mode):
     return mode
 
 
-def chamfer_dist(points_x, points_y):
+def chamfer_dist(points_x, points_y, *, counts_x=None, counts_y=None, per_sample=False):
     """Symmetric Chamfer monitor: mean over all B*(M+N) nearest squared distances
-    (code/loss.py:236-252).  Scalar tensor on points_x's device, differentiable."""
-    return _ops.chamfer(points_x, points_y)
+    (code/loss.py:236-252).  Scalar tensor on points_x's device, differentiable.
+    Keyword-only extras (not in the reference): counts_x / counts_y (B,) -- a RAGGED batch in one call: sample b is the pair
+    points_x[b, :counts_x[b]], points_y[b, :counts_y[b]], the rows beyond a count are never read as data and get zero
+    gradient, and the scalar is the mean over all present minima --; per_sample=True returns the (B,) distances of the
+    pairs, each what this function returns for that pair alone (ops.chamfer)."""
+    return _ops.chamfer(points_x, points_y, counts_x=counts_x, counts_y=counts_y, per_sample=per_sample)
 
 
 # ------------------------------------------------------------------------------- sampler

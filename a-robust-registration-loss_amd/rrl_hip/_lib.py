@@ -68,6 +68,8 @@ _SIGS = {
     "rrl_chamfer_tree_fwd": [_P, _P, _P, _Z, _P, _P, _P, _I, _I, _I, _P],
     "rrl_chamfer_from_loss": [_P, _P, _Z, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P],
     "rrl_chamfer_tree_fwd_ex": [_P, _P, _P, _Z, _P, _P, _P, _I, _I, _I, _P, _P, _P, _c.c_longlong, _P],
+    "rrl_chamfer_tree_fwd_counted": [_P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "rrl_chamfer_bwd_counted": [_P] * 9 + [_I] * 3 + [_P],
     "rrl_chamfer_from_loss_ex": [_P, _P, _Z, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _c.c_longlong, _P],
     "rrl_aabb": [_P, _P, _I, _I, _P],
     "rrl_aabb_counted": [_P, _P, _P, _I, _I, _P],

@@ -404,7 +404,8 @@ def cloud_order(tri, counts=None):
     return order
 
 
-def _check_order(order, B, n, dev, name):
+def _check_order(order, B, n, dev, name, counts=None):
+    """counts: the (B,) device counts of a ragged cloud -- only a row's first counts[b] entries are a permutation then."""
     if order is None:
         return None
     if not (isinstance(order, torch.Tensor) and order.dtype == torch.int32 and order.is_cuda and order.device == dev
@@ -413,9 +414,13 @@ def _check_order(order, B, n, dev, name):
                          f"ops.cloud_order on the op's GPU ({dev}); got "
                          + (f"{order.dtype} {tuple(order.shape)} on {order.device}" if isinstance(order, torch.Tensor) else repr(type(order))))
     if ORDER_DEBUG and n > 0:  # RRL_ORDER_DEBUG=1: a host-side permutation check (synchronises; debugging only)
-        srt = torch.sort(order[:, :n].to(torch.int64), dim=1).values
-        if not bool((srt == torch.arange(n, device=dev)).all()):
-            raise ValueError(f"{name}: every row's first n entries must be a permutation of [0, n)")
+        pos = torch.arange(n, device=dev)
+        head = order[:, :n].to(torch.int64)
+        if counts is not None:  # entries beyond a count are not read: they sort last
+            head = torch.where(pos[None, :] < counts.clamp(0, n).to(torch.int64)[:, None], head, pos[None, :].expand(B, n))
+        srt = torch.sort(head, dim=1).values
+        if not bool((srt == pos).all()):
+            raise ValueError(f"{name}: every row's first n entries (a ragged cloud: counts[b]) must be a permutation of [0, n)")
     return order
 
 
@@ -1673,11 +1678,101 @@ class _Chamfer(torch.autograd.Function):
                 gy.to(ctx.devs[1]) if gy is not None else None, None, None)
 
 
-def chamfer(x, y, order_x=None, order_y=None):
+class _ChamferCounted(torch.autograd.Function):
+    """The ragged Chamfer distance (include/rrl.h rrl_chamfer_tree_fwd_counted): ONE node for both outputs -- values (B,)
+    per sample and the scalar value over all present minima --, ONE rrl_chamfer_bwd_counted call backwards."""
+
+    @staticmethod
+    def forward(ctx, x, y, cx, cy, order_x, order_y):
+        dev = cx.device
+        xs, ys = _prep(x, "points_x", 3, dev), _prep(y, "points_y", 3, dev)
+        B, N, _ = xs.shape
+        M = ys.shape[1]
+        bx = torch.empty(B, N, dtype=torch.int64, device=dev)
+        by = torch.empty(B, M, dtype=torch.int64, device=dev)
+        vals, val = torch.empty(B, device=dev), torch.empty(1, device=dev)
+        nb = _scratch_size("rrl_chamfer_workspace_bytes", B, N, M)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ox, oy = _check_order(order_x, B, N, dev, "order_x", cx), _check_order(order_y, B, M, dev, "order_y", cy)
+        _run(dev, "rrl_chamfer_tree_fwd_counted", _p(xs), _p(ys), _p(cx), _p(cy), _p(ws), nb, _p(bx), _p(by), _p(vals), _p(val),
+             B, N, M, _p(ox), _p(oy))
+        ctx.save_for_backward(xs, ys, bx, by, cx, cy)
+        ctx.devs = (x.device, y.device)
+        ctx.mark_non_differentiable(bx, by)
+        return vals.to(x.device), val.reshape(()).to(x.device), bx, by
+
+    @staticmethod
+    def backward(ctx, gvals, gval, _gbx, _gby):
+        xs, ys, bx, by, cx, cy = ctx.saved_tensors
+        B, N, _ = xs.shape
+        M = ys.shape[1]
+        dev = xs.device
+        g = torch.zeros(B, device=dev)
+        if gvals is not None:
+            g = g + gvals.detach().to(device=dev, dtype=torch.float32).reshape(B)
+        if gval is not None:  # d value / d values[b] = (cx_b + cy_b) / sum over the samples that count -- on the device
+            n = torch.where((cx > 0) & (cy > 0), cx.clamp(0, N) + cy.clamp(0, M), torch.zeros_like(cx)).to(torch.float32)
+            g = g + gval.detach().to(device=dev, dtype=torch.float32).reshape(()) * n / n.sum()
+        g = g.contiguous()
+        gx = torch.zeros_like(xs) if ctx.needs_input_grad[0] else None
+        gy = torch.zeros_like(ys) if ctx.needs_input_grad[1] else None
+        _run(dev, "rrl_chamfer_bwd_counted", _p(xs), _p(ys), _p(bx), _p(by), _p(g), _p(cx), _p(cy), _p(gx), _p(gy), B, N, M)
+        return (gx.to(ctx.devs[0]) if gx is not None else None,
+                gy.to(ctx.devs[1]) if gy is not None else None, None, None, None, None)
+
+
+def _chamfer_counted(x, y, counts_x, counts_y, order_x=None, order_y=None):
+    """(values (B,), value (), best_x (B, N), best_y (B, M)) of the ragged call -- the keys as int64 views of the u64 keys
+    (distance bits << 32 | argmin; -1 = all-ones on the rows beyond a count); every ValueError before anything touches a GPU."""
+    if (counts_x is None) != (counts_y is None):
+        raise ValueError("chamfer: counts_x and counts_y come together (a ragged batch gives the points of BOTH clouds of "
+                         "every sample); for one ragged cloud pass the other's counts at its capacity")
+    if (order_x is None) != (order_y is None):
+        raise ValueError("chamfer: order_x and order_y come together (ops.cloud_order(tri, counts=) of both clouds), or neither")
+    for t, name in ((x, "points_x"), (y, "points_y")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError(f"chamfer_dist expects (B, M, 3) and (B, N, 3); {name} is not")
+    if x.shape[0] != y.shape[0]:
+        raise ValueError("chamfer_dist expects (B, M, 3) and (B, N, 3)")
+    B, N, M = x.shape[0], x.shape[1], y.shape[1]
+    on_gpu = [t.device for t in (x, y, counts_x, counts_y) if isinstance(t, torch.Tensor) and t.is_cuda]
+    # host counts: type, shape and range are judged here (dev = None: nothing is uploaded yet)
+    for c, cap, name in ((counts_x, N, "counts_x"), (counts_y, M, "counts_y")):
+        if c is not None and not (isinstance(c, torch.Tensor) and c.is_cuda):
+            check_counts(c, B, cap, None, name)
+    if B < 1 or B > 32767 or min(N, M) < 1:
+        raise ValueError(f"chamfer with counts / per_sample: 1 <= B <= 32767 samples and capacities >= 1; got {(B, N, M)} -- "
+                         "evaluate the pairs with ops.chamfer one after the other")
+    if max(N, M) > sort_capacity():
+        raise ValueError(f"chamfer with counts / per_sample: capacities beyond {sort_capacity()} points are not sorted and there "
+                         f"is no ragged brute-force kernel; got {(N, M)} -- evaluate each pair with ops.chamfer(x[b:b+1, :cx], "
+                         "y[b:b+1, :cy]) instead")
+    dev = on_gpu[0] if on_gpu else require_gpu()
+    if counts_x is None:  # per_sample alone: the same call with the counts at the capacities
+        cx = torch.full((B,), N, dtype=torch.int32, device=dev)
+        cy = torch.full((B,), M, dtype=torch.int32, device=dev)
+    else:
+        cx, cy = check_counts(counts_x, B, N, dev, "counts_x"), check_counts(counts_y, B, M, dev, "counts_y")
+    return _ChamferCounted.apply(x, y, cx, cy, order_x, order_y)
+
+
+def chamfer(x, y, order_x=None, order_y=None, *, counts_x=None, counts_y=None, per_sample=False):
     """chamfer_dist (code/loss.py:236-252) of x (B, N, 3), y (B, M, 3): scalar, differentiable.  order_x / order_y:
     ops.cloud_order of the two point clouds (or of the pseudo-triangles they are the first points of) in any rigid pose
-    -- both given, the per-call sort is skipped (same keys, same value)."""
-    return _Chamfer.apply(x, y, order_x, order_y)
+    -- both given, the per-call sort is skipped (same keys, same value).
+    counts_x / counts_y ((B,) int32 on the GPU -- taken as they are, never read back --, or a list / CPU tensor, validated
+    and uploaded): a RAGGED batch in one call (include/rrl.h rrl_chamfer_tree_fwd_counted).  N, M are capacities; sample b
+    is the pair x[b, :counts_x[b]], y[b, :counts_y[b]]; rows beyond a count are never read as data (any filler, NaN
+    included) and get zero gradient.  The scalar is the mean over ALL present minima (the reference's mean over the
+    concatenated lists); per_sample=True returns the (B,) means instead, each what chamfer returns for that pair alone (0
+    for a sample with an empty cloud).  Both are differentiable in x and y through one node; the orders then come from
+    ops.cloud_order(tri, counts=).  per_sample=True without counts: the counts are the capacities."""
+    if counts_x is None and counts_y is None and not per_sample:
+        return _Chamfer.apply(x, y, order_x, order_y)
+    vals, val, _, _ = _chamfer_counted(x, y, counts_x, counts_y, order_x, order_y)
+    return vals if per_sample else val
+
+
 
 
 def chamfer_from_state(state=None, keys=False):
@@ -1699,7 +1794,8 @@ def chamfer_from_state(state=None, keys=False):
     return (val.reshape(()), bx, by) if keys else val.reshape(())
 
 
-_RAGGED_CHAMFER = "evaluate the monitor per sample with ops.chamfer on the truncated clouds"
+_RAGGED_CHAMFER = ("evaluate the monitor in one call with ops.chamfer(..., counts_x=, counts_y=) on the clouds' first points "
+                   "(tri1[..., :3], tri2[..., :3] and the same counts)")
 
 
 def _chamfer_from_loss(st):

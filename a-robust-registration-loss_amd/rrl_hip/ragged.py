@@ -1,6 +1,6 @@
 """Ragged batches: lists of per-sample arrays -> the capacity-shaped tensors + counts that the batched entries take
 (ops.intersection_loss / registration_loss / LossStep / RegistrationStep, loss.batched_intersection_loss: counts1=,
-counts2=, nlines=; include/rrl.h rrl_opts.count1).  Host-side helpers (numpy / torch on the CPU): move the results to the
+counts2=, nlines=; include/rrl.h rrl_opts.count1) and the ragged Chamfer distance (pack_points -> ops.chamfer(counts_x=, counts_y=)).  Host-side helpers (numpy / torch on the CPU): move the results to the
 GPU with `.cuda()`.  A DataLoader collate_fn for items with `src_tri`, `tar_tri`, `lines` (and `kd_order` rows):
 
     def collate(items):
@@ -36,6 +36,12 @@ def pack_clouds(clouds, capacity=None, fill=0.0, multiple=1):
     """[(n_b, 9) pseudo-triangles] -> (tri (B, cap, 9) fp32, counts (B,) int32); cap = the largest n_b (or `capacity`),
     rounded up to `multiple`; rows beyond counts[b] hold `fill`."""
     return _pack(clouds, 9, capacity, fill, multiple, "pack_clouds")
+
+
+def pack_points(clouds, capacity=None, fill=0.0, multiple=1):
+    """[(n_b, 3) points] -> (pts (B, cap, 3) fp32, counts (B,) int32): the inputs of ops.chamfer(x, y, counts_x=, counts_y=)
+    / loss.chamfer_dist(..., counts_x=, counts_y=); cap and fill as in pack_clouds."""
+    return _pack(clouds, 3, capacity, fill, multiple, "pack_points")
 
 
 def pack_lines(lines, capacity=None, fill=0.0, multiple=1):

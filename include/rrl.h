@@ -755,6 +755,44 @@ int rrl_chamfer_from_loss_ex(void *ws_src, const void *ws_tar, size_t loss_ws_by
 int rrl_chamfer_bwd(const float *x, const float *y, const uint64_t *best_x,
                     const uint64_t *best_y, const float *grad_value, float *gx, float *gy, int B,
                     int N, int M, void *stream);
+/* RAGGED batches: the Chamfer distance of B pairs whose clouds differ in size, in ONE call (DESIGN.md "Ragged batches").
+ * x [B][N][3], y [B][M][3]: N, M are capacities and strides; count_x, count_y: DEVICE int32 [B], clamped by the kernels to
+ * [0, N] / [0, M] and never read on the host (no synchronisation; the call can be captured in a graph).  Sample b is the
+ * pair x[b][0 .. cx_b), y[b][0 .. cy_b).
+ *   absent rows  (beyond a count) are never interpreted: no nearest neighbour, no query, no NaN source, no tree node, no
+ *                term of any sum; their key rows best_x[b][cx_b ..], best_y[b][cy_b ..] are written as all-ones by the call.
+ *   present rows hold the keys of the uniform entries (distance bits << 32 | original index, first occurrence on ties):
+ *                bit-identical to the B = 1 call on the truncated clouds.
+ *   values [B]   values[b] = (sum of the sample's cx_b + cy_b minima) / (cx_b + cy_b): chamfer_dist of that pair alone.
+ *   value [1]    (may be NULL) the sum of ALL present minima / sum_b (cx_b + cy_b): the mean over the concatenated lists.
+ *   empty clouds a sample with cx_b = 0 or cy_b = 0 has no minima: values[b] = 0, all-ones keys, and it is left out of
+ *                value's numerator and denominator; if no sample counts, value = 0.
+ *   NaN          per sample and over present rows only: a NaN among the present TARGET points makes that direction's
+ *                minima NaN, a NaN query its own minimum; a NaN beyond a count is invisible.
+ * The sums are the fixed-order double sums of the uniform walk; the denominators are computed on the device by the
+ * wavefront that finishes the mean.  count_x == count_y == NULL: the counts are the capacities (keys and value are the bits
+ * of rrl_chamfer_tree_fwd, plus values).  order_x / order_y: both or neither; the layout of rrl_cloud_order_counted
+ * ([B][64 ceil(N / 64)], the first count[b] entries of a row a permutation of [0, count[b])); same bits as without.
+ * ws: rrl_chamfer_workspace_bytes(B, N, M).
+ * Who reads which count, and where a workgroup leaves: the records kernels and the sorts take a sample's rows from its own
+ * count (workgroups past them leave after the clearing of the histogram / the arrival counters, before their first load;
+ * pads sort last, tree nodes only for supergroups [0, ceil(count / 64))); the walk reads both counts of its sample -- two
+ * scalar loads --, a patch at or beyond ceil(count / 64) writes its all-ones keys and takes the ticket path with a sum of
+ * +0.0 (the grid and the arrival counts stay those of the capacities).
+ * Refusals, on the host and before any launch, in this order: RRL_E_ARG -- a NULL required pointer (x, y, ws, best_x,
+ * best_y, values), exactly one count pointer NULL, exactly one order given, B <= 0 or a negative size, N == 0 or M == 0,
+ * B > 32767, max(N, M) > the sort capacity (there is no counted brute-force kernel) --, then RRL_E_WS (a short workspace). */
+int rrl_chamfer_tree_fwd_counted(const float *x, const float *y, const int32_t *count_x, const int32_t *count_y, void *ws,
+                                 size_t ws_bytes, uint64_t *best_x, uint64_t *best_y, float *values, float *value, int B,
+                                 int N, int M, const int32_t *order_x, const int32_t *order_y, void *stream);
+/* Its backward, from the keys it left: accumulates into gx [B][N][3], gy [B][M][3] like rrl_chamfer_bwd (zero them first;
+ * either may be NULL).  grad_values [B]: the upstream gradient of values; sample b's minima are scaled by
+ * 2 grad_values[b] / (cx_b + cy_b).  (For the scalar value with upstream g: grad_values[b] = g (cx_b + cy_b) / sum.)  The
+ * threads of absent rows and of samples with an empty cloud do nothing: those gradient rows stay as they were (zero).
+ * RRL_E_ARG as the forward (required: x, y, best_x, best_y, grad_values); B == 0 is a no-op. */
+int rrl_chamfer_bwd_counted(const float *x, const float *y, const uint64_t *best_x, const uint64_t *best_y,
+                            const float *grad_values, const int32_t *count_x, const int32_t *count_y, float *gx, float *gy,
+                            int B, int N, int M, void *stream);
 
 /* ---- dense (line x triangle) tables of code/loss.py:68-112 ------------------------------- */
 /* What cal_intersection_batch2_points_with_line returns besides the expanded view of its input:
