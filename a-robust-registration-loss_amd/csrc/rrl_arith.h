@@ -1,8 +1,10 @@
-// rrl_arith.h -- the per-value arithmetic of the sparse stages, shared by the narrow pipeline (rrl_sparse.hip and its
-// .inc sections) and the wide one (rrl_wide.hip): weights, intersection points, triangle gathers and the Welsch term are
-// the same source in both, so the same inputs give the same bits.
+// rrl_arith.h -- the per-value arithmetic of the sparse stages, shared by the narrow pipeline (the rrl_stage_*.h kernels of
+// rrl_sparse.hip) and the wide one (rrl_wide.hip): weights, intersection points, triangle gathers, the Welsch term and the
+// fixed-point unit of the bucket sums are the same source in both, so the same inputs give the same bits.
 #pragma once
 #include "rrl_common.h"
+
+constexpr int FIX_SHIFT = 40;  // bucket sums in 2^-40 fixed point: order-independent, bit-deterministic
 
 // sqrt(dist_sq) of the three points of triangle f and the detached weights of
 // code/loss.py:92: w_k = d_k / ((d0 + d1) + d2).  Same arithmetic as the scan, so the

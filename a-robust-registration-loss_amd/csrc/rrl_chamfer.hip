@@ -275,9 +275,9 @@ extern "C" int rrl_chamfer_from_loss_ex(void *ws_src, const void *ws_tar, size_t
     char *w = (char *)ws;
     const int nmax = N > M ? N : M, nsgmax = (nmax + SGT - 1) / SGT;
     // arrival counters of the mean: words of the evaluation's own workspace that every forward leaves zero and that
-    // rewind themselves (MCTL[b][30 + direction] per group, MCTL[0][32] for the groups): any number of calls per forward
+    // rewind themselves (MCTL[b][RRL_MCTL_CHAM_GROUP + direction] per group, MCTL[0][RRL_MCTL_CHAM_TOP] for the groups): any number of calls per forward
     uint32_t *mctl = (uint32_t *)((char *)ws_src + lw.off[RRL_WS_MCTL]);
-    const ChamTick tick = {mctl + 32, mctl + 30, 64, 1};
+    const ChamTick tick = cham_tick_in_mctl(mctl);
 #define RRL_NN_LAUNCH(COUNT)                                                                                     \
     hipLaunchKernelGGL((chamfer_tree_kernel<COUNT, true>), dim3((unsigned)(2 * B), (unsigned)nsgmax), dim3(64 * NWV), 0, \
                        s, (const float4 *)lw.at<RRL_WS_P0S1>(ws_src), (const float4 *)lw.at<RRL_WS_P0S2>(ws_tar), \

@@ -123,6 +123,10 @@ struct ChamTick {
     uint32_t *top, *group;
     int stride_b, stride_d;
 };
+// ... of a walk on the LOSS workspace (rrl_chamfer_from_loss, the culled scan's rider): its MCTL rows lend them
+inline ChamTick cham_tick_in_mctl(uint32_t *mctl) {
+    return ChamTick{mctl + RRL_MCTL_CHAM_TOP, mctl + RRL_MCTL_CHAM_GROUP, RRL_MCTL_WORDS, 1};
+}
 
 // COUNT: executed-work counters (rrl_chamfer_counters): [0] patch-level leaf tests (lane-parallel),
 // [1] per-lane leaf sphere tests (wave x leaf), [2] (query, leaf) entries evaluated, [3] (query, target)

@@ -38,6 +38,9 @@ struct RrlRange {
 // captured hipGraph (the bench and the demo replay their step as one) memset nodes were observed
 // to race with the kernels that follow them on this stack -- the captured demo step
 // intermittently read half-initialised Chamfer keys until the memsets became a kernel.
+// (static kernels: every unit that includes this gets its own pair, used or not -- a unit that launches nothing defines
+//  RRL_NO_LAUNCH_UNIT first and then holds no kernel at all: rrl_call.hip)
+#ifndef RRL_NO_LAUNCH_UNIT
 static __global__ void rrl_fill_words_kernel(uint32_t *__restrict__ p, uint32_t v, size_t n) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = v;
 }
@@ -64,6 +67,7 @@ static inline int rrl_copy(void *d, const void *src, size_t nbytes, hipStream_t 
     RRL_LAUNCH_CHECK();
     return 0;
 }
+#endif
 
 // Ragged batches (include/rrl.h rrl_opts.count1 / count2 / nlines): the rows sample b really has -- its entry of the call's
 // count array, clamped to the capacity (memory safety only), or the capacity itself when the call has no counts.  b is

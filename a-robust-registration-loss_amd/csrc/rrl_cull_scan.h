@@ -983,7 +983,7 @@ struct ChainKArgs {
     int z2;                // grid planes [zrec, zrec + z2): the target cloud's slices; the source cloud's follow
     int B, N, M, L, spw, nblk_apart;
     const float *line;
-    uint32_t *chain;       // CHAIN words [B][4]
+    uint32_t *chain;       // CHAIN words [B][RRL_CHAIN_WORDS]
     const float *apart;
     const float4 *p0s1, *p0s2, *tree1, *tree2;
     uint32_t *pmax;
@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
         __syncthreads();
         STAMPR(2);
         if (threadIdx.x == 0)  // ... then ONE lane publishes: the payload went out write-through, so a relaxed ticket is all
-            __hip_atomic_fetch_add(&ch.chain[4 * b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(&ch.chain[RRL_CHAIN_WORDS * b + RRL_CHAIN_READY], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (threadIdx.x < 64) STAMPR(3);
         // what nobody in this launch waits for: the moved rows (TRI1) and index entries, then the clearing
 #ifndef RRL_NO_LATE
@@ -1052,13 +1052,13 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
         if (cloud == 0) {  // the source's records of THIS launch: wait for the sample's ready word (its records are then read by sc1 loads)
 #endif
             if (threadIdx.x == 0) {
-                const uint32_t *rdy = ch.chain + 4 * b;
+                const uint32_t *rdy = ch.chain + RRL_CHAIN_WORDS * b + RRL_CHAIN_READY;
                 bool ok = false;
                 for (unsigned it = 0; it <= ch.spin_limit; ++it) {
                     if (__hip_atomic_load(rdy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)ch.nrec_b) { ok = true; break; }
                     __builtin_amdgcn_s_sleep(8);
                 }
-                if (!ok) __hip_atomic_fetch_add(&ch.chain[4 * b + 3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (!ok) __hip_atomic_fetch_add(&ch.chain[RRL_CHAIN_WORDS * b + RRL_CHAIN_TIMEOUT], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             __syncthreads();
             STAMPR(5);
@@ -1067,7 +1067,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6, 8))
     ScanArgs a;  // (no counters, no per-sample counts, one problem: rrl_cull_scan_can_fuse declines the calls that have them)
     a.ptri1 = ptri1; a.ptri2 = ptri2; a.p0s1 = ch.p0s1; a.p0s2 = ch.p0s2; a.idx1 = idx1; a.idx2 = idx2; a.tree1 = ch.tree1; a.tree2 = ch.tree2;
     a.line = ch.line; a.count1 = count1; a.hit1 = hit1; a.count2 = count2; a.hit2 = hit2;
-    a.status = (int32_t *)(ch.chain + 4 * b + 1);  // this launch's NaN flag / fallback count are per sample
+    a.status = (int32_t *)(ch.chain + RRL_CHAIN_WORDS * b + RRL_CHAIN_NAN);  // this launch's NaN flag / fallback count ([FALLBACK] = [NAN] + 1, rrl_ws.h) are per sample
     a.pmax = ch.pmax; a.del1 = del1; a.del2 = del2; a.lmax = nullptr; a.apart = ch.apart; a.aflag = ch.apart;
     a.nblk_apart = ch.nblk_apart; a.B = B; a.N = ch.N; a.M = ch.M; a.L = ch.L; a.spw = ch.spw; a.Bt = 0;
     cull_scan_body<V, false, true>(lds_.scan, a, cloud * B + b, by, bz, 2 * B, ch.gy, wait_ready);
@@ -1148,7 +1148,7 @@ static int launch_variant(const RrlCall &o, const float *line, const CullGeom &g
             c.value = o.rider->value;
             c.denom = (double)B * (double)(N + M);
             uint32_t *mctl = (uint32_t *)o.at<RRL_WS_MCTL>();  // arrival counters of the walk's mean (rrl_chamfer_from_loss_ex)
-            c.tick = ChamTick{mctl + 32, mctl + 30, 64, 1};
+            c.tick = cham_tick_in_mctl(mctl);
             c.gx = 2 * B; c.gy = ((N > M ? N : M) + SGT - 1) / SGT;  // patches of the larger cloud (either direction)
             const unsigned nwg = (unsigned)(c.gx * c.gy) + (unsigned)(a.gx * a.gy * g.slices);
             hipLaunchKernelGGL(cull_scan_chamfer_kernel<V>, dim3(nwg), dim3(64 * WPB), 0, o.s, a, c);

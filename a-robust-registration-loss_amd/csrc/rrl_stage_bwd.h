@@ -1,5 +1,11 @@
-// rrl_stage_bwd.inc -- K5 backward variants: loss_bwd_kernel (scatter to points; fixed-point deterministic mode), loss_bwd_rt_kernel (to dR, dt), the single-tile kernels that carry them
-// (a section of rrl_sparse.hip, included there: one translation unit; split by stage in round 6, no code change)
+// rrl_stage_bwd.h -- K5 backward variants: loss_bwd_kernel (scatter to points; fixed-point deterministic mode), loss_bwd_rt_kernel (to dR, dt), the single-tile kernels that carry them
+// This header DEFINES kernels: it is included by rrl_sparse.hip only (one translation unit holds every stage behind the scan).
+#pragma once
+#include "rrl_stage_args.h"
+#include "rrl_stamps.h"
+#include "rrl_sampler.h"       // the sampler's write pass as a device function: bwd_write_kernel carries it
+#include "rrl_stage_pair.h"    // pair_body, wave_scatter_rows, xcd_sample_of
+#include "rrl_stage_reduce.h"  // reduce_body, tiled_payload
 // ---------------------------------------------------------------------------------------
 // K5 backward.  dL/dD[a][b] = gout * w_kj / C * exp(-D/(2 med)) / (2 med)
 //                              * ( [b = argmin_b(a)] / (S k) + [a = argmin_a(b)] / (S j) )
@@ -11,20 +17,9 @@
 // rank 32 (sub + BWDS_SUBS i) ..., eight lanes per line; workgroups beyond the tile's count return after one load.  The
 // round-1 grid covered every POSSIBLE slot of the sample's dense list (8 L lanes per sample, ~9 % live, every dead lane
 // walking the same chain of loads up to the DPP exchange): 11 us at C2, 53 us at B = 64; and every live lane issued its
-// nine atomics itself (wave_scatter_rows above).
+// nine atomics itself (wave_scatter_rows, rrl_stage_pair.h).
 #define BWDS_LINES 32  // selected lines per pass of a 256-lane workgroup
 #define BWDS_SUBS 4
-struct ScatArgs {
-    const uint32_t *lidc;
-    const int32_t *blkcnt, *hs1, *hs2, *bcnt, *info;
-    const float *w1, *w2, *D, *med, *grad_loss;
-    const float4 *Q1, *Q2;
-    float *g1, *g2;
-    int N, M, L;
-    unsigned long long *fx;  // deterministic mode: GFIX -- [B][N + M][9] fixed-point accumulators, then int32 [B][2] non-finite flags; or NULL
-    int fxbits;              // ... fractional bits below the sample's bound exponent (scat_unit_exp)
-    int fxB;                 // ... samples (the flags sit behind the B accumulators)
-};
 // Deterministic scatter: the exponent e with |any single contribution| < 2^e for a sample with upstream gradient gl, C valid
 // buckets and median m.  A contribution is w/3 * sum_{o < 4} 2 (q1 - q2)_c * scale * sw * exp(-D / 2m) / (2m) with w <= 1,
 // scale <= |gl| / C, sw <= 2 and |q1 - q2| exp(-D / 2m) / m <= sqrt(D) exp(-D / 2m) / m <= 0.607 / sqrt(m): below
@@ -222,11 +217,7 @@ __global__ __launch_bounds__(1024) void pair_reduce_scatter_kernel(const PairArg
     const int sc = lane < 16 ? so.s_cnt[lane] : 0, kk = (lane & 15) / 4 + 1, jj = (lane & 3) + 1;
     const int C = __popcll(__ballot(lane < 16 && sc > 0 && kk >= ra.s_m && kk < ra.e_m && jj >= ra.s_n && jj < ra.e_n));
     const float m = so.out_med;
-    if (tid == 64 * 15 && payload && C > 0) {  // (order-independent: fixed-point sum of the valid samples' losses)
-        TailArgs t;
-        t.payload = payload; t.mctl = mctl;
-        tail_payload(t, so.out_loss);
-    }
+    if (tid == 64 * 15 && payload && C > 0) tiled_payload(payload, mctl, so.out_loss);  // (order-independent: fixed-point sum of the valid samples' losses)
     if (small) {
         if ((tid & ~63) >> 3 >= cnt) return;  // wave-uniform: none of this wavefront's eight ranks holds a line
         const int side = (lane >> 2) & 1, h = lane & 3, k = kp.k, j = kp.j;
@@ -496,20 +487,6 @@ __global__ __launch_bounds__(256) void loss_bwd_rt_kernel(
 
 // The direct backward AND the write pass of the next epoch's line sampler in ONE launch (round 4b; rrl_ws.h RrlWriteRider,
 // rrl_demo_epoch): 256-lane workgroups both; workgroups [0, tiles x rounds) write, the others run the backward.
-struct BwdKArgs {
-    const uint8_t *kj;
-    const int32_t *sel, *nsel, *hs1;
-    const float *w1;
-    const float4 *Q1, *Q2;
-    const float *D, *med;
-    const int32_t *bcnt, *info;
-    const float *grad_loss, *src;
-    float *gR, *gt, *payload;
-    const float *loss;
-    int B, N, L, transpose_r;
-    float *part;
-    int gx;
-};
 template <bool DET>
 __global__ __launch_bounds__(256) void bwd_write_kernel(const BwdKArgs a, const WriteKArgs c) {
     extern __shared__ int s_tc_dyn[];  // the write pass's tile counts [rounds][tiles]
@@ -557,17 +534,6 @@ __global__ __launch_bounds__(256) void loss_bwd_rt_finalize_kernel(const float *
 // sample b ran the per-line stage and the reduce of sample b, so it holds everything the direct backward of sample b
 // reads -- no other workgroup is involved at all.  Same bodies (pair_body, reduce_body, bwd_rt_line), same results;
 // (dR, dt) of a sample by ONE workgroup in a fixed order (deterministic here), payload[0 .. 1] as in the tail kernel.
-struct SoloBwd {
-    const uint8_t *kj;
-    const int32_t *sel, *nsel, *hs1, *bcnt, *info;
-    const float *w1, *D, *med, *grad_loss, *src, *loss;
-    const float4 *Q1, *Q2;
-    float *gR, *gt, *payload;
-    uint32_t *mctl;
-    int B, N, L, transpose_r;
-    int Bt;  // multi-pose (rrl_opts.problems)
-};
-
 __global__ __launch_bounds__(1024) void pair_reduce_bwd_kernel(const PairArgs pa, const ReduceArgs ra, const SoloBwd a) {
     __shared__ float s_red[16][12];
     __shared__ __attribute__((aligned(16))) float s_dct[128 * 16];  // the first pass's compact D tiles and (k | j << 4) bytes
@@ -595,11 +561,7 @@ __global__ __launch_bounds__(1024) void pair_reduce_bwd_kernel(const PairArgs pa
     reduce_body(ra, b, &so);
     const int sc = lane < 16 ? so.s_cnt[lane] : 0, kk = (lane & 15) / 4 + 1, jj = (lane & 3) + 1;
     const int C = __popcll(__ballot(lane < 16 && sc > 0 && kk >= ra.s_m && kk < ra.e_m && jj >= ra.s_n && jj < ra.e_n));
-    if (tid == 64 * 15 && a.payload && C > 0) {  // payload[0 .. 1] as in the tail kernel (order-independent)
-        TailArgs t;
-        t.payload = a.payload; t.mctl = a.mctl;
-        tail_payload(t, so.out_loss);
-    }
+    if (tid == 64 * 15 && a.payload && C > 0) tiled_payload(a.payload, a.mctl, so.out_loss);  // payload[0 .. 1] as in the tail kernel (order-independent)
     float acc[12];
 #pragma unroll
     for (int q = 0; q < 12; ++q) acc[q] = 0.0f;

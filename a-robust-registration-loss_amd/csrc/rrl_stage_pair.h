@@ -1,10 +1,14 @@
-// rrl_stage_pair.inc -- K2, the per-line stage: line_pair_dist_kernel (+ pair_count_kernel: the demo sampler's count pass riding along), the gradient scatter's LDS transpose
-// (a section of rrl_sparse.hip, included there: one translation unit; split by stage in round 6, no code change)
+// rrl_stage_pair.h -- K2, the per-line stage: line_pair_dist_kernel (+ pair_count_kernel: the demo sampler's count pass riding along), the gradient scatter's LDS transpose
+// This header DEFINES kernels: it is included by rrl_sparse.hip only (one translation unit holds every stage behind the scan).
+#pragma once
+#include "rrl_arith.h"  // hit_weights, inter_point, tri_coords (shared with the wide pipeline, rrl_wide.hip)
+#include "rrl_stage_args.h"
+#include "rrl_stamps.h"   // (ahead of the sampler, whose count pass stamps through STAMPC)
+#include "rrl_sampler.h"  // the sampler's count pass as a device function: pair_count_kernel carries it
+
 // LDS-only workgroup barrier: this wavefront's LDS traffic is complete, its vector-memory loads AND STORES stay in flight
 // (__syncthreads() waits for both: a barrier behind a store costs the store's acknowledgement, ~0.5 us)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-#include "rrl_arith.h"  // hit_weights, inter_point, tri_coords (shared with the wide pipeline, rrl_wide.hip)
 
 __device__ __forceinline__ void sort4(int *h, int n) {  // ascending, n <= 4
 #pragma unroll
@@ -162,28 +166,6 @@ __device__ __forceinline__ void xcd_sample_of(int lin, int gx, int &x, int &b) {
 }
 // (the host side's switch: rrl_ws.h xcd_align_on)
 
-struct PairArgs {
-    const float *tri1, *tri2, *line;  // the triangles of both clouds (raw 36-byte rows: st1 = st2 = 9), the lines
-    const int32_t *count1, *hit1, *count2, *hit2;
-    uint8_t *kj;
-    int32_t *sel_out, *nsel, *hs1, *hs2;
-    float *w1, *w2;
-    float4 *Q1, *Q2;
-    float *D, *dc;
-    uint8_t *kjc;
-    uint32_t *lidc;          // line | kj << 24 at the compact slot (or NULL)
-    float *vlist;            // [B][ntile][16384] dense list of the tile's valid D values (with mhist; or NULL)
-    int32_t *vlcnt;
-    int32_t *blkcnt;
-    uint32_t *mhist, *mctl;  // tiled reduce: per-sample histogram of the D values' top 11 bits, bucket counts (or NULL)
-    int B, N, M, L, s_m, s_n, e_m, e_n, st1, st2;
-    int Bt;  // multi-pose evaluation (rrl_opts.problems): tri2, line and cloud 2's scan (count2, hit2) of instance b are those
-             // of problem b % Bt; 0: every instance has its own
-    int xcd_align;  // line_pair_dist_kernel: sample b's workgroups on XCD b % 8 (xcd_sample_of; B % 8 == 0)
-    int32_t *zc1, *zc2;  // chained steps (include/rrl.h RRL_F_CHAIN): COUNT1 / COUNT2 again, writable -- every lane zeroes its
-                         // line's two counts behind its own read, so that the NEXT step's scan finds them cleared; or NULL
-};
-
 // One tile of 1024 lines of sample b by a 1024-lane workgroup.  Phase 1: every lane classifies its line
 // and the selected ones (~9 %) are compacted through LDS, so that phase 2 -- the gather-heavy part -- runs
 // on dense wavefronts, eight lanes per line; the compacted line ids also go to SEL[b] for the backward.
@@ -302,7 +284,7 @@ __device__ __forceinline__ void pair_body(const PairArgs &a, int b, int tile, in
             const unsigned v = s_mh[tid + 1024 * q];
             if (v) atomicAdd(&mh[tid + 1024 * q], v);
         }
-        if (tid < 16 && s_bc[tid]) atomicAdd(&a.mctl[(size_t)b * 64 + tid], s_bc[tid]);
+        if (tid < 16 && s_bc[tid]) atomicAdd(&a.mctl[(size_t)b * RRL_MCTL_WORDS + RRL_MCTL_BUCKET0 + tid], s_bc[tid]);
         if (vl) {  // the list's length; padded with -1 (no D value is negative) to whole 16-byte groups
             const unsigned nv = s_nv;
             if (tid == 0) a.vlcnt[(size_t)b * ntile + tile] = (int)nv;
@@ -332,12 +314,6 @@ __global__ __launch_bounds__(1024) void line_pair_dist_kernel(const PairArgs a) 
 // rrl_demo_epoch): both run 1024-lane workgroups, the count pass needs nothing the scan produced, and launches of one
 // stream never overlap on this stack.  Workgroups [0, tiles x rounds) count (the long ones start first), the others run
 // the per-line stage.  Same bodies, same results as the two launches.
-struct CountKArgs {
-    const unsigned long long *rng_state;
-    const float *r, *centers, *aabb2, *rows;
-    unsigned long long *accept;
-    int n_rows, n, rounds, prefilter, gx, gy;
-};
 __global__ __launch_bounds__(1024) void pair_count_kernel(const PairArgs a, const CountKArgs c, int pair_gx) {
     __shared__ SampleCountLds clds;
     const int ncount = c.gx * c.gy, lin = (int)blockIdx.x;

@@ -1,9 +1,14 @@
-// rrl_stage_reduce.inc -- K3 + K4, median + Welsch reduce: loss_reduce_kernel (one workgroup per sample) and loss_reduce_tiled_kernel (the exchange reduce)
-// (a section of rrl_sparse.hip, included there: one translation unit; split by stage in round 6, no code change)
+// rrl_stage_reduce.h -- K3 + K4, median + Welsch reduce: loss_reduce_kernel (one workgroup per sample) and loss_reduce_tiled_kernel (the exchange reduce)
+// This header DEFINES kernels: it is included by rrl_sparse.hip only (one translation unit holds every stage behind the scan).
+#pragma once
+#include "rrl_ws.h"          // (the control-word map of include/rrl.h, asserted there)
+#include "rrl_arith.h"       // welsch(), FIX_SHIFT (shared with the wide pipeline, rrl_wide.hip)
+#include "rrl_stage_args.h"
+#include "rrl_stamps.h"
+#include "rrl_stage_pair.h"  // xcd_sample_of
 // ---------------------------------------------------------------------------------------
 // K3+K4: one 1024-lane workgroup per sample
 // ---------------------------------------------------------------------------------------
-// welsch(): rrl_arith.h (shared with the wide pipeline, rrl_wide.hip)
 
 // The k x j block of D values is stored row-major with stride j; bring it into a 4 x 4
 // register tile (static indices only; entries outside the block are +inf).
@@ -367,18 +372,6 @@ __device__ __forceinline__ BucketFinal bucket_final(unsigned long long srow, uns
     return r;
 }
 
-struct ReduceArgs {
-    const uint8_t *kjc;
-    const float *dc;
-    const int32_t *blkcnt;
-    float *med_out;
-    int32_t *bcnt_out;
-    int64_t *bsum_out;
-    int32_t *info;
-    float *loss;
-    const int32_t *status;
-    int B, nblk, s_m, s_n, e_m, e_n, pool;
-};
 
 // K3+K4 of one group g (a sample, or all samples with the last one's median when pool) by a 1024-lane workgroup
 // SOLO (the single-tile kernels, round 5): the workgroup has just run the per-line stage of sample g itself --
@@ -483,18 +476,12 @@ __global__ __launch_bounds__(1024) void loss_reduce_kernel(const ReduceArgs ra) 
 // Cross-workgroup words follow the guide's hand-off rules: relaxed agent-scope atomic stores / loads (sc1:
 // write-through, L1-bypassing), every storing wavefront drains (s_waitcnt vmcnt(0)) before its workgroup
 // arrives, one lane polls.  The spin needs the sample's workgroups co-resident: the host takes this path only
-// while B x tiles <= 1024 workgroups of 256 lanes (4 per CU) and bounds every spin (MCTL[19] + a NaN loss
+// while B x tiles <= 1024 workgroups of 256 lanes (4 per CU) and bounds every spin (MCTL[b][RRL_MCTL_ERR] + a NaN loss
 // instead of a hang).  More than 2048 values in the bin (near-identical D values): tile 0 finishes the
 // select alone with two more streaming passes and publishes the median; the others wait for it.
 // Same arithmetic and summation rules as reduce_body: bit-identical median and loss.
 // ---------------------------------------------------------------------------------------
-#define MCTL_CURSOR 16
-#define MCTL_TICK1 17
-#define MCTL_TICK2 18
-#define MCTL_ERR 19
-#define MCTL_MEDBITS 20
-#define MCTL_MEDRDY 21
-#define MCTL_BAD 22
+// (the control words: include/rrl.h RRL_MCTL_*)
 #define MCAND_CAP 2048
 
 __device__ __forceinline__ unsigned ld_agent(const uint32_t *p) {
@@ -546,33 +533,32 @@ __device__ __forceinline__ unsigned wave_select20(const unsigned *vals, unsigned
     return pre;
 }
 
-struct TiledArgs {
-    const uint8_t *kjc;
-    const float *dc;
-    const int32_t *blkcnt;
-    uint32_t *mhist, *mctl, *mcand;
-    unsigned long long *msum;
-    float *med_out;
-    int32_t *bcnt_out;
-    int64_t *bsum_out;
-    int32_t *info;
-    float *loss;
-    int32_t *status;      // [0] the scan's NaN flag (read); [2] += samples repaired after a hand-off time-out
-    int B, nblk, s_m, s_n, e_m, e_n;
-    unsigned spin_limit;  // polls before a waiting workgroup gives up (rrl_set_spin_limit: tests set 0)
-    int xcd_align;        // sample b's workgroups on XCD b % 8 (xcd_sample_of; B % 8 == 0): its in-launch hand-offs stay in one L2
-    float *payload;       // != NULL (rrl_loss_step_ex): the sample's last workgroup adds its loss to payload[0 .. 1] (tail_payload)
-    uint32_t *chain;      // chained steps (include/rrl.h RRL_F_CHAIN), as TailArgs: the CHAIN words the sample's last workgroup zeroes
-    int chain_flags;      //   (or NULL); != 0: this step's scan ran in the fused launch -- NaN flag / time-outs are CHAIN[b][1], [3]
-};
+
+// One sample's final loss into payload[0 .. 1] (one lane), without a last-of-all hand-over: every sample's finaliser adds
+// its loss to a 2^-40 fixed-point sum (row 0's RRL_MCTL_LSUM, a returning atomic) and offers float(sum so far) to payload[0]
+// by an unsigned atomicMax on the bit pattern (rrl_stage_tail.h's header).  Defined here, ahead of every kernel that calls
+// it: the tail kernel in the TailArgs form, the exchange reduce and the single-tile kernels in the pointer form.
+__device__ __forceinline__ void tail_payload(const TailArgs &a, float lv) {
+    atomicAdd(&a.payload[1], 1.0f);
+    if (lv != lv) { atomicMax((unsigned *)&a.payload[0], 0x7fc00000u); return; }
+    const unsigned long long mine = (unsigned long long)((double)lv * (double)(1ll << FIX_SHIFT) + 0.5);
+    const unsigned long long old = __hip_atomic_fetch_add((unsigned long long *)(a.mctl + RRL_MCTL_LSUM), mine, __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_AGENT);
+    const float tot = (float)((double)(old + mine) * (1.0 / (double)(1ll << FIX_SHIFT)));
+    atomicMax((unsigned *)&a.payload[0], __float_as_uint(tot));
+}
+__device__ __forceinline__ void tiled_payload(float *payload, uint32_t *mctl, float lv) {
+    TailArgs t;
+    t.payload = payload; t.mctl = mctl;
+    tail_payload(t, lv);
+}
 
 // Hand-offs between the workgroups of this launch (candidate list + TICK1, MEDRDY) are bounded spins.  A workgroup whose
-// spin times out (the others were not resident in time) adds NOTHING to the sample's sums, raises MCTL_ERR and still
+// spin times out (the others were not resident in time) adds NOTHING to the sample's sums, raises RRL_MCTL_ERR and still
 // draws its TICK2 ticket; the sample's LAST workgroup then sees the flag and recomputes the whole sample by itself --
 // median from all tiles' values, Welsch sums over all its lines, the single-workgroup kernel's arithmetic on the same
 // multiset -- so the result is bit-identical to the undisturbed one instead of NaN (round 3), at the cost of one
 // workgroup's serial pass over ~1000 lines.  STATUS[2] counts such samples.
-__device__ __forceinline__ void tiled_payload(float *payload, uint32_t *mctl, float lv);  // (= tail_payload, defined with the tail kernel)
 __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs a) {
     __shared__ unsigned s_vals[MCAND_CAP];  // the bin's values (usual route) / histogram of the streaming passes
     __shared__ unsigned s_wtot[4];
@@ -587,7 +573,7 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
     int tile = blockIdx.x, b = blockIdx.y;
     if (a.xcd_align) xcd_sample_of(tile + nblk * b, nblk, tile, b);  // (uniform)
     const size_t Lp = (size_t)nblk * 1024;
-    uint32_t *ctl = a.mctl + (size_t)b * 64;
+    uint32_t *ctl = a.mctl + (size_t)b * RRL_MCTL_WORDS;
     uint32_t *cand = a.mcand + (size_t)b * MCAND_CAP;
     const float *__restrict__ dc = a.dc;
     const uint8_t *__restrict__ kjc = a.kjc;
@@ -598,7 +584,8 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
     int st0;  // (for the info row: requested with round 1)
     bool chain_tmo = false;
     if (a.chain_flags) {
-        const uint4 cw = *(const uint4 *)(a.chain + 4 * (size_t)b);
+        static_assert(RRL_CHAIN_WORDS == 4 && RRL_CHAIN_NAN == 1 && RRL_CHAIN_TIMEOUT == 3, "one 16-byte load: .y the NaN flag, .w the time-outs");
+        const uint4 cw = *(const uint4 *)(a.chain + RRL_CHAIN_WORDS * (size_t)b);
         st0 = (int)cw.y;
         chain_tmo = cw.w != 0u;
     } else {
@@ -663,7 +650,7 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
                 a.loss[b] = 0.0f;
                 a.info[b * 4 + 0] = 0; a.info[b * 4 + 1] = 0; a.info[b * 4 + 2] = 0; a.info[b * 4 + 3] = st0;
                 if (chain_tmo) a.loss[b] = __builtin_nanf("");
-                if (a.chain) *(uint4 *)(a.chain + 4 * (size_t)b) = make_uint4(0u, 0u, 0u, 0u);
+                if (a.chain) *(uint4 *)(a.chain + RRL_CHAIN_WORDS * (size_t)b) = make_uint4(0u, 0u, 0u, 0u);
             }
         }
         return;
@@ -725,7 +712,7 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
         });
         const unsigned incl = (unsigned)wave_incl_scan((int)mine);
         unsigned wbase = 0;
-        if (lane == 63 && incl) wbase = __hip_atomic_fetch_add(&ctl[MCTL_CURSOR], incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 63 && incl) wbase = __hip_atomic_fetch_add(&ctl[RRL_MCTL_CURSOR], incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         wbase = (unsigned)__builtin_amdgcn_readlane((int)wbase, 63);
         unsigned at = wbase + incl - mine;
 #pragma unroll
@@ -742,8 +729,8 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wavefront drains before the workgroup arrives
         __syncthreads();
         if (tid == 0) {  // the last to arrive learns it from its own ticket and does not poll at all
-            const unsigned prev = __hip_atomic_fetch_add(&ctl[MCTL_TICK1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev + 1u < (unsigned)nblk && !spin_reach(&ctl[MCTL_TICK1], (unsigned)nblk, a.spin_limit)) s_flag[0] = 0u;
+            const unsigned prev = __hip_atomic_fetch_add(&ctl[RRL_MCTL_TICK1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (prev + 1u < (unsigned)nblk && !spin_reach(&ctl[RRL_MCTL_TICK1], (unsigned)nblk, a.spin_limit)) s_flag[0] = 0u;
         }
         __syncthreads();
         for (unsigned i = tid; i < pop; i += 256) s_vals[i] = ld_agent(&cand[i]);
@@ -758,14 +745,14 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
         // ---- crowded bin: this workgroup alone streams over ALL the sample's values twice more (bits 19..9, 8..0)
         prefix = crowded_select();
         if (tid == 0) {
-            st_agent(&ctl[MCTL_MEDBITS], prefix);
+            st_agent(&ctl[RRL_MCTL_MEDBITS], prefix);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            st_agent(&ctl[MCTL_MEDRDY], 1u);
+            st_agent(&ctl[RRL_MCTL_MEDRDY], 1u);
         }
     } else {
         if (tid == 0) {
-            if (!spin_reach(&ctl[MCTL_MEDRDY], 1u, a.spin_limit)) s_flag[0] = 0u;
-            s_med = ld_agent(&ctl[MCTL_MEDBITS]);
+            if (!spin_reach(&ctl[RRL_MCTL_MEDRDY], 1u, a.spin_limit)) s_flag[0] = 0u;
+            s_med = ld_agent(&ctl[RRL_MCTL_MEDBITS]);
         }
         __syncthreads();
         prefix = s_med;
@@ -797,18 +784,18 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
         if (v) atomicAdd(&a.msum[(size_t)b * 32 + tid], v);
     }
     if (tid == 32 && (s_flag[2] || !s_flag[0])) {
-        if (s_flag[2]) atomicOr(&ctl[MCTL_BAD], 1u);
-        if (!s_flag[0]) atomicOr(&ctl[MCTL_ERR], 1u);
+        if (s_flag[2]) atomicOr(&ctl[RRL_MCTL_BAD], 1u);
+        if (!s_flag[0]) atomicOr(&ctl[RRL_MCTL_ERR], 1u);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0)
-        s_flag[1] = __hip_atomic_fetch_add(&ctl[MCTL_TICK2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(nblk - 1) ? 1u : 0u;
+        s_flag[1] = __hip_atomic_fetch_add(&ctl[RRL_MCTL_TICK2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(nblk - 1) ? 1u : 0u;
     __syncthreads();
     if (!s_flag[1]) return;
 
-    // ---- the last workgroup of the sample.  A hand-off timed out somewhere (MCTL_ERR): recompute the sample alone.
-    const bool repair = ld_agent(&ctl[MCTL_ERR]) != 0u;  // uniform: every producer's flag precedes its ticket
+    // ---- the last workgroup of the sample.  A hand-off timed out somewhere (RRL_MCTL_ERR): recompute the sample alone.
+    const bool repair = ld_agent(&ctl[RRL_MCTL_ERR]) != 0u;  // uniform: every producer's flag precedes its ticket
     if (repair) {
         __syncthreads();
         if (tid < 32) s_sum[tid] = 0ull;
@@ -864,12 +851,13 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
         a.bsum_out[(size_t)b * 32 + tid] = (int64_t)v;
         __hip_atomic_store(&a.msum[(size_t)b * 32 + tid], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // a second reduce on this state starts clean
     }
+    static_assert(RRL_MCTL_BUCKET0 == 0 && RRL_MCTL_BAD < 32, "lanes 32 .. 63 read words 0 .. 31: the sixteen buckets first");
     if (tid >= 32 && tid < 64) {  // the sample's control words in the same round of loads: bucket counts, error / bad flags
         const unsigned v = ld_agent(&ctl[tid - 32]);
         if (tid < 48) {
             s_cnt[tid - 32] = (int)v;
             a.bcnt_out[b * 16 + tid - 32] = (int)v;
-        } else if (tid - 32 == MCTL_BAD && !repair) {
+        } else if (tid - 32 == RRL_MCTL_BAD && !repair) {
             if (v) atomicOr(&s_flag[2], 2u);  // (s_flag[2] bit 0 was this workgroup's own; bit 1: anyone's)
         }
     }
@@ -888,9 +876,9 @@ __global__ __launch_bounds__(256) void loss_reduce_tiled_kernel(const TiledArgs 
         a.info[b * 4 + 1] = nselected;
         a.info[b * 4 + 2] = nvalues;
         a.info[b * 4 + 3] = st0;
-        if (a.chain) *(uint4 *)(a.chain + 4 * (size_t)b) = make_uint4(0u, 0u, 0u, 0u);  // the next chained step finds them cleared
-        st_agent(&ctl[MCTL_CURSOR], 0u); st_agent(&ctl[MCTL_TICK1], 0u); st_agent(&ctl[MCTL_TICK2], 0u);
-        st_agent(&ctl[MCTL_MEDRDY], 0u); st_agent(&ctl[MCTL_BAD], 0u); st_agent(&ctl[MCTL_ERR], 0u);
+        if (a.chain) *(uint4 *)(a.chain + RRL_CHAIN_WORDS * (size_t)b) = make_uint4(0u, 0u, 0u, 0u);  // the next chained step finds them cleared
+        st_agent(&ctl[RRL_MCTL_CURSOR], 0u); st_agent(&ctl[RRL_MCTL_TICK1], 0u); st_agent(&ctl[RRL_MCTL_TICK2], 0u);
+        st_agent(&ctl[RRL_MCTL_MEDRDY], 0u); st_agent(&ctl[RRL_MCTL_BAD], 0u); st_agent(&ctl[RRL_MCTL_ERR], 0u);
         if (a.payload && C > 0) tiled_payload(a.payload, a.mctl, lv);  // (order-independent: tail_payload)
     }
 }

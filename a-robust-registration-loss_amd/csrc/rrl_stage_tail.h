@@ -1,5 +1,13 @@
-// rrl_stage_tail.inc -- K3 + K4 (+ K5) in the tail kernel: loss_tail_kernel / tail_write_kernel, and the single-tile pair_reduce_kernel
-// (a section of rrl_sparse.hip, included there: one translation unit; split by stage in round 6, no code change)
+// rrl_stage_tail.h -- K3 + K4 (+ K5) in the tail kernel: loss_tail_kernel / tail_write_kernel, and the single-tile pair_reduce_kernel
+// This header DEFINES kernels: it is included by rrl_sparse.hip only (one translation unit holds every stage behind the scan).
+#pragma once
+#include "rrl_ws.h"            // TAIL_MAX_TILES, TAIL_LANES (beside RrlPlan); the control-word map of include/rrl.h
+#include "rrl_arith.h"         // FIX_SHIFT
+#include "rrl_stage_args.h"
+#include "rrl_stamps.h"
+#include "rrl_sampler.h"       // the sampler's write pass as a device function: tail_write_kernel carries it
+#include "rrl_stage_pair.h"    // pair_body, lds_barrier, wave_scatter_rows, xcd_sample_of
+#include "rrl_stage_reduce.h"  // reduce_body, bucket_final, wave_select20, ld_agent / st_agent, tail_payload
 // ---------------------------------------------------------------------------------------
 // K3 + K4 (+ K5') "tail" kernel (round 3): the tiled reduce WITHOUT the exchange, and optionally the direct
 // backward of the fused training op in the same launch.
@@ -27,8 +35,7 @@
 // (dR, dt) up to the order of the float atomics, as before; payload[0] may differ from the two-call path's
 // double-precision sum in its last bit.
 // ---------------------------------------------------------------------------------------
-#define TAIL_MAX_TILES 32
-#define TAIL_LANES 512
+// (TAIL_MAX_TILES = 32 line tiles per sample, TAIL_LANES = 512: rrl_ws.h, the plan reads them)
 #define TAIL_LINES 64  // selected lines per workgroup (four lanes each)
 #ifndef TAIL_SUBS
 #define TAIL_SUBS 4    // workgroups per tile (grid z): workgroup s takes the tile's chunks s, s + 4, ... of TAIL_LINES lines
@@ -36,57 +43,6 @@
 #ifndef TAIL_RPL
 #define TAIL_RPL 4     // 16-byte groups of D values per lane and streaming round
 #endif
-#define MCTL_LSUM 34   // (row of sample 0, 8-byte aligned) uint64: fixed-point sum of the valid samples' losses
-
-struct TailArgs {
-    const uint32_t *lidc;
-    const float *dc;
-    const float *vlist;
-    const int32_t *vlcnt;
-    const int32_t *blkcnt;
-    const uint32_t *mhist;
-    uint32_t *mctl;
-    unsigned long long *msum;
-    float *med_out;
-    int32_t *bcnt_out;
-    int64_t *bsum_out;
-    int32_t *info;
-    float *loss;
-    const int32_t *status;
-    int B, nblk, s_m, s_n, e_m, e_n;
-    int do_bwd, N, L, transpose_r;
-    const int32_t *hs1;
-    const float *w1;
-    const float4 *Q1, *Q2;
-    const float *grad_loss, *src;
-    float *gR, *gt, *payload;
-    float *grad_tri1;  // != NULL: the backward SCATTERS dL/dpoints1 [B][N][9] (rrl_loss_step) instead of summing (dR, dt)
-    int Bt;            // multi-pose (rrl_opts.problems): src has Bt entries, instance b is a pose of entry b % Bt; 0: its own
-    int xcd_align;     // sample b's workgroups on XCD b % 8 (xcd_sample_of; B % 8 == 0)
-    // chained steps (include/rrl.h RRL_F_CHAIN): the CHAIN words [B][4], which the sample's last workgroup zeroes on exit
-    // (or NULL); chain_flags != 0: this step's scan ran in the fused launch -- its NaN flag and time-outs are CHAIN[b][1],
-    // CHAIN[b][3], not STATUS[0]
-    uint32_t *chain;
-    int chain_flags;
-};
-
-
-// one sample's final loss into payload[0 .. 1] (header); one lane
-__device__ __forceinline__ void tail_payload(const TailArgs &a, float lv) {
-    atomicAdd(&a.payload[1], 1.0f);
-    if (lv != lv) { atomicMax((unsigned *)&a.payload[0], 0x7fc00000u); return; }
-    const unsigned long long mine = (unsigned long long)((double)lv * (double)(1ll << FIX_SHIFT) + 0.5);
-    const unsigned long long old = __hip_atomic_fetch_add((unsigned long long *)(a.mctl + MCTL_LSUM), mine, __ATOMIC_RELAXED,
-                                                          __HIP_MEMORY_SCOPE_AGENT);
-    const float tot = (float)((double)(old + mine) * (1.0 / (double)(1ll << FIX_SHIFT)));
-    atomicMax((unsigned *)&a.payload[0], __float_as_uint(tot));
-}
-
-__device__ __forceinline__ void tiled_payload(float *payload, uint32_t *mctl, float lv) {
-    TailArgs t;
-    t.payload = payload; t.mctl = mctl;
-    tail_payload(t, lv);
-}
 
 // (>= 4 wavefronts per SIMD = two 512-lane workgroups per CU: beyond 128 VGPRs a grid of more than 256 live workgroups -- B >= 16
 //  at ten tiles -- would run in two generations: measured 17 -> 23.6 us at B = 16 when an edit pushed the kernel to 132)
@@ -116,7 +72,7 @@ __device__ __forceinline__ void tail_body(const TailArgs &a, int tile_in, int b_
     int tile = tile_in, b = b_in;
     if (a.xcd_align) xcd_sample_of(tile + nblk * b, nblk, tile, b);  // (uniform; every sub-grid of nblk x B workgroups is a multiple of 8)
     const size_t Lp = (size_t)nblk * 1024;
-    uint32_t *ctl = a.mctl + (size_t)b * 64;
+    uint32_t *ctl = a.mctl + (size_t)b * RRL_MCTL_WORDS;
     const float *__restrict__ dc = a.dc;
     const uint32_t *__restrict__ lidc = a.lidc;
     const size_t slot0 = (size_t)b * Lp + (size_t)tile * 1024;
@@ -149,14 +105,15 @@ __device__ __forceinline__ void tail_body(const TailArgs &a, int tile_in, int b_
         hb[0] = hq.x; hb[1] = hq.y; hb[2] = hq.z; hb[3] = hq.w;
         static_assert(BPL == 4, "one 16-byte load of the histogram per lane");
     }
-    const unsigned bkt = tid < 16 ? ctl[tid] : 0u;
+    const unsigned bkt = tid < 16 ? ctl[RRL_MCTL_BUCKET0 + tid] : 0u;
     const float gl_in0 = do_bwd ? a.grad_loss[b] : 0.0f;
     // (the scan's NaN flag, for the info row: at the end it would be one more round trip of the last arriver; a chained
     //  step's fused launch keeps it per sample, next to the count of source workgroups that gave up waiting for their records)
     int st0;
     bool chain_tmo = false;
     if (a.chain_flags) {
-        const uint4 cw = *(const uint4 *)(a.chain + 4 * (size_t)b);
+        static_assert(RRL_CHAIN_WORDS == 4 && RRL_CHAIN_NAN == 1 && RRL_CHAIN_TIMEOUT == 3, "one 16-byte load: .y the NaN flag, .w the time-outs");
+        const uint4 cw = *(const uint4 *)(a.chain + RRL_CHAIN_WORDS * (size_t)b);
         st0 = (int)cw.y;
         chain_tmo = cw.w != 0u;
     } else {
@@ -296,7 +253,7 @@ __device__ __forceinline__ void tail_body(const TailArgs &a, int tile_in, int b_
             a.loss[b] = 0.0f;
             a.info[b * 4 + 0] = 0; a.info[b * 4 + 1] = 0; a.info[b * 4 + 2] = 0; a.info[b * 4 + 3] = st0;
             if (chain_tmo) a.loss[b] = __builtin_nanf("");
-            if (a.chain) *(uint4 *)(a.chain + 4 * (size_t)b) = make_uint4(0u, 0u, 0u, 0u);
+            if (a.chain) *(uint4 *)(a.chain + RRL_CHAIN_WORDS * (size_t)b) = make_uint4(0u, 0u, 0u, 0u);
         }
         return;
     }
@@ -398,12 +355,12 @@ __device__ __forceinline__ void tail_body(const TailArgs &a, int tile_in, int b_
         const unsigned long long v = s_sum[lane];
         if (v) atomicAdd(&a.msum[(size_t)b * 32 + lane], v);
     }
-    if (lane == 32 && s_flag[1]) atomicOr(&ctl[MCTL_BAD], 1u);
+    if (lane == 32 && s_flag[1]) atomicOr(&ctl[RRL_MCTL_BAD], 1u);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's sums have arrived before it takes its ticket
     STAMPW(4);
     unsigned last = 0;
     if (lane == 0)
-        last = __hip_atomic_fetch_add(&ctl[MCTL_TICK2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(nlive - 1) ? 1u : 0u;
+        last = __hip_atomic_fetch_add(&ctl[RRL_MCTL_TICK2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(nlive - 1) ? 1u : 0u;
     STAMPW(5);
     if (!__builtin_amdgcn_readfirstlane((int)last)) return;
 
@@ -417,7 +374,7 @@ __device__ __forceinline__ void tail_body(const TailArgs &a, int tile_in, int b_
     } else if (lane < 48) {
         a.bcnt_out[b * 16 + lane - 32] = s_cnt[lane - 32];
     } else if (lane == 48) {
-        anybad = ld_agent(&ctl[MCTL_BAD]);
+        anybad = ld_agent(&ctl[RRL_MCTL_BAD]);
     }
     const bool bad = __builtin_amdgcn_readlane((int)anybad, 48) != 0;
     // lane 2 q + c holds sum c (row / column) of bucket q: one lane per bucket takes both (the double-precision means, as
@@ -435,8 +392,8 @@ __device__ __forceinline__ void tail_body(const TailArgs &a, int tile_in, int b_
         a.info[b * 4 + 1] = nselected;
         a.info[b * 4 + 2] = nvalues;
         a.info[b * 4 + 3] = st0;
-        st_agent(&ctl[MCTL_TICK2], 0u); st_agent(&ctl[MCTL_BAD], 0u);
-        if (a.chain) *(uint4 *)(a.chain + 4 * (size_t)b) = make_uint4(0u, 0u, 0u, 0u);  // the next chained step finds them cleared
+        st_agent(&ctl[RRL_MCTL_TICK2], 0u); st_agent(&ctl[RRL_MCTL_BAD], 0u);
+        if (a.chain) *(uint4 *)(a.chain + RRL_CHAIN_WORDS * (size_t)b) = make_uint4(0u, 0u, 0u, 0u);  // the next chained step finds them cleared
         if (do_bwd && a.payload && Cn > 0) tail_payload(a, lv);
     }
     STAMPW(6);
@@ -607,14 +564,6 @@ __global__ __launch_bounds__(TAIL_LANES) __attribute__((amdgpu_waves_per_eu(4, 8
 // the direct backward's own launch): the first gx * gy workgroups of a 1-D grid run one (tile of 1024 candidates, round) of the
 // write pass each, the rest are the tail kernel's (tile fastest, sub slowest, as in its own grid).  The write pass touches the
 // sampler's buffers and the line buffer only -- nothing the tail kernel reads.
-struct WriteKArgs {
-    unsigned long long *rng_state;
-    const float *r, *centers;
-    const unsigned long long *accept;
-    float *lines;
-    int32_t *filled;
-    int n, rounds, gx, gy;
-};
 template <bool SCATTER>
 __global__ __launch_bounds__(TAIL_LANES) __attribute__((amdgpu_waves_per_eu(4, 8))) void tail_write_kernel(const TailArgs a,
                                                                                                           const WriteKArgs c) {

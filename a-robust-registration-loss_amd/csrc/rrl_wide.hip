@@ -25,7 +25,6 @@
 #include "rrl_ws.h"
 
 #define WIDE_HITS 8      // hits kept per line and cloud (RRL_WIDE_MAX_HITS)
-#define WIDE_FIX_SHIFT 40  // = FIX_SHIFT of the narrow reduce (rrl_sparse.hip)
 
 static_assert(WIDE_HITS == RRL_WIDE_MAX_HITS, "include/rrl.h");
 
@@ -294,8 +293,8 @@ __global__ __launch_bounds__(1024) void wide_reduce_kernel(const WideArgs a) {
             // fixed-point sums: flag it
             if (!(row <= (float)WIDE_HITS) || !(col <= (float)WIDE_HITS)) { atomicOr(&s_bad, 1); row = col = 0.0f; }
             const int bi = (k - 1) * WIDE_HITS + (j - 1);
-            atomicAdd(&s_sum[bi * 2 + 0], (unsigned long long)((double)row * (double)(1ll << WIDE_FIX_SHIFT) + 0.5));
-            atomicAdd(&s_sum[bi * 2 + 1], (unsigned long long)((double)col * (double)(1ll << WIDE_FIX_SHIFT) + 0.5));
+            atomicAdd(&s_sum[bi * 2 + 0], (unsigned long long)((double)row * (double)(1ll << FIX_SHIFT) + 0.5));
+            atomicAdd(&s_sum[bi * 2 + 1], (unsigned long long)((double)col * (double)(1ll << FIX_SHIFT) + 0.5));
             atomicAdd(&s_cnt[bi], 1);
         }
     }
@@ -312,7 +311,7 @@ __global__ __launch_bounds__(1024) void wide_reduce_kernel(const WideArgs a) {
     const bool in = S > 0 && k >= a.s_m && k < a.e_m && j >= a.s_n && j < a.e_n;
     float term = 0.0f;
     if (in) {
-        const double sc = 1.0 / (double)(1ll << WIDE_FIX_SHIFT);
+        const double sc = 1.0 / (double)(1ll << FIX_SHIFT);
         const float mrow = (float)((double)srow * sc / ((double)S * k));
         const float mcol = (float)((double)scol * sc / ((double)S * j));
         const float wkj = expf(-0.5f * (float)abs(k - j));  // code/loss.py:215
@@ -336,7 +335,7 @@ __global__ __launch_bounds__(1024) void wide_reduce_kernel(const WideArgs a) {
 
 // ---- W5: backward.  dL/dD[p][r] = gout w_kj / C exp(-D / (2 med)) / (2 med) ([r = argmin row p] / (S k) +
 //      [p = argmin column r] / (S j)), dL/dq1[p] = sum_r 2 (q1_p - q2_r) dL/dD = -dL/dq2 summed the other way,
-//      dL/dP[f][kk] += w_kk / 3 dL/dq.  The narrow scatter's expressions and accumulation orders (rrl_stage_bwd.inc
+//      dL/dP[f][kk] += w_kk / 3 dL/dq.  The narrow scatter's expressions and accumulation orders (rrl_stage_bwd.h
 //      bwd_scatter_math: row p over r ascending, column r over p ascending); only the order of the float atomics differs.
 __global__ __launch_bounds__(256) void wide_bwd_kernel(const WideArgs a) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;

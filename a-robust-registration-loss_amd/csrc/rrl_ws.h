@@ -1,6 +1,6 @@
 // rrl_ws.h -- the host layer's shared types: the layouts of the caller-allocated workspaces (WsLayout, WwLayout: generated from
 // the field tables of include/rrl.h), the record of ONE call (RrlCall: options, plan, shape, bucket range, workspace + layout, stream -- set once at
-// the top of an extern "C" entry by rrl_begin_call, validated once by rrl_check_call, then handed to every host function
+// the top of an extern "C" entry by rrl_begin_call, validated once by rrl_check_call (both rrl_call.hip), then handed to every host function
 // below the entry), and the prototypes of the host functions that cross translation units.
 // Every field starts on a 256-byte boundary, the fields follow each other in table order.
 #pragma once
@@ -46,6 +46,33 @@ static_assert(RRL_WS_STATUS == 0 && RRL_WS_NVALS == 1 && RRL_WS_NSEL == 2 && RRL
                   RRL_WS_COUNT2 == 5, "zero_bytes: one fill clears the per-call state, the first six fields");
 static_assert(RRL_WS_MCTL == RRL_WS_MHIST + 1 && RRL_WS_MSUM == RRL_WS_MHIST + 2, "state_off / state_bytes span MHIST .. MSUM");
 static_assert(RRL_WS_KJC == RRL_WS_GACC + 1, "GACC is cleared up to KJC's offset (rrl_launch_tri_build)");
+// ... and about the control words inside MCTL and CHAIN rows (include/rrl.h RRL_MCTL_*, RRL_CHAIN_*), what used to be a
+// convention between five files: the rows are the tables' last extents, no two users share a word
+template <class... D>
+constexpr size_t rrl_last_extent(D... d) { size_t v = 0; ((v = (size_t)d), ...); return v; }
+#define RRL_ROW_LAST_(name, type, ...) rrl_last_extent(__VA_ARGS__),
+constexpr size_t rrl_ws_last_extent(int field) {
+    const size_t b = 1, n = 1, m = 1, l = 1, g = 1;
+    const size_t last[] = {RRL_WS_TABLE(RRL_ROW_LAST_)};
+    return last[field];
+}
+constexpr bool rrl_mctl_words_distinct() {
+    const int w[] = {RRL_MCTL_CURSOR, RRL_MCTL_TICK1, RRL_MCTL_TICK2, RRL_MCTL_ERR, RRL_MCTL_MEDBITS, RRL_MCTL_MEDRDY, RRL_MCTL_BAD,
+                     RRL_MCTL_CHAM_GROUP, RRL_MCTL_CHAM_GROUP + 1, RRL_MCTL_CHAM_TOP, RRL_MCTL_LSUM, RRL_MCTL_LSUM + 1};
+    const int nw = (int)(sizeof w / sizeof *w);
+    for (int i = 0; i < nw; ++i) {
+        if (w[i] < RRL_MCTL_BUCKET0 + 16 || w[i] >= RRL_MCTL_WORDS) return false;  // (the sixteen buckets come first)
+        for (int j = 0; j < i; ++j)
+            if (w[j] == w[i]) return false;
+    }
+    return true;
+}
+static_assert(rrl_ws_last_extent(RRL_WS_MCTL) == RRL_MCTL_WORDS && rrl_ws_last_extent(RRL_WS_CHAIN) == RRL_CHAIN_WORDS,
+              "the rows of MCTL and CHAIN as include/rrl.h's table sizes them");
+static_assert(rrl_mctl_words_distinct(), "MCTL: behind the buckets, inside the row, no word with two users");
+static_assert(RRL_MCTL_LSUM % 2 == 0 && RRL_MCTL_LSUM + 2 <= RRL_MCTL_WORDS, "MCTL: the loss sum is one aligned uint64 inside row 0");
+static_assert(RRL_CHAIN_READY == 0 && RRL_CHAIN_NAN == 1 && RRL_CHAIN_FALLBACK == 2 && RRL_CHAIN_TIMEOUT == 3 && RRL_CHAIN_WORDS == 4,
+              "CHAIN: one 16-byte row per sample; the fused launch's scan takes [NAN], [FALLBACK] as its STATUS[0], [1]");
 struct WsLayout : RrlLayout<0, RRL_WS_FIELDS> {
     size_t zero_bytes;
     size_t state_off, state_bytes;  // MHIST .. MSUM: per-call state of the tiled reduce (cleared by the records kernel)
@@ -95,7 +122,7 @@ struct RrlXform;
 // the reduce that serves a call (TILE: one tile of lines per sample, per-line stage + reduce + a backward in one launch).
 enum { RRL_WANT_NONE = -1, RRL_WANT_STAGE, RRL_WANT_FORWARD, RRL_WANT_SCATTER, RRL_WANT_SCATTER2, RRL_WANT_DIRECT };
 enum { RRL_RED_SINGLE, RRL_RED_XCHG, RRL_RED_TAIL, RRL_RED_TILE };
-// Which kernels serve ONE call of the narrow pipeline, decided by rrl_plan (rrl_sparse.hip) before its first launch; the
+// Which kernels serve ONE call of the narrow pipeline, decided by rrl_plan (rrl_call.hip) before its first launch; the
 // launchers read it and derive none of it again.  All zero (rrl_begin_call): nothing rides, nothing chains.
 struct RrlPlan {
     int scan_mode;          // cull demoted to auto beyond the sort capacity
@@ -108,6 +135,10 @@ struct RrlPlan {
     int fused_build;        // RRL_F_CHAINED honoured (only with leave_clean): records + both scans as ONE launch
     int count_rides, write_rides;  // the RrlCountRider rides in the per-line launch, the RrlWriteRider in the backward's
 };
+// The tail kernel's geometry as far as the plan needs it (rrl_stage_tail.h has the rest): line tiles per sample it serves,
+// lanes per workgroup
+constexpr int TAIL_MAX_TILES = 32;
+constexpr int TAIL_LANES = 512;
 struct RrlCall {
     int flags;
     int reduce_mode;    // 0 auto, 1 single, 2 tiled, 3 xchg
@@ -153,7 +184,7 @@ struct RrlCall {
     __host__ bool target_kept() const { return order1 != nullptr && (flags & RRL_F_TARGET_KEPT); }
     __host__ bool ragged() const { return count1 != nullptr || count2 != nullptr || nlines != nullptr; }
 };
-// The record of one call (rrl_sparse.hip): rrl_opts resolved + the shape, the workspace with its layout, the stream; bucket
+// The record of one call (rrl_call.hip): rrl_opts resolved + the shape, the workspace with its layout, the stream; bucket
 // range 1 .. 4, pool 0, scan mode cull, chunk 0 until the entry sets what it was given (RrlCall::set)
 RrlCall rrl_begin_call(const rrl_opts *opts, int B, int N, int M, int L, void *ws, size_t ws_bytes, void *stream);
 // THE validation of a narrow entry, before its first launch, in the order of include/rrl.h ("Refusals"): RRL_E_ARG --
@@ -192,7 +223,7 @@ int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, f
 int rrl_fused_backward(int B, int N, int M);
 int rrl_launch_reg_bwd(const RrlCall &o, const float *src, const float *R, float *grad_src, float *gR, float *gt,
                        float *payload, const float *loss, int transpose_r);  // (G1 -> grad_src, gR, gt; RPART, INFO, STATUS[3])
-// Sample b's workgroups on XCD b % 8 (rrl_stage_pair.inc xcd_sample_of; the records launch places (cloud, sample) pairs the
+// Sample b's workgroups on XCD b % 8 (rrl_stage_pair.h xcd_sample_of; the records launch places (cloud, sample) pairs the
 // same way).  RRL_XCD_ALIGN=0 turns it off (experimental builds): the one reader of that knob, for every launcher
 inline int xcd_align_on() {
     static int v = -1;
@@ -205,9 +236,15 @@ inline int xcd_align_on() {
     return v;
 }
 // the process-wide defaults, one accessor per translation unit that owns one
+bool rrl_default_deterministic(void);                                       // rrl_call.hip (rrl_set_deterministic)
+unsigned rrl_default_spin_limit(void);                                      // rrl_call.hip (rrl_set_spin_limit)
 int rrl_default_sort_parts(void);                                           // rrl_cull.hip
 void rrl_default_scan_counters(unsigned long long **buf, long long *rows);  // rrl_cull.hip
 int rrl_default_scan_variant(void);                                         // rrl_scan.hip
+
+// Workgroups of the exchange reduce that are co-resident on the current device: the plan's bound for choosing it
+// (rrl_sparse.hip, next to the kernel whose occupancy it queries)
+long rrl_xchg_capacity(void);
 
 // Rigid transform of the source cloud folded into the prepare step (the fused training op):
 // tri1 = src moved by (R, t) per sample, stored into the workspace field TRI1.

@@ -92,6 +92,9 @@ EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamf
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
 F_CHAIN = 2        # RRL_F_CHAIN: leave the hit counts / CHAIN words cleared for the next step on this workspace
 F_CHAINED = 4      # RRL_F_CHAINED: the previous step did (chain_left = 1): records + both scans as one launch
+# control words of a sample's MCTL / CHAIN row that Python reads (include/rrl.h RRL_MCTL_* / RRL_CHAIN_*: the one map)
+MCTL_ERR = 19      # RRL_MCTL_ERR: a hand-off of the exchange reduce ran into its time-out
+CHAIN_TIMEOUT = 3  # RRL_CHAIN_TIMEOUT: source workgroups of a chained step that gave up waiting for their records
 
 
 class ChamferRider(ctypes.Structure):

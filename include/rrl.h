@@ -147,7 +147,10 @@ extern "C" {
     X(MHIST, int32_t, b, 2048) /* histogram of the D values' bits 30..20, accumulated by the per-line stage (the
                           median's first radix pass); MHIST, MCTL, MSUM are contiguous and cleared per call                 */    \
     X(MCTL, int32_t, b, 64) /* [0..15] lines per (k,j) bucket (per-line stage); [16] candidate cursor, [17] / [18]
-                          arrival counters of the tiled reduce, [19] its error flag (spin time-out)                          */   \
+                          arrival counters of the tiled reduce, [19] its error flag (spin time-out), [20] / [21] the median's
+                          bits and their ready flag (crowded bin), [22] a non-finite Welsch term; [30], [31] arrival counters
+                          of the Chamfer walk on this workspace, per direction; row 0 only: [32] that walk's counter of the
+                          groups, [34..35] uint64 fixed-point sum of the valid losses (the step's payload): RRL_MCTL_* below */   \
     X(MSUM, int64_t, b, 32) /* bucket sums of the tiled reduce (2^-40 fixed point, device atomics) */                             \
     X(MCAND, int32_t, b, 2048) /* D values (bit patterns) of the median's bin, gathered by the tiled reduce */                    \
     X(LMAX, float, b, 64, 2) /* (max |dir|^2, max |x0|^2) over 1/64 of a sample's cullable lines: the culled scan's
@@ -201,6 +204,32 @@ enum { RRL_WS_TABLE(RRL_WS_ENUM_) RRL_WS_FIELDS };
     X(INFO, int32_t, g, 4)       /* nbuckets, nselected, nvalues, the scan's NaN flag (STATUS[0] of ws) */
 #define RRL_WW_ENUM_(name, type, ...) RRL_WW_##name,
 enum { RRL_WW_TABLE(RRL_WW_ENUM_) RRL_WW_FIELDS };
+
+/* ---- control words ---------------------------------------------------------------------------
+ * The words inside a sample's MCTL and CHAIN rows (RRL_WS_TABLE above) that kernels of different launches hand to each
+ * other: ONE map, so that nobody has to find every user to know that they do not overlap (csrc/rrl_ws.h asserts it).
+ * All of them are zero between calls: their last user rewinds them. */
+enum {
+    RRL_MCTL_BUCKET0 = 0,     /* [0..15] lines per (k, j) bucket, index (k - 1) 4 + (j - 1): per-line stage -> reduce */
+    RRL_MCTL_CURSOR = 16,     /* exchange reduce: cursor of the sample's candidate list (MCAND) */
+    RRL_MCTL_TICK1 = 17,      /* exchange reduce: workgroups that have published their candidates */
+    RRL_MCTL_TICK2 = 18,      /* exchange reduce, tail kernel: workgroups whose sums are in MSUM; the last arriver finishes */
+    RRL_MCTL_ERR = 19,        /* exchange reduce: a hand-off timed out (rrl_set_spin_limit): the last workgroup repairs */
+    RRL_MCTL_MEDBITS = 20,    /* exchange reduce, crowded bin: the median's bit pattern, published by tile 0 ... */
+    RRL_MCTL_MEDRDY = 21,     /* ... and its ready flag */
+    RRL_MCTL_BAD = 22,        /* exchange reduce, tail kernel: a non-finite Welsch term (median 0): the loss is NaN */
+    RRL_MCTL_CHAM_GROUP = 30, /* [30], [31] Chamfer walk on the loss workspace: arrival counter of the sample's direction */
+    RRL_MCTL_CHAM_TOP = 32,   /* row 0 only: ... and of the (sample, direction) groups */
+    RRL_MCTL_LSUM = 34,       /* row 0 only, [34..35]: uint64 2^-40 fixed-point sum of the valid samples' losses (payload[0]) */
+    RRL_MCTL_WORDS = 64       /* the row */
+};
+enum {
+    RRL_CHAIN_READY,    /* records workgroups of the sample that have finished in the chained step's build + scan launch */
+    RRL_CHAIN_NAN,      /* that launch's NaN flag of the sample (the plain scan: STATUS[0]) */
+    RRL_CHAIN_FALLBACK, /* ... its wavefronts that fell back to the strict loop (STATUS[1]) */
+    RRL_CHAIN_TIMEOUT,  /* source workgroups that gave up waiting for their records: the sample's loss is NaN */
+    RRL_CHAIN_WORDS     /* the row */
+};
 
 const char *rrl_version(void);
 /* Largest cloud (triangles of either cloud) that the SORTED layout serves: the per-step cell sort and sphere tree, the
@@ -552,7 +581,7 @@ int rrl_loss_reduce_rows(const float *rows16, const uint8_t *kj, int nrows, int3
                          int s_n, int e_m, int e_n, void *stream);
 
 /* Which reduce kernel rrl_loss_reduce (and the fused forwards) launch -- the DEFAULT; a call's rrl_opts.reduce_mode
- * overrides it.  Three kernels, bit-identical median, loss and bucket sums (csrc/rrl_sparse.hip reduce_kind):
+ * overrides it.  Three kernels, bit-identical median, loss and bucket sums (csrc/rrl_call.hip reduce_kind):
  *   single   one 1024-lane workgroup per sample (always legal; the only one for pool != 0);
  *   xchg     loss_reduce_tiled_kernel: one 256-lane workgroup per 1024-line tile; the median's first radix pass comes as a
  *            histogram from the per-line stage, the tiles exchange the values of the median's bin through the workspace

@@ -1656,7 +1656,7 @@ def test_tiled_reduce_equals_single_workgroup(L, case):
                 ops._run(st.ws.device, "rrl_loss_reduce", ops._p(st.ws), st.nbytes, ops._p(st.loss), B, N, M, Ll, 1, 1, 5, 5, 0)
                 torch.cuda.synchronize()
                 out["again_" + mode] = [t.cpu().numpy().copy() for t in (st.loss, st.med, st.info, st.bcnt, st.bsum)]
-                assert int(st.mctl[:, 19].sum()) == 0  # no spin ran into its time-out
+                assert int(st.mctl[:, _lib.MCTL_ERR].sum()) == 0  # no spin ran into its time-out
     finally:
         ops.set_reduce_mode("auto")
     for other in ("tiled", "xchg", "again_tiled", "again_xchg"):

@@ -261,3 +261,55 @@ def test_ctypes_structs_match_the_header(tmp_path):
         assert int(got[name]) == ctypes.sizeof(cls), name
         for f, _ in cls._fields_:
             assert int(got[f"{name}.{f}"]) == getattr(cls, f).offset, (name, f)
+
+
+STAGE_HEADERS = ["rrl_stage_pair.h", "rrl_stage_reduce.h", "rrl_stage_tail.h", "rrl_stage_bwd.h", "rrl_stage_args.h", "rrl_stamps.h"]
+
+
+@pytest.mark.parametrize("header", STAGE_HEADERS)
+def test_stage_headers_stand_alone(tmp_path, header):
+    """Every header of the stages behind the scan includes what it uses and needs no macro from its includer: a unit that
+    holds nothing but `#include "<header>"` passes hipcc with the library's flags."""
+    import subprocess
+    from rrl_hip import build
+    unit = tmp_path / "alone.hip"
+    unit.write_text(f'#include "{os.path.join(build.CSRC, header)}"\n')
+    subprocess.check_call([build._hipcc(), *build.FLAGS, "-fsyntax-only", str(unit)])
+
+
+def test_control_word_map():
+    """The control words of a sample's MCTL / CHAIN row have ONE map, include/rrl.h's RRL_MCTL_* / RRL_CHAIN_* enumerators:
+    the values the Python binding mirrors equal it, the row lengths are the last extents of the two fields in the workspace
+    table, and no two users of an MCTL word share one."""
+    from rrl_hip import _lib
+    header = open(os.path.join(ROOT, "include", "rrl.h")).read()
+    words = {}
+    for body in re.findall(r"enum\s*\{([^}]*)\}", header):
+        if "RRL_MCTL_" not in body and "RRL_CHAIN_" not in body:
+            continue
+        value = -1
+        for item in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(","):
+            if not item.strip():
+                continue
+            name, _, explicit = (x.strip() for x in item.partition("="))
+            value = int(explicit) if explicit else value + 1
+            words[name] = value
+    mctl = {k[len("RRL_MCTL_"):]: v for k, v in words.items() if k.startswith("RRL_MCTL_")}
+    chain = {k[len("RRL_CHAIN_"):]: v for k, v in words.items() if k.startswith("RRL_CHAIN_")}
+    assert set(mctl) == {"BUCKET0", "CURSOR", "TICK1", "TICK2", "ERR", "MEDBITS", "MEDRDY", "BAD", "CHAM_GROUP", "CHAM_TOP", "LSUM",
+                         "WORDS"}
+    assert list(chain) == ["READY", "NAN", "FALLBACK", "TIMEOUT", "WORDS"] and list(chain.values()) == [0, 1, 2, 3, 4]
+    mirrored = {k: v for k, v in vars(_lib).items() if k.startswith(("MCTL_", "CHAIN_"))}
+    assert mirrored and "MCTL_ERR" in mirrored
+    for name, value in mirrored.items():
+        assert words["RRL_" + name] == value, name
+    # the rows: the last extent of the field's row in RRL_WS_TABLE
+    for field, row in (("MCTL", mctl["WORDS"]), ("CHAIN", chain["WORDS"])):
+        extents = re.search(r"X\(%s, int32_t, ([^)]*)\)" % field, header).group(1)
+        assert int(extents.split(",")[-1]) == row, field
+    # MCTL: sixteen buckets, then every user's words (two Chamfer directions, a 64-bit loss sum), distinct and inside the row
+    used = [mctl[k] for k in ("CURSOR", "TICK1", "TICK2", "ERR", "MEDBITS", "MEDRDY", "BAD", "CHAM_TOP")]
+    used += [mctl["CHAM_GROUP"], mctl["CHAM_GROUP"] + 1, mctl["LSUM"], mctl["LSUM"] + 1]
+    used += list(range(mctl["BUCKET0"], mctl["BUCKET0"] + 16))
+    assert len(set(used)) == len(used) and min(used) >= 0 and max(used) < mctl["WORDS"]
+    assert mctl["LSUM"] % 2 == 0
