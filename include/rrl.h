@@ -870,11 +870,15 @@ int rrl_sample_lines_rng(uint64_t *rng_state, const float *r, const float *cente
 
 /* ---- pseudo-triangle builder (code/loss.py:473-485 + code/utils.py:275-296) --------------- */
 /* Farthest-point sampling of S <= n points per cloud, starting at start[b] (the reference draws it
- * with torch.randint): out_idx [B][S] in selection order.  pts [B][n][3]; dist_scratch [B][n]. */
+ * with torch.randint; 0 <= start[b] < n is the caller's to guarantee): out_idx [B][S] in selection order.  pts [B][n][3];
+ * dist_scratch [B][n].  Distances start at 1e10 like the reference's, so squared distances above it tie; ties go to the
+ * lower index; once every distance is 0 the remaining samples are index 0. */
 int rrl_fps(const float *pts, const int32_t *start, int32_t *out_idx, float *dist_scratch, int B,
             int n, int S, void *stream);
-/* 3 nearest neighbours (itself first) of the points query_idx [B][S] among the n points of their
- * cloud: nn [B][S][3], ascending distance, ties to the lower index (sklearn KDTree.query, k=3). */
+/* 3 nearest neighbours of the points query_idx [B][S] among ALL n points of their cloud (the query itself and its
+ * duplicates included): nn [B][S][3], ascending distance, the lowest index among equals (sklearn KDTree.query, k=3) --
+ * a query comes first unless a duplicate of it has a lower index.  n >= 3 and 0 <= query_idx < n are the caller's to
+ * guarantee (rrl_hip.neighbors checks both on the host). */
 int rrl_knn3(const float *pts, const int32_t *query_idx, int32_t *nn, int B, int n, int S,
              void *stream);
 
