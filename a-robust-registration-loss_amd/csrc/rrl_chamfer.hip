@@ -100,6 +100,17 @@ __global__ __launch_bounds__(256) void pts_records_kernel(const float *__restric
     }
 }
 
+// pts_records_kernel for ONE cloud pts [B][n][3] (rrl_knn_tree.hip: the 3-NN of a cloud's own points builds the same records):
+// crec [B][16 ceil(n / 16)], apart [B][nblk][8], zero / zero_vec4: 16-byte words the launch clears; cnt: NULL or the points
+// sample b really has.
+int rrl_launch_pts_records(const float *pts, float4 *crec, float *apart, void *zero, size_t zero_vec4, int B, int n, int nblk,
+                           const int32_t *cnt, hipStream_t s) {
+    hipLaunchKernelGGL(pts_records_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B, 1u), dim3(256), 0, s, pts, pts, crec,
+                       crec, apart, (uint4 *)zero, zero_vec4, B, n, n, nblk, cnt, cnt);
+    RRL_LAUNCH_CHECK();
+    return 0;
+}
+
 // Prepared point clouds (round 4; include/rrl.h rrl_chamfer_tree_fwd_ex, order_x / order_y from rrl_cloud_order on the
 // same clouds in any rigid pose): the sort leaves the call.  One lane per SORTED position gathers its point, writes the
 // (x, y, z, original index) record there and the wavefront -- one supergroup -- refits its 13 tree nodes (wave_tree,

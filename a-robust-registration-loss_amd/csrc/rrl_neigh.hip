@@ -4,6 +4,7 @@
 // Preprocessing outside the timed loss path; correctness first, but no host round trips:
 // the S sequential FPS iterations run inside ONE workgroup with one barrier per iteration.
 #include "rrl_common.h"
+#include "rrl_knn3_loop.h"
 
 // (value, index) key: larger distance wins, then the SMALLER index (torch.max's first occurrence)
 __device__ __forceinline__ unsigned long long fps_key(float d, int i) {
@@ -147,6 +148,139 @@ extern "C" int rrl_knn3(const float *pts, const int32_t *query_idx, int32_t *nn,
     if (B == 0 || S == 0) return 0;
     hipLaunchKernelGGL(knn3_kernel, dim3((unsigned)((S + 255) / 256), (unsigned)B), dim3(256), 0,
                        (hipStream_t)stream, pts, query_idx, nn, n, S);
+    RRL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- counted entries (include/rrl.h "pseudo-triangles on the device"): ragged batches, no host round trip ----------------
+// Kernels of their own, so that fps_kernel and knn3_kernel above keep their code.
+
+// fps_kernel on the first n_b = clamp(counts[b], 0, n) points of sample b (counts == NULL: n): the same arithmetic in the
+// same order, so the S_b = min(S, n_b) indices are those of rrl_fps on pts[b, :n_b]; the entries beyond S_b are 0 and the
+// rows beyond n_b are never read.  start[b] is clamped into [0, n_b) (memory safety only).  out_cnt (optional): S_b.
+template <bool IN_LDS>
+__global__ __launch_bounds__(1024) void fps_counted_kernel(const float *__restrict__ pts, const int32_t *__restrict__ counts,
+                                                           const int32_t *__restrict__ start, int32_t *__restrict__ out,
+                                                           int32_t *__restrict__ out_cnt, float *__restrict__ dist_g,
+                                                           int ncap, int S) {
+    extern __shared__ __attribute__((aligned(16))) float4 cache[];  // IN_LDS: (x, y, z, distance)
+    __shared__ unsigned long long wbest[2][16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = rrl_rows(counts, b, ncap);  // uniform
+    const int Sb = min(S, n);
+    const float *p = pts + (size_t)b * ncap * 3;
+    float *dg = dist_g + (size_t)b * ncap;
+    for (int i = Sb + tid; i < S; i += 1024) out[(size_t)b * S + i] = 0;
+    if (tid == 0 && out_cnt != nullptr) out_cnt[b] = Sb;
+    if (Sb == 0) return;  // uniform
+    for (int i = tid; i < n; i += 1024) {
+        if (IN_LDS) cache[i] = make_float4(p[3 * i], p[3 * i + 1], p[3 * i + 2], 1e10f);
+        else dg[i] = 1e10f;
+    }
+    int far = min(max(start[b], 0), n - 1);
+    __syncthreads();
+    for (int it = 0; it < Sb; ++it) {
+        if (tid == 0) out[(size_t)b * S + it] = far;
+        float cx, cy, cz;
+        if (IN_LDS) { const float4 c = cache[far]; cx = c.x; cy = c.y; cz = c.z; }
+        else { cx = p[3 * far]; cy = p[3 * far + 1]; cz = p[3 * far + 2]; }
+        unsigned long long best = 0;
+        for (int i = tid; i < n; i += 1024) {
+            float x, y, z, d;
+            if (IN_LDS) { const float4 q = cache[i]; x = q.x; y = q.y; z = q.z; d = q.w; }
+            else { x = p[3 * i]; y = p[3 * i + 1]; z = p[3 * i + 2]; d = dg[i]; }
+            const float dx = x - cx, dy = y - cy, dz = z - cz;
+            float s = dx * dx;
+            s = s + dy * dy;
+            s = s + dz * dz;
+            if (s < d) {  // distance[mask] = dist[mask]
+                d = s;
+                if (IN_LDS) cache[i].w = d; else dg[i] = d;
+            }
+            const unsigned long long k = fps_key(d, i);
+            best = k > best ? k : best;
+        }
+        best = wave_max_u64(best);
+        if (lane == 0) wbest[it & 1][wave] = best;
+        __syncthreads();
+        unsigned long long all = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const unsigned long long x = wbest[it & 1][w];
+            all = x > all ? x : all;
+        }
+        far = (int)(0xffffffffu - (unsigned)all);
+        far = min(far, n - 1);  // (all distances NaN: no key beats 0 -- memory safety only)
+    }
+}
+
+extern "C" int rrl_fps_counted(const float *pts, const int32_t *counts, const int32_t *start, int32_t *out_idx,
+                               int32_t *out_counts, float *dist_scratch, int B, int n, int S, void *stream) {
+    if (!pts || !start || !out_idx || !dist_scratch || B < 0 || n <= 0 || S < 0 || S > n) return RRL_E_ARG;
+    if (B == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if ((size_t)n * 16 <= 128 * 1024)
+        hipLaunchKernelGGL(fps_counted_kernel<true>, dim3((unsigned)B), dim3(1024), (size_t)n * 16, s, pts, counts, start,
+                           out_idx, out_counts, dist_scratch, n, S);
+    else
+        hipLaunchKernelGGL(fps_counted_kernel<false>, dim3((unsigned)B), dim3(1024), 0, s, pts, counts, start, out_idx,
+                           out_counts, dist_scratch, n, S);
+    RRL_LAUNCH_CHECK();
+    return 0;
+}
+
+// knn3_kernel's loop over the first n_b points of sample b for its first S_b = clamp(qcounts[b], 0, S) queries (NULL: S);
+// query_idx == NULL: query q is point q.  A sample of fewer than three points has no neighbours: S_b = 0.  Query indices
+// are clamped into [0, n_b).  Rows beyond S_b are zero.  tri (optional): [pts[nn0], pts[nn1], pts[nn2]] per query;
+// tri_cnt (optional): S_b.
+__global__ __launch_bounds__(256) void knn3_counted_kernel(const float *__restrict__ pts, const int32_t *__restrict__ counts,
+                                                           const int32_t *__restrict__ query_idx,
+                                                           const int32_t *__restrict__ qcounts, int32_t *__restrict__ nn,
+                                                           float *__restrict__ tri, int32_t *__restrict__ tri_cnt, int ncap,
+                                                           int S) {
+    const int b = blockIdx.y;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const int nraw = rrl_rows(counts, b, ncap);  // uniform
+    const int n = nraw >= 3 ? nraw : 0;
+    const int Sb = n ? rrl_rows(qcounts, b, S) : 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && tri_cnt != nullptr) tri_cnt[b] = Sb;
+    const float *p = pts + (size_t)b * ncap * 3;
+    if ((int)blockIdx.x * 256 >= Sb) {  // uniform: nothing but absent rows
+        if (q < S) {
+            int32_t *o = nn + ((size_t)b * S + q) * 3;
+            o[0] = 0; o[1] = 0; o[2] = 0;
+            if (tri != nullptr)
+                for (int c = 0; c < 9; ++c) tri[((size_t)b * S + q) * 9 + c] = 0.0f;
+        }
+        return;
+    }
+    int qi = q < Sb ? (query_idx ? query_idx[(size_t)b * S + q] : q) : 0;
+    qi = min(max(qi, 0), n - 1);
+    int i0, i1, i2;
+    knn3_brute_loop(p, n, qi, i0, i1, i2);
+    if (q < S) {
+        const bool live = q < Sb;
+        int32_t *o = nn + ((size_t)b * S + q) * 3;
+        o[0] = live ? i0 : 0; o[1] = live ? i1 : 0; o[2] = live ? i2 : 0;
+        if (tri != nullptr) {
+            float *t = tri + ((size_t)b * S + q) * 9;
+            const int src[3] = {i0, i1, i2};
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) t[3 * k + c] = live ? p[3 * src[k] + c] : 0.0f;
+        }
+    }
+}
+
+extern "C" int rrl_knn3_counted(const float *pts, const int32_t *counts, const int32_t *query_idx, const int32_t *qcounts,
+                                int32_t *nn, float *tri, int32_t *tri_counts, int B, int n, int S, void *stream) {
+    if (!pts || !nn || B < 0 || n <= 0 || S < 0) return RRL_E_ARG;
+    if (query_idx == nullptr && S > n) return RRL_E_ARG;  // row order: query q is point q
+    if (B == 0) return 0;
+    if (S == 0 && tri_counts == nullptr) return 0;
+    hipLaunchKernelGGL(knn3_counted_kernel, dim3((unsigned)((S + 255) / 256 > 0 ? (S + 255) / 256 : 1), (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, pts, counts, query_idx, qcounts, nn, tri, tri_counts, n, S);
     RRL_LAUNCH_CHECK();
     return 0;
 }

@@ -219,6 +219,9 @@ int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, f
                           float4 *p0s1, float4 *p0s2, int32_t *idx1, int32_t *idx2, float4 *grp1, float4 *grp2,
                           uint32_t *pmax, unsigned *histg, uint32_t *zwords, int nzwords, int B, int N, int M,
                           const int32_t *cnt1, const int32_t *cnt2, hipStream_t s);
+// the Chamfer path's records launch for one cloud (rrl_chamfer.hip), for the 3-NN tree's build (rrl_knn_tree.hip)
+int rrl_launch_pts_records(const float *pts, float4 *crec, float *apart, void *zero, size_t zero_vec4, int B, int n, int nblk,
+                           const int32_t *cnt, hipStream_t s);
 // the rigid backward behind the scatter (rrl_geom.hip)
 int rrl_fused_backward(int B, int N, int M);
 int rrl_launch_reg_bwd(const RrlCall &o, const float *src, const float *R, float *grad_src, float *gR, float *gt,

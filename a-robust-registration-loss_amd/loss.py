@@ -264,3 +264,16 @@ def Sample_neighs(points, num_sample=5000, num_neigh=3, device='cpu'):
     drawn with torch.randint from the CPU generator like the reference's."""
     from rrl_hip import neighbors
     return neighbors.sample_neighs(points, num_sample, num_neigh)
+
+
+def pseudo_triangles(points, num_sample=None, **kw):
+    """Sample_neighs for a whole batch, on the device (rrl_hip.neighbors.pseudo_triangles): points (B, n, 3) ->
+    (tri (B, S, 9), tri_counts, ...); per-sample counts, no host round trip."""
+    from rrl_hip import neighbors
+    return neighbors.pseudo_triangles(points, num_sample, **kw)
+
+
+def knn3_self(points, counts=None, method="auto"):
+    """The three nearest neighbours of every point of its cloud (rrl_hip.neighbors.knn3_self): (B, n, 3) int32."""
+    from rrl_hip import neighbors
+    return neighbors.knn3_self(points, counts, method)

@@ -83,11 +83,15 @@ _SIGS = {
     "rrl_dense_scan": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "rrl_fps": [_P, _P, _P, _P, _I, _I, _I, _P],
     "rrl_knn3": [_P, _P, _P, _I, _I, _I, _P],
+    "rrl_fps_counted": [_P] * 6 + [_I] * 3 + [_P],
+    "rrl_knn3_counted": [_P] * 7 + [_I] * 3 + [_P],
+    "rrl_knn3_self": [_P, _P, _P, _Z, _P, _P, _P, _I, _I, _P],
     "rrl_sample_lines": [_P] * 8 + [_I] * 3 + [_P],
     "rrl_sample_lines_rng": [_P] * 8 + [_I] * 3 + [_P],
 }
 EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamfer_workspace_bytes",
-                                 "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes", "rrl_sort_capacity"])
+                                 "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes", "rrl_sort_capacity",
+                                 "rrl_knn3_self_workspace_bytes"])
 
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
 F_CHAIN = 2        # RRL_F_CHAIN: leave the hit counts / CHAIN words cleared for the next step on this workspace
@@ -161,6 +165,8 @@ def load():
     lib.rrl_chamfer_workspace_bytes.restype = _Z
     lib.rrl_cloud_order_workspace_bytes.argtypes = [_I, _I]
     lib.rrl_cloud_order_workspace_bytes.restype = _Z
+    lib.rrl_knn3_self_workspace_bytes.argtypes = [_I, _I]
+    lib.rrl_knn3_self_workspace_bytes.restype = _Z
     lib.rrl_sort_capacity.argtypes = []
     lib.rrl_sort_capacity.restype = _I
     _lib = lib

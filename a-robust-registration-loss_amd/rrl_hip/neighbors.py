@@ -3,6 +3,7 @@ utils.farthest_point_sample, code/utils.py:275-296, and sklearn's KDTree).  SURV
 import numpy as np
 import torch
 
+from . import ops as _ops
 from .ops import _home, _p, _run
 
 
@@ -68,3 +69,167 @@ def sample_neighs(points, num_sample=5000, num_neigh=3):
     nn = knn3(pts, idx)[0].long().cpu().numpy()
     out = pts_np[nn.reshape(-1)]  # gathers from the caller's array: keeps its dtype
     return out.reshape(-1, 3)
+
+
+# ---- pseudo-triangles on the device: batched, ragged, tree 3-NN (include/rrl.h) -------------------
+METHODS = ("auto", "brute", "tree")
+# method="auto" takes the tree for the all-points form from this many points per cloud (the capacity n): the smallest
+# measured size from which the tree was faster than brute force on BOTH cloud kinds (a volume and a surface), at B = 1 and
+# B = 8 -- profiles/pseudo_triangles_timing.json, written by tools/pseudo_triangles_timing.py: 1024 is the smallest size measured,
+# and the tree won there and at every larger one (72 .. 109 us against 122 at n = 1024, 0.4 .. 0.8 ms against 37 at 262144).
+# None: never.
+TREE_MIN_POINTS = 1024
+
+
+def _use_tree(method, n):
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if method == "auto":
+        return TREE_MIN_POINTS is not None and TREE_MIN_POINTS <= n <= _ops.sort_capacity()
+    return method == "tree"
+
+
+def _points3(points):
+    if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError("points must be a (B, n, 3) tensor")
+    return points.shape[0], points.shape[1]
+
+
+def _host_counts(counts, B, n, name):
+    """Host-side counts validated before any device is touched (ops.check_counts_host) as int64; None: none, or device data."""
+    host = _ops.check_counts_host(counts, B, n, name)
+    return None if host is None else host.to(torch.int64)
+
+
+def _check_index_counted(idx, hcounts, n, name, shape):
+    """_check_index against each sample's own count where the counts are known on the host (an empty sample admits 0)."""
+    _check_index(idx, n, name, shape)
+    if hcounts is not None and idx.numel():
+        lim = hcounts.clamp(min=1).reshape((-1,) + (1,) * (idx.dim() - 1))
+        if bool((idx.to(torch.int64) >= lim).any()):
+            raise ValueError(f"{name} holds an index outside its sample's count")
+
+
+def knn3_self(points, counts=None, method="auto"):
+    """points (B, n, 3) -> (B, n, 3) int32: the 3 nearest points of EVERY point among its cloud's points, as knn3 orders them
+    (ascending float64 distance, the lowest index among equals, the point itself and its duplicates included).
+    method="tree" walks the sorted layout (include/rrl.h rrl_knn3_self; n <= ops.sort_capacity()), "brute" is knn3's loop,
+    "auto" picks by TREE_MIN_POINTS; the result is the same, bit for bit.  counts: (B,) int32 on the GPU (read by the kernels
+    only: clamped to [0, n], never validated on the host), or a list / CPU tensor (validated, ValueError).  Rows beyond a
+    count, and every row of a sample with fewer than three points, are zero.  ValueError for n < 3."""
+    return _neighbours(points, None, counts, None, method, False)[2]
+
+
+def knn3_counted(points, query_idx, counts=None, qcounts=None):
+    """knn3 for ragged batches (include/rrl.h rrl_knn3_counted; brute force: the tool for S << n): sample b's first qcounts[b]
+    queries among its first counts[b] points; rows beyond are zero.  Device-resident indices and counts are not validated
+    on the host (the kernel clamps them); host-side ones are, as knn3 validates (ValueError before any launch)."""
+    B, n = _points3(points)
+    if n < 3:
+        raise ValueError(f"knn3 needs at least 3 points per cloud, got {n}")
+    if not isinstance(query_idx, torch.Tensor) or query_idx.dim() != 2:
+        raise ValueError("query_idx must be a (B, S) tensor")
+    S = query_idx.shape[1]
+    hc, hq = _host_counts(counts, B, n, "counts"), _host_counts(qcounts, B, S, "qcounts")
+    if not query_idx.is_cuda:
+        _check_index_counted(query_idx, hc, n, "query_idx", (B, S))
+    elif tuple(query_idx.shape) != (B, S) or query_idx.dtype.is_floating_point:
+        raise ValueError(f"query_idx must be an integer tensor of shape {(B, S)}")
+    dev = _home(points, query_idx, counts)
+    pts = _ops._prep(points, "points", 3, dev)
+    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    cnt = _ops.check_counts(counts if hc is None else hc, B, n, dev, "counts")
+    qcnt = _ops.check_counts(qcounts if hq is None else hq, B, S, dev, "qcounts")
+    nn = torch.empty(B, S, 3, dtype=torch.int32, device=dev)
+    _run(dev, "rrl_knn3_counted", _p(pts), _p(cnt), _p(qi), _p(qcnt), _p(nn), None, None, B, n, S)
+    return nn
+
+
+def _neighbours(points, num_sample, counts, start, method, want_tri):
+    """The launches of pseudo_triangles / knn3_self after every host-side refusal: (sample_idx or None, tri or None, nn,
+    tri_counts)."""
+    B, n = _points3(points)
+    tree = _use_tree(method, n)
+    if n < 3:
+        raise ValueError(f"pseudo-triangles need at least 3 points per cloud, got {n}")
+    hc = _host_counts(counts, B, n, "counts")
+    device_counts = counts is not None and hc is None
+    if num_sample is None:
+        if start is not None:
+            raise ValueError("start belongs to the farthest-point sampler: give num_sample with it")
+        if method == "tree" and n > _ops.sort_capacity():
+            raise ValueError(f"the tree serves clouds up to {_ops.sort_capacity()} points, got {n}")
+        S = n
+    else:
+        if method == "tree":
+            raise ValueError('method="tree" serves the all-points form (num_sample=None); given queries take brute force')
+        S = min(int(num_sample), n)
+        if S < 0:
+            raise ValueError(f"num_sample must not be negative, got {num_sample}")
+        if start is not None and not (isinstance(start, torch.Tensor) and start.is_cuda):
+            start = torch.as_tensor(start)
+            _check_index_counted(start, hc, n, "start", (B,))
+        elif start is not None and (tuple(start.shape) != (B,) or start.dtype.is_floating_point):
+            raise ValueError(f"start must be an integer tensor of shape {(B,)}")
+    dev = _home(points, counts, start)
+    pts = _ops._prep(points, "points", 3, dev)
+    cnt = _ops.check_counts(counts if hc is None else hc, B, n, dev, "counts")
+    nn = torch.empty(B, S, 3, dtype=torch.int32, device=dev)
+    tri = torch.empty(B, S, 9, dtype=torch.float32, device=dev) if want_tri else None
+    tric = torch.empty(B, dtype=torch.int32, device=dev) if want_tri else None
+    if num_sample is None:
+        if tree and n <= _ops.sort_capacity():
+            ws = torch.empty(_ops._scratch_size("rrl_knn3_self_workspace_bytes", B, n), dtype=torch.uint8, device=dev)
+            _run(dev, "rrl_knn3_self", _p(pts), _p(cnt), _p(ws), ws.numel(), _p(nn), _p(tri), _p(tric), B, n)
+        else:
+            _run(dev, "rrl_knn3_counted", _p(pts), _p(cnt), None, _p(cnt), _p(nn), _p(tri), _p(tric), B, n, S)
+        return None, tri, nn, tric
+    if start is None:
+        if device_counts:  # drawn on the device and reduced modulo the count: no read-back
+            start = torch.randint(0, n, (B,), device=dev) % cnt.clamp(1, n).to(torch.int64)
+        else:  # like the reference (and fps): the CPU generator; with counts all equal to n the uniform call's draw
+            start = torch.randint(0, n, (B,), dtype=torch.long)
+            if hc is not None:
+                start = start % hc.clamp(min=1)
+    st = start.to(device=dev, dtype=torch.int32).contiguous()
+    idx = torch.empty(B, S, dtype=torch.int32, device=dev)
+    qcnt = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = torch.empty(B, n, dtype=torch.float32, device=dev)
+    _run(dev, "rrl_fps_counted", _p(pts), _p(cnt), _p(st), _p(idx), _p(qcnt), _p(scratch), B, n, S)
+    _run(dev, "rrl_knn3_counted", _p(pts), _p(cnt), _p(idx), _p(qcnt), _p(nn), _p(tri), _p(tric), B, n, S)
+    return idx, tri, nn, tric
+
+
+def pseudo_triangles(points, num_sample=None, *, counts=None, start=None, method="auto", order=False, return_index=False):
+    """The pseudo-triangles of a batch of clouds, built on the device: points (B, n, 3) -> tri (B, S, 9) float32, rows
+    [p, nn1, nn2] as loss.Sample_neighs lays them out (the rows points[nn0], points[nn1], points[nn2]), and tri_counts.
+
+    num_sample=None: every point gets a triangle, in row order (S = n, no sampling).  num_sample given: the counted
+    farthest-point sampler first (S = min(num_sample, n); sample b emits min(S, counts[b]) points, exactly fps's sequence
+    on its own points), then the three neighbours of the samples by brute force.
+    counts: the points each sample really has -- (B,) int32 on the GPU, read by the kernels only, or a list / CPU tensor,
+    validated (ops.check_counts) and uploaded.  points[b, counts[b]:] is never read.  tri_counts (B,) int32 on the GPU holds
+    each sample's triangles (0 for a sample of fewer than three points: three neighbours do not exist) and feeds counts1= /
+    counts2= of the loss and counts= of ops.cloud_order directly; None without counts.  Rows beyond a count are zero.
+    start (B,): the sampler's first index per sample.  By default drawn like the reference's, torch.randint on the CPU
+    generator (torch.manual_seed reproduces loss.Sample_neighs), when counts are absent or host-side; with device counts
+    it is drawn on the device and reduced modulo the count, with no read-back.
+    method: "brute", "tree" (the all-points form only: the sorted layout's sphere tree, n <= ops.sort_capacity()) or
+    "auto" (TREE_MIN_POINTS).  Same result, bit for bit.
+    order=True appends ops.cloud_order(tri, counts=tri_counts); return_index=True appends (sample_idx (B, S) int32 -- the
+    row numbers when nothing was sampled --, nn (B, S, 3) int32), so that a caller can gather differentiably: the output
+    itself carries no grad_fn, like the reference's numpy.
+
+    Device-resident counts and start are NOT validated on the host: the kernels clamp them (counts into [0, n], start into
+    [0, count)).  Host-side ones are validated as fps / knn3 validate, and refused with ValueError before any launch, as
+    are n < 3 and an unknown method.  With device counts and a given start nothing synchronises and the call can be
+    captured in a graph (one plain chain of launches)."""
+    idx, tri, nn, tric = _neighbours(points, num_sample, counts, start, method, True)
+    out = [tri, tric if counts is not None else None]
+    if order:
+        out.append(_ops.cloud_order(tri, counts=out[1]))
+    if return_index:
+        if idx is None:
+            idx = torch.arange(tri.shape[1], dtype=torch.int32, device=tri.device).expand(tri.shape[0], -1)
+        out += [idx, nn]
+    return tuple(out)

@@ -351,6 +351,21 @@ def _refuse_ragged_state(st, what, instead):
                          f"sample's own rows only; {instead}")
 
 
+def check_counts_host(counts, B, cap, name):
+    """The host half of check_counts, usable before any device is touched: a list / numpy array / CPU tensor of per-sample
+    counts validated ((B,) integers in [0, cap], else ValueError) -> CPU tensor; None for None and for a CUDA tensor
+    (device data: check_counts takes it as it is)."""
+    if counts is None or (isinstance(counts, torch.Tensor) and counts.is_cuda):
+        return None
+    host = torch.as_tensor(counts)
+    if host.dtype.is_floating_point or host.dtype == torch.bool or tuple(host.shape) != (B,):
+        raise ValueError(f"{name} must hold {B} integers (one per sample); got {host.dtype} {tuple(host.shape)}")
+    if B and (int(host.min()) < 0 or int(host.max()) > cap):
+        raise ValueError(f"{name}: every count must lie in [0, {cap}] (the capacity: the tensor's dimension); got "
+                         f"{int(host.min())} .. {int(host.max())}")
+    return host
+
+
 def check_counts(counts, B, cap, dev, name):
     """The per-sample row counts of a ragged batch as the kernels read them: None, or int32 (B,) on the op's GPU.  A CUDA
     tensor is DEVICE data -- taken as it is (int32, contiguous, (B,), on `dev`; the kernels clamp it to [0, cap], nothing is
@@ -362,13 +377,7 @@ def check_counts(counts, B, cap, dev, name):
             raise ValueError(f"{name} on the GPU must be a contiguous int32 ({B},) tensor on {dev}; got {counts.dtype} "
                              f"{tuple(counts.shape)} on {counts.device}")
         return counts
-    host = torch.as_tensor(counts)
-    if host.dtype.is_floating_point or host.dtype == torch.bool or tuple(host.shape) != (B,):
-        raise ValueError(f"{name} must hold {B} integers (one per sample); got {host.dtype} {tuple(host.shape)}")
-    if B and (int(host.min()) < 0 or int(host.max()) > cap):
-        raise ValueError(f"{name}: every count must lie in [0, {cap}] (the capacity: the tensor's dimension); got "
-                         f"{int(host.min())} .. {int(host.max())}")
-    return host.to(device=dev, dtype=torch.int32).contiguous()
+    return check_counts_host(counts, B, cap, name).to(device=dev, dtype=torch.int32).contiguous()
 
 
 def cloud_order(tri, counts=None):

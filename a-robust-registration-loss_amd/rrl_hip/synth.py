@@ -18,6 +18,11 @@ def _surface(rng, n):
     return (u * rad[:, None]) * np.array([1.0, 0.7, 0.5])
 
 
+def surface_cloud(seed, n):
+    """(n, 3) float32 points on the bumpy ellipsoid of make_pair, seeded: a SURFACE cloud for timing tools."""
+    return _surface(np.random.default_rng(seed), n).astype(np.float32)
+
+
 def _rotation(axis, deg):
     axis = axis / np.linalg.norm(axis)
     a = np.deg2rad(deg)

@@ -882,6 +882,39 @@ int rrl_fps(const float *pts, const int32_t *start, int32_t *out_idx, float *dis
 int rrl_knn3(const float *pts, const int32_t *query_idx, int32_t *nn, int B, int n, int S,
              void *stream);
 
+/* ---- pseudo-triangles on the device: batched, ragged, tree 3-NN ---------------------------------
+ * What a trainer that augments per step needs: triangles, their counts and (rrl_cloud_order_counted) their orders for a
+ * whole batch, built on the device every step.  Plain device pointers, sizes and a stream; nothing is allocated, nothing
+ * synchronises, every refusal happens on the host before the first launch (RRL_E_ARG: a NULL pointer that is not marked
+ * optional, B < 0, n <= 0, S < 0, S > n where stated, n > rrl_sort_capacity() for the tree; RRL_E_WS: a short scratch).
+ * counts [B] (device int32, or NULL = n everywhere): sample b has n_b = clamp(counts[b], 0, n) points, the first n_b rows
+ * of pts[b]; the rows beyond are never read (they may hold NaN).  n stays the stride of every array.
+ *
+ * rrl_fps_counted: sample b emits S_b = min(S, n_b) indices, exactly the sequence rrl_fps gives on pts[b, :n_b] with the
+ * same start (NULL counts: rrl_fps's bits); out_idx [B][S], the entries beyond S_b are 0.  start[b] is clamped into
+ * [0, n_b) for memory safety only.  out_counts (optional) [B]: S_b.  dist_scratch [B][n].  S <= n. */
+int rrl_fps_counted(const float *pts, const int32_t *counts, const int32_t *start, int32_t *out_idx, int32_t *out_counts,
+                    float *dist_scratch, int B, int n, int S, void *stream);
+/* rrl_knn3_counted: rrl_knn3's brute-force loop for given queries -- the FPS-subsample case, S << n.  query_idx [B][S]
+ * (NULL: query q is point q; then S <= n), qcounts [B] (NULL: S): sample b has S_b = clamp(qcounts[b], 0, S) queries
+ * among its n_b points; query indices are clamped into [0, n_b).  A sample of fewer than three points has no neighbours:
+ * S_b = 0.  nn [B][S][3] as rrl_knn3 writes it, rows beyond S_b zero.  Optional outputs: tri [B][S][9] = the rows
+ * pts[nn0], pts[nn1], pts[nn2] (= [p, nn1, nn2] of code/loss.py:473-485; rows beyond S_b zero) and tri_counts [B] = S_b,
+ * which feeds rrl_opts.count1 / count2 directly. */
+int rrl_knn3_counted(const float *pts, const int32_t *counts, const int32_t *query_idx, const int32_t *qcounts, int32_t *nn,
+                     float *tri, int32_t *tri_counts, int B, int n, int S, void *stream);
+/* rrl_knn3_self: the three nearest neighbours of EVERY point of its cloud, nn [B][n][3] in the original row order with
+ * original indices, bit-equal to rrl_knn3 with query q = point q on every finite cloud -- through the sorted layout
+ * (16^3-cell Hilbert sort, supergroups of 64 records, sphere tree) and a pruned walk instead of n^2 distances
+ * (csrc/rrl_knn_tree.hip holds the bound's derivation).  A sample with a NaN, an infinite or a huge (|P| > 1e15)
+ * coordinate within its count is served by the brute-force loop inside the same launch, with rrl_knn3's result.  Rows
+ * beyond n_b, and every row of a sample with n_b < 3, are zero.  Optional outputs: tri [B][n][9] and tri_counts [B]
+ * (n_b, or 0 when n_b < 3) as above.  ws: scratch of rrl_knn3_self_workspace_bytes(B, n) bytes.
+ * n <= rrl_sort_capacity(), B <= 32767.  3 launches up to 4096 points, 5 beyond. */
+size_t rrl_knn3_self_workspace_bytes(int B, int n);
+int rrl_knn3_self(const float *pts, const int32_t *counts, void *ws, size_t ws_bytes, int32_t *nn, float *tri,
+                  int32_t *tri_counts, int B, int n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
