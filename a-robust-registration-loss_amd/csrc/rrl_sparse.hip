@@ -524,12 +524,13 @@ static int registration_backward_impl(const RrlCall &o, const float *src, const 
         RRL_LAUNCH_CHECK();
         return 0;
     }
-    // dL/dsrc wanted too: scatter of the line gradients into G1 (cleared first) ...
+    // dL/dsrc wanted too: scatter of the line gradients into G1 (cleared first; in deterministic mode through the fixed-point
+    // accumulators, like rrl_loss_backward: the rigid backward behind it sums in a fixed order either way) ...
     if (rrl_fused_backward(B, N, M)) {  // ... then rigid backward + payload (reg_bwd_kernel)
-        if (int rc = loss_backward_impl(o, grad_loss, g1, nullptr, true, false)) return rc;
+        if (int rc = loss_backward_impl(o, grad_loss, g1, nullptr, true, o.deterministic != 0)) return rc;
         return rrl_launch_reg_bwd(o, src, R, grad_src, gR, gt, payload, loss, transpose_r);
     }
-    int rc = loss_backward_impl(o, grad_loss, g1, nullptr, true, rrl_default_deterministic());
+    int rc = loss_backward_impl(o, grad_loss, g1, nullptr, true, o.deterministic != 0);
     if (rc) return rc;
     rc = rrl_rigid_apply_bwd(src, R, g1, grad_src, gR, gt, o.at<RRL_WS_RPART>(), B, 3 * N, transpose_r, 0, o.s);
     if (rc) return rc;

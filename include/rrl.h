@@ -420,7 +420,8 @@ int rrl_loss_forward_info(const float *tri1, const float *tri2, const float *lin
 /* Opt-in bit-reproducible backward (the reference's CPU autograd is deterministic).  on != 0 (or rrl_opts.deterministic = 1)
  *   - replaces the float atomics of rrl_registration_backward's direct route (grad_src == NULL) by per-workgroup partial
  *     sums added in a fixed order by a second, tiny launch;
- *   - (round 6) makes the SCATTER backward to points1.grad / points2.grad -- rrl_loss_backward, rrl_loss_step_ex -- accumulate
+ *   - (round 6) makes the SCATTER backward to points1.grad / points2.grad -- rrl_loss_backward, rrl_loss_step_ex, and the
+ *     scatter in front of the rigid backward when rrl_registration_backward is asked for grad_src -- accumulate
  *     in 64-bit fixed point (workspace field GFIX; the unit is a power of two derived per sample from |dL/dloss|, the
  *     bucket count and the median, so that 2^24 contributions cannot overflow): integer sums do not depend on the order of the
  *     atomics.  One more launch converts them to fp32; rrl_loss_step_ex then runs forward + backward + conversion instead of
