@@ -70,3 +70,50 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
                              nullptr, a->loss, a->cham_value, a->table, a->cursor, a->table_rows, a->row, rows,
                              (N + 255) / 256, a->box1, stream);
 }
+
+// One epoch for a BATCH of pairs as one call (include/rrl.h rrl_register_epoch): the same entries, B samples each -- sampler
+// (2 launches, 3 from 512 workgroups on; skipped without rng_state) -> fused registration step with the caller's options (prepared orders, counts, kept
+// target; 4 or 5 launches) -> optionally the Chamfer monitor per sample (walk + group means, 2) -> batched pose step (1), whose
+// gate is the workspace's INFO (stride 4), whose rows are cloud 1 of APART and whose box output is box1.  No riders, no
+// pipelining across epochs, no environment switch, no host read-back; every refusal before the first launch, RRL_E_ARG first.
+extern "C" int rrl_register_epoch(const rrl_register_epoch_args *a, void *stream) {
+    if (!a || a->struct_bytes < (int32_t)sizeof(rrl_register_epoch_args)) return RRL_E_ARG;
+    const int B = a->B, N = a->N, M = a->M, L = a->L;
+    if (B <= 0 || N <= 0 || M <= 0 || L <= 0) return RRL_E_ARG;
+    const bool sample = a->rng_state != nullptr, monitor = a->value != nullptr;
+    if (sample && (a->rounds <= 0 || a->rounds > 65535 || B > 65535 || !a->radius || !a->centers || !a->box2 || !a->filled ||
+                   !a->tile_counts || (((uintptr_t)a->tile_counts) & 7) != 0))
+        return RRL_E_ARG;
+    RrlCall o = rrl_begin_call(a->opts, B, N, M, L, a->ws, a->ws_bytes, stream);
+    if (o.problems > 0 || o.nlines) return RRL_E_ARG;  // (one pose per pair; the sampler owns the line set)
+    // the walk of rrl_chamfer_from_loss reads whole clouds: not on a ragged workspace (include/rrl.h rrl_opts.count1)
+    if (monitor && (o.ragged() || !a->cham_ws || !a->best_x || !a->best_y || !a->cham_mean || !rrl_sorted_layout(N, M) || B > 32767))
+        return RRL_E_ARG;
+    if (!a->xi || !a->m || !a->v || !a->adam_state || !a->lr || !a->box1) return RRL_E_ARG;
+    o.rider = nullptr;  // (no launch of this epoch carries another's work)
+    o.flags &= ~(RRL_F_CHAIN | RRL_F_CHAINED);
+    o.chain_left = nullptr;
+    const RrlXform xf = {a->src_tri, a->R, a->T, a->transpose_r, 1};
+    const bool pointers = a->src_tri && a->R && a->T && a->tar_tri && a->lines && a->loss && a->grad_loss && a->gR && a->gt;
+    int rc = rrl_check_call(o, pointers, RRL_WANT_DIRECT, nullptr, &xf);
+    if (rc) return rc;
+    if (monitor && a->cham_ws_bytes < rrl_chamfer_workspace_bytes(B, N, M)) return RRL_E_WS;
+    if (sample) {
+        rc = rrl_sample_lines_rng(a->rng_state, a->radius, a->centers, a->box1, a->box2, a->lines, a->filled, a->tile_counts, B, L,
+                                  a->rounds, stream);
+        if (rc) return rc;
+    }
+    rc = rrl_registration_step_call(o, xf, a->tar_tri, a->lines, a->loss, a->grad_loss, a->gR, a->gt, nullptr);
+    if (rc) return rc;
+    if (monitor) {
+        rc = rrl_chamfer_from_loss(a->ws, a->ws, a->ws_bytes, B, N, M, L, a->cham_ws, a->cham_ws_bytes, a->best_x, a->best_y,
+                                   a->cham_mean, stream);
+        if (rc) return rc;
+        rc = rrl_chamfer_group_means(a->cham_ws, a->cham_ws_bytes, a->value, B, B, N, M, stream);
+        if (rc) return rc;
+    }
+    const int nblk = ((N > M ? N : M) + 255) / 256;  // APART [2][B][nblk][8]: cloud 1 first
+    return rrl_se3_adam_step_batch(a->xi, a->gR, a->gt, a->m, a->v, a->adam_state, a->lr, o.at<RRL_WS_INFO>(), 4, a->b1, a->b2,
+                                   a->eps, a->R, a->T, a->gxi, a->loss, a->value, a->table, a->cursor, a->table_rows, a->row,
+                                   o.at<RRL_WS_APART>(), (long long)nblk * 8, o.count1, N, a->box1, B, stream);
+}

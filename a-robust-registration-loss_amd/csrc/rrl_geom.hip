@@ -590,6 +590,23 @@ extern "C" int rrl_adam_gated(float *p, const float *g, float *m, float *v, floa
 // expressions in the same order), the exponential of the UPDATED xi into (R, T) for the next epoch (== se3_exp_kernel)
 // and the epoch's log row (== log_row_kernel).  As four launches these cost ~18 us of pure launch latency per epoch
 // on 6 floats; results are bit-identical to the four (tests/test_gpu_harness.py).
+//
+// What the batched launch of se3_adam_step_kernel adds to the arguments (include/rrl.h rrl_se3_adam_step_batch)
+struct Se3Batch {
+    long long gate_stride, row_stride;  // words from one sample's gate to the next; floats from one sample's partial rows to the next
+    const int32_t *count1;              // NULL, or the source rows each sample has (device; clamped to [0, N]: rrl_rows)
+    int N, B;
+};
+// ONE body for both launches.  se3_adam_step_kernel<>: a single pose on the caller's pointers.  se3_adam_step_kernel<Se3Batch>
+// (grid B): workgroup b = one wavefront = pose b -- the pointers are advanced to sample b's slices (xi, m, v [B][6], state, lr,
+// loss, value, cursor [B], R [B][9], T [B][3], row [B][3], box [B][6], gate[b * gate_stride], column b of the table
+// [nrows][B][3], the partial rows aabb_rows + b * row_stride, [0, ceil(count1[b] / 256)) of them), then the same statements
+// run: sample b has the bits of the single launch on its slices.  Rows beyond a sample's count are never read (a ragged
+// build does not write them); no rows: (+inf, -inf), as aabb_kernel.  Every wavefront reads and advances its own cursor
+// word: no word is read by one workgroup and written by another.  (A template, not a __device__ function called by two
+// kernels: inlined, the same statements came back with commuted operands; the empty pack is the old kernel instruction for
+// instruction -- profiles/register_batch_device_asm.json.)
+template <class... BATCH>
 __global__ __launch_bounds__(64) void se3_adam_step_kernel(float *__restrict__ xi, const float *__restrict__ gR,
                                                            const float *__restrict__ gT, float *__restrict__ m,
                                                            float *__restrict__ v, float *__restrict__ state,
@@ -601,7 +618,31 @@ __global__ __launch_bounds__(64) void se3_adam_step_kernel(float *__restrict__ x
                                                            const float *__restrict__ value, float *__restrict__ table,
                                                            long long *__restrict__ cursor, long long nrows,
                                                            float *__restrict__ row, const float *__restrict__ aabb_rows,
-                                                           int n_aabb_rows, float *__restrict__ box) {
+                                                           int n_aabb_rows, float *__restrict__ box, BATCH... batch) {
+    static_assert(sizeof...(BATCH) <= 1, "se3_adam_step_kernel<> or se3_adam_step_kernel<Se3Batch>");
+    long long tstride = 3;  // floats from one row of the log table to the next
+    if constexpr (sizeof...(BATCH) != 0) {
+        const Se3Batch e = (batch, ...);
+        const int b = blockIdx.x;
+        if (b >= e.B) return;
+        const size_t s = (size_t)b;
+        xi += s * 6; m += s * 6; v += s * 6; state += s; lr += s; R += s * 9; T += s * 3;
+        if (gR) gR += s * 9;
+        if (gT) gT += s * 3;
+        if (gate) gate += (long long)b * e.gate_stride;
+        if (gxi) gxi += s * 6;
+        if (loss) loss += s;
+        if (value) value += s;
+        if (table) table += s * 3;
+        if (cursor) cursor += s;
+        if (row) row += s * 3;
+        tstride = 3ll * e.B;
+        if (box) {
+            box += s * 6;
+            aabb_rows += (long long)b * e.row_stride;
+            n_aabb_rows = (rrl_rows(e.count1, b, e.N) + 255) / 256;
+        }
+    }
     const int k = threadIdx.x;
     const bool ok = gate == nullptr || gate[0] > 0;
     // (the log row's inputs are requested with the first loads, not after the arithmetic)
@@ -660,10 +701,27 @@ __global__ __launch_bounds__(64) void se3_adam_step_kernel(float *__restrict__ x
         const float q[3] = {q0, q1, ok ? 1.0f : 0.0f};
         for (int c = 0; c < 3; ++c) {
             if (row) row[c] = q[c];
-            if (at >= 0 && at < nrows) table[at * 3 + c] = q[c];
+            if (at >= 0 && at < nrows) table[at * tstride + c] = q[c];
         }
         cursor[0] = at + 1;
     }
+}
+
+extern "C" int rrl_se3_adam_step_batch(float *xi, const float *gR, const float *gT, float *m, float *v, float *state,
+                                       const float *lr, const int32_t *gate, long long gate_stride, double b1, double b2,
+                                       double eps, float *R, float *T, float *gxi, const float *loss, const float *value,
+                                       float *table, long long *cursor, long long nrows, float *row, const float *aabb_rows,
+                                       long long row_stride, const int32_t *count1, int N, float *box, int B, void *stream) {
+    if (B < 0 || !xi || !m || !v || !state || !lr || !R || !T) return RRL_E_ARG;
+    if (gate && gate_stride < 0) return RRL_E_ARG;
+    if (box && (!aabb_rows || N <= 0 || row_stride < 8ll * ((N + 255) / 256))) return RRL_E_ARG;
+    if (B == 0) return 0;
+    const Se3Batch e = {gate_stride, row_stride, count1, N, B};
+    hipLaunchKernelGGL((se3_adam_step_kernel<Se3Batch>), dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, xi, gR, gT, m, v,
+                       state, lr, gate, b1, b2, eps, log2(b1), log2(b2), R, T, gxi, loss, value, table, cursor, nrows, row,
+                       aabb_rows, 0, box, e);
+    RRL_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int rrl_se3_adam_step(float *xi, const float *gR, const float *gT, float *m, float *v, float *state,
@@ -672,7 +730,7 @@ extern "C" int rrl_se3_adam_step(float *xi, const float *gR, const float *gT, fl
                                  long long *cursor, long long nrows, float *row, const float *aabb_rows, int n_aabb_rows,
                                  float *box, void *stream) {
     if (!xi || !m || !v || !state || !lr || !R || !T || (box && (!aabb_rows || n_aabb_rows <= 0))) return RRL_E_ARG;
-    hipLaunchKernelGGL(se3_adam_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, xi, gR, gT, m, v, state, lr,
+    hipLaunchKernelGGL(se3_adam_step_kernel<>, dim3(1), dim3(64), 0, (hipStream_t)stream, xi, gR, gT, m, v, state, lr,
                        gate, b1, b2, eps, log2(b1), log2(b2), R, T, gxi, loss, value, table, cursor, nrows, row, aabb_rows,
                        n_aabb_rows, box);
     RRL_LAUNCH_CHECK();

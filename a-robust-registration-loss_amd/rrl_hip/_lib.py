@@ -76,6 +76,9 @@ _SIGS = {
     "rrl_box_accept": [_P, _P, _P, _P, _P, _I, _I, _P],
     "rrl_log_row": [_P, _P, _P, _P, _P, _c.c_longlong, _P, _P],
     "rrl_se3_adam_step": [_P] * 8 + [_c.c_double] * 3 + [_P] * 7 + [_c.c_longlong, _P, _P, _I, _P, _P],
+    "rrl_se3_adam_step_batch": [_P] * 8 + [_c.c_longlong] + [_c.c_double] * 3 + [_P] * 7 + [_c.c_longlong, _P, _P, _c.c_longlong,
+                                                                                            _P, _I, _P, _I, _P],
+    "rrl_register_epoch": [_P, _P],
     "rrl_rigid_apply_aabb": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "rrl_se3_exp": [_P, _P, _P, _I, _P],
     "rrl_se3_exp_bwd": [_P, _P, _P, _P, _I, _P],
@@ -133,6 +136,19 @@ class DemoEpochArgs(ctypes.Structure):
                 ("xi", _P), ("m", _P), ("v", _P), ("adam_state", _P), ("lr", _P), ("b1", _c.c_double), ("b2", _c.c_double),
                 ("eps", _c.c_double), ("table", _P), ("cursor", _P), ("table_rows", _c.c_longlong), ("row", _P),
                 ("pipeline", _P)]
+
+
+class RegisterEpochArgs(ctypes.Structure):
+    """include/rrl.h rrl_register_epoch_args (same field order)."""
+    _fields_ = [("struct_bytes", _c.c_int32), ("B", _c.c_int32), ("N", _c.c_int32), ("M", _c.c_int32), ("L", _c.c_int32),
+                ("rounds", _c.c_int32), ("transpose_r", _c.c_int32), ("reserved", _c.c_int32),
+                ("rng_state", _P), ("radius", _P), ("centers", _P), ("box1", _P), ("box2", _P), ("lines", _P),
+                ("filled", _P), ("tile_counts", _P),
+                ("src_tri", _P), ("tar_tri", _P), ("R", _P), ("T", _P), ("ws", _P), ("ws_bytes", _Z), ("loss", _P),
+                ("grad_loss", _P), ("gR", _P), ("gt", _P), ("opts", _P),
+                ("cham_ws", _P), ("cham_ws_bytes", _Z), ("best_x", _P), ("best_y", _P), ("cham_mean", _P), ("value", _P),
+                ("xi", _P), ("m", _P), ("v", _P), ("adam_state", _P), ("lr", _P), ("b1", _c.c_double), ("b2", _c.c_double),
+                ("eps", _c.c_double), ("gxi", _P), ("table", _P), ("cursor", _P), ("table_rows", _c.c_longlong), ("row", _P)]
 
 
 _lib = None

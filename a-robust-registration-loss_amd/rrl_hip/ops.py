@@ -2005,6 +2005,27 @@ def se3_adam_step(xi, gR, gT, m, v, state, lr, gate, R, T, *, gxi=None, loss=Non
          _p(cursor), nrows, _p(row), _p(aabb_rows), 0 if aabb_rows is None else int(aabb_rows.shape[0]), _p(box))
 
 
+def se3_adam_step_batch(xi, gR, gT, m, v, state, lr, gate, R, T, *, gate_stride=1, gxi=None, loss=None, value=None,
+                        table=None, cursor=None, row=None, betas=(0.9, 0.999), eps=1e-8, aabb_rows=None, row_stride=None,
+                        counts=None, capacity=None, box=None):
+    """se3_adam_step for B poses in one launch (rrl_se3_adam_step_batch), sample b on its own slices with the bits of the
+    single call: xi, m, v (B, 6); state, lr (B,); R (B, 3, 3), T (B, 3); gate int32 with sample b's word at
+    gate[b * gate_stride] (a loss state's `info`, stride 4); loss, value (B,); table (rows, B, 3) with cursor (B,) int64;
+    row (B, 3).  aabb_rows (B, rows, 8) + box (B, 6): sample b's box over its first ceil(counts[b] / 256) rows (counts: int32
+    (B,) on the GPU, or None: ceil(capacity / 256) rows; capacity defaults to 256 * rows) -- a loss state's `apart[0]` with
+    capacity = N gives every moved source's box; row_stride (floats) defaults to the rows' own."""
+    B = xi.shape[0]
+    nrows = 0 if table is None else table.shape[0]
+    N = 0
+    if aabb_rows is not None:
+        if row_stride is None:
+            row_stride = aabb_rows.stride(0) if aabb_rows.dim() == 3 else aabb_rows.numel() // max(B, 1)
+        N = int(capacity) if capacity is not None else 256 * int(aabb_rows.shape[-2])
+    _run(xi.device, "rrl_se3_adam_step_batch", _p(xi), _p(gR), _p(gT), _p(m), _p(v), _p(state), _p(lr), _p(gate),
+         int(gate_stride), float(betas[0]), float(betas[1]), float(eps), _p(R), _p(T), _p(gxi), _p(loss), _p(value), _p(table),
+         _p(cursor), nrows, _p(row), _p(aabb_rows), int(row_stride or 0), _p(counts), N, _p(box), B)
+
+
 def log_row(loss, value, info, table, cursor, row=None):
     """table[cursor[0]] = (loss[0], value[0], info[0] > 0); cursor[0] += 1 -- one launch, on the device."""
     _run(table.device, "rrl_log_row", _p(loss), _p(value), _p(info), _p(table), _p(cursor), table.shape[0], _p(row))

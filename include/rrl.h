@@ -696,6 +696,25 @@ int rrl_se3_adam_step(float *xi, const float *gR, const float *gT, float *m, flo
                       float *gxi, const float *loss, const float *value, float *table, long long *cursor,
                       long long nrows, float *row, const float *aabb_rows, int n_aabb_rows, float *box, void *stream);
 
+/* rrl_se3_adam_step for a BATCH of B poses in one launch: workgroup b (one wavefront) does for sample b exactly what
+ * rrl_se3_adam_step does on that sample's slices -- the same device code, the same bits.  Everything is per sample:
+ *   xi, m, v, gxi [B][6]; state, lr, loss, value, cursor [B]; gR, R [B][9]; gT, T [B][3]; row [B][3]; box [B][6];
+ *   gate: sample b's word is gate[b * gate_stride] (NULL: every sample steps; stride 4 reads INFO[b][0] of a workspace);
+ *   table [nrows][B][3]: sample b writes table[cursor[b]][b] and advances ITS OWN cursor[b] -- no word is read by one
+ *     workgroup and written by another within the launch;
+ *   box[b] = min xyz, max xyz over the rows aabb_rows + b * row_stride (floats; [..][8]), rows [0, ceil(count1[b] / 256)) --
+ *     count1: DEVICE int32 [B], read by the kernel and clamped to [0, N], or NULL: ceil(N / 256) rows.  Rows beyond a
+ *     sample's count are never read (a ragged build does not write them); a zero count gives (+inf, -inf) like
+ *     rrl_aabb_counted.  With a loss workspace: aabb_rows = the APART field (cloud 1), row_stride = 8 ceil(max(N, M) / 256).
+ * gR, gT, gate, gxi, loss, value, table, cursor, row, box (with aabb_rows, count1) may be NULL.  Refusals, before any launch:
+ * RRL_E_ARG for B < 0, a NULL required pointer (xi, m, v, state, lr, R, T), a negative gate_stride, and box without rows
+ * (aabb_rows NULL, N <= 0, or row_stride < 8 ceil(N / 256)); B == 0 returns 0 without a launch. */
+int rrl_se3_adam_step_batch(float *xi, const float *gR, const float *gT, float *m, float *v, float *state, const float *lr,
+                            const int32_t *gate, long long gate_stride, double b1, double b2, double eps, float *R, float *T,
+                            float *gxi, const float *loss, const float *value, float *table, long long *cursor,
+                            long long nrows, float *row, const float *aabb_rows, long long row_stride, const int32_t *count1,
+                            int N, float *box, int B, void *stream);
+
 /* One epoch of the single-pair demo (code/test_demo_optimized_Lie_Algebra.py:46-82) as ONE call: line sampler with the
  * library's generator (rrl_sample_lines_rng, against box1 = the previous epoch's moved source) -> fused registration step
  * (rrl_registration_step_ex; pass prepared orders in opts) with the Chamfer walk between the step's own sorted clouds
@@ -725,6 +744,43 @@ typedef struct rrl_demo_epoch_args {
     int32_t *pipeline;
 } rrl_demo_epoch_args;
 int rrl_demo_epoch(const rrl_demo_epoch_args *args, void *stream);
+
+/* One epoch of the registration loop for a BATCH of B pairs as ONE call: what rrl_demo_epoch is for one pair, from the
+ * batched and ragged entries only, issued back to back on the caller's stream --
+ *   1. rrl_sample_lines_rng with B samples against box1 [B][6] (the previous epoch's moved sources) and box2 [B][6];
+ *      skipped when rng_state == NULL: `lines` are used as given;
+ *   2. the fused registration step (rrl_registration_step_ex) with the caller's opts: prepared orders, count1 / count2 (a
+ *      ragged batch), RRL_F_TARGET_KEPT -- the caller switches from its first to its kept options between epochs, as the
+ *      demo does.  The chain flags and the Chamfer rider of opts are ignored: no launch here carries another's work;
+ *   3. when value != NULL, the monitor: rrl_chamfer_from_loss, then rrl_chamfer_group_means with G = B -> value [B];
+ *   4. rrl_se3_adam_step_batch: gate = the workspace's INFO (stride 4), rows = cloud 1 of APART, box output = box1.
+ * 7 launches per epoch where the backward rides in the reduce's launch (8 from 512 sampler workgroups on, + 2 with the
+ * monitor), for any B.  No host read-back, no environment switch, no pipelining across epochs.  Every pointer a device
+ * pointer as in the four entries.
+ * Refusals, all before the first launch, in the order of "Refusals" above.  RRL_E_ARG: a NULL or short struct (struct_bytes
+ * < sizeof); B, N, M or L <= 0; with rng_state: rounds <= 0 (or > 65535, B > 65535), a NULL radius / centers / box2 /
+ * filled / tile_counts, tile_counts not 8-byte aligned; opts->problems or opts->nlines set (one pose per pair; the sampler
+ * owns the line set); the monitor together with count1 / count2 -- rrl_chamfer_from_loss must not run on a ragged
+ * workspace: call rrl_chamfer_tree_fwd_counted on the first points instead --, with a NULL cham_ws / best_x / best_y /
+ * cham_mean, with clouds beyond rrl_sort_capacity() or B > 32767; a NULL xi / m / v / adam_state / lr / box1; and whatever
+ * rrl_registration_step_ex refuses.  Then RRL_E_RANGE (never: the range is 1..4), then RRL_E_WS: a short ws or cham_ws. */
+typedef struct rrl_register_epoch_args {
+    int32_t struct_bytes, B, N, M, L, rounds, transpose_r, reserved;
+    /* sampler: rng_state (NULL: keep `lines`), radius [B], centers [B][3], box1 [B][6] (in / out), box2 [B][6],
+     * lines [B][L][6], filled [B], tile_counts int32 [B * rounds * ceil(L / 1024) * 32] (8-byte aligned) */
+    uint64_t *rng_state; const float *radius, *centers; float *box1; const float *box2; float *lines; int32_t *filled, *tile_counts;
+    /* loss step: src_tri [B][N][9], tar_tri [B][M][9], poses (R [B][9], T [B][3]: in / out), workspace of
+     * rrl_workspace_bytes(B, N, M, L), loss [B], grad_loss [B], gR [B][9], gt [B][3] (ideally the workspace's GACC field) */
+    const float *src_tri, *tar_tri; float *R, *T; void *ws; size_t ws_bytes; float *loss; const float *grad_loss; float *gR, *gt;
+    const rrl_opts *opts;
+    /* monitor (value == NULL: none): scratch of rrl_chamfer_workspace_bytes(B, N, M), keys [B][N], [B][M], the pooled
+     * mean [1] and value [B] = each pair's own Chamfer distance (moved first points against the target's) */
+    void *cham_ws; size_t cham_ws_bytes; uint64_t *best_x, *best_y; float *cham_mean, *value;
+    /* poses: xi, m, v [B][6], adam_state, lr [B], gxi [B][6] or NULL, log table [table_rows][B][3] + cursor [B], row [B][3] */
+    float *xi, *m, *v, *adam_state; const float *lr; double b1, b2, eps; float *gxi; float *table; long long *cursor;
+    long long table_rows; float *row;
+} rrl_register_epoch_args;
+int rrl_register_epoch(const rrl_register_epoch_args *args, void *stream);
 
 /* ---- Chamfer monitor (code/loss.py:38-52, 236-252) -------------------------------------- */
 /* best_x [B][N], best_y [B][M] are u64 keys (dist bits << 32 | argmin), set to all-ones by
