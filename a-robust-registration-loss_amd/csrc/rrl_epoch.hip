@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include "rrl_ws.h"
 
 extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
@@ -116,4 +117,66 @@ extern "C" int rrl_register_epoch(const rrl_register_epoch_args *a, void *stream
     return rrl_se3_adam_step_batch(a->xi, a->gR, a->gt, a->m, a->v, a->adam_state, a->lr, o.at<RRL_WS_INFO>(), 4, a->b1, a->b2,
                                    a->eps, a->R, a->T, a->gxi, a->loss, a->value, a->table, a->cursor, a->table_rows, a->row,
                                    o.at<RRL_WS_APART>(), (long long)nblk * 8, o.count1, N, a->box1, B, stream);
+}
+
+// One Gauss-Newton epoch for a batch of pairs as one call (include/rrl.h rrl_register_newton_epoch): rrl_register_epoch's
+// sequence with the FORWARD in place of the fused step and the second-order pose side -- sampler -> registration forward with
+// the caller's options -> optionally the monitor -> rrl_pose_normal_eq (2 launches) -> rrl_se3_newton_step_batch (1).  Existing
+// entries plus the two of rrl_newton.hip, nothing else; every refusal before the first launch, RRL_E_ARG first.
+extern "C" int rrl_register_newton_epoch(const rrl_register_newton_args *a, void *stream) {
+    if (!a || a->struct_bytes < (int32_t)sizeof(rrl_register_newton_args)) return RRL_E_ARG;
+    const int B = a->B, N = a->N, M = a->M, L = a->L;
+    if (B <= 0 || B > 65535 || N <= 0 || M <= 0 || L <= 0) return RRL_E_ARG;
+    const bool sample = a->rng_state != nullptr, monitor = a->value != nullptr;
+    if (sample && (a->rounds <= 0 || a->rounds > 65535 || !a->radius || !a->centers || !a->box2 || !a->filled ||
+                   !a->tile_counts || (((uintptr_t)a->tile_counts) & 7) != 0))
+        return RRL_E_ARG;
+    // the forward's options: the caller's, without what would make a launch of this epoch carry or leave something for another
+    rrl_opts fo;
+    memset(&fo, 0, sizeof fo);
+    fo.reduce_mode = fo.deterministic = fo.sort_parts = fo.scan_variant = -1;
+    if (a->opts && a->opts->struct_bytes >= 8)
+        memcpy(&fo, a->opts, (size_t)a->opts->struct_bytes < sizeof fo ? (size_t)a->opts->struct_bytes : sizeof fo);
+    fo.struct_bytes = (int32_t)sizeof fo;
+    fo.flags &= ~(RRL_F_CHAIN | RRL_F_CHAINED);
+    fo.chamfer = nullptr;
+    fo.chain_left = nullptr;
+    fo.payload = nullptr;
+    RrlCall o = rrl_begin_call(&fo, B, N, M, L, a->ws, a->ws_bytes, stream);
+    if (o.problems > 0 || o.nlines) return RRL_E_ARG;  // (one pose per pair; the sampler owns the line set)
+    if (monitor && (o.ragged() || !a->cham_ws || !a->best_x || !a->best_y || !a->cham_mean || !rrl_sorted_layout(N, M) || B > 32767))
+        return RRL_E_ARG;
+    // the pose side's own pointers (rrl_pose_normal_eq, rrl_se3_newton_step_batch)
+    if (!a->box1 || !a->neq || !a->part || (((uintptr_t)a->part) & 7) != 0 || !a->state || !a->damping || !a->step || !a->max_rot ||
+        !a->max_trans || !(a->eps >= 0.0) || (a->patience > 0 && (!a->tol_rot || !a->tol_trans)))
+        return RRL_E_ARG;
+    const RrlXform xf = {a->src_tri, a->R, a->T, 0, 1};
+    const bool pointers = a->src_tri && a->R && a->T && a->tar_tri && a->lines && a->loss;
+    int rc = rrl_check_call(o, pointers, RRL_WANT_FORWARD, nullptr, &xf);
+    if (rc) return rc;
+    if (monitor && a->cham_ws_bytes < rrl_chamfer_workspace_bytes(B, N, M)) return RRL_E_WS;
+    if (a->part_bytes < rrl_pose_normal_eq_part_bytes(B, L)) return RRL_E_WS;
+    if (sample) {
+        rc = rrl_sample_lines_rng(a->rng_state, a->radius, a->centers, a->box1, a->box2, a->lines, a->filled, a->tile_counts, B, L,
+                                  a->rounds, stream);
+        if (rc) return rc;
+    }
+    rc = rrl_registration_forward_ex(a->src_tri, a->R, a->T, a->tar_tri, a->lines, a->ws, a->ws_bytes, a->loss, B, N, M, L, 0, 1, 1,
+                                     RRL_MAX_HITS + 1, RRL_MAX_HITS + 1, RRL_SCAN_CULL, 0, nullptr, &fo, stream);
+    if (rc) return rc;
+    if (monitor) {
+        rc = rrl_chamfer_from_loss(a->ws, a->ws, a->ws_bytes, B, N, M, L, a->cham_ws, a->cham_ws_bytes, a->best_x, a->best_y,
+                                   a->cham_mean, stream);
+        if (rc) return rc;
+        rc = rrl_chamfer_group_means(a->cham_ws, a->cham_ws_bytes, a->value, B, B, N, M, stream);
+        if (rc) return rc;
+    }
+    rc = rrl_pose_normal_eq(a->ws, a->ws_bytes, B, N, M, L, 1, 1, RRL_MAX_HITS + 1, RRL_MAX_HITS + 1, a->neq, a->part, a->part_bytes,
+                            nullptr, stream);
+    if (rc) return rc;
+    const int nblk = ((N > M ? N : M) + 255) / 256;  // APART [2][B][nblk][8]: cloud 1 first
+    return rrl_se3_newton_step_batch(a->neq, o.at<RRL_WS_INFO>(), 4, a->damping, a->step, a->max_rot, a->max_trans, a->tol_rot,
+                                     a->tol_trans, a->patience, a->eps, a->R, a->T, a->loss, a->value, a->table, a->cursor,
+                                     a->table_rows, a->row, o.at<RRL_WS_APART>(), (long long)nblk * 8, o.count1, N, a->box1,
+                                     a->delta, a->last_step, a->state, B, stream);
 }

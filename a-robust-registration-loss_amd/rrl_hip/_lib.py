@@ -79,6 +79,10 @@ _SIGS = {
     "rrl_se3_adam_step_batch": [_P] * 8 + [_c.c_longlong] + [_c.c_double] * 3 + [_P] * 7 + [_c.c_longlong, _P, _P, _c.c_longlong,
                                                                                             _P, _I, _P, _I, _P],
     "rrl_register_epoch": [_P, _P],
+    "rrl_pose_normal_eq": [_P, _Z] + [_I] * 8 + [_P, _P, _Z, _P, _P],
+    "rrl_se3_newton_step_batch": [_P, _P, _c.c_longlong] + [_P] * 6 + [_I, _c.c_double] + [_P] * 6 + [_c.c_longlong, _P, _P,
+                                                                                                  _c.c_longlong, _P, _I] + [_P] * 4 + [_I, _P],
+    "rrl_register_newton_epoch": [_P, _P],
     "rrl_rigid_apply_aabb": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "rrl_se3_exp": [_P, _P, _P, _I, _P],
     "rrl_se3_exp_bwd": [_P, _P, _P, _P, _I, _P],
@@ -94,7 +98,7 @@ _SIGS = {
 }
 EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamfer_workspace_bytes",
                                  "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes", "rrl_sort_capacity",
-                                 "rrl_knn3_self_workspace_bytes"])
+                                 "rrl_knn3_self_workspace_bytes", "rrl_pose_normal_eq_part_bytes"])
 
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
 F_CHAIN = 2        # RRL_F_CHAIN: leave the hit counts / CHAIN words cleared for the next step on this workspace
@@ -151,6 +155,23 @@ class RegisterEpochArgs(ctypes.Structure):
                 ("eps", _c.c_double), ("gxi", _P), ("table", _P), ("cursor", _P), ("table_rows", _c.c_longlong), ("row", _P)]
 
 
+class RegisterNewtonArgs(ctypes.Structure):
+    """include/rrl.h rrl_register_newton_args (same field order)."""
+    _fields_ = [("struct_bytes", _c.c_int32), ("B", _c.c_int32), ("N", _c.c_int32), ("M", _c.c_int32), ("L", _c.c_int32),
+                ("rounds", _c.c_int32), ("patience", _c.c_int32), ("reserved", _c.c_int32),
+                ("rng_state", _P), ("radius", _P), ("centers", _P), ("box1", _P), ("box2", _P), ("lines", _P),
+                ("filled", _P), ("tile_counts", _P),
+                ("src_tri", _P), ("tar_tri", _P), ("R", _P), ("T", _P), ("ws", _P), ("ws_bytes", _Z), ("loss", _P), ("opts", _P),
+                ("cham_ws", _P), ("cham_ws_bytes", _Z), ("best_x", _P), ("best_y", _P), ("cham_mean", _P), ("value", _P),
+                ("neq", _P), ("part", _P), ("part_bytes", _Z),
+                ("damping", _P), ("step", _P), ("max_rot", _P), ("max_trans", _P), ("tol_rot", _P), ("tol_trans", _P),
+                ("eps", _c.c_double), ("delta", _P), ("last_step", _P), ("state", _P),
+                ("table", _P), ("cursor", _P), ("table_rows", _c.c_longlong), ("row", _P)]
+
+
+# rrl_se3_newton_step_batch's state[b][3] (include/rrl.h RRL_NEWTON_*)
+NEWTON_STEPPED, NEWTON_GATED, NEWTON_FAILED, NEWTON_DONE = 0, 1, 2, 3
+
 _lib = None
 
 
@@ -183,6 +204,8 @@ def load():
     lib.rrl_cloud_order_workspace_bytes.restype = _Z
     lib.rrl_knn3_self_workspace_bytes.argtypes = [_I, _I]
     lib.rrl_knn3_self_workspace_bytes.restype = _Z
+    lib.rrl_pose_normal_eq_part_bytes.argtypes = [_I, _I]
+    lib.rrl_pose_normal_eq_part_bytes.restype = _Z
     lib.rrl_sort_capacity.argtypes = []
     lib.rrl_sort_capacity.restype = _I
     _lib = lib

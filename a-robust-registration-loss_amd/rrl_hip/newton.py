@@ -1,0 +1,145 @@
+"""Registration of a BATCH of pairs by damped Gauss-Newton steps on the loss's own pairs -- the second-order companion of
+rrl_hip.register (include/rrl.h rrl_register_newton_epoch: line sampler -> registration forward ->
+optional Chamfer monitor -> normal equations -> batched Gauss-Newton pose step, one C call per epoch).
+
+    reg = NewtonRegistration(src_tri, tar_tri, 4000, counts1=c1, counts2=c2)   # (B, N, 9), (B, M, 9): capacities
+    reg.run(200, check_every=10)                                               # returns early when every pair is done
+    R, T, done = reg.R, reg.T, reg.done_epoch
+
+With the weights, the median and the labels frozen for one step -- they carry no gradient in the loss either -- the loss is a
+weighted sum of squared point distances, and one step is one IRLS step of a Welsch-weighted point-to-point fit: tens of epochs
+where the first-order loop takes a thousand, and a step whose length means something, so that "converged" is decided on the
+device (`patience` consecutive epochs below tol_rot / tol_trans).  Nothing is read back unless .run is asked to check.
+"""
+import ctypes
+
+import torch
+
+from . import _lib, ops
+from .register import PairRegistration
+
+# The defaults, from the sweep of tools/register_newton_sweep.py (profiles/register_newton_sweep.json)
+DAMPING = 1e-2     # Levenberg-Marquardt: H + damping diag(H)
+STEP = 1.0         # fraction of the solved step that is applied
+MAX_ROT = 0.2      # radians per epoch
+MAX_TRANS = 0.1    # per epoch, as a fraction of the sampler radius (the target box's diagonal)
+TOL_ROT = 5e-3     # radians: an epoch below both tolerances is calm (the line sets' own noise moves a converged pose by
+                   # 3e-3 .. 4e-3 rad and 7e-4 .. 9e-4 of the radius per epoch at 20000 lines: the sweep's tail columns)
+TOL_TRANS = 1.5e-3  # as a fraction of the sampler radius
+PATIENCE = 3       # calm epochs in a row that end a pair
+EPS = 1e-12        # H + eps I: a pivot that does not exceed it fails the step
+
+
+class NewtonRegistration(PairRegistration):
+    """PairRegistration's constructor contract, sampler geometry, .history(), .moved_points(), .loss, .R, .T -- with
+    Gauss-Newton steps in place of Adam on se(3).
+
+    Starting poses: R0 (B, 3, 3) and T0 (B, 3), or xi0 (B, 6) (default: the identity).  damping, step, max_rot, max_trans,
+    tol_rot, tol_trans: a number or one per pair; max_trans and tol_trans are FRACTIONS of each pair's sampler radius (the
+    target box's diagonal), multiplied once here.  patience = 0 turns the stopping rule off.
+
+    .done_epoch (B,) int32: the number of epochs after which pair b was declared done, or -1; a done pair's pose is frozen.
+    .last_step (B, 2): (|omega|, |v|) of the latest applied step.  .failed (B,) int32: what the latest epoch did per pair --
+    0 stepped, 1 no populated bucket, 2 the factorisation failed (pose unchanged), 3 done.  All device tensors."""
+
+    def __init__(self, src_tri, tar_tri, n_lines, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, damping=DAMPING,
+                 step=STEP, max_rot=MAX_ROT, max_trans=MAX_TRANS, tol_rot=TOL_ROT, tol_trans=TOL_TRANS, patience=PATIENCE,
+                 eps=EPS, rounds=10, seed=None, lines=None, monitor=False, table_rows=4096):
+        if (R0 is None) != (T0 is None) or (R0 is not None and xi0 is not None):
+            raise ValueError("starting poses: R0 and T0 together, or xi0, not both")
+        if int(patience) < 0 or not float(eps) >= 0.0:
+            raise ValueError("patience and eps must be non-negative")
+        super().__init__(src_tri, tar_tri, n_lines, counts1=counts1, counts2=counts2, xi0=xi0, rounds=rounds, seed=seed,
+                         monitor=monitor, table_rows=table_rows, lines=lines)
+        for name in ("xi", "m", "v", "adam_state", "lr", "lr_value", "gxi"):  # the first-order state: not part of this loop
+            self.__dict__.pop(name)
+        dev, B = self.dev, self.B
+        L = self.step.dims[3]
+        f32 = dict(dtype=torch.float32, device=dev)
+        if R0 is not None:
+            self.R.copy_(ops._prep(R0, "R0", 3, dev).reshape(B, 3, 3))
+            self.T.copy_(ops._prep(T0, "T0", 3, dev).reshape(B, 3))
+
+        def per_pair(x, scale=None):
+            t = torch.as_tensor(x, dtype=torch.float32).to(dev).reshape(-1).expand(B).clone() if not isinstance(x, torch.Tensor) \
+                else x.detach().to(**f32).reshape(-1).expand(B).clone()
+            return (t * scale if scale is not None else t).contiguous()
+        self.damping, self.step_scale = per_pair(damping), per_pair(step)
+        self.max_rot, self.max_trans = per_pair(max_rot), per_pair(max_trans, self.radius)
+        self.tol_rot, self.tol_trans = per_pair(tol_rot), per_pair(tol_trans, self.radius)
+        self.patience, self.eps = int(patience), float(eps)
+        self.neq = torch.zeros(B, 16, **f32)
+        self.part = ops.pose_normal_eq_part(B, L, dev)
+        self.delta = torch.zeros(B, 6, **f32)
+        self.last_step = torch.zeros(B, 2, **f32)
+        self.state = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        self.state[:, 2] = -1
+        P, a = ops._p, self._args  # (what _make_args left open: the pose side)
+        a.patience = self.patience
+        a.neq, a.part, a.part_bytes = P(self.neq), P(self.part), self.part.numel() * 8
+        a.damping, a.step, a.max_rot, a.max_trans = P(self.damping), P(self.step_scale), P(self.max_rot), P(self.max_trans)
+        a.tol_rot, a.tol_trans, a.eps = P(self.tol_rot), P(self.tol_trans), self.eps
+        a.delta, a.last_step, a.state = P(self.delta), P(self.last_step), P(self.state)
+
+    def _make_args(self):
+        """rrl_register_newton_args of this object's sampler, forward, monitor and log (PairRegistration.__init__ calls this
+        where it builds its rrl_register_epoch_args); the constructor adds the pose side once its buffers exist."""
+        st, P = self.step, ops._p
+        B, N, M, L = st.dims
+        a = _lib.RegisterNewtonArgs()
+        a.struct_bytes, a.B, a.N, a.M, a.L = ctypes.sizeof(_lib.RegisterNewtonArgs), B, N, M, L
+        a.rounds = self.rounds
+        a.rng_state, a.radius, a.centers, a.box1, a.box2 = P(self.rng), P(self.radius), P(self.centers), P(self.box1), P(self.box2)
+        a.lines, a.filled, a.tile_counts = P(self.lines), P(self.filled), P(self.tiles)
+        a.src_tri, a.tar_tri, a.R, a.T = P(st.src), P(st.tar), P(self.R), P(self.T)
+        a.ws, a.ws_bytes, a.loss = P(st.st.ws), st.st.nbytes, P(st.st.loss)
+        if self.monitor:
+            ws, bx, by, mean = self.cham
+            a.cham_ws, a.cham_ws_bytes, a.best_x, a.best_y, a.cham_mean, a.value = P(ws), ws.numel(), P(bx), P(by), P(mean), P(self.value)
+        a.table, a.cursor, a.table_rows, a.row = P(self.table), P(self.cursor), self.table.shape[0], P(self.row)
+        self._opts_first, self._opts_kept = ctypes.addressof(st._opts), ctypes.addressof(st._opts_kept)
+        return a
+
+    def set_lr(self, lr):
+        raise AttributeError("NewtonRegistration has no learning rate: see damping / step")
+
+    def epoch(self):
+        """One epoch of all B pairs: ONE C call (rrl_register_newton_epoch), nothing read back."""
+        self._args.opts = self._opts_kept if self._target_built else self._opts_first
+        with ops._guard(self.dev):
+            _lib.check(self._lib.rrl_register_newton_epoch(self._aref, ops._stream(self.dev)), "rrl_register_newton_epoch")
+        self._target_built = True
+        self.epochs += 1
+        self.step.st.ragged = self.step.ragged
+
+    def run(self, n_epoch, check_every=0):
+        """Up to n_epoch epochs.  check_every = k > 0: .done_epoch is read once every k epochs and the loop returns early when
+        every pair is done -- the only synchronisation, and only on request."""
+        k = int(check_every)
+        for i in range(int(n_epoch)):
+            self.epoch()
+            if k > 0 and (i + 1) % k == 0 and bool((self.done_epoch >= 0).all()):
+                break
+        return self
+
+    @property
+    def done_epoch(self):
+        return self.state[:, 2]
+
+    @property
+    def failed(self):
+        return self.state[:, 3]
+
+    def xi(self):
+        """(B, 6) on the host: LieAlgebra.se3.log of the current poses (rrl_se3_exp of it gives R, T back), on request."""
+        from LieAlgebra import se3
+        g = torch.zeros(self.B, 4, 4, dtype=torch.float64)
+        g[:, :3, :3], g[:, :3, 3], g[:, 3, 3] = self.R.double().cpu(), self.T.double().cpu(), 1.0
+        return se3.log(g).to(torch.float32)
+
+
+def register_pairs_newton(src_tri, tar_tri, n_lines, n_epoch=100, check_every=0, **kw):
+    """NewtonRegistration(...).run(n_epoch, check_every) -> (R (B, 3, 3), T (B, 3), history)."""
+    reg = NewtonRegistration(src_tri, tar_tri, n_lines, **kw)
+    reg.run(n_epoch, check_every)
+    return reg.R, reg.T, reg.history()

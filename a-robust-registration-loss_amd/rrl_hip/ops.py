@@ -2026,6 +2026,48 @@ def se3_adam_step_batch(xi, gR, gT, m, v, state, lr, gate, R, T, *, gate_stride=
          _p(cursor), nrows, _p(row), _p(aabb_rows), int(row_stride or 0), _p(counts), N, _p(box), B)
 
 
+def pose_normal_eq_part(B, L, dev):
+    """The scratch of pose_normal_eq for B samples of L lines (rrl_pose_normal_eq_part_bytes), as float64."""
+    return torch.empty(int(_lib.load().rrl_pose_normal_eq_part_bytes(B, L)) // 8, dtype=torch.float64, device=dev)
+
+
+def pose_normal_eq(state, rng=(1, 1, 5, 5), *, neq=None, part=None):
+    """The sixteen Gauss-Newton sums per sample (rrl_pose_normal_eq; include/rrl.h: S_QQ[6], S_sQ[3], S_ss, g_w[3], g_v[3])
+    from the LossState `state` of a registration forward or step that just ran (a RegistrationStep's .st): neq (B, 16)
+    float32, bit-reproducible.  neq / part (pose_normal_eq_part): buffers to reuse."""
+    B, N, M, L, _ = state.dims
+    dev = state.ws.device
+    if neq is None:
+        neq = torch.empty(B, 16, dtype=torch.float32, device=dev)
+    if part is None:
+        part = pose_normal_eq_part(B, L, dev)
+    _run(dev, "rrl_pose_normal_eq", state.wsp, state.nbytes, B, N, M, L, *(int(v) for v in rng), _p(neq), _p(part),
+         part.numel() * part.element_size(), None)
+    return neq
+
+
+def se3_newton_step_batch(neq, gate, R, T, state, *, damping, step, max_rot, max_trans, tol_rot=None, tol_trans=None,
+                          patience=0, eps=1e-12, gate_stride=1, loss=None, value=None, table=None, cursor=None, row=None,
+                          aabb_rows=None, row_stride=None, counts=None, capacity=None, box=None, delta=None, last_step=None):
+    """One damped Gauss-Newton step for B poses in one launch (rrl_se3_newton_step_batch): neq (B, 16) from pose_normal_eq;
+    R (B, 3, 3), T (B, 3) updated in place (x -> x R + T); state (B, 4) int32 = (epochs, calm epochs, done epoch or -1,
+    RRL_NEWTON_* of this call) -- fill column 2 with -1 before the first call; damping, step, max_rot, max_trans, tol_rot,
+    tol_trans (B,) float32; delta (B, 6): the solved step before scale and clamps; last_step (B, 2) = (|omega|, |v|) applied.
+    gate, the log (loss, value, table, cursor, row) and the box (aabb_rows, row_stride, counts, capacity, box) are
+    se3_adam_step_batch's."""
+    B = R.shape[0]
+    nrows = 0 if table is None else table.shape[0]
+    N = 0
+    if aabb_rows is not None:
+        if row_stride is None:
+            row_stride = aabb_rows.stride(0) if aabb_rows.dim() == 3 else aabb_rows.numel() // max(B, 1)
+        N = int(capacity) if capacity is not None else 256 * int(aabb_rows.shape[-2])
+    _run(R.device, "rrl_se3_newton_step_batch", _p(neq), _p(gate), int(gate_stride), _p(damping), _p(step), _p(max_rot),
+         _p(max_trans), _p(tol_rot), _p(tol_trans), int(patience), float(eps), _p(R), _p(T), _p(loss), _p(value), _p(table),
+         _p(cursor), nrows, _p(row), _p(aabb_rows), int(row_stride or 0), _p(counts), N, _p(box), _p(delta), _p(last_step),
+         _p(state), B)
+
+
 def log_row(loss, value, info, table, cursor, row=None):
     """table[cursor[0]] = (loss[0], value[0], info[0] > 0); cursor[0] += 1 -- one launch, on the device."""
     _run(table.device, "rrl_log_row", _p(loss), _p(value), _p(info), _p(table), _p(cursor), table.shape[0], _p(row))

@@ -782,6 +782,107 @@ typedef struct rrl_register_epoch_args {
 } rrl_register_epoch_args;
 int rrl_register_epoch(const rrl_register_epoch_args *args, void *stream);
 
+/* ---- Gauss-Newton pose steps from the loss's own pairs ---------------------------------
+ * With its weights frozen for one step the loss is a weighted point-to-point problem: every selected (line, source hit h,
+ * target hit o) that carries gradient in the backward is a pair of points Q1, Q2 of the workspace with the weight
+ * a = dL/dD (the backward's gD at upstream gradient 1; weights, median and labels carry no gradient), and
+ * Q1 = sum_k (w_k / 3)(x_k R + T) is affine in the pose.  Poses move ROW vectors, y = x R + T (transpose_r = 0).  A step is a
+ * world-frame twist (omega, v): y' = y Rot(omega)^T + v with Rot(omega) = exp([omega]x), i.e. R <- R Rot^T, T <- T Rot^T + v.
+ * With Q = Q1, e = Q1 - Q2 and s = (w_0 + w_1 + w_2) / 3 of hit h the residual moves by de = omega x Q + s v, and the
+ * Gauss-Newton normal equations H (omega, v) = -g are made of sixteen sums per pair of clouds, neq[b][16]:
+ *   [0..5]  S_QQ = sum 2a Q Q^T  (xx, xy, xz, yy, yz, zz)      H_ww = tr(S_QQ) I - S_QQ
+ *   [6..8]  S_sQ = sum 2a s Q                                   H_wv = [S_sQ]x = -H_vw
+ *   [9]     S_ss = sum 2a s^2                                   H_vv = S_ss I
+ *   [10..12] g_w = sum 2a Q x e,   [13..15] g_v = sum 2a s e   (g_v = dL/dT; g_w = vee(A - A^T) + T x dL/dT, A = R^T dL/dR)
+ * One step of it is one IRLS step of a Welsch-weighted point-to-point fit.
+ *
+ * rrl_pose_normal_eq: the sixteen sums of every sample from the workspace of ANY registration forward (or step) that ran
+ * before it on `ws` with the same B, N, M, L -- scan mode cull or strict, prepared or cold, uniform or ragged: it reads the
+ * per-line stage's and the reduce's fields KJ, W1, Q1, Q2, D, MED, BCNT, INFO and nothing of a cloud, a line or a count (an
+ * absent line has hit count 0, hence KJ = 0).  A chained step's workspace (RRL_F_CHAIN) keeps these fields too; what such a
+ * step clears (COUNT1 / COUNT2, the CHAIN words) is not read here.  Deterministic: the lines of a 1024-line tile go to sixteen
+ * workgroups in a fixed order (by rank among the tile's KJ bytes, like the deterministic direct backward), every workgroup
+ * stores its sixteen partial sums -- float32 terms accumulated in double -- into `part`, and a second small launch adds them
+ * in index order and rounds to float32 once: the same bits on every run.  A sample without a populated bucket
+ * (INFO[b][0] == 0) gets sixteen zeros.  part: scratch of rrl_pose_normal_eq_part_bytes(B, L) bytes, 8-byte aligned.
+ * opts: NULL, or the forward's options (only `problems` is looked at).
+ * Refusals, before any launch: RRL_E_ARG -- a NULL ws / neq / part, B, N, M or L <= 0, B > 65535, L >= 2^24, a misaligned
+ * part, a bucket range outside 1..RRL_MAX_HITS hits (s < 1, e > 5: the wide path is not served) or empty, multi-pose
+ * `problems` (0 < problems < B) --, then RRL_E_WS: ws_bytes < rrl_workspace_bytes(B, N, M, L) or a short part. */
+#define RRL_NEQ_SUMS 16
+size_t rrl_pose_normal_eq_part_bytes(int B, int L);
+int rrl_pose_normal_eq(const void *ws, size_t ws_bytes, int B, int N, int M, int L, int s_m, int s_n, int e_m, int e_n,
+                       float *neq, void *part, size_t part_bytes, const rrl_opts *opts, void *stream);
+
+/* One damped Gauss-Newton step for a BATCH of B poses in one launch (one wavefront per pose, like rrl_se3_adam_step_batch;
+ * every array per sample: neq [B][16]; damping, step, max_rot, max_trans, tol_rot, tol_trans [B]; R [B][9], T [B][3];
+ * loss, value, cursor [B]; table [nrows][B][3]; row [B][3]; box [B][6]; delta [B][6]; last_step [B][2]; state [B][4] int32).
+ * Sample b:
+ *   1. H (6 x 6), g from neq[b];
+ *   2. skipped (RRL_NEWTON_GATED) when its gate word gate[b * gate_stride] <= 0 (NULL: open; a workspace's INFO, stride 4),
+ *      or when the pair is done (RRL_NEWTON_DONE, see 9): the pose keeps its bits;
+ *   3. (H + damping[b] diag(H) + eps I) x = -g by Cholesky in double.  A pivot that does not exceed eps -- the matrix without
+ *      the eps term contributes nothing positive there: a singular H, all-zero sums -- or is not finite (a NaN sum), or a
+ *      non-finite solution or pose, leaves the pose unchanged: RRL_NEWTON_FAILED.  delta[b] = x as float32 (optional);
+ *   4. (omega, v) = step[b] x, then |omega| <= max_rot[b] and |v| <= max_trans[b] by scaling;
+ *   5. R[b] <- R[b] Rot(omega)^T, T[b] <- T[b] Rot(omega)^T + v with the exact Rodrigues rotation in double, then one
+ *      Gram-Schmidt pass over the rows of R, then rounded to float32;
+ *   6. last_step[b] = (|omega|, |v|) as applied (optional; written only when the sample stepped; a clamped norm IS the clamp);
+ *   7. the log row (loss[b], value[b], gate word > 0) into table[cursor[b]][b] and row[b], cursor[b] += 1 -- as the Adam step;
+ *   8. box[b] = min xyz, max xyz over the rows aabb_rows + b * row_stride, [0, ceil(count1[b] / 256)) of them -- the contract
+ *      of rrl_se3_adam_step_batch (count1 NULL: ceil(N / 256) rows; no rows: (+inf, -inf));
+ *   9. the stopping rule, when patience > 0: state[b][1] counts the consecutive stepped epochs with |omega| < tol_rot[b] and
+ *      |v| < tol_trans[b] (any other epoch resets it); when it reaches `patience`, state[b][2] = the number of epochs issued
+ *      so far, this one included.  From then on the pair is done: its pose is frozen, bit for bit.
+ * state[b] = { epochs issued, calm epochs, done epoch or -1 (the caller writes -1 before the first call), RRL_NEWTON_* of
+ * this call }.  gate, tol_rot, tol_trans (patience <= 0), loss, value, table, cursor, row, box (with aabb_rows, count1),
+ * delta, last_step may be NULL.  Refusals, before any launch: RRL_E_ARG for B < 0, a NULL neq / damping / step / max_rot /
+ * max_trans / R / T / state, a negative gate_stride, eps < 0 or NaN, patience > 0 without both tolerances, a box without
+ * rows (aabb_rows NULL, N <= 0, or row_stride < 8 ceil(N / 256)); B == 0 returns 0 without a launch. */
+#define RRL_NEWTON_STEPPED 0
+#define RRL_NEWTON_GATED 1
+#define RRL_NEWTON_FAILED 2
+#define RRL_NEWTON_DONE 3
+int rrl_se3_newton_step_batch(const float *neq, const int32_t *gate, long long gate_stride, const float *damping,
+                              const float *step, const float *max_rot, const float *max_trans, const float *tol_rot,
+                              const float *tol_trans, int patience, double eps, float *R, float *T, const float *loss,
+                              const float *value, float *table, long long *cursor, long long nrows, float *row,
+                              const float *aabb_rows, long long row_stride, const int32_t *count1, int N, float *box,
+                              float *delta, float *last_step, int32_t *state, int B, void *stream);
+
+/* One Gauss-Newton epoch for a BATCH of B pairs as ONE call: rrl_register_epoch with the second-order pose step, issued
+ * back to back on the caller's stream --
+ *   1. rrl_sample_lines_rng (skipped when rng_state == NULL: `lines` as given);
+ *   2. the registration FORWARD (rrl_registration_forward_ex, range 1..4, scan mode cull, y = x R + T) with the caller's
+ *      opts: prepared orders, count1 / count2, RRL_F_TARGET_KEPT after the first epoch.  The point backward is not run.  The
+ *      chain flags and the Chamfer rider of opts are dropped;
+ *   3. when value != NULL, the monitor exactly as rrl_register_epoch runs it (uniform batches only);
+ *   4. rrl_pose_normal_eq -> neq [B][16];
+ *   5. rrl_se3_newton_step_batch: gate = the workspace's INFO (stride 4), rows = cloud 1 of APART, box output = box1.
+ * No host read-back: the epoch can be captured.  Refusals, all before the first launch, RRL_E_ARG first: a NULL or short
+ * struct; B, N, M or L <= 0; B > 65535; the sampler's (rounds, pointers, alignment) as rrl_register_epoch; opts->problems or
+ * opts->nlines set; the monitor together with count1 / count2, with a NULL cham_ws / best_x / best_y / cham_mean, with clouds
+ * beyond rrl_sort_capacity() or B > 32767; a NULL box1 / neq / part / state or whatever the step (above) refuses; whatever
+ * rrl_registration_forward_ex refuses.  Then RRL_E_WS: a short ws, cham_ws or part. */
+typedef struct rrl_register_newton_args {
+    int32_t struct_bytes, B, N, M, L, rounds, patience, reserved;
+    /* sampler, as rrl_register_epoch_args */
+    uint64_t *rng_state; const float *radius, *centers; float *box1; const float *box2; float *lines; int32_t *filled, *tile_counts;
+    /* forward: src_tri [B][N][9], tar_tri [B][M][9], poses (R [B][9], T [B][3]: in / out), workspace of
+     * rrl_workspace_bytes(B, N, M, L), loss [B] */
+    const float *src_tri, *tar_tri; float *R, *T; void *ws; size_t ws_bytes; float *loss;
+    const rrl_opts *opts;
+    /* monitor (value == NULL: none), as rrl_register_epoch_args */
+    void *cham_ws; size_t cham_ws_bytes; uint64_t *best_x, *best_y; float *cham_mean, *value;
+    /* normal equations: neq [B][16], part of rrl_pose_normal_eq_part_bytes(B, L) bytes */
+    float *neq; void *part; size_t part_bytes;
+    /* step (rrl_se3_newton_step_batch): per-sample controls [B], eps, delta [B][6] or NULL, last_step [B][2] or NULL,
+     * state [B][4]; log table [table_rows][B][3] + cursor [B], row [B][3] */
+    const float *damping, *step, *max_rot, *max_trans, *tol_rot, *tol_trans; double eps; float *delta, *last_step; int32_t *state;
+    float *table; long long *cursor; long long table_rows; float *row;
+} rrl_register_newton_args;
+int rrl_register_newton_epoch(const rrl_register_newton_args *args, void *stream);
+
 /* ---- Chamfer monitor (code/loss.py:38-52, 236-252) -------------------------------------- */
 /* best_x [B][N], best_y [B][M] are u64 keys (dist bits << 32 | argmin), set to all-ones by
  * the call itself.  value[0] = mean of all B*(N+M) minima. */

@@ -7,7 +7,8 @@ source trees with equal digests launch the same machine code: a host-side change
 
     python tools/device_asm_digest.py [--csrc DIR] [--json OUT] [--label NAME]
 
---json merges {NAME: {file: digest}} into OUT (profiles/call_record_device_asm.json holds `parent` and `branch`).
+--json merges {NAME: {file: digest}} into OUT (profiles/call_record_device_asm.json holds `parent` and `branch`); units of
+the build list that --csrc does not hold are left out (a parent tree against a branch that adds one: `new_units`).
 
 A change that renames kernels moves the whole-file digest although no instruction moved.  For that case
 
@@ -161,8 +162,9 @@ def main():
     if args.kernels:
         return kernels_main(args, build, csrc)
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=args.jobs) as pool:
-        sums = dict(zip(build.SOURCES, pool.map(lambda s: digest(build, csrc, s, tmp), build.SOURCES)))
-    for src in build.SOURCES:
+        sources = [s for s in build.SOURCES if os.path.exists(os.path.join(csrc, s))]  # (a parent tree lacks a unit its branch adds)
+        sums = dict(zip(sources, pool.map(lambda s: digest(build, csrc, s, tmp), sources)))
+    for src in sources:
         print(sums[src], src)
     if args.json:
         doc = {}
@@ -171,7 +173,8 @@ def main():
                 doc = json.load(f)
         doc[args.label] = sums
         if "parent" in doc and "branch" in doc:
-            doc["identical"] = doc["parent"] == doc["branch"]
+            doc["identical"] = all(doc["branch"].get(k) == v for k, v in doc["parent"].items())  # every unit the parent has
+            doc["new_units"] = sorted(set(doc["branch"]) - set(doc["parent"]))
         with open(args.json, "w") as f:
             json.dump(doc, f, indent=1, sort_keys=True)
             f.write("\n")

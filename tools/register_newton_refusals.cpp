@@ -1,0 +1,148 @@
+// The refusal paths of rrl_pose_normal_eq, rrl_se3_newton_step_batch and rrl_register_newton_epoch (include/rrl.h) as a
+// stand-alone host program, for a sanitizer build of the library's host side (tools/register_newton_sanitize.sh): calls of
+// tests/test_newton_refs_host.py's tables with fake pointers -- every one is refused on the host before a launch, so no pointer
+// is dereferenced and no GPU is needed.  Exit status 0: every call returned its documented code.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+
+#include "rrl.h"
+
+static int failures = 0;
+static void expect(const char *what, int got, int want) {
+    if (got != want) { std::printf("FAIL %s: got %d, want %d\n", what, got, want); ++failures; }
+    else std::printf("ok   %s: %d\n", what, got);
+}
+
+template <class T> static T *fake(size_t at = 256) { return reinterpret_cast<T *>(at); }
+
+static rrl_opts opts_base() {
+    rrl_opts o;
+    std::memset(&o, 0, sizeof o);
+    o.struct_bytes = (int32_t)sizeof o;
+    o.reduce_mode = o.deterministic = o.sort_parts = o.scan_variant = -1;
+    return o;
+}
+
+struct NeqCall {
+    void *ws = fake<void>();
+    size_t ws_bytes = (size_t)1 << 50;
+    int B = 3, N = 300, M = 300, L = 2048, s_m = 1, s_n = 1, e_m = 5, e_n = 5;
+    float *neq = fake<float>();
+    void *part = fake<void>();
+    size_t part_bytes = (size_t)1 << 50;
+    const rrl_opts *opts = nullptr;
+    int run() const { return rrl_pose_normal_eq(ws, ws_bytes, B, N, M, L, s_m, s_n, e_m, e_n, neq, part, part_bytes, opts, nullptr); }
+};
+
+struct StepCall {
+    float *neq = fake<float>();
+    int32_t *gate = fake<int32_t>();
+    long long gate_stride = 4;
+    float *damping = fake<float>(), *step = fake<float>(), *max_rot = fake<float>(), *max_trans = fake<float>(), *tol_rot = fake<float>(),
+          *tol_trans = fake<float>();
+    int patience = 3;
+    double eps = 1e-12;
+    float *R = fake<float>(), *T = fake<float>(), *loss = fake<float>(), *value = fake<float>(), *table = fake<float>();
+    long long *cursor = fake<long long>();
+    long long nrows = 16;
+    float *row = fake<float>(), *aabb_rows = fake<float>();
+    long long row_stride = 16;
+    int32_t *count1 = fake<int32_t>();
+    int N = 300;
+    float *box = fake<float>(), *delta = fake<float>(), *last_step = fake<float>();
+    int32_t *state = fake<int32_t>();
+    int B = 3;
+    int run() const {
+        return rrl_se3_newton_step_batch(neq, gate, gate_stride, damping, step, max_rot, max_trans, tol_rot, tol_trans, patience, eps, R, T,
+                                         loss, value, table, cursor, nrows, row, aabb_rows, row_stride, count1, N, box, delta, last_step,
+                                         state, B, nullptr);
+    }
+};
+
+static rrl_register_newton_args epoch_base() {
+    rrl_register_newton_args a;
+    std::memset(&a, 0, sizeof a);
+    a.struct_bytes = (int32_t)sizeof a;
+    a.B = 3; a.N = 300; a.M = 300; a.L = 2048; a.rounds = 10; a.patience = 3;
+    a.rng_state = fake<uint64_t>(); a.radius = fake<float>(); a.centers = fake<float>(); a.box1 = fake<float>(); a.box2 = fake<float>();
+    a.lines = fake<float>(); a.filled = fake<int32_t>(); a.tile_counts = fake<int32_t>();
+    a.src_tri = fake<float>(); a.tar_tri = fake<float>(); a.R = fake<float>(); a.T = fake<float>(); a.ws = fake<void>();
+    a.ws_bytes = (size_t)1 << 50; a.loss = fake<float>();
+    a.cham_ws = fake<void>(); a.cham_ws_bytes = (size_t)1 << 50; a.best_x = fake<uint64_t>(); a.best_y = fake<uint64_t>();
+    a.cham_mean = fake<float>(); a.value = fake<float>();
+    a.neq = fake<float>(); a.part = fake<void>(); a.part_bytes = (size_t)1 << 50;
+    a.damping = fake<float>(); a.step = fake<float>(); a.max_rot = fake<float>(); a.max_trans = fake<float>(); a.tol_rot = fake<float>();
+    a.tol_trans = fake<float>(); a.eps = 1e-12; a.delta = fake<float>(); a.last_step = fake<float>(); a.state = fake<int32_t>();
+    a.table = fake<float>(); a.cursor = fake<long long>(); a.table_rows = 16; a.row = fake<float>();
+    return a;
+}
+static void epoch(const char *what, int want, const std::function<void(rrl_register_newton_args &, rrl_opts &)> &edit) {
+    rrl_register_newton_args a = epoch_base();
+    rrl_opts o = opts_base();
+    edit(a, o);
+    expect(what, rrl_register_newton_epoch(&a, nullptr), want);
+}
+
+int main() {
+    const int cap1 = rrl_sort_capacity() + 1;
+    int32_t *const counts = fake<int32_t>(512);
+    { NeqCall c; c.ws = nullptr; expect("neq: null workspace", c.run(), RRL_E_ARG); }
+    { NeqCall c; c.neq = nullptr; expect("neq: null output", c.run(), RRL_E_ARG); }
+    { NeqCall c; c.part = fake<void>(260); expect("neq: misaligned scratch", c.run(), RRL_E_ARG); }
+    { NeqCall c; c.B = 0; expect("neq: empty batch", c.run(), RRL_E_ARG); }
+    { NeqCall c; c.B = 65536; expect("neq: a batch beyond the grid", c.run(), RRL_E_ARG); }
+    { NeqCall c; c.L = 1 << 24; expect("neq: L = 2^24", c.run(), RRL_E_ARG); }
+    { NeqCall c; c.e_m = 9; expect("neq: a wide range", c.run(), RRL_E_ARG); }
+    { NeqCall c; c.s_n = 0; expect("neq: a range from 0", c.run(), RRL_E_ARG); }
+    { NeqCall c; rrl_opts o = opts_base(); o.problems = 2; c.B = 4; c.opts = &o; expect("neq: multi-pose", c.run(), RRL_E_ARG); }
+    { NeqCall c; rrl_opts o = opts_base(); o.struct_bytes = 8; o.problems = 2; c.B = 4; c.opts = &o; c.ws_bytes = 0;
+      expect("neq: short options are not read beyond their size", c.run(), RRL_E_WS); }
+    { NeqCall c; c.ws_bytes = 4096; expect("neq: short workspace", c.run(), RRL_E_WS); }
+    { NeqCall c; c.part_bytes = rrl_pose_normal_eq_part_bytes(3, 2048) - 8; expect("neq: short scratch", c.run(), RRL_E_WS); }
+    { NeqCall c; c.e_m = 9; c.ws_bytes = 0; expect("neq: a wide range + short workspace", c.run(), RRL_E_ARG); }
+    { StepCall c; c.neq = nullptr; expect("step: null neq", c.run(), RRL_E_ARG); }
+    { StepCall c; c.state = nullptr; expect("step: null state", c.run(), RRL_E_ARG); }
+    { StepCall c; c.T = nullptr; expect("step: null T", c.run(), RRL_E_ARG); }
+    { StepCall c; c.B = -1; expect("step: negative batch", c.run(), RRL_E_ARG); }
+    { StepCall c; c.eps = -1.0; expect("step: negative eps", c.run(), RRL_E_ARG); }
+    { StepCall c; c.eps = std::nan(""); expect("step: NaN eps", c.run(), RRL_E_ARG); }
+    { StepCall c; c.tol_rot = nullptr; expect("step: a stopping rule without its tolerances", c.run(), RRL_E_ARG); }
+    { StepCall c; c.aabb_rows = nullptr; expect("step: a box without rows", c.run(), RRL_E_ARG); }
+    { StepCall c; c.row_stride = 8; expect("step: overlapping rows", c.run(), RRL_E_ARG); }
+    { StepCall c; c.gate_stride = -4; expect("step: negative gate stride", c.run(), RRL_E_ARG); }
+    { StepCall c; c.B = 0; expect("step: an empty batch launches nothing", c.run(), 0); }
+    expect("epoch: null struct", rrl_register_newton_epoch(nullptr, nullptr), RRL_E_ARG);
+    epoch("epoch: a struct too short", RRL_E_ARG, [](auto &a, auto &) { a.struct_bytes = 64; });
+    epoch("epoch: empty batch", RRL_E_ARG, [](auto &a, auto &) { a.B = 0; });
+    epoch("epoch: negative size", RRL_E_ARG, [](auto &a, auto &) { a.N = -1; });
+    epoch("epoch: no lines", RRL_E_ARG, [](auto &a, auto &) { a.L = 0; });
+    epoch("epoch: no sampler rounds", RRL_E_ARG, [](auto &a, auto &) { a.rounds = 0; });
+    epoch("epoch: misaligned ballots", RRL_E_ARG, [](auto &a, auto &) { a.tile_counts = fake<int32_t>(260); });
+    epoch("epoch: multi-pose", RRL_E_ARG, [](auto &a, auto &o) { a.B = 4; o.problems = 2; a.opts = &o; });
+    epoch("epoch: line counts", RRL_E_ARG, [&](auto &a, auto &o) { o.nlines = counts; a.opts = &o; });
+    epoch("epoch: the monitor on a ragged batch", RRL_E_ARG, [&](auto &a, auto &o) { o.count1 = o.count2 = counts; a.opts = &o; });
+    epoch("epoch: the monitor without its scratch", RRL_E_ARG, [](auto &a, auto &) { a.cham_ws = nullptr; });
+    epoch("epoch: the monitor beyond the sort capacity", RRL_E_ARG, [&](auto &a, auto &) { a.N = cap1; });
+    epoch("epoch: null neq", RRL_E_ARG, [](auto &a, auto &) { a.neq = nullptr; });
+    epoch("epoch: null state", RRL_E_ARG, [](auto &a, auto &) { a.state = nullptr; });
+    epoch("epoch: null src_tri", RRL_E_ARG, [](auto &a, auto &) { a.src_tri = nullptr; });
+    epoch("epoch: a stopping rule without its tolerances", RRL_E_ARG, [](auto &a, auto &) { a.tol_trans = nullptr; });
+    epoch("epoch: ragged beyond the sort capacity", RRL_E_ARG,
+          [&](auto &a, auto &o) { a.N = cap1; a.value = nullptr; o.count1 = o.count2 = counts; a.opts = &o; });
+    epoch("epoch: L = 2^24", RRL_E_ARG, [](auto &a, auto &) { a.L = 1 << 24; a.value = nullptr; });
+    epoch("epoch: short workspace", RRL_E_WS, [](auto &a, auto &) { a.ws_bytes = 4096; });
+    epoch("epoch: short workspace, ragged", RRL_E_WS,
+          [&](auto &a, auto &o) { a.ws_bytes = 0; a.value = nullptr; o.count1 = o.count2 = counts; a.opts = &o; });
+    epoch("epoch: short Chamfer workspace", RRL_E_WS, [](auto &a, auto &) { a.cham_ws_bytes = 64; });
+    epoch("epoch: short scratch", RRL_E_WS, [](auto &a, auto &) { a.part_bytes = 64; });
+    epoch("epoch: short options", RRL_E_WS, [](auto &a, auto &o) { o.struct_bytes = 12; o.problems = 2; a.opts = &o; a.ws_bytes = 0; });
+    epoch("epoch: chain flags are dropped", RRL_E_WS, [](auto &a, auto &o) { o.flags = RRL_F_CHAIN | RRL_F_CHAINED; a.opts = &o; a.ws_bytes = 0; });
+    epoch("epoch: given lines need no rounds", RRL_E_WS,
+          [](auto &a, auto &) { a.rng_state = nullptr; a.rounds = 0; a.radius = nullptr; a.ws_bytes = 0; });
+    epoch("epoch: multi-pose + short workspace", RRL_E_ARG, [](auto &a, auto &o) { a.B = 4; o.problems = 2; a.opts = &o; a.ws_bytes = 0; });
+    epoch("epoch: null pointer + short workspace", RRL_E_ARG, [](auto &a, auto &) { a.state = nullptr; a.ws_bytes = 0; });
+    std::printf("%d failure(s)\n", failures);
+    return failures ? 1 : 0;
+}
