@@ -1,4 +1,7 @@
-// rrl_epoch.hip -- one epoch of the single-pair demo as ONE C call (include/rrl.h rrl_demo_epoch).
+// rrl_epoch.hip -- one registration epoch as ONE C call, host code only: rrl_demo_epoch (a single pair, the demo's loop, the
+// next epoch's sampler pipelined into this epoch's launches) and the two batched epochs rrl_register_epoch (first order: fused
+// step + Adam on se(3)) and rrl_register_newton_epoch (second order: forward + normal equations + Gauss-Newton step), which
+// share one sequence written once below (include/rrl.h).
 //
 // code/test_demo_optimized_Lie_Algebra.py:46-82 does, per epoch: sample lines through both clouds' boxes (against the
 // PREVIOUS epoch's moved source), move the source by the current pose, evaluate the loss, backward, Adam step, Chamfer
@@ -11,7 +14,6 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
-#include <cstring>
 #include "rrl_ws.h"
 
 extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
@@ -72,111 +74,117 @@ extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
                              (N + 255) / 256, a->box1, stream);
 }
 
-// One epoch for a BATCH of pairs as one call (include/rrl.h rrl_register_epoch): the same entries, B samples each -- sampler
-// (2 launches, 3 from 512 workgroups on; skipped without rng_state) -> fused registration step with the caller's options (prepared orders, counts, kept
-// target; 4 or 5 launches) -> optionally the Chamfer monitor per sample (walk + group means, 2) -> batched pose step (1), whose
-// gate is the workspace's INFO (stride 4), whose rows are cloud 1 of APART and whose box output is box1.  No riders, no
-// pipelining across epochs, no environment switch, no host read-back; every refusal before the first launch, RRL_E_ARG first.
-extern "C" int rrl_register_epoch(const rrl_register_epoch_args *a, void *stream) {
-    if (!a || a->struct_bytes < (int32_t)sizeof(rrl_register_epoch_args)) return RRL_E_ARG;
-    const int B = a->B, N = a->N, M = a->M, L = a->L;
-    if (B <= 0 || N <= 0 || M <= 0 || L <= 0) return RRL_E_ARG;
-    const bool sample = a->rng_state != nullptr, monitor = a->value != nullptr;
-    if (sample && (a->rounds <= 0 || a->rounds > 65535 || B > 65535 || !a->radius || !a->centers || !a->box2 || !a->filled ||
-                   !a->tile_counts || (((uintptr_t)a->tile_counts) & 7) != 0))
-        return RRL_E_ARG;
-    RrlCall o = rrl_begin_call(a->opts, B, N, M, L, a->ws, a->ws_bytes, stream);
-    if (o.problems > 0 || o.nlines) return RRL_E_ARG;  // (one pose per pair; the sampler owns the line set)
-    // the walk of rrl_chamfer_from_loss reads whole clouds: not on a ragged workspace (include/rrl.h rrl_opts.count1)
-    if (monitor && (o.ragged() || !a->cham_ws || !a->best_x || !a->best_y || !a->cham_mean || !rrl_sorted_layout(N, M) || B > 32767))
-        return RRL_E_ARG;
-    if (!a->xi || !a->m || !a->v || !a->adam_state || !a->lr || !a->box1) return RRL_E_ARG;
-    o.rider = nullptr;  // (no launch of this epoch carries another's work)
+// ---------------------------------------------------------------------------------------
+// The batched epochs (include/rrl.h rrl_register_epoch, rrl_register_newton_epoch): the same entries, B samples each --
+// sampler (2 launches, 3 from 512 workgroups on; skipped without rng_state) -> the loss with the caller's options (prepared
+// orders, counts, kept target) -> optionally the Chamfer monitor per sample (walk + group means, 2) -> the pose side, whose
+// last launch is a batched pose step.  No riders, no pipelining across epochs, no environment switch, no host read-back;
+// every refusal before the first launch, RRL_E_ARG first.  What both do is written once, as templates over the argument
+// struct: rrl_register_epoch_args and rrl_register_newton_args name every shared field alike.
+// ---------------------------------------------------------------------------------------
+// RRL_E_ARG before there is a record: the struct, the shape, and the sampler's fields when the epoch samples (rng_state)
+template <class A>
+static bool epoch_front_ok(const A *a) {
+    if (!a || a->struct_bytes < (int32_t)sizeof(A)) return false;
+    if (a->B <= 0 || a->N <= 0 || a->M <= 0 || a->L <= 0) return false;
+    return !a->rng_state || (a->rounds > 0 && a->rounds <= 65535 && a->B <= 65535 && a->radius && a->centers && a->box2 &&
+                             a->filled && a->tile_counts && (((uintptr_t)a->tile_counts) & 7) == 0);
+}
+// RRL_E_ARG on the record of rrl_begin_call: one pose per pair, the sampler owns the line set; and the monitor's (value):
+// the walk of rrl_chamfer_from_loss reads whole clouds -- not on a ragged workspace (include/rrl.h rrl_opts.count1)
+template <class A>
+static bool epoch_record_ok(const A *a, const RrlCall &o) {
+    if (o.problems > 0 || o.nlines) return false;
+    return !a->value || !(o.ragged() || !a->cham_ws || !a->best_x || !a->best_y || !a->cham_mean || !rrl_sorted_layout(a->N, a->M) ||
+                          a->B > 32767);
+}
+// no launch of a one-call epoch carries another's work or leaves something for a later call (the chain flags are dropped, not
+// refused; the payload belongs to rrl_loss_step_ex)
+static void epoch_own_launches(RrlCall &o) {
+    o.rider = nullptr;
     o.flags &= ~(RRL_F_CHAIN | RRL_F_CHAINED);
     o.chain_left = nullptr;
+    o.payload = nullptr;
+}
+// RRL_E_WS after rrl_check_call's own: the monitor's scratch
+template <class A>
+static bool epoch_cham_ws_ok(const A *a) {
+    return !a->value || a->cham_ws_bytes >= rrl_chamfer_workspace_bytes(a->B, a->N, a->M);
+}
+template <class A>
+static int epoch_sample(const A *a, void *stream) {
+    if (!a->rng_state) return 0;
+    return rrl_sample_lines_rng(a->rng_state, a->radius, a->centers, a->box1, a->box2, a->lines, a->filled, a->tile_counts, a->B,
+                                a->L, a->rounds, stream);
+}
+template <class A>
+static int epoch_monitor(const A *a, void *stream) {
+    if (!a->value) return 0;
+    const int B = a->B, N = a->N, M = a->M;
+    if (const int rc = rrl_chamfer_from_loss(a->ws, a->ws, a->ws_bytes, B, N, M, a->L, a->cham_ws, a->cham_ws_bytes, a->best_x,
+                                             a->best_y, a->cham_mean, stream))
+        return rc;
+    return rrl_chamfer_group_means(a->cham_ws, a->cham_ws_bytes, a->value, B, B, N, M, stream);
+}
+// What a batched pose step takes from the call's workspace: its gate, the loss's bucket counts (INFO, stride 4); the partial
+// rows of the moved sources, cloud 1 of APART [2][B][nblk][8]; the floats from one sample's rows to the next
+struct EpochPoseInputs {
+    const int32_t *gate;
+    const float *rows;
+    long long row_stride;
+};
+static EpochPoseInputs epoch_pose_inputs(const RrlCall &o) {
+    const int nblk = ((o.N > o.M ? o.N : o.M) + 255) / 256;
+    return {o.at<RRL_WS_INFO>(), o.at<RRL_WS_APART>(), (long long)nblk * 8};
+}
+
+// fused registration step (4 or 5 launches) -> batched Adam pose step (1), whose box output is box1
+extern "C" int rrl_register_epoch(const rrl_register_epoch_args *a, void *stream) {
+    if (!epoch_front_ok(a)) return RRL_E_ARG;
+    RrlCall o = rrl_begin_call(a->opts, a->B, a->N, a->M, a->L, a->ws, a->ws_bytes, stream);
+    if (!epoch_record_ok(a, o)) return RRL_E_ARG;
+    if (!a->xi || !a->m || !a->v || !a->adam_state || !a->lr || !a->box1) return RRL_E_ARG;
+    epoch_own_launches(o);
     const RrlXform xf = {a->src_tri, a->R, a->T, a->transpose_r, 1};
     const bool pointers = a->src_tri && a->R && a->T && a->tar_tri && a->lines && a->loss && a->grad_loss && a->gR && a->gt;
     int rc = rrl_check_call(o, pointers, RRL_WANT_DIRECT, nullptr, &xf);
     if (rc) return rc;
-    if (monitor && a->cham_ws_bytes < rrl_chamfer_workspace_bytes(B, N, M)) return RRL_E_WS;
-    if (sample) {
-        rc = rrl_sample_lines_rng(a->rng_state, a->radius, a->centers, a->box1, a->box2, a->lines, a->filled, a->tile_counts, B, L,
-                                  a->rounds, stream);
-        if (rc) return rc;
-    }
+    if (!epoch_cham_ws_ok(a)) return RRL_E_WS;
+    if ((rc = epoch_sample(a, stream))) return rc;
     rc = rrl_registration_step_call(o, xf, a->tar_tri, a->lines, a->loss, a->grad_loss, a->gR, a->gt, nullptr);
     if (rc) return rc;
-    if (monitor) {
-        rc = rrl_chamfer_from_loss(a->ws, a->ws, a->ws_bytes, B, N, M, L, a->cham_ws, a->cham_ws_bytes, a->best_x, a->best_y,
-                                   a->cham_mean, stream);
-        if (rc) return rc;
-        rc = rrl_chamfer_group_means(a->cham_ws, a->cham_ws_bytes, a->value, B, B, N, M, stream);
-        if (rc) return rc;
-    }
-    const int nblk = ((N > M ? N : M) + 255) / 256;  // APART [2][B][nblk][8]: cloud 1 first
-    return rrl_se3_adam_step_batch(a->xi, a->gR, a->gt, a->m, a->v, a->adam_state, a->lr, o.at<RRL_WS_INFO>(), 4, a->b1, a->b2,
-                                   a->eps, a->R, a->T, a->gxi, a->loss, a->value, a->table, a->cursor, a->table_rows, a->row,
-                                   o.at<RRL_WS_APART>(), (long long)nblk * 8, o.count1, N, a->box1, B, stream);
+    if ((rc = epoch_monitor(a, stream))) return rc;
+    const EpochPoseInputs p = epoch_pose_inputs(o);
+    return rrl_se3_adam_step_batch(a->xi, a->gR, a->gt, a->m, a->v, a->adam_state, a->lr, p.gate, 4, a->b1, a->b2, a->eps, a->R, a->T,
+                                   a->gxi, a->loss, a->value, a->table, a->cursor, a->table_rows, a->row, p.rows, p.row_stride,
+                                   o.count1, a->N, a->box1, a->B, stream);
 }
 
-// One Gauss-Newton epoch for a batch of pairs as one call (include/rrl.h rrl_register_newton_epoch): rrl_register_epoch's
-// sequence with the FORWARD in place of the fused step and the second-order pose side -- sampler -> registration forward with
-// the caller's options -> optionally the monitor -> rrl_pose_normal_eq (2 launches) -> rrl_se3_newton_step_batch (1).  Existing
-// entries plus the two of rrl_newton.hip, nothing else; every refusal before the first launch, RRL_E_ARG first.
+// registration FORWARD (y = x R + T; the record's defaults are its arguments: range 1 .. 4, pool 0, scan mode cull, chunk 0)
+// -> rrl_pose_normal_eq (2 launches) -> rrl_se3_newton_step_batch (1): the two entries of rrl_newton.hip.  The grids of the
+// normal equations take B <= 65535 whether or not the epoch samples
 extern "C" int rrl_register_newton_epoch(const rrl_register_newton_args *a, void *stream) {
-    if (!a || a->struct_bytes < (int32_t)sizeof(rrl_register_newton_args)) return RRL_E_ARG;
-    const int B = a->B, N = a->N, M = a->M, L = a->L;
-    if (B <= 0 || B > 65535 || N <= 0 || M <= 0 || L <= 0) return RRL_E_ARG;
-    const bool sample = a->rng_state != nullptr, monitor = a->value != nullptr;
-    if (sample && (a->rounds <= 0 || a->rounds > 65535 || !a->radius || !a->centers || !a->box2 || !a->filled ||
-                   !a->tile_counts || (((uintptr_t)a->tile_counts) & 7) != 0))
-        return RRL_E_ARG;
-    // the forward's options: the caller's, without what would make a launch of this epoch carry or leave something for another
-    rrl_opts fo;
-    memset(&fo, 0, sizeof fo);
-    fo.reduce_mode = fo.deterministic = fo.sort_parts = fo.scan_variant = -1;
-    if (a->opts && a->opts->struct_bytes >= 8)
-        memcpy(&fo, a->opts, (size_t)a->opts->struct_bytes < sizeof fo ? (size_t)a->opts->struct_bytes : sizeof fo);
-    fo.struct_bytes = (int32_t)sizeof fo;
-    fo.flags &= ~(RRL_F_CHAIN | RRL_F_CHAINED);
-    fo.chamfer = nullptr;
-    fo.chain_left = nullptr;
-    fo.payload = nullptr;
-    RrlCall o = rrl_begin_call(&fo, B, N, M, L, a->ws, a->ws_bytes, stream);
-    if (o.problems > 0 || o.nlines) return RRL_E_ARG;  // (one pose per pair; the sampler owns the line set)
-    if (monitor && (o.ragged() || !a->cham_ws || !a->best_x || !a->best_y || !a->cham_mean || !rrl_sorted_layout(N, M) || B > 32767))
-        return RRL_E_ARG;
-    // the pose side's own pointers (rrl_pose_normal_eq, rrl_se3_newton_step_batch)
+    if (!epoch_front_ok(a) || a->B > 65535) return RRL_E_ARG;
+    RrlCall o = rrl_begin_call(a->opts, a->B, a->N, a->M, a->L, a->ws, a->ws_bytes, stream);
+    if (!epoch_record_ok(a, o)) return RRL_E_ARG;
     if (!a->box1 || !a->neq || !a->part || (((uintptr_t)a->part) & 7) != 0 || !a->state || !a->damping || !a->step || !a->max_rot ||
         !a->max_trans || !(a->eps >= 0.0) || (a->patience > 0 && (!a->tol_rot || !a->tol_trans)))
         return RRL_E_ARG;
+    epoch_own_launches(o);
     const RrlXform xf = {a->src_tri, a->R, a->T, 0, 1};
     const bool pointers = a->src_tri && a->R && a->T && a->tar_tri && a->lines && a->loss;
     int rc = rrl_check_call(o, pointers, RRL_WANT_FORWARD, nullptr, &xf);
     if (rc) return rc;
-    if (monitor && a->cham_ws_bytes < rrl_chamfer_workspace_bytes(B, N, M)) return RRL_E_WS;
-    if (a->part_bytes < rrl_pose_normal_eq_part_bytes(B, L)) return RRL_E_WS;
-    if (sample) {
-        rc = rrl_sample_lines_rng(a->rng_state, a->radius, a->centers, a->box1, a->box2, a->lines, a->filled, a->tile_counts, B, L,
-                                  a->rounds, stream);
-        if (rc) return rc;
-    }
-    rc = rrl_registration_forward_ex(a->src_tri, a->R, a->T, a->tar_tri, a->lines, a->ws, a->ws_bytes, a->loss, B, N, M, L, 0, 1, 1,
-                                     RRL_MAX_HITS + 1, RRL_MAX_HITS + 1, RRL_SCAN_CULL, 0, nullptr, &fo, stream);
+    if (!epoch_cham_ws_ok(a) || a->part_bytes < rrl_pose_normal_eq_part_bytes(a->B, a->L)) return RRL_E_WS;
+    if ((rc = epoch_sample(a, stream))) return rc;
+    rc = rrl_registration_forward_call(o, a->tar_tri, a->lines, a->loss);
     if (rc) return rc;
-    if (monitor) {
-        rc = rrl_chamfer_from_loss(a->ws, a->ws, a->ws_bytes, B, N, M, L, a->cham_ws, a->cham_ws_bytes, a->best_x, a->best_y,
-                                   a->cham_mean, stream);
-        if (rc) return rc;
-        rc = rrl_chamfer_group_means(a->cham_ws, a->cham_ws_bytes, a->value, B, B, N, M, stream);
-        if (rc) return rc;
-    }
-    rc = rrl_pose_normal_eq(a->ws, a->ws_bytes, B, N, M, L, 1, 1, RRL_MAX_HITS + 1, RRL_MAX_HITS + 1, a->neq, a->part, a->part_bytes,
-                            nullptr, stream);
+    if ((rc = epoch_monitor(a, stream))) return rc;
+    rc = rrl_pose_normal_eq(a->ws, a->ws_bytes, a->B, a->N, a->M, a->L, 1, 1, RRL_MAX_HITS + 1, RRL_MAX_HITS + 1, a->neq, a->part,
+                            a->part_bytes, nullptr, stream);
     if (rc) return rc;
-    const int nblk = ((N > M ? N : M) + 255) / 256;  // APART [2][B][nblk][8]: cloud 1 first
-    return rrl_se3_newton_step_batch(a->neq, o.at<RRL_WS_INFO>(), 4, a->damping, a->step, a->max_rot, a->max_trans, a->tol_rot,
-                                     a->tol_trans, a->patience, a->eps, a->R, a->T, a->loss, a->value, a->table, a->cursor,
-                                     a->table_rows, a->row, o.at<RRL_WS_APART>(), (long long)nblk * 8, o.count1, N, a->box1,
-                                     a->delta, a->last_step, a->state, B, stream);
+    const EpochPoseInputs p = epoch_pose_inputs(o);
+    return rrl_se3_newton_step_batch(a->neq, p.gate, 4, a->damping, a->step, a->max_rot, a->max_trans, a->tol_rot, a->tol_trans,
+                                     a->patience, a->eps, a->R, a->T, a->loss, a->value, a->table, a->cursor, a->table_rows, a->row,
+                                     p.rows, p.row_stride, o.count1, a->N, a->box1, a->delta, a->last_step, a->state, a->B, stream);
 }

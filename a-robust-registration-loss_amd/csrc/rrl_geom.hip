@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "rrl_ws.h"
+#include "rrl_pose_tail.h"
 
 typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load
 
@@ -603,7 +604,8 @@ struct Se3Batch {
 // [nrows][B][3], the partial rows aabb_rows + b * row_stride, [0, ceil(count1[b] / 256)) of them), then the same statements
 // run: sample b has the bits of the single launch on its slices.  Rows beyond a sample's count are never read (a ragged
 // build does not write them); no rows: (+inf, -inf), as aabb_kernel.  Every wavefront reads and advances its own cursor
-// word: no word is read by one workgroup and written by another.  (A template, not a __device__ function called by two
+// word: no word is read by one workgroup and written by another.  The log row and the next box are rrl_pose_tail.h's, which
+// the Newton step shares.  (The body is a template, not a __device__ function called by two
 // kernels: inlined, the same statements came back with commuted operands; the empty pack is the old kernel instruction for
 // instruction -- profiles/register_batch_device_asm.json.)
 template <class... BATCH>
@@ -645,26 +647,8 @@ __global__ __launch_bounds__(64) void se3_adam_step_kernel(float *__restrict__ x
     }
     const int k = threadIdx.x;
     const bool ok = gate == nullptr || gate[0] > 0;
-    // (the log row's inputs are requested with the first loads, not after the arithmetic)
-    long long at = -1;
-    float q0 = 0.0f, q1 = 0.0f;
-    if (k == 0 && table && cursor) {
-        at = cursor[0];
-        q0 = loss ? loss[0] : 0.0f;
-        q1 = value ? value[0] : 0.0f;
-    }
-    // the moved source's AABB for the NEXT epoch's sampler (code/test_demo_optimized_Lie_Algebra.py:46-51 samples against
-    // the previous epoch's moved source) from the per-workgroup partial rows the loss step's records launch just left
-    // (APART: min xyz, max xyz of the moved first points) -- one launch (rigid apply + AABB) less per epoch
-    if (box != nullptr && k >= 8 && k < 14) {
-        const int c = k - 8;
-        float v = c < 3 ? INFINITY : -INFINITY;
-        for (int r = 0; r < n_aabb_rows; ++r) {
-            const float q = aabb_rows[(size_t)r * 8 + c];
-            v = c < 3 ? fminf(v, q) : fmaxf(v, q);
-        }
-        box[c] = v;
-    }
+    const PoseLog plog = pose_log_load(k, table, cursor, loss, value);
+    pose_next_box(k, box, aabb_rows, n_aabb_rows);
     const float step = state[0] + (ok ? 1.0f : 0.0f);
     float pk = k < 6 ? xi[k] : 0.0f;
     if (k < 6) {
@@ -697,14 +681,7 @@ __global__ __launch_bounds__(64) void se3_adam_step_kernel(float *__restrict__ x
     for (int i = 0; i < 9; ++i) R[i] = r[i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) T[i] = t[i];
-    if (table && cursor) {
-        const float q[3] = {q0, q1, ok ? 1.0f : 0.0f};
-        for (int c = 0; c < 3; ++c) {
-            if (row) row[c] = q[c];
-            if (at >= 0 && at < nrows) table[at * tstride + c] = q[c];
-        }
-        cursor[0] = at + 1;
-    }
+    pose_log_store(plog, ok, table, tstride, nrows, cursor, row);
 }
 
 extern "C" int rrl_se3_adam_step_batch(float *xi, const float *gR, const float *gT, float *m, float *v, float *state,
@@ -743,13 +720,7 @@ __global__ void log_row_kernel(const float *__restrict__ loss, const float *__re
                                const int32_t *__restrict__ info, float *__restrict__ table,
                                long long *__restrict__ cursor, long long nrows, float *__restrict__ row) {
     if (threadIdx.x != 0) return;
-    const long long at = cursor[0];
-    const float r[3] = {loss[0], value[0], info[0] > 0 ? 1.0f : 0.0f};
-    for (int c = 0; c < 3; ++c) {
-        if (row) row[c] = r[c];
-        if (at >= 0 && at < nrows) table[at * 3 + c] = r[c];
-    }
-    cursor[0] = at + 1;
+    pose_log_row({cursor[0], loss[0], value[0]}, info[0] > 0, table, 3, nrows, cursor, row);
 }
 
 extern "C" int rrl_log_row(const float *loss, const float *value, const int32_t *info, float *table,

@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "rrl_ws.h"
+#include "rrl_pose_tail.h"
 
 #define NEQ_LINES 64  // selected lines per 256-lane workgroup (four hit slots each): loss_bwd_rt_kernel's BWD_LINES
 #define NEQ_SUBS 16   // workgroups per 1024-line tile: every selected line of a tile has one (64 x 16 = 1024)
@@ -229,7 +230,7 @@ extern "C" int rrl_pose_normal_eq(const void *ws, size_t ws_bytes, int B, int N,
 
 // ---------------------------------------------------------------------------------------
 // The batched Gauss-Newton pose step: one wavefront per pose, grid B (se3_adam_step_kernel<Se3Batch>'s shape).  Lanes 8 .. 13
-// reduce the next sampler box from the step's partial rows (that kernel's text); lane 0 does the pose: H (6 x 6) and g from the
+// reduce the next sampler box from the step's partial rows and lane 0 logs (rrl_pose_tail.h); lane 0 does the pose: H (6 x 6) and g from the
 // sixteen sums, H + damping diag(H) + eps I, Cholesky and both substitutions in double, step scale, clamps, the exact
 // Rodrigues rotation, R <- R Rot^T, T <- T Rot^T + v, one Gram-Schmidt pass over R's rows, the log row, the stopping rule.
 // state [B][4] int32: [0] epochs issued, [1] consecutive calm epochs, [2] the epoch count at which the pair was declared
@@ -307,28 +308,11 @@ __global__ __launch_bounds__(64) void se3_newton_step_kernel(const NewtonArgs a)
     const int epochs = st[0] + 1, done_at = st[2];
     const bool done = done_at >= 0;        // a done pair's gate is treated as closed: its pose is frozen
     const bool open = raw > 0 && !done;
-    // (the log row's inputs are requested with the first loads, not after the arithmetic)
-    long long at = -1;
-    float q0 = 0.0f, q1 = 0.0f;
-    if (k == 0 && a.table && a.cursor) {
-        at = a.cursor[s];
-        q0 = a.loss ? a.loss[s] : 0.0f;
-        q1 = a.value ? a.value[s] : 0.0f;
-    }
-    // the moved source's AABB for the NEXT epoch's sampler from the partial rows the forward's records launch just left
-    // (APART: min xyz, max xyz of the moved first points): se3_adam_step_kernel's statements.  Rows beyond a sample's count are
-    // never read; no rows: (+inf, -inf)
-    if (a.box != nullptr && k >= 8 && k < 14) {
-        const float *__restrict__ rows = a.aabb_rows + (long long)b * a.row_stride;
-        const int n_rows = (rrl_rows(a.count1, b, a.N) + 255) / 256;
-        const int c = k - 8;
-        float v = c < 3 ? INFINITY : -INFINITY;
-        for (int r = 0; r < n_rows; ++r) {
-            const float q = rows[(size_t)r * 8 + c];
-            v = c < 3 ? fminf(v, q) : fmaxf(v, q);
-        }
-        a.box[s * 6 + c] = v;
-    }
+    // the shared tail on sample b's slices: column b of the table [nrows][B][3], [0, ceil(count1[b] / 256)) of its partial rows
+    const PoseLog plog = pose_log_load(k, a.table ? a.table + s * 3 : nullptr, a.cursor ? a.cursor + s : nullptr,
+                                       a.loss ? a.loss + s : nullptr, a.value ? a.value + s : nullptr);
+    pose_next_box(k, a.box ? a.box + s * 6 : nullptr, a.aabb_rows + (long long)b * a.row_stride,
+                  (rrl_rows(a.count1, b, a.N) + 255) / 256);
     if (k != 0) return;
     int status = done ? RRL_NEWTON_DONE : (raw > 0 ? RRL_NEWTON_STEPPED : RRL_NEWTON_GATED);
     int calm = done ? st[1] : 0;
@@ -453,14 +437,8 @@ __global__ __launch_bounds__(64) void se3_newton_step_kernel(const NewtonArgs a)
     st[1] = calm;
     st[2] = done_new;
     st[3] = status;
-    if (a.table && a.cursor) {
-        const float q[3] = {q0, q1, raw > 0 ? 1.0f : 0.0f};
-        for (int c = 0; c < 3; ++c) {
-            if (a.row) a.row[s * 3 + c] = q[c];
-            if (at >= 0 && at < a.nrows) a.table[(at * a.B + (long long)b) * 3 + c] = q[c];
-        }
-        a.cursor[s] = at + 1;
-    }
+    pose_log_store(plog, raw > 0, a.table ? a.table + s * 3 : nullptr, 3ll * a.B, a.nrows, a.cursor ? a.cursor + s : nullptr,
+                   a.row ? a.row + s * 3 : nullptr);
 }
 
 extern "C" int rrl_se3_newton_step_batch(const float *neq, const int32_t *gate, long long gate_stride, const float *damping,

@@ -442,6 +442,9 @@ extern "C" int rrl_registration_forward_ex(const float *src, const float *R, con
     // the transform runs inside the prepare step
     const RrlXform xf = {src, R, t, transpose_r, 1};  // 1: clear GACC for the backward's atomics
     if (const int rc = rrl_check_call(o, src && R && t && tri2 && line && loss, RRL_WANT_FORWARD, target_ws, &xf)) return rc;
+    return rrl_registration_forward_call(o, tri2, line, loss);
+}
+int rrl_registration_forward_call(RrlCall &o, const float *tri2, const float *line, float *loss) {
     return loss_forward_impl(o, o.at<RRL_WS_TRI1>(), tri2, line, loss);
 }
 extern "C" int rrl_registration_forward_cached(const float *src, const float *R, const float *t,

@@ -202,6 +202,9 @@ int rrl_sample_count_pass(const uint64_t *rng_state, const float *r, const float
 int rrl_sample_write_pass(uint64_t *rng_state, const float *r, const float *centers, float *lines, int32_t *filled,
                           int32_t *tile_counts, int B, int n, int rounds, void *stream);
 int rrl_sample_prefilter(void);
+// rrl_registration_forward_ex on a record that went through rrl_check_call(o, .., RRL_WANT_FORWARD, target_ws, &xf)
+// (rrl_sparse.hip; rrl_epoch.hip checks the whole epoch before its first launch)
+int rrl_registration_forward_call(RrlCall &o, const float *tri2, const float *line, float *loss);
 // rrl_registration_step_ex on a record that went through rrl_check_call(o, .., RRL_WANT_DIRECT, target_ws, &xf)
 // (rrl_sparse.hip; rrl_epoch.hip adds its riders before the check)
 int rrl_registration_step_call(RrlCall &o, const RrlXform &xf, const float *tri2, const float *line, float *loss,

@@ -11,8 +11,6 @@ weighted sum of squared point distances, and one step is one IRLS step of a Wels
 where the first-order loop takes a thousand, and a step whose length means something, so that "converged" is decided on the
 device (`patience` consecutive epochs below tol_rot / tol_trans).  Nothing is read back unless .run is asked to check.
 """
-import ctypes
-
 import torch
 
 from . import _lib, ops
@@ -42,6 +40,8 @@ class NewtonRegistration(PairRegistration):
     .last_step (B, 2): (|omega|, |v|) of the latest applied step.  .failed (B,) int32: what the latest epoch did per pair --
     0 stepped, 1 no populated bucket, 2 the factorisation failed (pose unchanged), 3 done.  All device tensors."""
 
+    _ARGS, _ENTRY = _lib.RegisterNewtonArgs, "rrl_register_newton_epoch"
+
     def __init__(self, src_tri, tar_tri, n_lines, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, damping=DAMPING,
                  step=STEP, max_rot=MAX_ROT, max_trans=MAX_TRANS, tol_rot=TOL_ROT, tol_trans=TOL_TRANS, patience=PATIENCE,
                  eps=EPS, rounds=10, seed=None, lines=None, monitor=False, table_rows=4096):
@@ -49,16 +49,21 @@ class NewtonRegistration(PairRegistration):
             raise ValueError("starting poses: R0 and T0 together, or xi0, not both")
         if int(patience) < 0 or not float(eps) >= 0.0:
             raise ValueError("patience and eps must be non-negative")
-        super().__init__(src_tri, tar_tri, n_lines, counts1=counts1, counts2=counts2, xi0=xi0, rounds=rounds, seed=seed,
-                         monitor=monitor, table_rows=table_rows, lines=lines)
-        for name in ("xi", "m", "v", "adam_state", "lr", "lr_value", "gxi"):  # the first-order state: not part of this loop
-            self.__dict__.pop(name)
+        pose = dict(R0=R0, T0=T0, xi0=xi0, damping=damping, step=step, max_rot=max_rot, max_trans=max_trans, tol_rot=tol_rot,
+                    tol_trans=tol_trans, patience=patience, eps=eps)
+        self._build(src_tri, tar_tri, n_lines, counts1=counts1, counts2=counts2, rounds=rounds, seed=seed, monitor=monitor,
+                    deterministic=None, table_rows=table_rows, lines=lines, pose=pose)
+
+    def _init_pose_side(self, R0, T0, xi0, damping, step, max_rot, max_trans, tol_rot, tol_trans, patience, eps):
+        """The second-order state: (R, T) as given or exp(xi0), the controls one per pair, the normal equations with their
+        scratch, the step's outputs and the stopping rule's state."""
         dev, B = self.dev, self.B
-        L = self.step.dims[3]
         f32 = dict(dtype=torch.float32, device=dev)
         if R0 is not None:
             self.R.copy_(ops._prep(R0, "R0", 3, dev).reshape(B, 3, 3))
             self.T.copy_(ops._prep(T0, "T0", 3, dev).reshape(B, 3))
+        else:
+            self._pose_from_xi(torch.zeros(B, 6, **f32) if xi0 is None else ops._prep(xi0, "xi0", 6, dev).reshape(B, 6))
 
         def per_pair(x, scale=None):
             t = torch.as_tensor(x, dtype=torch.float32).to(dev).reshape(-1).expand(B).clone() if not isinstance(x, torch.Tensor) \
@@ -69,48 +74,26 @@ class NewtonRegistration(PairRegistration):
         self.tol_rot, self.tol_trans = per_pair(tol_rot), per_pair(tol_trans, self.radius)
         self.patience, self.eps = int(patience), float(eps)
         self.neq = torch.zeros(B, 16, **f32)
-        self.part = ops.pose_normal_eq_part(B, L, dev)
+        self.part = ops.pose_normal_eq_part(B, self.step.dims[3], dev)
         self.delta = torch.zeros(B, 6, **f32)
         self.last_step = torch.zeros(B, 2, **f32)
         self.state = torch.zeros(B, 4, dtype=torch.int32, device=dev)
         self.state[:, 2] = -1
-        P, a = ops._p, self._args  # (what _make_args left open: the pose side)
-        a.patience = self.patience
+
+    def _pose_args(self, a):
+        P = ops._p
+        a.patience, a.eps = self.patience, self.eps
         a.neq, a.part, a.part_bytes = P(self.neq), P(self.part), self.part.numel() * 8
         a.damping, a.step, a.max_rot, a.max_trans = P(self.damping), P(self.step_scale), P(self.max_rot), P(self.max_trans)
-        a.tol_rot, a.tol_trans, a.eps = P(self.tol_rot), P(self.tol_trans), self.eps
+        a.tol_rot, a.tol_trans = P(self.tol_rot), P(self.tol_trans)
         a.delta, a.last_step, a.state = P(self.delta), P(self.last_step), P(self.state)
-
-    def _make_args(self):
-        """rrl_register_newton_args of this object's sampler, forward, monitor and log (PairRegistration.__init__ calls this
-        where it builds its rrl_register_epoch_args); the constructor adds the pose side once its buffers exist."""
-        st, P = self.step, ops._p
-        B, N, M, L = st.dims
-        a = _lib.RegisterNewtonArgs()
-        a.struct_bytes, a.B, a.N, a.M, a.L = ctypes.sizeof(_lib.RegisterNewtonArgs), B, N, M, L
-        a.rounds = self.rounds
-        a.rng_state, a.radius, a.centers, a.box1, a.box2 = P(self.rng), P(self.radius), P(self.centers), P(self.box1), P(self.box2)
-        a.lines, a.filled, a.tile_counts = P(self.lines), P(self.filled), P(self.tiles)
-        a.src_tri, a.tar_tri, a.R, a.T = P(st.src), P(st.tar), P(self.R), P(self.T)
-        a.ws, a.ws_bytes, a.loss = P(st.st.ws), st.st.nbytes, P(st.st.loss)
-        if self.monitor:
-            ws, bx, by, mean = self.cham
-            a.cham_ws, a.cham_ws_bytes, a.best_x, a.best_y, a.cham_mean, a.value = P(ws), ws.numel(), P(bx), P(by), P(mean), P(self.value)
-        a.table, a.cursor, a.table_rows, a.row = P(self.table), P(self.cursor), self.table.shape[0], P(self.row)
-        self._opts_first, self._opts_kept = ctypes.addressof(st._opts), ctypes.addressof(st._opts_kept)
-        return a
 
     def set_lr(self, lr):
         raise AttributeError("NewtonRegistration has no learning rate: see damping / step")
 
     def epoch(self):
         """One epoch of all B pairs: ONE C call (rrl_register_newton_epoch), nothing read back."""
-        self._args.opts = self._opts_kept if self._target_built else self._opts_first
-        with ops._guard(self.dev):
-            _lib.check(self._lib.rrl_register_newton_epoch(self._aref, ops._stream(self.dev)), "rrl_register_newton_epoch")
-        self._target_built = True
-        self.epochs += 1
-        self.step.st.ragged = self.step.ragged
+        super().epoch()
 
     def run(self, n_epoch, check_every=0):
         """Up to n_epoch epochs.  check_every = k > 0: .done_epoch is read once every k epochs and the loop returns early when

@@ -48,8 +48,16 @@ class PairRegistration:
 
     The poses move x -> x R + T (Reconstruction_point's row convention)."""
 
+    _ARGS, _ENTRY = _lib.RegisterEpochArgs, "rrl_register_epoch"  # the epoch's argument struct and its C entry
+
     def __init__(self, src_tri, tar_tri, n_lines, *, counts1=None, counts2=None, xi0=None, lr=DEMO_LR, rounds=10, seed=None,
                  monitor=False, deterministic=None, table_rows=4096, lines=None):
+        self._build(src_tri, tar_tri, n_lines, counts1=counts1, counts2=counts2, rounds=rounds, seed=seed, monitor=monitor,
+                    deterministic=deterministic, table_rows=table_rows, lines=lines, pose=dict(xi0=xi0, lr=lr))
+
+    def _build(self, src_tri, tar_tri, n_lines, *, counts1, counts2, rounds, seed, monitor, deterministic, table_rows, lines, pose):
+        """What every batched registration loop is made of: the request's refusals, the step, the sampler, the log and the
+        monitor; then the pose side (_init_pose_side(**pose): the subclass's), then the epoch's argument struct."""
         ragged = counts1 is not None or counts2 is not None
         if src_tri.dim() != 3 or tar_tri.dim() != 3 or src_tri.shape[0] != tar_tri.shape[0]:
             raise ValueError("src_tri / tar_tri must be (B, n, 9) with the same B")
@@ -65,13 +73,6 @@ class PairRegistration:
         B, N, M, L = st.dims
         self.B, self.rounds, self.monitor = B, int(rounds), bool(monitor)
         f32 = dict(dtype=torch.float32, device=dev)
-        self.xi = torch.zeros(B, 6, **f32) if xi0 is None else ops._prep(xi0, "xi0", 6, dev).reshape(B, 6).clone()
-        self.m, self.v = torch.zeros(B, 6, **f32), torch.zeros(B, 6, **f32)
-        self.adam_state = torch.zeros(B, **f32)
-        self.lr_value = float(lr)
-        self.lr = torch.full((B,), self.lr_value, **f32)
-        self.R, self.T = torch.empty(B, 3, 3, **f32), torch.empty(B, 3, **f32)
-        ops._run(dev, "rrl_se3_exp", ops._p(self.xi), ops._p(self.R), ops._p(self.T), B)
         # the sampler's geometry, the demo's way and once: box2 and radius = the target's AABB and its diagonal, centers = the
         # mean of the target's points, box1 = the source's AABB as given (every later one comes out of the pose launch)
         src_pts, tar_pts = st.src[:, :, :3].contiguous(), st.tar[:, :, :3].contiguous()
@@ -94,7 +95,6 @@ class PairRegistration:
             self.rng = None
         self.filled = torch.zeros(B, dtype=torch.int32, device=dev)
         self.tiles = torch.empty(B * self.rounds * ((L + 1023) // 1024) * 32, dtype=torch.int32, device=dev)
-        self.gxi = torch.zeros(B, 6, **f32)
         self.table = torch.zeros(int(table_rows), B, 3, **f32)
         self.cursor = torch.zeros(B, dtype=torch.int64, device=dev)
         self.row = torch.zeros(B, 3, **f32)
@@ -104,31 +104,54 @@ class PairRegistration:
             self.cham = (torch.empty(nb, dtype=torch.uint8, device=dev), torch.empty(B, N, dtype=torch.int64, device=dev),
                          torch.empty(B, M, dtype=torch.int64, device=dev), torch.empty(1, **f32))
             self.value = torch.zeros(B, **f32)
+        self.R, self.T = torch.empty(B, 3, 3, **f32), torch.empty(B, 3, **f32)
+        self._init_pose_side(**pose)
         self.epochs = 0  # epochs issued (the schedule's clock)
         self._target_built = False
+        self._opts_first, self._opts_kept = ctypes.addressof(st._opts), ctypes.addressof(st._opts_kept)
         self._args = self._make_args()
         self._aref = ctypes.byref(self._args)
-        self._lib = _lib.load()
+        self._call = getattr(_lib.load(), self._ENTRY)
+
+    def _pose_from_xi(self, xi):
+        """(R, T) = exp(xi), per pair."""
+        ops._run(self.dev, "rrl_se3_exp", ops._p(xi), ops._p(self.R), ops._p(self.T), self.B)
+
+    def _init_pose_side(self, xi0, lr):
+        """The first-order state: xi (B, 6) with Adam's moments, step counts and rates, and (R, T) = exp(xi)."""
+        B, f32 = self.B, dict(dtype=torch.float32, device=self.dev)
+        self.xi = torch.zeros(B, 6, **f32) if xi0 is None else ops._prep(xi0, "xi0", 6, self.dev).reshape(B, 6).clone()
+        self.m, self.v = torch.zeros(B, 6, **f32), torch.zeros(B, 6, **f32)
+        self.adam_state = torch.zeros(B, **f32)
+        self.lr_value = float(lr)
+        self.lr = torch.full((B,), self.lr_value, **f32)
+        self.gxi = torch.zeros(B, 6, **f32)
+        self._pose_from_xi(self.xi)
 
     def _make_args(self):
+        """The epoch's argument struct: the fields both structs name alike, then the pose side's (_pose_args)."""
         st, P = self.step, ops._p
-        B, N, M, L = st.dims
-        a = _lib.RegisterEpochArgs()
-        a.struct_bytes, a.B, a.N, a.M, a.L = ctypes.sizeof(_lib.RegisterEpochArgs), B, N, M, L
-        a.rounds, a.transpose_r = self.rounds, st.tr
+        a = self._ARGS()
+        a.struct_bytes = ctypes.sizeof(a)
+        a.B, a.N, a.M, a.L = st.dims
+        a.rounds = self.rounds
         a.rng_state, a.radius, a.centers, a.box1, a.box2 = P(self.rng), P(self.radius), P(self.centers), P(self.box1), P(self.box2)
         a.lines, a.filled, a.tile_counts = P(self.lines), P(self.filled), P(self.tiles)
         a.src_tri, a.tar_tri, a.R, a.T = P(st.src), P(st.tar), P(self.R), P(self.T)
-        a.ws, a.ws_bytes, a.loss, a.grad_loss = P(st.st.ws), st.st.nbytes, P(st.st.loss), P(st.ones)
-        a.gR, a.gt = P(st.gR), P(st.gt)
+        a.ws, a.ws_bytes, a.loss = P(st.st.ws), st.st.nbytes, P(st.st.loss)
         if self.monitor:
             ws, bx, by, mean = self.cham
             a.cham_ws, a.cham_ws_bytes, a.best_x, a.best_y, a.cham_mean, a.value = P(ws), ws.numel(), P(bx), P(by), P(mean), P(self.value)
+        a.table, a.cursor, a.table_rows, a.row = P(self.table), P(self.cursor), self.table.shape[0], P(self.row)
+        self._pose_args(a)
+        return a
+
+    def _pose_args(self, a):
+        st, P = self.step, ops._p
+        a.transpose_r, a.grad_loss, a.gR, a.gt = st.tr, P(st.ones), P(st.gR), P(st.gt)
         a.xi, a.m, a.v, a.adam_state, a.lr = P(self.xi), P(self.m), P(self.v), P(self.adam_state), P(self.lr)
         a.b1, a.b2, a.eps = 0.9, 0.999, 1e-8
-        a.gxi, a.table, a.cursor, a.table_rows, a.row = P(self.gxi), P(self.table), P(self.cursor), self.table.shape[0], P(self.row)
-        self._opts_first, self._opts_kept = ctypes.addressof(st._opts), ctypes.addressof(st._opts_kept)
-        return a
+        a.gxi = P(self.gxi)
 
     def invalidate_target(self):
         """The next epoch rebuilds the targets' records (after a write into tar_tri or counts2)."""
@@ -147,7 +170,7 @@ class PairRegistration:
             self.set_lr(lr)
         self._args.opts = self._opts_kept if self._target_built else self._opts_first
         with ops._guard(self.dev):
-            _lib.check(self._lib.rrl_register_epoch(self._aref, ops._stream(self.dev)), "rrl_register_epoch")
+            _lib.check(self._call(self._aref, ops._stream(self.dev)), self._ENTRY)
         self._target_built = True
         self.epochs += 1
         self.step.st.ragged = self.step.ragged

@@ -8,19 +8,18 @@ rrl_register_newton_epoch; rrl_hip/newton.py).
    of Q1(delta); and the loss twin's own directional derivative along -H^-1 g is negative.
 2. What the three entries refuse and with which code -- fake pointers, no GPU: every refusal happens on the host before the
    first launch, RRL_E_ARG before RRL_E_WS --, the ctypes mirror of rrl_register_newton_args against the header compiled by
-   gcc, and the ValueErrors of NewtonRegistration that need no GPU.  tools/register_newton_sanitize.sh runs the same calls
-   from a stand-alone program under AddressSanitizer + UBSan."""
+   gcc, and the ValueErrors of NewtonRegistration that need no GPU.  tools/register_newton_refusals.cpp makes the same calls
+   from a stand-alone program, which tools/refusals_sanitize.sh runs under AddressSanitizer + UBSan."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import loss_refs
 import newton_refs as NR
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 # (fixture, bucket range, pose of the source: rotation vector and translation)
 CASES = [("loss_synth_s0.npz", (1, 1, 5, 5), (0.05, -0.02, 0.03), (0.02, 0.01, -0.015)),
@@ -337,21 +336,8 @@ def test_the_epoch_struct_matches_the_header(tmp_path):
     """rrl_register_newton_args as rrl_hip/_lib.py declares it against include/rrl.h compiled by gcc: same size, same offset
     of every field; the status codes and the number of sums as the header defines them."""
     from rrl_hip import _lib
-    cls, name = _lib.RegisterNewtonArgs, "rrl_register_newton_args"
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "rrl.h")}"', 'int main(void) {',
-           f'  printf("{name} %zu\\n", sizeof({name}));']
-    src += [f'  printf("{name}.{f} %zu\\n", offsetof({name}, {f}));' for f, _ in cls._fields_]
-    src += ['  printf("codes %d%d%d%d%d\\n", RRL_NEWTON_STEPPED, RRL_NEWTON_GATED, RRL_NEWTON_FAILED, RRL_NEWTON_DONE, RRL_NEQ_SUMS);',
-            '  return 0;', '}']
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-std=c99", "-o", str(exe), str(c)])
-    got = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert int(got[name]) == ctypes.sizeof(cls)
-    for f, _ in cls._fields_:
-        assert int(got[f"{name}.{f}"]) == getattr(cls, f).offset, f
-    assert cls.struct_bytes.offset == 0
+    codes = '  printf("codes %d%d%d%d%d\\n", RRL_NEWTON_STEPPED, RRL_NEWTON_GATED, RRL_NEWTON_FAILED, RRL_NEWTON_DONE, RRL_NEQ_SUMS);'
+    got = abi_layout.assert_struct_matches_header(_lib.RegisterNewtonArgs, "rrl_register_newton_args", tmp_path, [codes])
     assert got["codes"] == f"{_lib.NEWTON_STEPPED}{_lib.NEWTON_GATED}{_lib.NEWTON_FAILED}{_lib.NEWTON_DONE}{NR.NSUMS}"
     assert (NR.STEPPED, NR.GATED, NR.FAILED, NR.DONE) == (_lib.NEWTON_STEPPED, _lib.NEWTON_GATED, _lib.NEWTON_FAILED, _lib.NEWTON_DONE)
 

@@ -5,13 +5,11 @@ rrl_register_epoch_args against the header compiled by gcc, the ValueErrors of P
 learning-rate schedule of PairRegistration.run against the demo's adjust_learning_rate."""
 import ctypes
 import importlib
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import ROOT
+import abi_layout
 
 FAKE = ctypes.c_void_p(256)
 BIG = 1 << 50
@@ -150,20 +148,7 @@ def test_the_epoch_struct_matches_the_header(tmp_path):
     """rrl_register_epoch_args as rrl_hip/_lib.py declares it against include/rrl.h compiled by gcc: same size, same
     offset of every field."""
     from rrl_hip import _lib
-    cls, name = _lib.RegisterEpochArgs, "rrl_register_epoch_args"
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "rrl.h")}"', 'int main(void) {',
-           f'  printf("{name} %zu\\n", sizeof({name}));']
-    src += [f'  printf("{name}.{f} %zu\\n", offsetof({name}, {f}));' for f, _ in cls._fields_]
-    src += ['  return 0;', '}']
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-std=c99", "-o", str(exe), str(c)])
-    got = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert int(got[name]) == ctypes.sizeof(cls)
-    for f, _ in cls._fields_:
-        assert int(got[f"{name}.{f}"]) == getattr(cls, f).offset, f
-    assert cls.struct_bytes.offset == 0  # struct_bytes first, like rrl_demo_epoch_args
+    abi_layout.assert_struct_matches_header(_lib.RegisterEpochArgs, "rrl_register_epoch_args", tmp_path)
 
 
 def test_pair_registration_refuses_with_the_alternative(lib):

@@ -1,5 +1,5 @@
 // The refusal paths of rrl_se3_adam_step_batch and rrl_register_epoch (include/rrl.h) as a stand-alone host program, for a
-// sanitizer build of the library's host side (tools/register_batch_sanitize.sh): the calls of tests/test_register_batch_host.py's
+// sanitizer build of the library's host side (tools/refusals_sanitize.sh <this file>): the calls of tests/test_register_batch_host.py's
 // tables with fake pointers -- every one is refused on the host before a launch, so no pointer is dereferenced and no GPU
 // is needed.  Exit status 0: every call returned its documented code.
 #include <cstdio>
