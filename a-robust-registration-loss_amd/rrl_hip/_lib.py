@@ -83,6 +83,10 @@ _SIGS = {
     "rrl_se3_newton_step_batch": [_P, _P, _c.c_longlong] + [_P] * 6 + [_I, _c.c_double] + [_P] * 6 + [_c.c_longlong, _P, _P,
                                                                                                   _c.c_longlong, _P, _I] + [_P] * 4 + [_I, _P],
     "rrl_register_newton_epoch": [_P, _P],
+    "rrl_kabsch_fwd": [_P, _P],
+    "rrl_kabsch_bwd": [_P] * 7,
+    "rrl_icp_step_batch": [_P] * 8 + [_I, _P, _P, _P, _c.c_longlong, _P, _P, _P, _I, _P],
+    "rrl_icp_epoch": [_P, _P],
     "rrl_rigid_apply_aabb": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "rrl_se3_exp": [_P, _P, _P, _I, _P],
     "rrl_se3_exp_bwd": [_P, _P, _P, _P, _I, _P],
@@ -98,7 +102,7 @@ _SIGS = {
 }
 EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamfer_workspace_bytes",
                                  "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes", "rrl_sort_capacity",
-                                 "rrl_knn3_self_workspace_bytes", "rrl_pose_normal_eq_part_bytes"])
+                                 "rrl_knn3_self_workspace_bytes", "rrl_pose_normal_eq_part_bytes", "rrl_kabsch_part_bytes"])
 
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
 F_CHAIN = 2        # RRL_F_CHAIN: leave the hit counts / CHAIN words cleared for the next step on this workspace
@@ -169,6 +173,32 @@ class RegisterNewtonArgs(ctypes.Structure):
                 ("table", _P), ("cursor", _P), ("table_rows", _c.c_longlong), ("row", _P)]
 
 
+class KabschArgs(ctypes.Structure):
+    """include/rrl.h rrl_kabsch_args (same field order)."""
+    _fields_ = [("struct_bytes", _c.c_int32), ("B", _c.c_int32), ("n", _c.c_int32), ("m", _c.c_int32), ("a_stride", _c.c_int32),
+                ("b_stride", _c.c_int32), ("transpose_r", _c.c_int32), ("reserved", _c.c_int32),
+                ("a", _P), ("b", _P), ("w", _P), ("keys", _P), ("count_a", _P), ("count_b", _P), ("gate_sq", _P),
+                ("eps_w", _c.c_double), ("rank_tol", _c.c_float), ("reserved_f", _c.c_float),
+                ("part", _P), ("part_bytes", _Z), ("R", _P), ("T", _P), ("fit", _P), ("info", _P)]
+
+
+class IcpEpochArgs(ctypes.Structure):
+    """include/rrl.h rrl_icp_epoch_args (same field order)."""
+    _fields_ = [("struct_bytes", _c.c_int32), ("B", _c.c_int32), ("N", _c.c_int32), ("M", _c.c_int32), ("patience", _c.c_int32),
+                ("reserved", _c.c_int32),
+                ("src", _P), ("tar", _P), ("count1", _P), ("count2", _P), ("R", _P), ("T", _P), ("moved", _P),
+                ("cham_ws", _P), ("cham_ws_bytes", _Z), ("best_x", _P), ("best_y", _P), ("values", _P), ("order_x", _P),
+                ("order_y", _P), ("w", _P), ("gate_sq", _P), ("eps_w", _c.c_double), ("rank_tol", _c.c_float),
+                ("reserved_f", _c.c_float),
+                ("part", _P), ("part_bytes", _Z), ("Rk", _P), ("Tk", _P), ("fit", _P), ("info", _P),
+                ("tol_rot", _P), ("tol_trans", _P), ("last_step", _P), ("state", _P),
+                ("table", _P), ("cursor", _P), ("table_rows", _c.c_longlong), ("row", _P)]
+
+
+# rrl_kabsch_fwd's fit [B][32] doubles and info[b][1] (include/rrl.h RRL_FIT_*); rrl_icp_step_batch's state[b][3]
+FIT_W, FIT_ABAR, FIT_BBAR, FIT_U, FIT_S, FIT_V, FIT_DELTA, FIT_RES, FIT_KEYMEAN, FIT_DOUBLES = 0, 1, 4, 7, 16, 19, 28, 29, 30, 32
+FIT_OK, FIT_FEW, FIT_DEGENERATE, ICP_DONE = 0, 1, 2, 3
+
 # rrl_se3_newton_step_batch's state[b][3] (include/rrl.h RRL_NEWTON_*)
 NEWTON_STEPPED, NEWTON_GATED, NEWTON_FAILED, NEWTON_DONE = 0, 1, 2, 3
 
@@ -206,6 +236,8 @@ def load():
     lib.rrl_knn3_self_workspace_bytes.restype = _Z
     lib.rrl_pose_normal_eq_part_bytes.argtypes = [_I, _I]
     lib.rrl_pose_normal_eq_part_bytes.restype = _Z
+    lib.rrl_kabsch_part_bytes.argtypes = [_I, _I]
+    lib.rrl_kabsch_part_bytes.restype = _Z
     lib.rrl_sort_capacity.argtypes = []
     lib.rrl_sort_capacity.restype = _I
     _lib = lib

@@ -354,3 +354,22 @@ def fmr_intersection_loss(g_series, data, n_lines=15000, lines=None, last=3, mod
         total = total + (loss / 5.0).sum().reshape(1) * 0.5 ** (maxiter - i - 1)
         valid.append(ok)
     return total / B, _monitor(moved, tar, data), lines, torch.stack(valid)  # the last estimate's evaluation is the latest
+
+
+# ---- the trainers' pose heads: the weighted Kabsch solve the loss fragments above take their (R, t) from ---------------
+def rpm_compute_rigid_transform(a, b, weights):
+    """rpm/models/rpmnet.py:121-157 compute_rigid_transform as ONE node (rrl_hip.kabsch): a (B, n, 3), b (B, n, 3), weights
+    (B, n) -> (B, 3, 4) = [rot_mat | translation] with rot_mat moving column vectors, differentiable in all three; the
+    reference's 1e-5 in the weight normalisation included.  Where the reference's assert on det(rot_mat) would pass and
+    torch.svd's backward is finite this is the same function; on collinear correspondences it returns a rotation with zero
+    gradient instead of NaN."""
+    from .kabsch import kabsch
+    R, T = kabsch(a, b, weights, eps=1e-5, transpose_r=True)
+    return torch.cat([R, T.unsqueeze(-1)], dim=2)
+
+
+def dcp_svd_head_pose(src, src_corr):
+    """dcp/model.py:405-455 SVDHead's pose from its correspondences, channel-first as DCP holds its clouds: src, src_corr
+    (B, 3, n) -> (R (B, 3, 3), t (B, 3)) with R moving column vectors -- the head's per-sample torch.svd loop as one call."""
+    from .kabsch import kabsch
+    return kabsch(src.transpose(2, 1).contiguous(), src_corr.transpose(2, 1).contiguous(), None, eps=0.0, transpose_r=True)

@@ -883,6 +883,103 @@ typedef struct rrl_register_newton_args {
 } rrl_register_newton_args;
 int rrl_register_newton_epoch(const rrl_register_newton_args *args, void *stream);
 
+/* ---- Closed-form rigid fits: batched weighted Kabsch, and an ICP epoch around it ----------
+ * In the row convention of the registration loops (x -> x R + T) the fit of sample b is
+ *   wn_i = w_i / (sum_i w_i + eps_w),   abar = sum wn_i a_i,   bbar = sum wn_i b_i        (RPM's normalisation: eps_w = 1e-5),
+ *   H = sum wn_i (a_i - abar)^T (b_i - bbar) = U S V^T,   delta = det(U V^T),   D = diag(1, 1, delta),
+ *   R = U D V^T,   T = bbar - abar R:   the minimiser of sum wn_i |a_i R + T - b_i|^2 (eps_w = 0).
+ * transpose_r != 0 returns R^T, the matrix that moves COLUMN vectors: rpm/models/rpmnet.py:121-157 rot_mat for
+ * cov = a^T (b wn); dcp/model.py:405-455 r for H.
+ * Pairs: without keys the partner of a[b][i] is b[b][i] (m == n); with keys [B][n] -- the u64 keys a Chamfer walk left for the
+ * rows of a, (squared distance bits << 32 | index) -- it is b[b][key & 0xffffffff].  No key is followed unchecked: a row at
+ * or beyond count_a[b], an all-ones key, a key whose index is >= m or >= count_b[b] (without keys: a row >= count_b[b])
+ * contributes NOTHING and is counted in info[b][3].  gate_sq [B] (keys only): a pair whose key distance word exceeds
+ * gate_sq[b] gets weight 0 (it is neither used nor skipped).  Counts are device int32 [B], clamped to [0, n] / [0, m] by the
+ * kernel, never read on the host; rows beyond a count may hold anything (NaN).  a_stride / b_stride: floats per row (>= 3;
+ * 9 reads the first points of pseudo-triangles in place).  w [B][n] or NULL (= 1).
+ * Arithmetic: every sum is a fixed-order DOUBLE sum -- per-lane accumulators over the float32 inputs (differences to a
+ * per-sample pivot, row 0 of each cloud, taken in double, so that a cloud far from the origin loses nothing), the
+ * wavefront's DPP tree, four wavefronts, one partial row per 512-row workgroup in `part`, the partials in index order; no
+ * atomics.  H, a one-sided Jacobi SVD of it, delta, R and T are double and rounded to float32 once.  Same bits on every call.
+ * Launches: partials (grid ceil(n / 512) x B), then one wavefront per sample; ONE launch when n <= 512.  Nothing synchronises.
+ * Outputs: R [B][9], T [B][3]; fit [B][32] double (RRL_FIT_*): W = sum w, abar, bbar, U (row-major), S, V, delta, res_after =
+ * sum wn |a R + T - b|^2 from the moments in closed form (clamped at 0), key_mean = sum wn (key distance word) (0 without
+ * keys), [31] = 0; info [B][4] int32: pairs used, status, 1 when delta = -1 (the reflection was fixed), pairs skipped.
+ * Status: RRL_FIT_OK; RRL_FIT_FEW -- fewer than 3 pairs or sum w <= 0 (or NaN): R = I, T = 0, the rest of fit 0;
+ * RRL_FIT_DEGENERATE -- (s1 + delta s2) <= rank_tol s0 (collinear or coincident points): R, T and fit are written (U, V
+ * completed to orthonormal bases) but the rotation about the line is not determined.
+ * Refusals, before any launch: RRL_E_ARG -- a NULL args / a / b / R / T / fit / info / part, B < 0, n <= 0, m <= 0, a stride
+ * below 3, no keys and m != n, gate_sq without keys, B > 32767, struct_bytes != sizeof, a misaligned part or fit --, then
+ * RRL_E_WS: part_bytes < rrl_kabsch_part_bytes(B, n).  B == 0 returns 0 without a launch. */
+#define RRL_FIT_W 0
+#define RRL_FIT_ABAR 1
+#define RRL_FIT_BBAR 4
+#define RRL_FIT_U 7
+#define RRL_FIT_S 16
+#define RRL_FIT_V 19
+#define RRL_FIT_DELTA 28
+#define RRL_FIT_RES 29
+#define RRL_FIT_KEYMEAN 30
+#define RRL_FIT_DOUBLES 32
+#define RRL_FIT_OK 0
+#define RRL_FIT_FEW 1
+#define RRL_FIT_DEGENERATE 2
+typedef struct rrl_kabsch_args {
+    int32_t struct_bytes, B, n, m, a_stride, b_stride, transpose_r, reserved;
+    const float *a, *b, *w; const uint64_t *keys; const int32_t *count_a, *count_b; const float *gate_sq;
+    double eps_w; float rank_tol, reserved_f;
+    void *part; size_t part_bytes;
+    float *R, *T; double *fit; int32_t *info;
+} rrl_kabsch_args;
+size_t rrl_kabsch_part_bytes(int B, int n);
+int rrl_kabsch_fwd(const rrl_kabsch_args *args, void *stream);
+/* Backward of the DENSE fit (args->keys == NULL, else RRL_E_ARG), one launch, double up to the final rounding: from the
+ * forward's args (a, b, w, counts, strides, eps_w, transpose_r, fit, info as it left them) and the upstream gR [B][9] (of the
+ * matrix as returned), gT [B][3] -- either may be NULL (zero) -- into ga [B][n][3], gb [B][n][3], gw [B][n] (each may be NULL;
+ * all rows are written).  With Gt = U^T (gR - abar^T gT) V and s' = (s0, s1, delta s2), d = (1, 1, delta):
+ *   gH = U Z V^T,  Z_ii = 0,  Z_ij = (Gt_ij - d_i d_j Gt_ji) / (s'_i + s'_j);
+ * then the routes through T, the centroids and wn (eps_w included).  The gradient does not exist where s'_i + s'_j = 0: a
+ * sample whose forward status is RRL_FIT_FEW or RRL_FIT_DEGENERATE gets ZERO gradient rows -- its forward info says why --,
+ * as do the rows beyond a count. */
+int rrl_kabsch_bwd(const rrl_kabsch_args *args, const float *gR, const float *gT, float *ga, float *gb, float *gw, void *stream);
+
+/* The pose step of point-to-point ICP for a batch, one launch, one wavefront per pair: from the fit (Rk [B][9], Tk [B][3],
+ * info, fit of rrl_kabsch_fwd on the source AS GIVEN, so that (Rk, Tk) is the total pose) and the current pose R [B][9],
+ * T [B][3].  state [B][4] int32 are rrl_se3_newton_step_batch's words: { epochs issued, calm epochs, done epoch or -1 (the
+ * caller writes -1 first), what this call did: the fit's status RRL_FIT_*, or RRL_ICP_DONE }.  Pair b, unless done, with
+ * status RRL_FIT_OK and a finite (Rk, Tk): in double, the rotation angle between R and Rk and the motion of the weighted
+ * source centroid |abar Rk + Tk - abar R - T| -> last_step [B][2]; (R, T) <- (Rk, Tk), bit for bit; the epoch is calm when
+ * both lie below tol_rot[b] / tol_trans[b], and after `patience` (> 0) calm epochs in a row the pair is done: from then on
+ * its pose is frozen.  Any other status keeps the pose and resets the calm count (a non-finite fit: RRL_FIT_DEGENERATE).
+ * The log row (res_after, value[b], status == RRL_FIT_OK) goes to table[cursor[b]][b] and row[b], cursor[b] += 1, as
+ * rrl_se3_adam_step_batch logs.  value, table, cursor, row, last_step, tol_rot / tol_trans (patience <= 0) may be NULL.
+ * RRL_E_ARG before the launch: B < 0, a NULL Rk / Tk / info / fit / R / T / state, patience > 0 without both tolerances. */
+#define RRL_ICP_DONE 3
+int rrl_icp_step_batch(const float *Rk, const float *Tk, const int32_t *info, const double *fit, float *R, float *T,
+                       const float *tol_rot, const float *tol_trans, int patience, const float *value, float *table,
+                       long long *cursor, long long nrows, float *row, float *last_step, int32_t *state, int B, void *stream);
+
+/* One ICP epoch for a batch of B pairs as ONE call: the existing entries back to back on the caller's stream, nothing else --
+ *   1. rrl_rigid_apply_fwd: moved = src R + T                                   (src [B][N][3], transpose_r = 0);
+ *   2. rrl_chamfer_tree_fwd_counted on (moved, tar, count1, count2) with the prepared orders -> best_x, best_y, values [B];
+ *   3. rrl_kabsch_fwd with a = src (as given, NOT moved), keys = best_x, b = tar, the counts, w, gate_sq -> Rk, Tk, fit, info;
+ *   4. rrl_icp_step_batch with value = values (the pair's Chamfer distance, which the walk's other half supplies).
+ * Fitting the source as given yields the total pose: nothing is composed, nothing drifts.  No host read-back.  Refusals, all
+ * before the first launch: RRL_E_ARG -- a NULL or wrongly sized struct, B <= 0 or > 32767, N or M <= 0 or beyond
+ * rrl_sort_capacity(), any NULL pointer among src, tar, R, T, moved, cham_ws, best_x, best_y, values, part, Rk, Tk, fit,
+ * info, state, exactly one count or one order, patience > 0 without both tolerances, a misaligned part or fit --, then
+ * RRL_E_WS: a short cham_ws or part. */
+typedef struct rrl_icp_epoch_args {
+    int32_t struct_bytes, B, N, M, patience, reserved;
+    const float *src, *tar; const int32_t *count1, *count2; float *R, *T, *moved;
+    void *cham_ws; size_t cham_ws_bytes; uint64_t *best_x, *best_y; float *values; const int32_t *order_x, *order_y;
+    const float *w, *gate_sq; double eps_w; float rank_tol, reserved_f;
+    void *part; size_t part_bytes; float *Rk, *Tk; double *fit; int32_t *info;
+    const float *tol_rot, *tol_trans; float *last_step; int32_t *state;
+    float *table; long long *cursor; long long table_rows; float *row;
+} rrl_icp_epoch_args;
+int rrl_icp_epoch(const rrl_icp_epoch_args *args, void *stream);
+
 /* ---- Chamfer monitor (code/loss.py:38-52, 236-252) -------------------------------------- */
 /* best_x [B][N], best_y [B][M] are u64 keys (dist bits << 32 | argmin), set to all-ones by
  * the call itself.  value[0] = mean of all B*(N+M) minima. */
