@@ -87,6 +87,8 @@ _SIGS = {
     "rrl_kabsch_bwd": [_P] * 7,
     "rrl_icp_step_batch": [_P] * 8 + [_I, _P, _P, _P, _c.c_longlong, _P, _P, _P, _I, _P],
     "rrl_icp_epoch": [_P, _P],
+    "rrl_sinkhorn_fwd": [_P, _P],
+    "rrl_sinkhorn_bwd": [_P] * 7,
     "rrl_rigid_apply_aabb": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "rrl_se3_exp": [_P, _P, _P, _I, _P],
     "rrl_se3_exp_bwd": [_P, _P, _P, _P, _I, _P],
@@ -102,7 +104,8 @@ _SIGS = {
 }
 EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamfer_workspace_bytes",
                                  "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes", "rrl_sort_capacity",
-                                 "rrl_knn3_self_workspace_bytes", "rrl_pose_normal_eq_part_bytes", "rrl_kabsch_part_bytes"])
+                                 "rrl_knn3_self_workspace_bytes", "rrl_pose_normal_eq_part_bytes", "rrl_kabsch_part_bytes",
+                                 "rrl_sinkhorn_workspace_bytes"])
 
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
 F_CHAIN = 2        # RRL_F_CHAIN: leave the hit counts / CHAIN words cleared for the next step on this workspace
@@ -195,6 +198,14 @@ class IcpEpochArgs(ctypes.Structure):
                 ("table", _P), ("cursor", _P), ("table_rows", _c.c_longlong), ("row", _P)]
 
 
+class SinkhornArgs(ctypes.Structure):
+    """include/rrl.h rrl_sinkhorn_args (same field order)."""
+    _fields_ = [("struct_bytes", _c.c_int32), ("B", _c.c_int32), ("J", _c.c_int32), ("K", _c.c_int32), ("n_iters", _c.c_int32),
+                ("slack", _c.c_int32), ("reserved0", _c.c_int32), ("reserved1", _c.c_int32),
+                ("log_alpha", _P), ("xyz_ref", _P), ("count_src", _P), ("count_ref", _P), ("eps", _c.c_double),
+                ("ws", _P), ("ws_bytes", _Z), ("W", _P), ("s", _P), ("c", _P), ("log_perm", _P), ("info", _P)]
+
+
 # rrl_kabsch_fwd's fit [B][32] doubles and info[b][1] (include/rrl.h RRL_FIT_*); rrl_icp_step_batch's state[b][3]
 FIT_W, FIT_ABAR, FIT_BBAR, FIT_U, FIT_S, FIT_V, FIT_DELTA, FIT_RES, FIT_KEYMEAN, FIT_DOUBLES = 0, 1, 4, 7, 16, 19, 28, 29, 30, 32
 FIT_OK, FIT_FEW, FIT_DEGENERATE, ICP_DONE = 0, 1, 2, 3
@@ -238,6 +249,8 @@ def load():
     lib.rrl_pose_normal_eq_part_bytes.restype = _Z
     lib.rrl_kabsch_part_bytes.argtypes = [_I, _I]
     lib.rrl_kabsch_part_bytes.restype = _Z
+    lib.rrl_sinkhorn_workspace_bytes.argtypes = [_I, _I, _I, _I]
+    lib.rrl_sinkhorn_workspace_bytes.restype = _Z
     lib.rrl_sort_capacity.argtypes = []
     lib.rrl_sort_capacity.restype = _I
     _lib = lib

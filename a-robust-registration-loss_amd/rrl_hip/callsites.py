@@ -373,3 +373,22 @@ def dcp_svd_head_pose(src, src_corr):
     (B, 3, n) -> (R (B, 3, 3), t (B, 3)) with R moving column vectors -- the head's per-sample torch.svd loop as one call."""
     from .kabsch import kabsch
     return kabsch(src.transpose(2, 1).contiguous(), src_corr.transpose(2, 1).contiguous(), None, eps=0.0, transpose_r=True)
+
+
+# ---- RPM's match head: Sinkhorn soft assignment in front of the solve above ----------------------------------------------
+def rpm_soft_correspondences(affinity, xyz_ref, n_iters=5, slack=True):
+    """rpm/models/rpmnet.py:211-222 up to the solve, as ONE node (rrl_hip.sinkhorn): affinity (B, J, K), xyz_ref (B, K, 3) ->
+    (weighted_ref (B, J, 3), src_weights (B, J), ref_weights (B, K)) with perm = exp(sinkhorn(affinity, n_iters, slack)),
+    weighted_ref = perm @ xyz_ref / (perm.sum(2, keepdim=True) + 1e-5), src_weights = perm.sum(2) -- the weights of the
+    solve -- and ref_weights = perm.sum(1); the two sums are what the trainer's outlier regulariser takes
+    (rpm/Train_RPM.py:237-240).  Differentiable in affinity and xyz_ref; perm itself is never stored."""
+    from .sinkhorn import soft_assign
+    return soft_assign(affinity, xyz_ref, n_iters=n_iters, slack=slack, eps=1e-5)
+
+
+def rpm_match_head(affinity, xyz_src, xyz_ref, n_iters=5, slack=True):
+    """The loop body of RPMNet.forward behind compute_affinity (rpmnet.py:211-222) as TWO nodes: rpm_soft_correspondences,
+    then rpm_compute_rigid_transform(xyz_src, weighted_ref, src_weights).  Returns (transform (B, 3, 4), weighted_ref,
+    src_weights, ref_weights)."""
+    weighted_ref, src_weights, ref_weights = rpm_soft_correspondences(affinity, xyz_ref, n_iters, slack)
+    return rpm_compute_rigid_transform(xyz_src, weighted_ref, src_weights), weighted_ref, src_weights, ref_weights

@@ -980,6 +980,51 @@ typedef struct rrl_icp_epoch_args {
 } rrl_icp_epoch_args;
 int rrl_icp_epoch(const rrl_icp_epoch_args *args, void *stream);
 
+/* ---- Sinkhorn soft assignment: RPM's match head in front of the Kabsch solve ---------------
+ * rpm/models/rpmnet.py:48-118 sinkhorn(log_alpha, n_iters, slack) and the lines 214-222 behind it, as a dual-potential
+ * iteration.  With A = log_alpha [B][J][K], x = xyz_ref [B][K][3], sigma = 1 with slack (the padded row and column, never
+ * normalised themselves) and 0 without, u^0 = v^0 = 0 and for t = 0 .. n_iters - 1
+ *   u^{t+1}[j] = log(sum_k exp(A[j][k] - v^t[k]) + sigma),   v^{t+1}[k] = log(sum_j exp(A[j][k] - u^{t+1}[j]) + sigma):
+ *   P = exp(A - u^n - v^n) = exp(sinkhorn(A)),   s[j] = sum_k P,   c[k] = sum_j P,   W[j] = sum_k P x[k] / (s[j] + eps).
+ * P is never stored; log_perm [B][J][K] (optional) receives A - u^n - v^n, rounded once, in the output pass.
+ * Ragged: count_src / count_ref, device int32 [B] or NULL, clamped to [0, J] / [0, K] by the kernels, never read on the
+ * host: rows and columns at or beyond them are never read, get s = 0, W = 0, c = 0 (log_perm -inf) and a zero gradient.
+ * Arithmetic: potentials, adjoint vectors and every sum are DOUBLE; a matrix term is the exponential of the double
+ * double(A) - u - v, evaluated in double to 2^-36, so nothing is rounded to float32 before the results are; logsumexp runs
+ * under a running maximum; lanes, wavefronts and the ceil(J / 128) row slices of a column sum are combined in a fixed
+ * order, without atomics: the same bits on every call, and sample b of a batch has the bits of a B = 1 call on its own
+ * rows and columns.
+ * Non-finite entries: -inf is an entry with P = 0 and gradient 0 (without slack, a row or column of nothing but -inf has no
+ * normalisation: its outputs are not finite).  A NaN or +inf entry inside the counts sets info[b] = 1 (else 0); the outputs
+ * of that sample are then NaN or inf wherever the entry reaches; nothing is indexed by data.
+ * Launches (all on `stream`, no host read-back, capturable): forward 3 n_iters + 2 (a memset of info, per iteration a row
+ * pass, a column pass and its finish, then the output row pass; c comes out of the last finish; n_iters = 0: 4); backward
+ * 3 n_iters + 2 (n_iters = 0: 4).
+ * ws: rrl_sinkhorn_workspace_bytes(B, J, K, n_iters) bytes, 8-byte aligned: the potential history, (n_iters + 1) (J + K)
+ * doubles per sample, which the backward reads, the same for the adjoints, s and N in double, and the column partials.  The
+ * backward takes the forward's args with ws as the forward left it.
+ * Refusals, on the host before any HIP call: RRL_E_ARG -- a NULL args / log_alpha / xyz_ref / ws / W / s / c / info (backward:
+ * g_log_alpha), struct_bytes != sizeof, B < 1 or > 32767, J or K < 1 or > 16384, n_iters < 0 or > 64, a misaligned ws --,
+ * then RRL_E_WS: ws_bytes below the size above (which is 0 for a shape that is refused). */
+typedef struct rrl_sinkhorn_args {
+    int32_t struct_bytes, B, J, K, n_iters, slack, reserved0, reserved1;
+    const float *log_alpha, *xyz_ref; const int32_t *count_src, *count_ref;
+    double eps;
+    void *ws; size_t ws_bytes;
+    float *W, *s, *c, *log_perm; int32_t *info;
+} rrl_sinkhorn_args;
+size_t rrl_sinkhorn_workspace_bytes(int B, int J, int K, int n_iters);
+int rrl_sinkhorn_fwd(const rrl_sinkhorn_args *args, void *stream);
+/* Backward: from upstream gW [B][J][3], gs [B][J], gc [B][K] (each may be NULL: zero) into g_log_alpha [B][J][K] (every
+ * entry written) and g_xyz_ref [B][K][3] (may be NULL; the route through W only).  With gN = gW / (s + eps),
+ * gs' = gs - (gW . W) / (s + eps) and G[j][k] = gs'[j] + gc[k] + gN[j] . x[k] (rank 5, never stored):
+ *   gx[k] = sum_j P gN[j],   ubar^n[j] = -sum_k P G,   vbar^n[k] = -sum_j P G;   for t = n - 1 .. 0, with
+ *   Q = exp(A - u^{t+1} - v^{t+1}) and S = exp(A - u^{t+1} - v^t):   ubar^{t+1}[j] -= sum_k vbar^{t+1}[k] Q,
+ *   vbar^t[k] = -sum_j ubar^{t+1}[j] S (ubar^t starts from 0);   dA = P G + sum_t (vbar^{t+1}[k] Q + ubar^{t+1}[j] S),
+ * 2 n matrix-vector passes that leave vectors only, and one assembly pass: one read of A, one write of dA. */
+int rrl_sinkhorn_bwd(const rrl_sinkhorn_args *args, const float *gW, const float *gs, const float *gc, float *g_log_alpha,
+                     float *g_xyz_ref, void *stream);
+
 /* ---- Chamfer monitor (code/loss.py:38-52, 236-252) -------------------------------------- */
 /* best_x [B][N], best_y [B][M] are u64 keys (dist bits << 32 | argmin), set to all-ones by
  * the call itself.  value[0] = mean of all B*(N+M) minima. */
