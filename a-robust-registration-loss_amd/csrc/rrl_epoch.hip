@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include "rrl_ws.h"
+#include "rrl_pose_tail.h"  // (pose_stop_args_ok: the stopping rule's refusal)
 
 extern "C" int rrl_demo_epoch(const rrl_demo_epoch_args *a, void *stream) {
     if (!a || a->struct_bytes < (int32_t)offsetof(rrl_demo_epoch_args, pipeline)) return RRL_E_ARG;  // (pipeline: appended in round 4b)
@@ -168,7 +169,7 @@ extern "C" int rrl_register_newton_epoch(const rrl_register_newton_args *a, void
     RrlCall o = rrl_begin_call(a->opts, a->B, a->N, a->M, a->L, a->ws, a->ws_bytes, stream);
     if (!epoch_record_ok(a, o)) return RRL_E_ARG;
     if (!a->box1 || !a->neq || !a->part || (((uintptr_t)a->part) & 7) != 0 || !a->state || !a->damping || !a->step || !a->max_rot ||
-        !a->max_trans || !(a->eps >= 0.0) || (a->patience > 0 && (!a->tol_rot || !a->tol_trans)))
+        !a->max_trans || !(a->eps >= 0.0) || !pose_stop_args_ok(a->patience, a->tol_rot, a->tol_trans))
         return RRL_E_ARG;
     epoch_own_launches(o);
     const RrlXform xf = {a->src_tri, a->R, a->T, 0, 1};

@@ -483,7 +483,8 @@ extern "C" int rrl_kabsch_bwd(const rrl_kabsch_args *p, const float *gR, const f
 }
 
 // ---------------------------------------------------------------------------------------
-// The ICP pose step: one wavefront per pair, lane 0 works (se3_newton_step_kernel's shape and state words).
+// The ICP pose step: one wavefront per pair, lane 0 works (se3_newton_step_kernel's shape; the state words and the stopping
+// rule are rrl_pose_tail.h's PoseStop, [3] = the fit's status or RRL_ICP_DONE).
 // ---------------------------------------------------------------------------------------
 struct IcpStepArgs {
     const float *Rk, *Tk;
@@ -509,10 +510,9 @@ __global__ __launch_bounds__(64) void icp_step_kernel(const IcpStepArgs a) {
     const int fstat = a.info[s * 4 + 1];
     PoseLog plog = {-1, (float)fit[RRL_FIT_RES], a.value ? a.value[s] : 0.0f};
     if (a.table && a.cursor) plog.at = a.cursor[s];
-    const int epochs = st[0] + 1, done_at = st[2];
-    const bool done = done_at >= 0;
-    int status = done ? RRL_ICP_DONE : fstat, calm = done ? st[1] : 0, done_new = done_at;
-    if (!done && fstat == RRL_FIT_OK) {
+    PoseStop stop = pose_stop_load(st);
+    int status = stop.done ? RRL_ICP_DONE : fstat;
+    if (!stop.done && fstat == RRL_FIT_OK) {
         double Rk[3][3], Ro[3][3], Tk[3], To[3], ab[3];
         bool finite = true;
 #pragma unroll
@@ -553,20 +553,10 @@ __global__ __launch_bounds__(64) void icp_step_kernel(const IcpStepArgs a) {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) a.R[s * 9 + 3 * i + j] = a.Rk[s * 9 + 3 * i + j];
             }
-            if (a.last_step) {
-                a.last_step[s * 2] = (float)ang;
-                a.last_step[s * 2 + 1] = (float)mv;
-            }
-            if (a.patience > 0 && a.tol_rot && a.tol_trans) {
-                calm = ((float)ang < a.tol_rot[s] && (float)mv < a.tol_trans[s]) ? st[1] + 1 : 0;
-                if (calm >= a.patience) done_new = epochs;
-            }
+            pose_stop_update(stop, s, (float)ang, (float)mv, a.last_step, a.tol_rot, a.tol_trans, a.patience);
         }
     }
-    st[0] = epochs;
-    st[1] = calm;
-    st[2] = done_new;
-    st[3] = status;
+    pose_stop_store(stop, status, st);
     pose_log_store(plog, fstat == RRL_FIT_OK, a.table ? a.table + s * 3 : nullptr, 3ll * a.B, a.nrows, a.cursor ? a.cursor + s : nullptr,
                    a.row ? a.row + s * 3 : nullptr);
 }
@@ -576,7 +566,7 @@ extern "C" int rrl_icp_step_batch(const float *Rk, const float *Tk, const int32_
                                   long long *cursor, long long nrows, float *row, float *last_step, int32_t *state, int B,
                                   void *stream) {
     if (B < 0 || !Rk || !Tk || !info || !fit || !R || !T || !state) return RRL_E_ARG;
-    if (patience > 0 && (!tol_rot || !tol_trans)) return RRL_E_ARG;
+    if (!pose_stop_args_ok(patience, tol_rot, tol_trans)) return RRL_E_ARG;
     if (B == 0) return 0;
     const IcpStepArgs a = {Rk, Tk, info, fit, R, T, tol_rot, tol_trans, patience, value, table, cursor, nrows, row, last_step, state, B};
     hipLaunchKernelGGL(icp_step_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, a);
@@ -593,7 +583,7 @@ extern "C" int rrl_icp_epoch(const rrl_icp_epoch_args *a, void *stream) {
         !a->Rk || !a->Tk || !a->fit || !a->info || !a->state)
         return RRL_E_ARG;
     if ((a->count1 == nullptr) != (a->count2 == nullptr) || (a->order_x == nullptr) != (a->order_y == nullptr)) return RRL_E_ARG;
-    if (a->patience > 0 && (!a->tol_rot || !a->tol_trans)) return RRL_E_ARG;
+    if (!pose_stop_args_ok(a->patience, a->tol_rot, a->tol_trans)) return RRL_E_ARG;
     if ((((uintptr_t)a->part) & 7) != 0 || (((uintptr_t)a->fit) & 7) != 0) return RRL_E_ARG;
     if (a->cham_ws_bytes < rrl_chamfer_workspace_bytes(B, N, M) || a->part_bytes < rrl_kabsch_part_bytes(B, N)) return RRL_E_WS;
     int rc = rrl_rigid_apply_fwd(a->src, a->R, a->T, a->moved, B, N, 0, 0, stream);

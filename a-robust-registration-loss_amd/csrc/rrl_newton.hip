@@ -219,8 +219,7 @@ extern "C" int rrl_pose_normal_eq(const void *ws, size_t ws_bytes, int B, int N,
 // reduce the next sampler box from the step's partial rows and lane 0 logs (rrl_pose_tail.h); lane 0 does the pose: H (6 x 6) and g from the
 // sixteen sums, H + damping diag(H) + eps I, Cholesky and both substitutions in double, step scale, clamps, the exact
 // Rodrigues rotation, R <- R Rot^T, T <- T Rot^T + v, one Gram-Schmidt pass over R's rows, the log row, the stopping rule.
-// state [B][4] int32: [0] epochs issued, [1] consecutive calm epochs, [2] the epoch count at which the pair was declared
-// done (-1: not yet), [3] what this call did (RRL_NEWTON_*).
+// state [B][4] int32: the pose-step state words and their rule, rrl_pose_tail.h (PoseStop); [3] = RRL_NEWTON_*.
 // ---------------------------------------------------------------------------------------
 struct NewtonArgs {
     const float *neq;
@@ -291,18 +290,15 @@ __global__ __launch_bounds__(64) void se3_newton_step_kernel(const NewtonArgs a)
     const size_t s = (size_t)b;
     int32_t *__restrict__ st = a.state + s * 4;
     const int raw = a.gate ? a.gate[(long long)b * a.gate_stride] : 1;
-    const int epochs = st[0] + 1, done_at = st[2];
-    const bool done = done_at >= 0;        // a done pair's gate is treated as closed: its pose is frozen
-    const bool open = raw > 0 && !done;
+    PoseStop stop = pose_stop_load(st);
+    const bool open = raw > 0 && !stop.done;  // a done pair's gate is treated as closed: its pose is frozen
     // the shared tail on sample b's slices: column b of the table [nrows][B][3], [0, ceil(count1[b] / 256)) of its partial rows
     const PoseLog plog = pose_log_load(k, a.table ? a.table + s * 3 : nullptr, a.cursor ? a.cursor + s : nullptr,
                                        a.loss ? a.loss + s : nullptr, a.value ? a.value + s : nullptr);
     pose_next_box(k, a.box ? a.box + s * 6 : nullptr, a.aabb_rows + (long long)b * a.row_stride,
                   (rrl_rows(a.count1, b, a.N) + 255) / 256);
     if (k != 0) return;
-    int status = done ? RRL_NEWTON_DONE : (raw > 0 ? RRL_NEWTON_STEPPED : RRL_NEWTON_GATED);
-    int calm = done ? st[1] : 0;
-    int done_new = done_at;
+    int status = stop.done ? RRL_NEWTON_DONE : (raw > 0 ? RRL_NEWTON_STEPPED : RRL_NEWTON_GATED);
     if (open) {
         double S[NEQ_SUMS];
 #pragma unroll
@@ -407,22 +403,11 @@ __global__ __launch_bounds__(64) void se3_newton_step_kernel(const NewtonArgs a)
 #pragma unroll
                     for (int j = 0; j < 3; ++j) a.R[s * 9 + 3 * i + j] = (float)Rn[i][j];
                 }
-                if (a.last_step) {
-                    a.last_step[s * 2] = (float)nw;
-                    a.last_step[s * 2 + 1] = (float)nv;
-                }
-                // the stopping rule: `patience` consecutive epochs whose step stayed below both tolerances
-                if (a.patience > 0 && a.tol_rot && a.tol_trans) {
-                    calm = ((float)nw < a.tol_rot[s] && (float)nv < a.tol_trans[s]) ? st[1] + 1 : 0;
-                    if (calm >= a.patience) done_new = epochs;
-                }
+                pose_stop_update(stop, s, (float)nw, (float)nv, a.last_step, a.tol_rot, a.tol_trans, a.patience);
             }
         }
     }
-    st[0] = epochs;
-    st[1] = calm;
-    st[2] = done_new;
-    st[3] = status;
+    pose_stop_store(stop, status, st);
     pose_log_store(plog, raw > 0, a.table ? a.table + s * 3 : nullptr, 3ll * a.B, a.nrows, a.cursor ? a.cursor + s : nullptr,
                    a.row ? a.row + s * 3 : nullptr);
 }
@@ -435,7 +420,7 @@ extern "C" int rrl_se3_newton_step_batch(const float *neq, const int32_t *gate, 
                                          float *delta, float *last_step, int32_t *state, int B, void *stream) {
     if (B < 0 || !neq || !damping || !step || !max_rot || !max_trans || !R || !T || !state) return RRL_E_ARG;
     if (gate && gate_stride < 0) return RRL_E_ARG;
-    if (!(eps >= 0.0) || (patience > 0 && (!tol_rot || !tol_trans))) return RRL_E_ARG;
+    if (!(eps >= 0.0) || !pose_stop_args_ok(patience, tol_rot, tol_trans)) return RRL_E_ARG;
     if (box && (!aabb_rows || N <= 0 || row_stride < 8ll * ((N + 255) / 256))) return RRL_E_ARG;
     if (B == 0) return 0;
     const NewtonArgs a = {neq, gate, gate_stride, damping, step, max_rot, max_trans, tol_rot, tol_trans, patience, eps, R, T, loss,

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib, ops
 from .kabsch import RANK_TOL
+from .register import PoseLoop, StoppingLoop
 
 # The defaults of the stopping rule, from tools/icp_timing.py (profiles/icp_timing.json: eight make_pair pairs at 20 degrees,
 # N = M = 1024).  An ICP pose changes only when a nearest neighbour changes: in that run every step that still moved a pair
@@ -44,7 +45,7 @@ def check_request(src_shape, tar_shape, capacity, max_dist=None, patience=PATIEN
         raise ValueError("patience must be non-negative (0 turns the stopping rule off)")
 
 
-class IcpRegistration:
+class IcpRegistration(StoppingLoop, PoseLoop):
     """B pairs src (B, N, 3 or 9) / tar (B, M, 3 or 9); N, M are capacities when counts1 / counts2 are given (both, or one:
     the other is then full).  R0 (B, 3, 3) with T0 (B, 3), or xi0 (B, 6): starting poses (default: the identity); the poses
     move x -> x R + T.  max_dist: partners farther than this fraction of the target box's diagonal get weight 0 (None: no
@@ -53,14 +54,16 @@ class IcpRegistration:
 
     .R, .T: the poses.  .done_epoch (B,) int32 (-1: not yet), .failed (B,) int32: what the latest epoch did -- 0 stepped, 1
     fewer than 3 pairs, 2 degenerate pairs (pose kept in both), 3 done.  .last_step (B, 2): (angle, centroid motion) of the
-    latest step.  .value (B,): each pair's Chamfer distance before the latest step.  All device tensors."""
+    latest step.  .value (B,): each pair's Chamfer distance before the latest step.  All device tensors.
+    .history(): PairRegistration's row format -- (epoch, the fit's mean squared residual, the pair's Chamfer distance)."""
+
+    _ARGS, _ENTRY = _lib.IcpEpochArgs, "rrl_icp_epoch"  # .epoch(): ONE C call
 
     def __init__(self, src, tar, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, max_dist=None, tol_rot=TOL_ROT,
                  tol_trans=TOL_TRANS, patience=PATIENCE, table_rows=4096):
         if not isinstance(src, torch.Tensor) or not isinstance(tar, torch.Tensor):
             raise TypeError("src / tar must be torch.Tensors")
-        if (R0 is None) != (T0 is None) or (R0 is not None and xi0 is not None):
-            raise ValueError("starting poses: R0 and T0 together, or xi0, not both")
+        self._check_start(R0, T0, xi0)
         if int(table_rows) < 0:
             raise ValueError("table_rows must be non-negative")
         check_request(tuple(src.shape), tuple(tar.shape), ops.sort_capacity(), max_dist, patience)
@@ -86,21 +89,9 @@ class IcpRegistration:
         self.order_x, self.order_y = order(self.src, s, self.counts1), order(self.tar, t, self.counts2)
         self.box2 = ops.aabb(self.tar, self.counts2)
         self.radius = (self.box2[:, 3:] - self.box2[:, :3]).norm(p=2, dim=1).contiguous()
-        self.R, self.T = torch.empty(B, 3, 3, **f32), torch.empty(B, 3, **f32)
-        if R0 is not None:
-            self.R.copy_(ops._prep(R0, "R0", 3, dev).reshape(B, 3, 3))
-            self.T.copy_(ops._prep(T0, "T0", 3, dev).reshape(B, 3))
-        else:
-            xi = torch.zeros(B, 6, **f32) if xi0 is None else ops._prep(xi0, "xi0", 6, dev).reshape(B, 6)
-            ops._run(dev, "rrl_se3_exp", ops._p(xi), ops._p(self.R), ops._p(self.T), B)
-
-        def per_pair(x, scale=None):
-            v = x.detach().to(**f32) if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=torch.float32).to(dev)
-            v = v.reshape(-1).expand(B).clone()
-            return (v * scale if scale is not None else v).contiguous()
-        self.tol_rot, self.tol_trans = per_pair(tol_rot), per_pair(tol_trans, self.radius)
-        self.patience = int(patience)
-        self.gate_sq = (per_pair(max_dist, self.radius) ** 2).contiguous() if max_dist is not None else None
+        self._start_poses(R0, T0, xi0)
+        self._init_stop(tol_rot, tol_trans, patience)
+        self.gate_sq = (self._per_pair(max_dist, self.radius) ** 2).contiguous() if max_dist is not None else None
         lib = _lib.load()
         self.moved = torch.empty(B, N, 3, **f32)
         self.cham_ws = torch.empty(int(lib.rrl_chamfer_workspace_bytes(B, N, M)), dtype=torch.uint8, device=dev)
@@ -111,22 +102,14 @@ class IcpRegistration:
         self.Rk, self.Tk = torch.zeros(B, 3, 3, **f32), torch.zeros(B, 3, **f32)
         self.fit = torch.zeros(B, _lib.FIT_DOUBLES, dtype=torch.float64, device=dev)
         self.info = torch.zeros(B, 4, dtype=torch.int32, device=dev)
-        self.last_step = torch.zeros(B, 2, **f32)
-        self.state = torch.zeros(B, 4, dtype=torch.int32, device=dev)
-        self.state[:, 2] = -1
-        self.table = torch.zeros(int(table_rows), B, 3, **f32)
-        self.cursor = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.row = torch.zeros(B, 3, **f32)
-        self.epochs = 0
-        self._args = self._make_args()
-        self._aref = ctypes.byref(self._args)
-        self._call = lib.rrl_icp_epoch
+        self._init_log(table_rows)
+        self._bind()
 
     def _make_args(self):
         P = ops._p
-        a = _lib.IcpEpochArgs()
+        a = self._ARGS()
         a.struct_bytes = ctypes.sizeof(a)
-        a.B, a.N, a.M, a.patience = self.B, self.N, self.M, self.patience
+        a.B, a.N, a.M = self.B, self.N, self.M
         a.src, a.tar, a.count1, a.count2 = P(self.src), P(self.tar), P(self.counts1), P(self.counts2)
         a.R, a.T, a.moved = P(self.R), P(self.T), P(self.moved)
         a.cham_ws, a.cham_ws_bytes, a.best_x, a.best_y, a.values = P(self.cham_ws), self.cham_ws.numel(), P(self.best_x), P(self.best_y), P(self.value)
@@ -134,44 +117,9 @@ class IcpRegistration:
         a.w, a.gate_sq, a.eps_w, a.rank_tol = None, P(self.gate_sq), 0.0, RANK_TOL
         a.part, a.part_bytes = P(self.part), self.part.numel() * 8
         a.Rk, a.Tk, a.fit, a.info = P(self.Rk), P(self.Tk), P(self.fit), P(self.info)
-        a.tol_rot, a.tol_trans, a.last_step, a.state = P(self.tol_rot), P(self.tol_trans), P(self.last_step), P(self.state)
-        a.table, a.cursor, a.table_rows, a.row = P(self.table), P(self.cursor), self.table.shape[0], P(self.row)
+        self._stop_args(a)
+        self._log_args(a)
         return a
-
-    def epoch(self):
-        """One epoch of all B pairs: ONE C call (rrl_icp_epoch), nothing read back."""
-        with ops._guard(self.dev):
-            _lib.check(self._call(self._aref, ops._stream(self.dev)), "rrl_icp_epoch")
-        self.epochs += 1
-
-    def run(self, n_epoch, check_every=0):
-        """Up to n_epoch epochs.  check_every = k > 0: .done_epoch is read once every k epochs and the loop returns early when
-        every pair is done -- the only synchronisation, and only on request."""
-        k = int(check_every)
-        for i in range(int(n_epoch)):
-            self.epoch()
-            if k > 0 and (i + 1) % k == 0 and bool((self.done_epoch >= 0).all()):
-                break
-        return self
-
-    @property
-    def done_epoch(self):
-        return self.state[:, 2]
-
-    @property
-    def failed(self):
-        return self.state[:, 3]
-
-    def history(self):
-        """[per pair][(epoch, residual or None, value or None)] of the logged epochs, PairRegistration's row format: the
-        fit's mean squared residual and the pair's Chamfer distance; an epoch whose fit failed: (e, None, None)."""
-        n = min(self.epochs, self.table.shape[0])
-        rows = self.table[:n].cpu().tolist()
-        out = [[] for _ in range(self.B)]
-        for e, per in enumerate(rows):
-            for b, (res, cf, ok) in enumerate(per):
-                out[b].append((e, res, cf) if ok else (e, None, None))
-        return out
 
     def moved_points(self):
         """(B, N, 3): the source points under the CURRENT pose (one rigid apply; rows beyond a count are not meaningful)."""

@@ -14,7 +14,7 @@ device (`patience` consecutive epochs below tol_rot / tol_trans).  Nothing is re
 import torch
 
 from . import _lib, ops
-from .register import PairRegistration
+from .register import PairRegistration, StoppingLoop
 
 # The defaults, from the sweep of tools/register_newton_sweep.py (profiles/register_newton_sweep.json)
 DAMPING = 1e-2     # Levenberg-Marquardt: H + damping diag(H)
@@ -28,7 +28,7 @@ PATIENCE = 3       # calm epochs in a row that end a pair
 EPS = 1e-12        # H + eps I: a pivot that does not exceed it fails the step
 
 
-class NewtonRegistration(PairRegistration):
+class NewtonRegistration(StoppingLoop, PairRegistration):
     """PairRegistration's constructor contract, sampler geometry, .history(), .moved_points(), .loss, .R, .T -- with
     Gauss-Newton steps in place of Adam on se(3).
 
@@ -45,8 +45,7 @@ class NewtonRegistration(PairRegistration):
     def __init__(self, src_tri, tar_tri, n_lines, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, damping=DAMPING,
                  step=STEP, max_rot=MAX_ROT, max_trans=MAX_TRANS, tol_rot=TOL_ROT, tol_trans=TOL_TRANS, patience=PATIENCE,
                  eps=EPS, rounds=10, seed=None, lines=None, monitor=False, table_rows=4096):
-        if (R0 is None) != (T0 is None) or (R0 is not None and xi0 is not None):
-            raise ValueError("starting poses: R0 and T0 together, or xi0, not both")
+        self._check_start(R0, T0, xi0)
         if int(patience) < 0 or not float(eps) >= 0.0:
             raise ValueError("patience and eps must be non-negative")
         pose = dict(R0=R0, T0=T0, xi0=xi0, damping=damping, step=step, max_rot=max_rot, max_trans=max_trans, tol_rot=tol_rot,
@@ -57,36 +56,24 @@ class NewtonRegistration(PairRegistration):
     def _init_pose_side(self, R0, T0, xi0, damping, step, max_rot, max_trans, tol_rot, tol_trans, patience, eps):
         """The second-order state: (R, T) as given or exp(xi0), the controls one per pair, the normal equations with their
         scratch, the step's outputs and the stopping rule's state."""
-        dev, B = self.dev, self.B
+        dev, B, per_pair = self.dev, self.B, self._per_pair
         f32 = dict(dtype=torch.float32, device=dev)
-        if R0 is not None:
-            self.R.copy_(ops._prep(R0, "R0", 3, dev).reshape(B, 3, 3))
-            self.T.copy_(ops._prep(T0, "T0", 3, dev).reshape(B, 3))
-        else:
-            self._pose_from_xi(torch.zeros(B, 6, **f32) if xi0 is None else ops._prep(xi0, "xi0", 6, dev).reshape(B, 6))
-
-        def per_pair(x, scale=None):
-            t = torch.as_tensor(x, dtype=torch.float32).to(dev).reshape(-1).expand(B).clone() if not isinstance(x, torch.Tensor) \
-                else x.detach().to(**f32).reshape(-1).expand(B).clone()
-            return (t * scale if scale is not None else t).contiguous()
+        self._start_poses(R0, T0, xi0)
         self.damping, self.step_scale = per_pair(damping), per_pair(step)
         self.max_rot, self.max_trans = per_pair(max_rot), per_pair(max_trans, self.radius)
-        self.tol_rot, self.tol_trans = per_pair(tol_rot), per_pair(tol_trans, self.radius)
-        self.patience, self.eps = int(patience), float(eps)
+        self._init_stop(tol_rot, tol_trans, patience)
+        self.eps = float(eps)
         self.neq = torch.zeros(B, 16, **f32)
         self.part = ops.pose_normal_eq_part(B, self.step.dims[3], dev)
         self.delta = torch.zeros(B, 6, **f32)
-        self.last_step = torch.zeros(B, 2, **f32)
-        self.state = torch.zeros(B, 4, dtype=torch.int32, device=dev)
-        self.state[:, 2] = -1
 
     def _pose_args(self, a):
         P = ops._p
-        a.patience, a.eps = self.patience, self.eps
+        self._stop_args(a)
+        a.eps = self.eps
         a.neq, a.part, a.part_bytes = P(self.neq), P(self.part), self.part.numel() * 8
         a.damping, a.step, a.max_rot, a.max_trans = P(self.damping), P(self.step_scale), P(self.max_rot), P(self.max_trans)
-        a.tol_rot, a.tol_trans = P(self.tol_rot), P(self.tol_trans)
-        a.delta, a.last_step, a.state = P(self.delta), P(self.last_step), P(self.state)
+        a.delta = P(self.delta)
 
     def set_lr(self, lr):
         raise AttributeError("NewtonRegistration has no learning rate: see damping / step")
@@ -94,24 +81,6 @@ class NewtonRegistration(PairRegistration):
     def epoch(self):
         """One epoch of all B pairs: ONE C call (rrl_register_newton_epoch), nothing read back."""
         super().epoch()
-
-    def run(self, n_epoch, check_every=0):
-        """Up to n_epoch epochs.  check_every = k > 0: .done_epoch is read once every k epochs and the loop returns early when
-        every pair is done -- the only synchronisation, and only on request."""
-        k = int(check_every)
-        for i in range(int(n_epoch)):
-            self.epoch()
-            if k > 0 and (i + 1) % k == 0 and bool((self.done_epoch >= 0).all()):
-                break
-        return self
-
-    @property
-    def done_epoch(self):
-        return self.state[:, 2]
-
-    @property
-    def failed(self):
-        return self.state[:, 3]
 
     def xi(self):
         """(B, 6) on the host: LieAlgebra.se3.log of the current poses (rrl_se3_exp of it gives R, T back), on request."""

@@ -2005,6 +2005,17 @@ def se3_adam_step(xi, gR, gT, m, v, state, lr, gate, R, T, *, gxi=None, loss=Non
          _p(cursor), nrows, _p(row), _p(aabb_rows), 0 if aabb_rows is None else int(aabb_rows.shape[0]), _p(box))
 
 
+def _box_args(B, table, aabb_rows, row_stride, capacity):
+    """(nrows, row_stride, N) of a batched pose step: the log table's rows, the floats between two samples' box rows (default:
+    the rows' own) and the capacity whose ceil(N / 256) rows a sample without a count reads (default: 256 * rows)."""
+    nrows = 0 if table is None else table.shape[0]
+    if aabb_rows is None:
+        return nrows, int(row_stride or 0), 0
+    if row_stride is None:
+        row_stride = aabb_rows.stride(0) if aabb_rows.dim() == 3 else aabb_rows.numel() // max(B, 1)
+    return nrows, int(row_stride or 0), int(capacity) if capacity is not None else 256 * int(aabb_rows.shape[-2])
+
+
 def se3_adam_step_batch(xi, gR, gT, m, v, state, lr, gate, R, T, *, gate_stride=1, gxi=None, loss=None, value=None,
                         table=None, cursor=None, row=None, betas=(0.9, 0.999), eps=1e-8, aabb_rows=None, row_stride=None,
                         counts=None, capacity=None, box=None):
@@ -2015,15 +2026,10 @@ def se3_adam_step_batch(xi, gR, gT, m, v, state, lr, gate, R, T, *, gate_stride=
     (B,) on the GPU, or None: ceil(capacity / 256) rows; capacity defaults to 256 * rows) -- a loss state's `apart[0]` with
     capacity = N gives every moved source's box; row_stride (floats) defaults to the rows' own."""
     B = xi.shape[0]
-    nrows = 0 if table is None else table.shape[0]
-    N = 0
-    if aabb_rows is not None:
-        if row_stride is None:
-            row_stride = aabb_rows.stride(0) if aabb_rows.dim() == 3 else aabb_rows.numel() // max(B, 1)
-        N = int(capacity) if capacity is not None else 256 * int(aabb_rows.shape[-2])
+    nrows, row_stride, N = _box_args(B, table, aabb_rows, row_stride, capacity)
     _run(xi.device, "rrl_se3_adam_step_batch", _p(xi), _p(gR), _p(gT), _p(m), _p(v), _p(state), _p(lr), _p(gate),
          int(gate_stride), float(betas[0]), float(betas[1]), float(eps), _p(R), _p(T), _p(gxi), _p(loss), _p(value), _p(table),
-         _p(cursor), nrows, _p(row), _p(aabb_rows), int(row_stride or 0), _p(counts), N, _p(box), B)
+         _p(cursor), nrows, _p(row), _p(aabb_rows), row_stride, _p(counts), N, _p(box), B)
 
 
 def pose_normal_eq_part(B, L, dev):
@@ -2056,16 +2062,10 @@ def se3_newton_step_batch(neq, gate, R, T, state, *, damping, step, max_rot, max
     gate, the log (loss, value, table, cursor, row) and the box (aabb_rows, row_stride, counts, capacity, box) are
     se3_adam_step_batch's."""
     B = R.shape[0]
-    nrows = 0 if table is None else table.shape[0]
-    N = 0
-    if aabb_rows is not None:
-        if row_stride is None:
-            row_stride = aabb_rows.stride(0) if aabb_rows.dim() == 3 else aabb_rows.numel() // max(B, 1)
-        N = int(capacity) if capacity is not None else 256 * int(aabb_rows.shape[-2])
+    nrows, row_stride, N = _box_args(B, table, aabb_rows, row_stride, capacity)
     _run(R.device, "rrl_se3_newton_step_batch", _p(neq), _p(gate), int(gate_stride), _p(damping), _p(step), _p(max_rot),
          _p(max_trans), _p(tol_rot), _p(tol_trans), int(patience), float(eps), _p(R), _p(T), _p(loss), _p(value), _p(table),
-         _p(cursor), nrows, _p(row), _p(aabb_rows), int(row_stride or 0), _p(counts), N, _p(box), _p(delta), _p(last_step),
-         _p(state), B)
+         _p(cursor), nrows, _p(row), _p(aabb_rows), row_stride, _p(counts), N, _p(box), _p(delta), _p(last_step), _p(state), B)
 
 
 def log_row(loss, value, info, table, cursor, row=None):

@@ -36,7 +36,112 @@ def check_request(N, M, ragged, monitor, capacity):
                          "counts_y=counts2, per_sample=True) instead")
 
 
-class PairRegistration:
+class PoseLoop:
+    """What every batched pose loop is made of besides its own epoch: per-pair controls, starting poses, the log table with
+    .history(), and the one C call per epoch (the struct _ARGS filled by the subclass's _make_args, passed to _ENTRY).  The
+    subclass sets .dev and .B first."""
+
+    _ARGS = _ENTRY = None
+    monitor = True  # the log's value column is reported by .history() (the loss loops: only when they were asked to monitor)
+
+    def _per_pair(self, x, scale=None):
+        """A number or a tensor -> contiguous float32 (B,), times `scale` (B,) where one is given (the sampler radius)."""
+        t = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=torch.float32)
+        t = t.to(dtype=torch.float32, device=self.dev).reshape(-1).expand(self.B).clone()
+        return (t * scale if scale is not None else t).contiguous()
+
+    @staticmethod
+    def _check_start(R0, T0, xi0):
+        if (R0 is None) != (T0 is None) or (R0 is not None and xi0 is not None):
+            raise ValueError("starting poses: R0 and T0 together, or xi0, not both")
+
+    def _pose_from_xi(self, xi):
+        """(R, T) = exp(xi), per pair."""
+        ops._run(self.dev, "rrl_se3_exp", ops._p(xi), ops._p(self.R), ops._p(self.T), self.B)
+
+    def _start_poses(self, R0=None, T0=None, xi0=None):
+        """.R (B, 3, 3), .T (B, 3): R0 and T0 as given, else exp(xi0) (default: the identity); returns the xi used, or None."""
+        B, dev, f32 = self.B, self.dev, dict(dtype=torch.float32, device=self.dev)
+        self.R, self.T = torch.empty(B, 3, 3, **f32), torch.empty(B, 3, **f32)
+        if R0 is not None:
+            self.R.copy_(ops._prep(R0, "R0", 3, dev).reshape(B, 3, 3))
+            self.T.copy_(ops._prep(T0, "T0", 3, dev).reshape(B, 3))
+            return None
+        xi = torch.zeros(B, 6, **f32) if xi0 is None else ops._prep(xi0, "xi0", 6, dev).reshape(B, 6)
+        self._pose_from_xi(xi)
+        return xi
+
+    def _init_log(self, table_rows):
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.table = torch.zeros(int(table_rows), self.B, 3, **f32)
+        self.cursor = torch.zeros(self.B, dtype=torch.int64, device=self.dev)
+        self.row = torch.zeros(self.B, 3, **f32)
+
+    def _log_args(self, a):
+        a.table, a.cursor, a.table_rows, a.row = ops._p(self.table), ops._p(self.cursor), self.table.shape[0], ops._p(self.row)
+
+    def _bind(self):
+        """Last in a constructor: the argument struct, its reference and the entry, looked up once."""
+        self.epochs = 0  # epochs issued (the schedule's clock)
+        self._args = self._make_args()
+        self._aref = ctypes.byref(self._args)
+        self._call = getattr(_lib.load(), self._ENTRY)
+
+    def epoch(self):
+        """One epoch of all B pairs: ONE C call, nothing read back."""
+        with ops._guard(self.dev):
+            _lib.check(self._call(self._aref, ops._stream(self.dev)), self._ENTRY)
+        self.epochs += 1
+
+    def history(self):
+        """[per pair][(epoch, loss or None, value or None)] of the logged epochs, read from the device table once; value is
+        the pair's Chamfer distance with monitor=True, else None.  An epoch whose loss had no populated bucket: (e, None, None).
+        IcpRegistration: the fit's mean squared residual and, always, the Chamfer distance; an epoch whose fit failed: (e, None, None)."""
+        n = min(self.epochs, self.table.shape[0])
+        rows = self.table[:n].cpu().tolist()
+        out = [[] for _ in range(self.B)]
+        for e, per in enumerate(rows):
+            for b, (di, cf, ok) in enumerate(per):
+                out[b].append((e, di, cf if self.monitor else None) if ok else (e, None, None))
+        return out
+
+
+class StoppingLoop:
+    """For a PoseLoop whose step stops by itself (include/rrl.h, the pose-step state): the tolerances, the state words and
+    last_step, .done_epoch, .failed and the .run that may return early."""
+
+    def _init_stop(self, tol_rot, tol_trans, patience):
+        """tol_trans is a FRACTION of each pair's sampler radius (.radius), multiplied once here."""
+        self.tol_rot, self.tol_trans = self._per_pair(tol_rot), self._per_pair(tol_trans, self.radius)
+        self.patience = int(patience)
+        self.last_step = torch.zeros(self.B, 2, dtype=torch.float32, device=self.dev)
+        self.state = torch.zeros(self.B, 4, dtype=torch.int32, device=self.dev)
+        self.state[:, 2] = -1
+
+    def _stop_args(self, a):
+        P = ops._p
+        a.patience, a.tol_rot, a.tol_trans, a.last_step, a.state = self.patience, P(self.tol_rot), P(self.tol_trans), P(self.last_step), P(self.state)
+
+    def run(self, n_epoch, check_every=0):
+        """Up to n_epoch epochs.  check_every = k > 0: .done_epoch is read once every k epochs and the loop returns early when
+        every pair is done -- the only synchronisation, and only on request."""
+        k = int(check_every)
+        for i in range(int(n_epoch)):
+            self.epoch()
+            if k > 0 and (i + 1) % k == 0 and bool((self.done_epoch >= 0).all()):
+                break
+        return self
+
+    @property
+    def done_epoch(self):
+        return self.state[:, 2]
+
+    @property
+    def failed(self):
+        return self.state[:, 3]
+
+
+class PairRegistration(PoseLoop):
     """B pairs src_tri (B, N, 9) / tar_tri (B, M, 9) (pseudo-triangles whose first points are the clouds' points; N, M are
     capacities when counts1 / counts2 -- lists, CPU or int32 GPU tensors (B,) -- are given), n_lines lines per pair.
 
@@ -95,38 +200,27 @@ class PairRegistration:
             self.rng = None
         self.filled = torch.zeros(B, dtype=torch.int32, device=dev)
         self.tiles = torch.empty(B * self.rounds * ((L + 1023) // 1024) * 32, dtype=torch.int32, device=dev)
-        self.table = torch.zeros(int(table_rows), B, 3, **f32)
-        self.cursor = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.row = torch.zeros(B, 3, **f32)
+        self._init_log(table_rows)
         self.value = self.cham = None
         if self.monitor:
             nb = int(_lib.load().rrl_chamfer_workspace_bytes(B, N, M))
             self.cham = (torch.empty(nb, dtype=torch.uint8, device=dev), torch.empty(B, N, dtype=torch.int64, device=dev),
                          torch.empty(B, M, dtype=torch.int64, device=dev), torch.empty(1, **f32))
             self.value = torch.zeros(B, **f32)
-        self.R, self.T = torch.empty(B, 3, 3, **f32), torch.empty(B, 3, **f32)
         self._init_pose_side(**pose)
-        self.epochs = 0  # epochs issued (the schedule's clock)
         self._target_built = False
         self._opts_first, self._opts_kept = ctypes.addressof(st._opts), ctypes.addressof(st._opts_kept)
-        self._args = self._make_args()
-        self._aref = ctypes.byref(self._args)
-        self._call = getattr(_lib.load(), self._ENTRY)
-
-    def _pose_from_xi(self, xi):
-        """(R, T) = exp(xi), per pair."""
-        ops._run(self.dev, "rrl_se3_exp", ops._p(xi), ops._p(self.R), ops._p(self.T), self.B)
+        self._bind()
 
     def _init_pose_side(self, xi0, lr):
         """The first-order state: xi (B, 6) with Adam's moments, step counts and rates, and (R, T) = exp(xi)."""
         B, f32 = self.B, dict(dtype=torch.float32, device=self.dev)
-        self.xi = torch.zeros(B, 6, **f32) if xi0 is None else ops._prep(xi0, "xi0", 6, self.dev).reshape(B, 6).clone()
+        self.xi = self._start_poses(xi0=xi0).clone()  # (the parameter: never the caller's tensor)
         self.m, self.v = torch.zeros(B, 6, **f32), torch.zeros(B, 6, **f32)
         self.adam_state = torch.zeros(B, **f32)
         self.lr_value = float(lr)
         self.lr = torch.full((B,), self.lr_value, **f32)
         self.gxi = torch.zeros(B, 6, **f32)
-        self._pose_from_xi(self.xi)
 
     def _make_args(self):
         """The epoch's argument struct: the fields both structs name alike, then the pose side's (_pose_args)."""
@@ -142,7 +236,7 @@ class PairRegistration:
         if self.monitor:
             ws, bx, by, mean = self.cham
             a.cham_ws, a.cham_ws_bytes, a.best_x, a.best_y, a.cham_mean, a.value = P(ws), ws.numel(), P(bx), P(by), P(mean), P(self.value)
-        a.table, a.cursor, a.table_rows, a.row = P(self.table), P(self.cursor), self.table.shape[0], P(self.row)
+        self._log_args(a)
         self._pose_args(a)
         return a
 
@@ -169,10 +263,8 @@ class PairRegistration:
         if lr is not None:
             self.set_lr(lr)
         self._args.opts = self._opts_kept if self._target_built else self._opts_first
-        with ops._guard(self.dev):
-            _lib.check(self._call(self._aref, ops._stream(self.dev)), self._ENTRY)
+        super().epoch()
         self._target_built = True
-        self.epochs += 1
         self.step.st.ragged = self.step.ragged
 
     def run(self, n_epoch):
@@ -181,17 +273,6 @@ class PairRegistration:
         for _ in range(int(n_epoch)):
             self.epoch(scheduled_lr(self.epochs, self.lr_value))
         return self
-
-    def history(self):
-        """[per pair][(epoch, loss or None, value or None)] of the logged epochs, read from the device table once; value is
-        the pair's Chamfer distance with monitor=True, else None.  An epoch whose loss had no populated bucket: (e, None, None)."""
-        n = min(self.epochs, self.table.shape[0])
-        rows = self.table[:n].cpu().tolist()
-        out = [[] for _ in range(self.B)]
-        for e, per in enumerate(rows):
-            for b, (di, cf, ok) in enumerate(per):
-                out[b].append((e, di, cf if self.monitor else None) if ok else (e, None, None))
-        return out
 
     def moved_points(self):
         """(B, N, 3): the sources' first points as the latest epoch's step moved them (a view of the step's workspace; rows

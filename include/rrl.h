@@ -814,6 +814,20 @@ size_t rrl_pose_normal_eq_part_bytes(int B, int L);
 int rrl_pose_normal_eq(const void *ws, size_t ws_bytes, int B, int N, int M, int L, int s_m, int s_n, int e_m, int e_n,
                        float *neq, void *part, size_t part_bytes, const rrl_opts *opts, void *stream);
 
+/* The pose-step state: what the pose steps that stop by themselves (rrl_se3_newton_step_batch, rrl_icp_step_batch) keep per
+ * pose, and the one rule both apply.  state [B][4] int32 = { epochs issued, calm epochs, done epoch or -1 (the caller writes
+ * -1 before the first call), the pose-step status of this call }.  Every call adds 1 to word 0.  The stopping rule, when
+ * patience > 0: word 1 counts the consecutive epochs whose APPLIED step had its rotation length < tol_rot[b] and its
+ * translation length < tol_trans[b] (float32 comparisons; any other epoch -- skipped, failed, longer -- resets it); when it
+ * reaches `patience`, word 2 = the number of epochs issued so far, this one included.  From then on the pair is done: its pose
+ * is frozen, bit for bit, words 1 and 2 are kept and word 3 says RRL_POSE_DONE.  last_step [B][2] (optional) = the two
+ * lengths, written only when a step was applied.  Word 3: 0 the step was applied, 1 skipped and 2 failed (the pose keeps its
+ * bits; each step names its own reasons: RRL_NEWTON_*, RRL_FIT_*), 3 done. */
+#define RRL_POSE_STEPPED 0
+#define RRL_POSE_SKIPPED 1
+#define RRL_POSE_FAILED 2
+#define RRL_POSE_DONE 3
+
 /* One damped Gauss-Newton step for a BATCH of B poses in one launch (one wavefront per pose, like rrl_se3_adam_step_batch;
  * every array per sample: neq [B][16]; damping, step, max_rot, max_trans, tol_rot, tol_trans [B]; R [B][9], T [B][3];
  * loss, value, cursor [B]; table [nrows][B][3]; row [B][3]; box [B][6]; delta [B][6]; last_step [B][2]; state [B][4] int32).
@@ -831,18 +845,16 @@ int rrl_pose_normal_eq(const void *ws, size_t ws_bytes, int B, int N, int M, int
  *   7. the log row (loss[b], value[b], gate word > 0) into table[cursor[b]][b] and row[b], cursor[b] += 1 -- as the Adam step;
  *   8. box[b] = min xyz, max xyz over the rows aabb_rows + b * row_stride, [0, ceil(count1[b] / 256)) of them -- the contract
  *      of rrl_se3_adam_step_batch (count1 NULL: ceil(N / 256) rows; no rows: (+inf, -inf));
- *   9. the stopping rule, when patience > 0: state[b][1] counts the consecutive stepped epochs with |omega| < tol_rot[b] and
- *      |v| < tol_trans[b] (any other epoch resets it); when it reaches `patience`, state[b][2] = the number of epochs issued
- *      so far, this one included.  From then on the pair is done: its pose is frozen, bit for bit.
- * state[b] = { epochs issued, calm epochs, done epoch or -1 (the caller writes -1 before the first call), RRL_NEWTON_* of
- * this call }.  gate, tol_rot, tol_trans (patience <= 0), loss, value, table, cursor, row, box (with aabb_rows, count1),
+ *   9. the stopping rule of the pose-step state (above) on the lengths (|omega|, |v|) of 6.
+ * state[b]: the pose-step state, its status word RRL_NEWTON_* of this call.
+ * gate, tol_rot, tol_trans (patience <= 0), loss, value, table, cursor, row, box (with aabb_rows, count1),
  * delta, last_step may be NULL.  Refusals, before any launch: RRL_E_ARG for B < 0, a NULL neq / damping / step / max_rot /
  * max_trans / R / T / state, a negative gate_stride, eps < 0 or NaN, patience > 0 without both tolerances, a box without
  * rows (aabb_rows NULL, N <= 0, or row_stride < 8 ceil(N / 256)); B == 0 returns 0 without a launch. */
-#define RRL_NEWTON_STEPPED 0
-#define RRL_NEWTON_GATED 1
-#define RRL_NEWTON_FAILED 2
-#define RRL_NEWTON_DONE 3
+#define RRL_NEWTON_STEPPED RRL_POSE_STEPPED
+#define RRL_NEWTON_GATED RRL_POSE_SKIPPED
+#define RRL_NEWTON_FAILED RRL_POSE_FAILED
+#define RRL_NEWTON_DONE RRL_POSE_DONE
 int rrl_se3_newton_step_batch(const float *neq, const int32_t *gate, long long gate_stride, const float *damping,
                               const float *step, const float *max_rot, const float *max_trans, const float *tol_rot,
                               const float *tol_trans, int patience, double eps, float *R, float *T, const float *loss,
@@ -945,16 +957,15 @@ int rrl_kabsch_bwd(const rrl_kabsch_args *args, const float *gR, const float *gT
 
 /* The pose step of point-to-point ICP for a batch, one launch, one wavefront per pair: from the fit (Rk [B][9], Tk [B][3],
  * info, fit of rrl_kabsch_fwd on the source AS GIVEN, so that (Rk, Tk) is the total pose) and the current pose R [B][9],
- * T [B][3].  state [B][4] int32 are rrl_se3_newton_step_batch's words: { epochs issued, calm epochs, done epoch or -1 (the
- * caller writes -1 first), what this call did: the fit's status RRL_FIT_*, or RRL_ICP_DONE }.  Pair b, unless done, with
- * status RRL_FIT_OK and a finite (Rk, Tk): in double, the rotation angle between R and Rk and the motion of the weighted
- * source centroid |abar Rk + Tk - abar R - T| -> last_step [B][2]; (R, T) <- (Rk, Tk), bit for bit; the epoch is calm when
- * both lie below tol_rot[b] / tol_trans[b], and after `patience` (> 0) calm epochs in a row the pair is done: from then on
- * its pose is frozen.  Any other status keeps the pose and resets the calm count (a non-finite fit: RRL_FIT_DEGENERATE).
+ * T [B][3].  state [B][4] int32: the pose-step state (above), its status word the fit's status RRL_FIT_* (the same three
+ * values), or RRL_ICP_DONE.  Pair b, unless done, with status RRL_FIT_OK and a finite (Rk, Tk): in double, the rotation angle
+ * between R and Rk and the motion of the weighted source centroid |abar Rk + Tk - abar R - T| are the applied step's two
+ * lengths (-> last_step, the stopping rule); (R, T) <- (Rk, Tk), bit for bit.
+ * Any other status keeps the pose and resets the calm count (a non-finite fit: RRL_FIT_DEGENERATE).
  * The log row (res_after, value[b], status == RRL_FIT_OK) goes to table[cursor[b]][b] and row[b], cursor[b] += 1, as
  * rrl_se3_adam_step_batch logs.  value, table, cursor, row, last_step, tol_rot / tol_trans (patience <= 0) may be NULL.
  * RRL_E_ARG before the launch: B < 0, a NULL Rk / Tk / info / fit / R / T / state, patience > 0 without both tolerances. */
-#define RRL_ICP_DONE 3
+#define RRL_ICP_DONE RRL_POSE_DONE
 int rrl_icp_step_batch(const float *Rk, const float *Tk, const int32_t *info, const double *fit, float *R, float *T,
                        const float *tol_rot, const float *tol_trans, int patience, const float *value, float *table,
                        long long *cursor, long long nrows, float *row, float *last_step, int32_t *state, int B, void *stream);

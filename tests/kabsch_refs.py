@@ -146,6 +146,14 @@ def icp_step(Rk, Tk, status, abar, R, T, state, tol_rot, tol_trans, patience):
     return Rk, Tk, (ang, mv), [epochs, calm, done, FIT_OK]
 
 
+def stepped_fit(R, T, ang, mv):
+    """(Rk, Tk) float32: the pose (R, T) turned by `ang` about z and shifted by `mv` along x.  With abar = 0 the two step
+    lengths the rule measures from it are (ang, mv), up to the float32 rounding of the entries (1e-7)."""
+    c, s = np.cos(ang), np.sin(ang)
+    Rz = np.array([[c, s, 0.0], [-s, c, 0.0], [0.0, 0.0, 1.0]])
+    return (np.asarray(R, np.float64) @ Rz).astype(np.float32), (np.asarray(T, np.float64) + [mv, 0.0, 0.0]).astype(np.float32)
+
+
 def icp_epoch_from_keys(src, tar, keys, R, T, state, count1=None, count2=None, gate_sq=None, tol_rot=0.0, tol_trans=0.0, patience=0):
     """The host ICP epoch of one pair from GIVEN keys (those the walk left for the moved source): fit of the source as given
     against the keyed targets, then the step rule -> (fit dict, R, T, last_step, state)."""

@@ -168,6 +168,16 @@ def step(neq, gate, R, T, state, damping, step_scale, max_rot, max_trans, tol_ro
     return Rn, Tn, np.array([epochs, calm, done, STEPPED]), x, np.array([nw, nv])
 
 
+def diagonal_neq(nw, nv):
+    """Sixteen sums whose undamped system is the identity (S_QQ = I / 2, S_sQ = 0, S_ss = 1) and whose gradient is
+    -(nw, 0, 0, nv, 0, 0): with damping 0 and step 1 the solved twist is (nw, 0, 0), (nv, 0, 0) up to the eps term, so the two
+    step lengths are the two numbers given."""
+    S = np.zeros(NSUMS, np.float32)
+    S[0] = S[3] = S[5] = 0.5
+    S[9], S[10], S[13] = 1.0, -nw, -nv
+    return S
+
+
 def chain_rule_gradient(gR, gt, R, T):
     """(g_w, g_v) of the twist (omega, v) at 0 from dL/dR (3, 3) and dL/dT (3,) of y = x R + T: dy = omega x y + v, so
     g_v = dL/dT and g_w = sum y x g_y = vee(A - A^T) + T x dL/dT with A = R^T dL/dR."""

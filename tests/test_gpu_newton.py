@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import kabsch_refs as KR
 import newton_refs as NR
 from test_gpu_register_batch import C1, C2, N_CAP, clouds, given_lines, same, xi_start
 
@@ -325,6 +326,47 @@ def test_the_stopping_rule_on_the_device(ops):
                 assert st[b, 2] == -1
         assert st[2, 2] == -1 and st[2, 3] == NR.STEPPED and st[:, 0].tolist() == [e + 1] * 3
     assert float(t["last_step"][0].max()) < 1e-3 and float(t["last_step"][2, 0]) > 1e-3
+
+
+def test_both_steps_apply_one_stopping_rule(ops):
+    """rrl_se3_newton_step_batch (diagonal systems: NR.diagonal_neq) and rrl_icp_step_batch (crafted fits: KR.stepped_fit) fed
+    the same (rotation, translation) step lengths for 8 launches, B = 5, patience 3, tolerances 1e-3 and every length a
+    factor 4 from them.  Pose 0: not calm, calm twice, a reset (the rotation alone is calm), calm three times -> done at 7;
+    pose 1: calm from the start -> done at 3; pose 2: never calm; pose 3: done on entry; pose 4: fails in launches 3 and 7 on
+    each side's own terms (gate 0 / RRL_FIT_FEW), which resets its count, and is done at 6.  Columns 0 .. 2 of the two states
+    are equal after every launch, and the done pose keeps its bytes on both sides."""
+    B, patience = 5, 3
+    calm, far, mixed, fail = (2.5e-4, 2.5e-4), (4e-3, 4e-3), (2.5e-4, 4e-3), None
+    plan = [[far, calm, calm, mixed, calm, calm, calm, far], [calm] * 8, [far] * 8, [far] * 8,
+            [calm, calm, fail, calm, calm, calm, fail, calm]]
+    state0 = torch.tensor([[0, 0, -1, 0]] * 3 + [[9, 3, 7, 0], [0, 0, -1, 0]], dtype=torch.int32).cuda()
+    R0, T0 = poses(B)
+    tols, one, zero = torch.full((B,), 1e-3).cuda(), torch.ones(B).cuda(), torch.zeros(B).cuda()
+    fit = torch.zeros(B, 32, dtype=torch.float64).cuda()  # (abar = 0: the centroid moves by Tk - T)
+    Rn, Tn, sn, Ri, Ti, si = R0.clone(), T0.clone(), state0.clone(), R0.clone(), T0.clone(), state0.clone()
+    P = ops._p
+    for e in range(8):
+        row = [plan[b][e] for b in range(B)]
+        ok = torch.tensor([r is not fail for r in row])
+        lengths = [r or far for r in row]
+        neq = torch.from_numpy(np.stack([NR.diagonal_neq(*x) for x in lengths])).cuda()
+        ops.se3_newton_step_batch(neq, ok.to(torch.int32).cuda(), Rn, Tn, sn, damping=zero, step=one, max_rot=one, max_trans=one,
+                                  tol_rot=tols, tol_trans=tols, patience=patience)
+        fits = [KR.stepped_fit(Ri[b].cpu().numpy(), Ti[b].cpu().numpy(), *lengths[b]) for b in range(B)]
+        Rk, Tk = (torch.from_numpy(np.stack([f[k] for f in fits])).cuda() for k in (0, 1))
+        info = torch.zeros(B, 4, dtype=torch.int32)
+        info[:, 1] = torch.where(ok, KR.FIT_OK, KR.FIT_FEW)
+        info = info.cuda()
+        ops._run(Ri.device, "rrl_icp_step_batch", P(Rk), P(Tk), P(info), P(fit), P(Ri), P(Ti), P(tols), P(tols), patience, None, None,
+                 None, 0, None, None, P(si), B)
+        torch.cuda.synchronize()
+        assert torch.equal(sn[:, :3], si[:, :3]), (e, sn.tolist(), si.tolist())
+        assert sn[:, 0].tolist() == [e + 1, e + 1, e + 1, e + 10, e + 1]
+        for R, T in ((Rn, Tn), (Ri, Ti)):
+            same(R[3], R0[3], f"launch {e}: the done pose's R")
+            same(T[3], T0[3], f"launch {e}: the done pose's T")
+    assert sn[:, 2].tolist() == [7, 3, -1, 7, 6] and sn[:, 1].tolist() == [3, 3, 0, 3, 3]
+    assert sn[:, 3].tolist() == [NR.DONE] * 2 + [NR.STEPPED] + [NR.DONE] * 2 and si[:, 3].tolist() == [KR.ICP_DONE] * 2 + [KR.FIT_OK] + [KR.ICP_DONE] * 2
 
 
 # ------------------------------------------------------------------------------------- 3: the one-call epoch

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import kabsch_refs as KR
+import newton_refs as NR
 from conftest import ROOT, load_golden
 
 FAKE = 0x1000  # a non-NULL, 8-byte aligned pointer that is never dereferenced
@@ -113,6 +114,23 @@ def test_step_rule():
     assert st == [8, 0, -1, KR.FIT_OK] and last[0] < 1e-7
     R, T, last, st = KR.icp_step(Rs * np.float32("nan"), z, KR.FIT_OK, abar, I, z, [0, 1, -1, 0], 0.1, 0.1, 2)
     assert R is I and st == [1, 0, -1, KR.FIT_DEGENERATE]
+
+
+def test_step_rule_is_the_newton_twins_rule():
+    """The two twins' step rules, written apart, on ONE sequence of (rotation, translation) step lengths, patience 3 and both
+    tolerances 1e-3 (every length a factor 4 from them): not calm, calm, calm, a reset (the rotation alone is calm), calm x 3
+    -> done at 7, then two epochs after done.  Columns 0 .. 2 of the two states agree after every epoch."""
+    calm, far, mixed = (2.5e-4, 2.5e-4), (4e-3, 4e-3), (2.5e-4, 4e-3)
+    lengths = [far, calm, calm, mixed, calm, calm, calm, far, calm]
+    want = [[1, 0, -1], [2, 1, -1], [3, 2, -1], [4, 0, -1], [5, 1, -1], [6, 2, -1], [7, 3, 7], [8, 3, 7], [9, 3, 7]]
+    Rn, Tn, sn = np.eye(3), np.zeros(3), [0, 0, -1, 0]
+    Ri, Ti, si = np.eye(3, dtype=np.float32), np.zeros(3, np.float32), [0, 0, -1, 0]
+    for (rot, trans), w in zip(lengths, want):
+        Rn, Tn, sn, _, _ = NR.step(NR.diagonal_neq(rot, trans), 1, Rn, Tn, sn, 0.0, 1.0, 1.0, 1.0, 1e-3, 1e-3, 3, 1e-12)
+        Rk, Tk = KR.stepped_fit(Ri, Ti, rot, trans)
+        Ri, Ti, _, si = KR.icp_step(Rk, Tk, KR.FIT_OK, np.zeros(3), Ri, Ti, si, 1e-3, 1e-3, 3)
+        assert [int(x) for x in sn[:3]] == [int(x) for x in si[:3]] == w, (w, sn, si)
+    assert sn[3] == NR.DONE and si[3] == KR.ICP_DONE
 
 
 def test_python_refusals_need_no_gpu():
