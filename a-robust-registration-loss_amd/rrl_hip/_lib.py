@@ -99,6 +99,7 @@ _SIGS = {
     "rrl_fps_counted": [_P] * 6 + [_I] * 3 + [_P],
     "rrl_knn3_counted": [_P] * 7 + [_I] * 3 + [_P],
     "rrl_knn3_self": [_P, _P, _P, _Z, _P, _P, _P, _I, _I, _P],
+    "rrl_ball_group": [_P] * 5 + [_c.c_float, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
     "rrl_sample_lines": [_P] * 8 + [_I] * 3 + [_P],
     "rrl_sample_lines_rng": [_P] * 8 + [_I] * 3 + [_P],
 }
@@ -107,6 +108,7 @@ EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamf
                                  "rrl_knn3_self_workspace_bytes", "rrl_pose_normal_eq_part_bytes", "rrl_kabsch_part_bytes",
                                  "rrl_sinkhorn_workspace_bytes"])
 
+GROUP_XYZ, GROUP_DXYZ, GROUP_PPF, GROUP_MAX_SAMPLE = 1, 2, 4, 64  # include/rrl.h RRL_GROUP_*
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
 F_CHAIN = 2        # RRL_F_CHAIN: leave the hit counts / CHAIN words cleared for the next step on this workspace
 F_CHAINED = 4      # RRL_F_CHAINED: the previous step did (chain_left = 1): records + both scans as one launch

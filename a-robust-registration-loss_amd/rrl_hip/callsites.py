@@ -392,3 +392,33 @@ def rpm_match_head(affinity, xyz_src, xyz_ref, n_iters=5, slack=True):
     src_weights, ref_weights)."""
     weighted_ref, src_weights, ref_weights = rpm_soft_correspondences(affinity, xyz_ref, n_iters, slack)
     return rpm_compute_rigid_transform(xyz_src, weighted_ref, src_weights), weighted_ref, src_weights, ref_weights
+
+
+# ---- RPM's feature extractor: ball-query grouping and the raw xyz / dxyz / ppf features in front of its prepool layers -------
+def rpm_sample_and_group_multi(xyz, normals, radius=0.3, nsample=64, npoint=-1, returnfps=False):
+    """rpm/models/pointnet_util.py:197-244 sample_and_group_multi(npoint, radius, nsample, xyz, normals, returnfps) as ONE
+    launch (neighbors.ball_group): xyz, normals (B, N, 3) -> {'xyz': (B, S, 3), 'dxyz': (B, S, nsample, 3), 'ppf': (B, S,
+    nsample, 4)}, S = N unless npoint > 0 (then the farthest-point sampler first, neighbors.fps, with the reference's CPU
+    draw of its first index).  returnfps: also (grouped_xyz (B, S, nsample, 3), fps_idx (B, S) int64).  Forward only: the
+    reference calls it on detached clouds (rpm/models/rpmnet.py:204-205)."""
+    from . import neighbors
+    B, N = xyz.shape[0], xyz.shape[1]
+    fps_idx = neighbors.fps(xyz, npoint) if npoint > 0 else None
+    feat, idx, _ = neighbors.ball_group(xyz, normals, radius, nsample, features=("dxyz", "ppf"), query_idx=fps_idx)
+    pts = _ops._prep(xyz, "xyz", 3, feat.device)
+    new_xyz = pts if fps_idx is None else torch.gather(pts, 1, fps_idx.long().unsqueeze(-1).expand(-1, -1, 3))
+    out = {'xyz': new_xyz, 'dxyz': feat[..., :3], 'ppf': feat[..., 3:]}
+    if not returnfps:
+        return out
+    if fps_idx is None:
+        fps_idx = torch.arange(N, device=feat.device)[None].repeat(B, 1)
+    grouped = torch.gather(pts, 1, idx.long().reshape(B, -1, 1).expand(-1, -1, 3)).reshape(*idx.shape, 3)
+    return out, grouped, fps_idx.long()
+
+
+def rpm_raw_features(xyz, normals, features, radius=0.3, nsample=64):
+    """The tensor FeatExtractionEarlyFusion.forward concatenates before its permute (rpm/models/feature_nets.py:184-193):
+    (B, N, nsample, C) with the chosen channels sorted xyz, dxyz, ppf as the reference sorts them, written by the kernel
+    directly -- no expand, no cat."""
+    from . import neighbors
+    return neighbors.ball_group(xyz, normals, radius, nsample, features=features)[0]

@@ -3,6 +3,7 @@ utils.farthest_point_sample, code/utils.py:275-296, and sklearn's KDTree).  SURV
 import numpy as np
 import torch
 
+from . import _lib
 from . import ops as _ops
 from .ops import _home, _p, _run
 
@@ -143,6 +144,94 @@ def knn3_counted(points, query_idx, counts=None, qcounts=None):
     nn = torch.empty(B, S, 3, dtype=torch.int32, device=dev)
     _run(dev, "rrl_knn3_counted", _p(pts), _p(cnt), _p(qi), _p(qcnt), _p(nn), None, None, B, n, S)
     return nn
+
+
+# ---- ball-query grouping and raw point-pair features (include/rrl.h rrl_ball_group) ----------------
+FEATURES = ("xyz", "dxyz", "ppf")  # the reference's order (rpm/models/feature_nets.py _raw_features_order), 3 + 3 + 4 channels
+FEATURE_SIZES = {"xyz": 3, "dxyz": 3, "ppf": 4}
+MAX_NSAMPLE = _lib.GROUP_MAX_SAMPLE
+
+
+def _channel_mask(features):
+    if isinstance(features, str):
+        features = (features,)
+    features = tuple(features)
+    if not features or len(set(features)) != len(features) or any(f not in FEATURES for f in features):
+        raise ValueError(f"features must be distinct names out of {FEATURES}, got {features!r}")
+    return sum(1 << FEATURES.index(f) for f in features), sum(FEATURE_SIZES[f] for f in features)
+
+
+def _ball(points, normals, radius, nsample, mask, C, query_idx, counts, qcounts, exclude_self):
+    """Every host-side refusal, then the one launch: (feat or None, idx, found)."""
+    B, n = _points3(points)
+    if isinstance(nsample, bool) or int(nsample) != nsample or not 1 <= int(nsample) <= MAX_NSAMPLE:
+        raise ValueError(f"nsample must be an integer in [1, {MAX_NSAMPLE}], got {nsample!r}")
+    nsample = int(nsample)
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise ValueError(f"radius must not be negative or NaN, got {radius}")
+    try:  # the Python double squared, then rounded: what torch compares its float32 matrix against
+        r2 = float(np.float32(radius ** 2))
+    except OverflowError:
+        r2 = float("inf")
+    if not 1 <= B <= 32767 or n < 1:
+        raise ValueError(f"ball_query serves 1 .. 32767 clouds of at least one point, got {B} of {n}")
+    if n > _ops.sort_capacity():
+        raise ValueError(f"ball_query serves clouds up to {_ops.sort_capacity()} points, got {n}")
+    if mask & _lib.GROUP_PPF:
+        if normals is None:
+            raise ValueError('the "ppf" feature needs normals')
+        if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != tuple(points.shape):
+            raise ValueError(f"normals must be a tensor of the points' shape {tuple(points.shape)}")
+    hc = _host_counts(counts, B, n, "counts")
+    if query_idx is None:
+        S = n
+    else:
+        if not isinstance(query_idx, torch.Tensor) or query_idx.dim() != 2:
+            raise ValueError("query_idx must be a (B, S) tensor")
+        S = query_idx.shape[1]
+        if not query_idx.is_cuda:
+            _check_index_counted(query_idx, hc, n, "query_idx", (B, S))
+        elif tuple(query_idx.shape) != (B, S) or query_idx.dtype.is_floating_point:
+            raise ValueError(f"query_idx must be an integer tensor of shape {(B, S)}")
+    hq = _host_counts(qcounts, B, S, "qcounts")
+    dev = _home(points, query_idx, counts)
+    pts = _ops._prep(points, "points", 3, dev)
+    nrm = _ops._prep(normals, "normals", 3, dev) if mask & _lib.GROUP_PPF else None
+    qi = None if query_idx is None else query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    cnt = _ops.check_counts(counts if hc is None else hc, B, n, dev, "counts")
+    qcnt = _ops.check_counts(qcounts if hq is None else hq, B, S, dev, "qcounts")
+    idx = torch.empty(B, S, nsample, dtype=torch.int32, device=dev)
+    found = torch.empty(B, S, dtype=torch.int32, device=dev)
+    feat = torch.empty(B, S, nsample, C, dtype=torch.float32, device=dev) if mask else None
+    _run(dev, "rrl_ball_group", _p(pts), _p(nrm), _p(cnt), _p(qi), _p(qcnt), r2, nsample, int(bool(exclude_self)), mask,
+         _p(idx), _p(found), _p(feat), B, n, S)
+    return feat, idx, found
+
+
+def ball_query(points, radius, nsample, *, query_idx=None, counts=None, qcounts=None, exclude_self=True):
+    """points (B, n, 3) -> (idx (B, S, nsample) int32, found (B, S) int32): for every query the `nsample` lowest indices j of
+    its cloud with |x_j - x_i|^2 <= float32(radius ** 2), ascending -- the reference's query_ball_point
+    (rpm/models/pointnet_util.py:96-131) without its (B, S, n) index tensor, distance matrix and row sort.  The distance is
+    the float64 sum of rrl_knn3 (the reference's is the expanded float32 matmul: pairs within a few float32 roundings of
+    the radius can differ).  found counts the slots that hold a member; the rest hold the pad index.
+    exclude_self=True is the reference with `itself_indices` (sample_and_group_multi): the query itself is no member, and it
+    is the pad; False is `itself_indices=None` (sample_and_group): the pad is the first member.
+    query_idx (B, S) integers (default: every point, S = n), counts / qcounts (B,): as knn3_counted takes them -- on the
+    GPU they are read by the kernel only and clamped, on the host they are validated (ValueError before any launch).  Rows
+    beyond a count are zero.  Nothing synchronises with device-side arguments: the call can be captured in a graph."""
+    return _ball(points, None, radius, nsample, 0, 0, query_idx, counts, qcounts, exclude_self)[1:]
+
+
+def ball_group(points, normals, radius, nsample, *, features=FEATURES, query_idx=None, counts=None, qcounts=None,
+               exclude_self=True):
+    """ball_query plus the raw features of its groups in the same launch: (feat (B, S, nsample, C) float32, idx, found) with
+    the chosen channels in the reference's order whatever the order of `features`: "xyz" (3) the query's coordinates on
+    every slot, "dxyz" (3) x_j - x_i, "ppf" (4) angle(n_i, d), angle(n_j, d), angle(n_i, n_j), |d| with angle(a, b) =
+    atan2(|a x b|, a . b) (pointnet_util.py:173-244).  normals (B, n, 3) may be None without "ppf".  A pad slot with
+    exclude_self has d = 0: its dxyz and ppf values are exactly 0.  No gradient flows (the reference feeds detached clouds)."""
+    mask, C = _channel_mask(features)
+    return _ball(points, normals, radius, nsample, mask, C, query_idx, counts, qcounts, exclude_self)
 
 
 def _neighbours(points, num_sample, counts, start, method, want_tri):

@@ -1226,6 +1226,41 @@ size_t rrl_knn3_self_workspace_bytes(int B, int n);
 int rrl_knn3_self(const float *pts, const int32_t *counts, void *ws, size_t ws_bytes, int32_t *nn, float *tri,
                   int32_t *tri_counts, int B, int n, void *stream);
 
+/* ---- ball-query grouping and raw point-pair features ----------------------
+ * RPM-Net's feature extractor groups every point with "the first nsample in-radius indices, in index order"
+ * (rpm/models/pointnet_util.py:96-131 query_ball_point) and builds xyz / dxyz / ppf channels from the groups (:173-244).
+ * rrl_ball_group is that as one launch, forward only: plain device pointers, sizes and a stream; nothing is allocated, read
+ * back or synchronised, there is no scratch, and every refusal happens on the host before the launch.
+ *
+ * pts [B][n][3]; normals [B][n][3] (NULL unless RRL_GROUP_PPF is asked for); counts [B] (device int32 or NULL = n): sample b
+ * has n_b = clamp(counts[b], 0, n) points, rows beyond are never read.  query_idx [B][S] (device int32, or NULL: query q is
+ * point q, then S <= n and a sample has min(S_b, n_b) queries), clamped into [0, n_b); qcounts [B] (or NULL = S): S_b =
+ * clamp(qcounts[b], 0, S), and 0 for a sample without points.
+ *
+ * Membership: candidate j belongs to query i (a point index) iff d2 <= (double)r2, d2 = (dx dx + dy dy) + dz dz in double
+ * from the double differences of the float32 coordinates, uncontracted (rrl_knn3's distance) -- a NaN distance never --
+ * and, with exclude_self, j != i (a duplicate of the query at another index is a member).
+ * Selection: the nsample members of lowest index, ascending, in idx [B][S][nsample]; found [B][S] = how many slots hold a
+ * member; the slots beyond hold the pad index: i with exclude_self, else the first member (i when there is none).
+ * feat (optional; NULL iff channels == 0) [B][S][nsample][C], the chosen channels in this order:
+ *   RRL_GROUP_XYZ  (3) x_i, repeated over the slots;
+ *   RRL_GROUP_DXYZ (3) d = x_j - x_i, the float32 subtraction;
+ *   RRL_GROUP_PPF  (4) angle(n_i, d), angle(n_j, d), angle(n_i, n_j), |d| with angle(a, b) = atan2(|a x b|, a . b), evaluated
+ *                      in double from the float32 d and normals and rounded once.  A pad slot with exclude_self has d = 0 and
+ *                      n_j = n_i: its four values are exactly 0.
+ * Rows beyond S_b are zero in all three outputs.  Bit-reproducible; sample b of a ragged batch has the bits of its own call.
+ *
+ * RRL_E_ARG: NULL pts / idx / found; B outside 1..32767; n < 1 or beyond rrl_sort_capacity(); S < 0; S > n with NULL
+ * query_idx; nsample outside 1..RRL_GROUP_MAX_SAMPLE; r2 negative or NaN; channels outside the mask, channels without feat
+ * or feat without channels; RRL_GROUP_PPF without normals.  S == 0 returns 0 without a launch. */
+#define RRL_GROUP_XYZ 1
+#define RRL_GROUP_DXYZ 2
+#define RRL_GROUP_PPF 4
+#define RRL_GROUP_MAX_SAMPLE 64
+int rrl_ball_group(const float *pts, const float *normals, const int32_t *counts, const int32_t *query_idx,
+                   const int32_t *qcounts, float r2, int nsample, int exclude_self, int channels, int32_t *idx, int32_t *found,
+                   float *feat, int B, int n, int S, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
