@@ -13,6 +13,7 @@
 
 #include "rrl_ws.h"
 #include "rrl_pose_tail.h"
+#include "rrl_pose_solve.h"
 #include "rrl_wave_sum_d.h"
 
 #define NEQ_LINES 64  // selected lines per 256-lane workgroup (four hit slots each): loss_bwd_rt_kernel's BWD_LINES
@@ -241,48 +242,6 @@ struct NewtonArgs {
     int32_t *state;
     int B;
 };
-
-// solves (A + damping diag(A) + eps I) x = -g for the symmetric A; false: a pivot that does not exceed eps (what the
-// undamped matrix contributes there is not positive) or is not finite, or a solution that is not finite
-__device__ __forceinline__ bool newton_solve(const double (&H)[6][6], const double (&g)[6], double damping, double eps, double (&x)[6]) {
-    double Lm[6][6];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double p = H[j][j] + damping * H[j][j] + eps;
-#pragma unroll
-        for (int q = 0; q < j; ++q) p -= Lm[j][q] * Lm[j][q];
-        if (!(p > eps) || !(p < (double)INFINITY)) { ok = false; p = 1.0; }
-        const double d = sqrt(p);
-        Lm[j][j] = d;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = H[i][j];
-#pragma unroll
-            for (int q = 0; q < j; ++q) v -= Lm[i][q] * Lm[j][q];
-            Lm[i][j] = v / d;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) v -= Lm[i][q] * y[q];
-        y[i] = v / Lm[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int q = i + 1; q < 6; ++q) v -= Lm[q][i] * x[q];
-        x[i] = v / Lm[i][i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-        if (!(fabs(x[i]) < (double)INFINITY)) ok = false;
-    return ok;
-}
 
 __global__ __launch_bounds__(64) void se3_newton_step_kernel(const NewtonArgs a) {
     const int b = blockIdx.x, k = threadIdx.x;

@@ -100,13 +100,17 @@ _SIGS = {
     "rrl_knn3_counted": [_P] * 7 + [_I] * 3 + [_P],
     "rrl_knn3_self": [_P, _P, _P, _Z, _P, _P, _P, _I, _I, _P],
     "rrl_ball_group": [_P] * 5 + [_c.c_float, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
+    "rrl_idx_normals": [_P, _I, _P, _P, _P, _I, _c.c_float, _P, _P, _I, _I, _I, _P],
+    "rrl_plane_normal_eq": [_P, _P],
+    "rrl_plane_step_batch": [_P] * 9 + [_I, _c.c_double] + [_P] * 5 + [_c.c_longlong, _P, _P, _P, _I, _P],
+    "rrl_plane_icp_epoch": [_P, _P],
     "rrl_sample_lines": [_P] * 8 + [_I] * 3 + [_P],
     "rrl_sample_lines_rng": [_P] * 8 + [_I] * 3 + [_P],
 }
 EXPORTS = sorted(list(_SIGS) + ["rrl_version", "rrl_workspace_bytes", "rrl_chamfer_workspace_bytes",
                                  "rrl_cloud_order_workspace_bytes", "rrl_wide_workspace_bytes", "rrl_sort_capacity",
                                  "rrl_knn3_self_workspace_bytes", "rrl_pose_normal_eq_part_bytes", "rrl_kabsch_part_bytes",
-                                 "rrl_sinkhorn_workspace_bytes"])
+                                 "rrl_sinkhorn_workspace_bytes", "rrl_plane_part_bytes"])
 
 GROUP_XYZ, GROUP_DXYZ, GROUP_PPF, GROUP_MAX_SAMPLE = 1, 2, 4, 64  # include/rrl.h RRL_GROUP_*
 F_TARGET_KEPT = 1  # include/rrl.h RRL_F_TARGET_KEPT
@@ -208,9 +212,35 @@ class SinkhornArgs(ctypes.Structure):
                 ("ws", _P), ("ws_bytes", _Z), ("W", _P), ("s", _P), ("c", _P), ("log_perm", _P), ("info", _P)]
 
 
+class PlaneArgs(ctypes.Structure):
+    """include/rrl.h rrl_plane_args (same field order)."""
+    _fields_ = [("struct_bytes", _c.c_int32), ("B", _c.c_int32), ("N", _c.c_int32), ("M", _c.c_int32), ("tar_stride", _c.c_int32),
+                ("reserved", _c.c_int32),
+                ("moved", _P), ("keys", _P), ("tar", _P), ("normals", _P), ("count1", _P), ("count2", _P),
+                ("w", _P), ("gate_sq", _P), ("pivot", _P),
+                ("part", _P), ("part_bytes", _Z), ("neq", _P), ("info", _P)]
+
+
+class PlaneEpochArgs(ctypes.Structure):
+    """include/rrl.h rrl_plane_epoch_args (same field order)."""
+    _fields_ = [("struct_bytes", _c.c_int32), ("B", _c.c_int32), ("N", _c.c_int32), ("M", _c.c_int32), ("patience", _c.c_int32),
+                ("reserved", _c.c_int32),
+                ("src", _P), ("tar", _P), ("normals", _P), ("count1", _P), ("count2", _P), ("R", _P), ("T", _P), ("moved", _P),
+                ("cham_ws", _P), ("cham_ws_bytes", _Z), ("best_x", _P), ("best_y", _P), ("values", _P), ("order_x", _P),
+                ("order_y", _P), ("w", _P), ("gate_sq", _P), ("pivot", _P),
+                ("part", _P), ("part_bytes", _Z), ("neq", _P), ("info", _P),
+                ("damping", _P), ("step", _P), ("max_rot", _P), ("max_trans", _P), ("tol_rot", _P), ("tol_trans", _P),
+                ("eps", _c.c_double), ("last_step", _P), ("state", _P),
+                ("table", _P), ("cursor", _P), ("table_rows", _c.c_longlong), ("row", _P)]
+
+
 # rrl_kabsch_fwd's fit [B][32] doubles and info[b][1] (include/rrl.h RRL_FIT_*); rrl_icp_step_batch's state[b][3]
 FIT_W, FIT_ABAR, FIT_BBAR, FIT_U, FIT_S, FIT_V, FIT_DELTA, FIT_RES, FIT_KEYMEAN, FIT_DOUBLES = 0, 1, 4, 7, 16, 19, 28, 29, 30, 32
 FIT_OK, FIT_FEW, FIT_DEGENERATE, ICP_DONE = 0, 1, 2, 3
+
+# rrl_plane_normal_eq's neq [B][32] doubles (include/rrl.h RRL_PLANE_*); rrl_plane_step_batch's state[b][3]
+PLANE_H, PLANE_G, PLANE_W, PLANE_RES, PLANE_KEYMEAN, PLANE_USED, PLANE_SKIPPED, PLANE_DOUBLES = 0, 21, 27, 28, 29, 30, 31, 32
+PLANE_STEPPED, PLANE_FEW, PLANE_FAILED, PLANE_DONE = 0, 1, 2, 3
 
 # rrl_se3_newton_step_batch's state[b][3] (include/rrl.h RRL_NEWTON_*)
 NEWTON_STEPPED, NEWTON_GATED, NEWTON_FAILED, NEWTON_DONE = 0, 1, 2, 3
@@ -253,6 +283,8 @@ def load():
     lib.rrl_kabsch_part_bytes.restype = _Z
     lib.rrl_sinkhorn_workspace_bytes.argtypes = [_I, _I, _I, _I]
     lib.rrl_sinkhorn_workspace_bytes.restype = _Z
+    lib.rrl_plane_part_bytes.argtypes = [_I, _I]
+    lib.rrl_plane_part_bytes.restype = _Z
     lib.rrl_sort_capacity.argtypes = []
     lib.rrl_sort_capacity.restype = _I
     _lib = lib

@@ -8,6 +8,13 @@ free) -> the closed-form fit of the source AS GIVEN onto its keyed partners -> t
 
 The closed form has a wide basin where the loops that follow the loss are local; it is the coarse stage, they are the fine one.
 Nothing is read back unless .run is asked to check.
+
+PlaneIcpRegistration is the point-to-plane form of the same epoch (include/rrl.h rrl_plane_icp_epoch): the
+fit is one damped Gauss-Newton step of the distances to the target's tangent planes, which lets a surface slide along itself
+where point-to-point pairs hold it back.
+
+    icp = PlaneIcpRegistration(src, tar, normals_tar)                     # or normal_radius=0.25: normals estimated once
+    icp.run(20, check_every=5)
 """
 import ctypes
 
@@ -15,6 +22,8 @@ import torch
 
 from . import _lib, ops
 from .kabsch import RANK_TOL
+from .newton import DAMPING, MAX_ROT, MAX_TRANS, STEP
+from .newton import EPS as NEWTON_EPS
 from .register import PoseLoop, StoppingLoop
 
 # The defaults of the stopping rule, from tools/icp_timing.py (profiles/icp_timing.json: eight make_pair pairs at 20 degrees,
@@ -25,6 +34,16 @@ from .register import PoseLoop, StoppingLoop
 TOL_ROT = 1e-4     # radians
 TOL_TRANS = 1e-5   # as a fraction of the target box's diagonal
 PATIENCE = 3
+
+# PlaneIcpRegistration's step controls are NewtonRegistration's (rrl_hip.newton).  Its stopping tolerances, from
+# tools/plane_icp_timing.py (profiles/plane_icp_timing.json: eight make_pair pairs at 20 degrees, N = M = 1024): a damped
+# Gauss-Newton step shrinks about tenfold per epoch once the pairing has settled (down to the float32 rounding of the pose, 1e-8 ...
+# 4e-7 rad), so three calm epochs in a row mean the same pose under any tolerance below the first of them; but a pairing can
+# also settle into a cycle of a few pairs, which moved one of the eight poses by 3.2e-4 ... 3.8e-4 rad and 2.8e-5 ... 4.8e-5 of
+# the diagonal per epoch for good, 0.02 degrees about a pose 0.15 degrees from the generating rotation.  IcpRegistration's values
+# (1e-4, 1e-5) sit below that cycle and never end such a pair; these sit above it and below every step that still converged.
+PLANE_TOL_ROT = 1e-3     # radians
+PLANE_TOL_TRANS = 1e-4   # as a fraction of the target box's diagonal
 
 
 def check_request(src_shape, tar_shape, capacity, max_dist=None, patience=PATIENCE):
@@ -45,22 +64,11 @@ def check_request(src_shape, tar_shape, capacity, max_dist=None, patience=PATIEN
         raise ValueError("patience must be non-negative (0 turns the stopping rule off)")
 
 
-class IcpRegistration(StoppingLoop, PoseLoop):
-    """B pairs src (B, N, 3 or 9) / tar (B, M, 3 or 9); N, M are capacities when counts1 / counts2 are given (both, or one:
-    the other is then full).  R0 (B, 3, 3) with T0 (B, 3), or xi0 (B, 6): starting poses (default: the identity); the poses
-    move x -> x R + T.  max_dist: partners farther than this fraction of the target box's diagonal get weight 0 (None: no
-    gate).  tol_rot (radians), tol_trans (fraction of that diagonal), patience: a pair is done after `patience` epochs in a
-    row whose pose moved by less than both (patience = 0: never); a done pair's pose is frozen.  table_rows: epochs logged.
+class _CloudLoop(StoppingLoop, PoseLoop):
+    """What the two ICP loops share: the request's refusals, the clouds' first points with their counts, prepared orders and
+    the target's box, the starting poses, the stopping rule, the gate and the Chamfer walk's buffers."""
 
-    .R, .T: the poses.  .done_epoch (B,) int32 (-1: not yet), .failed (B,) int32: what the latest epoch did -- 0 stepped, 1
-    fewer than 3 pairs, 2 degenerate pairs (pose kept in both), 3 done.  .last_step (B, 2): (angle, centroid motion) of the
-    latest step.  .value (B,): each pair's Chamfer distance before the latest step.  All device tensors.
-    .history(): PairRegistration's row format -- (epoch, the fit's mean squared residual, the pair's Chamfer distance)."""
-
-    _ARGS, _ENTRY = _lib.IcpEpochArgs, "rrl_icp_epoch"  # .epoch(): ONE C call
-
-    def __init__(self, src, tar, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, max_dist=None, tol_rot=TOL_ROT,
-                 tol_trans=TOL_TRANS, patience=PATIENCE, table_rows=4096):
+    def _init_clouds(self, src, tar, counts1, counts2, R0, T0, xi0, max_dist, tol_rot, tol_trans, patience, table_rows):
         if not isinstance(src, torch.Tensor) or not isinstance(tar, torch.Tensor):
             raise TypeError("src / tar must be torch.Tensors")
         self._check_start(R0, T0, xi0)
@@ -98,7 +106,47 @@ class IcpRegistration(StoppingLoop, PoseLoop):
         self.best_x = torch.empty(B, N, dtype=torch.int64, device=dev)
         self.best_y = torch.empty(B, M, dtype=torch.int64, device=dev)
         self.value = torch.zeros(B, **f32)
-        self.part = torch.empty(max(int(lib.rrl_kabsch_part_bytes(B, N)) // 8, 1), dtype=torch.float64, device=dev)
+        return lib
+
+    def _cloud_args(self, a):
+        """The fields both epoch structs name alike."""
+        P = ops._p
+        a.struct_bytes = ctypes.sizeof(a)
+        a.B, a.N, a.M = self.B, self.N, self.M
+        a.src, a.tar, a.count1, a.count2 = P(self.src), P(self.tar), P(self.counts1), P(self.counts2)
+        a.R, a.T, a.moved = P(self.R), P(self.T), P(self.moved)
+        a.cham_ws, a.cham_ws_bytes, a.best_x, a.best_y, a.values = P(self.cham_ws), self.cham_ws.numel(), P(self.best_x), P(self.best_y), P(self.value)
+        a.order_x, a.order_y = P(self.order_x), P(self.order_y)
+        a.w, a.gate_sq = None, P(self.gate_sq)
+        self._stop_args(a)
+        self._log_args(a)
+
+    def moved_points(self):
+        """(B, N, 3): the source points under the CURRENT pose (one rigid apply; rows beyond a count are not meaningful)."""
+        out = torch.empty_like(self.moved)
+        ops._run(self.dev, "rrl_rigid_apply_fwd", ops._p(self.src), ops._p(self.R), ops._p(self.T), ops._p(out), self.B, self.N, 0, 0)
+        return out
+
+
+class IcpRegistration(_CloudLoop):
+    """B pairs src (B, N, 3 or 9) / tar (B, M, 3 or 9); N, M are capacities when counts1 / counts2 are given (both, or one:
+    the other is then full).  R0 (B, 3, 3) with T0 (B, 3), or xi0 (B, 6): starting poses (default: the identity); the poses
+    move x -> x R + T.  max_dist: partners farther than this fraction of the target box's diagonal get weight 0 (None: no
+    gate).  tol_rot (radians), tol_trans (fraction of that diagonal), patience: a pair is done after `patience` epochs in a
+    row whose pose moved by less than both (patience = 0: never); a done pair's pose is frozen.  table_rows: epochs logged.
+
+    .R, .T: the poses.  .done_epoch (B,) int32 (-1: not yet), .failed (B,) int32: what the latest epoch did -- 0 stepped, 1
+    fewer than 3 pairs, 2 degenerate pairs (pose kept in both), 3 done.  .last_step (B, 2): (angle, centroid motion) of the
+    latest step.  .value (B,): each pair's Chamfer distance before the latest step.  All device tensors.
+    .history(): PairRegistration's row format -- (epoch, the fit's mean squared residual, the pair's Chamfer distance)."""
+
+    _ARGS, _ENTRY = _lib.IcpEpochArgs, "rrl_icp_epoch"  # .epoch(): ONE C call
+
+    def __init__(self, src, tar, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, max_dist=None, tol_rot=TOL_ROT,
+                 tol_trans=TOL_TRANS, patience=PATIENCE, table_rows=4096):
+        lib = self._init_clouds(src, tar, counts1, counts2, R0, T0, xi0, max_dist, tol_rot, tol_trans, patience, table_rows)
+        B, dev, f32 = self.B, self.dev, dict(dtype=torch.float32, device=self.dev)
+        self.part = torch.empty(max(int(lib.rrl_kabsch_part_bytes(B, self.N)) // 8, 1), dtype=torch.float64, device=dev)
         self.Rk, self.Tk = torch.zeros(B, 3, 3, **f32), torch.zeros(B, 3, **f32)
         self.fit = torch.zeros(B, _lib.FIT_DOUBLES, dtype=torch.float64, device=dev)
         self.info = torch.zeros(B, 4, dtype=torch.int32, device=dev)
@@ -108,28 +156,92 @@ class IcpRegistration(StoppingLoop, PoseLoop):
     def _make_args(self):
         P = ops._p
         a = self._ARGS()
-        a.struct_bytes = ctypes.sizeof(a)
-        a.B, a.N, a.M = self.B, self.N, self.M
-        a.src, a.tar, a.count1, a.count2 = P(self.src), P(self.tar), P(self.counts1), P(self.counts2)
-        a.R, a.T, a.moved = P(self.R), P(self.T), P(self.moved)
-        a.cham_ws, a.cham_ws_bytes, a.best_x, a.best_y, a.values = P(self.cham_ws), self.cham_ws.numel(), P(self.best_x), P(self.best_y), P(self.value)
-        a.order_x, a.order_y = P(self.order_x), P(self.order_y)
-        a.w, a.gate_sq, a.eps_w, a.rank_tol = None, P(self.gate_sq), 0.0, RANK_TOL
+        self._cloud_args(a)
+        a.eps_w, a.rank_tol = 0.0, RANK_TOL
         a.part, a.part_bytes = P(self.part), self.part.numel() * 8
         a.Rk, a.Tk, a.fit, a.info = P(self.Rk), P(self.Tk), P(self.fit), P(self.info)
-        self._stop_args(a)
-        self._log_args(a)
         return a
-
-    def moved_points(self):
-        """(B, N, 3): the source points under the CURRENT pose (one rigid apply; rows beyond a count are not meaningful)."""
-        out = torch.empty_like(self.moved)
-        ops._run(self.dev, "rrl_rigid_apply_fwd", ops._p(self.src), ops._p(self.R), ops._p(self.T), ops._p(out), self.B, self.N, 0, 0)
-        return out
 
 
 def icp_pairs(src, tar, n_epoch=60, check_every=0, **kw):
     """IcpRegistration(...).run(n_epoch, check_every) -> (R (B, 3, 3), T (B, 3), history)."""
     reg = IcpRegistration(src, tar, **kw)
+    reg.run(n_epoch, check_every)
+    return reg.R, reg.T, reg.history()
+
+
+def check_plane_request(tar_shape, normals_shape, normal_radius, nsample, eps=NEWTON_EPS):
+    """The refusals of PlaneIcpRegistration beyond check_request's that need no GPU (ValueError)."""
+    if normals_shape is None and normal_radius is None:
+        raise ValueError("PlaneIcpRegistration needs the target's normals: give normals (B, M, 3), or normal_radius to "
+                         "estimate them (neighbors.estimate_normals); no radius is assumed")
+    if normals_shape is not None and tuple(normals_shape) != (tar_shape[0], tar_shape[1], 3):
+        raise ValueError(f"normals must be (B, M, 3) = {(tar_shape[0], tar_shape[1], 3)}, one per target point; got {tuple(normals_shape)}")
+    if normals_shape is None:
+        if not float(normal_radius) > 0.0:
+            raise ValueError("normal_radius must be positive")
+        if isinstance(nsample, bool) or int(nsample) != nsample or not 3 <= int(nsample) <= _lib.GROUP_MAX_SAMPLE:
+            raise ValueError(f"nsample must be an integer in [3, {_lib.GROUP_MAX_SAMPLE}] (a plane needs three members)")
+    if not float(eps) >= 0.0:
+        raise ValueError("eps must be non-negative")
+
+
+class PlaneIcpRegistration(_CloudLoop):
+    """Point-to-plane ICP for a batch of pairs, one C call per epoch (include/rrl.h rrl_plane_icp_epoch; DESIGN.md section
+    19): move the source -> the ragged Chamfer walk -> the sums of the fit linearised about the current pose, each source
+    point against the PLANE of its nearest target point -> one damped Gauss-Newton pose step about the target box's centre.
+    Where point-to-point pairs hold a surface back from sliding along itself, the plane residual lets it: a handful of
+    epochs where IcpRegistration takes tens.
+
+    src, tar, counts1, counts2, R0 / T0 / xi0, max_dist, tol_rot, tol_trans, patience, table_rows: as IcpRegistration.
+    normals (B, M, 3): the TARGET's normals (a dataset's normals_tar; unit length, any orientation; a zero or non-finite row
+    takes its point out of the fit).  Without them, normal_radius (in the clouds' units) and nsample estimate them once with
+    neighbors.estimate_normals(tar, normal_radius, nsample, counts=counts2); giving neither is a ValueError.
+    damping, step, max_rot, max_trans, eps: NewtonRegistration's step controls with its defaults (a number or one per pair;
+    max_trans is a fraction of the target box's diagonal).
+
+    .R, .T, .done_epoch, .last_step ((|omega|, |v|) of the latest step), .value, .history() (epoch, the mean squared plane
+    residual, the pair's Chamfer distance), .moved_points(): as IcpRegistration.  .normals (B, M, 3): the normals in use.
+    .failed (B,) int32: 0 stepped, 1 fewer than 6 usable pairs, 2 a singular or non-finite system (pose kept in both), 3 done."""
+
+    _ARGS, _ENTRY = _lib.PlaneEpochArgs, "rrl_plane_icp_epoch"  # .epoch(): ONE C call
+
+    def __init__(self, src, tar, normals=None, *, normal_radius=None, nsample=64, counts1=None, counts2=None, R0=None, T0=None,
+                 xi0=None, max_dist=None, damping=DAMPING, step=STEP, max_rot=MAX_ROT, max_trans=MAX_TRANS, eps=NEWTON_EPS,
+                 tol_rot=PLANE_TOL_ROT, tol_trans=PLANE_TOL_TRANS, patience=PATIENCE, table_rows=4096):
+        if not isinstance(tar, torch.Tensor):
+            raise TypeError("src / tar must be torch.Tensors")
+        check_plane_request(tuple(tar.shape), None if normals is None else tuple(normals.shape), normal_radius, nsample, eps)
+        lib = self._init_clouds(src, tar, counts1, counts2, R0, T0, xi0, max_dist, tol_rot, tol_trans, patience, table_rows)
+        B, dev = self.B, self.dev
+        if normals is not None:
+            self.normals = ops._prep(normals, "normals", 3, dev).reshape(B, self.M, 3).contiguous()
+        else:
+            from .neighbors import estimate_normals
+            self.normals = estimate_normals(self.tar, float(normal_radius), int(nsample), counts=self.counts2)
+        centre = 0.5 * (self.box2[:, :3] + self.box2[:, 3:])  # (an empty target's box is (+inf, -inf): the origin)
+        self.pivot = torch.where(torch.isfinite(centre), centre, torch.zeros_like(centre)).contiguous()
+        self.damping, self.step_scale = self._per_pair(damping), self._per_pair(step)
+        self.max_rot, self.max_trans = self._per_pair(max_rot), self._per_pair(max_trans, self.radius)
+        self.eps = float(eps)
+        self.part = torch.empty(max(int(lib.rrl_plane_part_bytes(B, self.N)) // 8, 1), dtype=torch.float64, device=dev)
+        self.neq = torch.zeros(B, _lib.PLANE_DOUBLES, dtype=torch.float64, device=dev)
+        self.info = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        self._init_log(table_rows)
+        self._bind()
+
+    def _make_args(self):
+        P = ops._p
+        a = self._ARGS()
+        self._cloud_args(a)
+        a.normals, a.pivot = P(self.normals), P(self.pivot)
+        a.part, a.part_bytes, a.neq, a.info = P(self.part), self.part.numel() * 8, P(self.neq), P(self.info)
+        a.damping, a.step, a.max_rot, a.max_trans, a.eps = P(self.damping), P(self.step_scale), P(self.max_rot), P(self.max_trans), self.eps
+        return a
+
+
+def plane_icp_pairs(src, tar, normals=None, n_epoch=20, check_every=0, **kw):
+    """PlaneIcpRegistration(...).run(n_epoch, check_every) -> (R (B, 3, 3), T (B, 3), history)."""
+    reg = PlaneIcpRegistration(src, tar, normals, **kw)
     reg.run(n_epoch, check_every)
     return reg.R, reg.T, reg.history()

@@ -234,6 +234,49 @@ def ball_group(points, normals, radius, nsample, *, features=FEATURES, query_idx
     return _ball(points, normals, radius, nsample, mask, C, query_idx, counts, qcounts, exclude_self)
 
 
+# ---- unit normals from ball groups (include/rrl.h rrl_idx_normals) -----------------------------------
+# l1 <= NORMAL_RANK_TOL l2 on the EIGENVALUES of a group's scatter matrix (squared lengths): the members are collinear or
+# coincident and have no plane.  Collinear float32 points leave l1 / l2 near 2^-48; 1e-10 is 1e-5 on the lengths themselves.
+NORMAL_RANK_TOL = 1e-10
+
+
+def normals_from_groups(points, idx, found, *, counts=None, return_quality=False):
+    """The kernel behind estimate_normals on given index lists: points (B, n, 3), idx (B, S, nsample) int32 and found (B, S)
+    int32 as ball_query returns them -> normals (B, S, 3) float32 [, quality (B, S)]."""
+    B, n = _points3(points)
+    if not (isinstance(idx, torch.Tensor) and isinstance(found, torch.Tensor)) or idx.dim() != 3 or idx.dtype != torch.int32 or \
+            found.dtype != torch.int32 or idx.shape[0] != B or tuple(found.shape) != tuple(idx.shape[:2]):
+        raise ValueError("idx must be an int32 (B, S, nsample) tensor and found an int32 (B, S) tensor, as ball_query returns them")
+    S, nsample = idx.shape[1], idx.shape[2]
+    if not 1 <= nsample <= MAX_NSAMPLE:
+        raise ValueError(f"nsample must lie in [1, {MAX_NSAMPLE}], got {nsample}")
+    if not 1 <= B <= 32767 or not 1 <= n <= _ops.sort_capacity():
+        raise ValueError(f"normals are served for 1 .. 32767 clouds of 1 .. {_ops.sort_capacity()} points, got {B} of {n}")
+    hc = _host_counts(counts, B, n, "counts")
+    dev = _home(points, idx, counts)
+    pts = _ops._prep(points, "points", 3, dev)
+    cnt = _ops.check_counts(counts if hc is None else hc, B, n, dev, "counts")
+    ix, fd = idx.to(device=dev).contiguous(), found.to(device=dev).contiguous()
+    normals = torch.empty(B, S, 3, dtype=torch.float32, device=dev)
+    quality = torch.empty(B, S, dtype=torch.float32, device=dev) if return_quality else None
+    _run(dev, "rrl_idx_normals", _p(pts), 3, _p(ix), _p(fd), _p(cnt), nsample, NORMAL_RANK_TOL, _p(normals), _p(quality), B, n, S)
+    return (normals, quality) if return_quality else normals
+
+
+def estimate_normals(points, radius, nsample=64, *, counts=None, return_quality=False):
+    """points (B, n, 3) -> unit normals (B, n, 3) float32: for every point the direction of least variance of its ball group --
+    the first `nsample` points (in index order, the point itself among them: ball_query(exclude_self=False)) within `radius`
+    --, as the eigenvector of the smallest eigenvalue of the group's scatter matrix (double sums and a double Jacobi
+    eigen-decomposition on the device, rounded once).  The normals are NOT oriented: the sign is fixed by a convention (the
+    component of largest magnitude is positive), not by an inside or an outside -- enough for point-to-plane residuals, which
+    do not see the sign.  A point whose group has fewer than three members, collinear or coincident members, or a non-finite
+    member gets the normal (0, 0, 0); so do the rows beyond a count.  counts: as ball_query takes them.
+    return_quality=True appends quality (B, n) = (l1 - l0) / l2 of the eigenvalues l0 <= l1 <= l2 (0 for a zero normal): near
+    0 where the group does not determine a plane.  Two launches, no read-back: the call can be captured in a graph."""
+    idx, found = ball_query(points, radius, nsample, counts=counts, exclude_self=False)
+    return normals_from_groups(points, idx, found, counts=counts, return_quality=return_quality)
+
+
 def _neighbours(points, num_sample, counts, start, method, want_tri):
     """The launches of pseudo_triangles / knn3_self after every host-side refusal: (sample_idx or None, tri or None, nn,
     tri_counts)."""

@@ -1261,6 +1261,106 @@ int rrl_ball_group(const float *pts, const float *normals, const int32_t *counts
                    const int32_t *qcounts, float r2, int nsample, int exclude_self, int channels, int32_t *idx, int32_t *found,
                    float *feat, int B, int n, int S, void *stream);
 
+/* ---- Point-to-plane ICP: normals from ball groups, the linearised fit, its pose step, an epoch ----
+ * The house rules of the closed-form fits hold for all four entries: float32 in, every sum a fixed-order DOUBLE sum
+ * (per-lane accumulators, the wavefront's DPP tree, four wavefronts, partial rows in index order), rounded once; no atomics,
+ * nothing indexed by unclamped data; counts are device int32 [B], clamped by the kernels, never read on the host; the same
+ * bits on every call, and sample b of a ragged batch has the bits of its own B = 1 call; nothing synchronises.
+ *
+ * rrl_idx_normals: unit normals from neighbour lists, one launch (one wavefront per row, four rows per workgroup).
+ * pts [B][n][stride] (stride >= 3 floats per row); idx [B][S][nsample], found [B][S] as rrl_ball_group writes them; counts [B]
+ * or NULL (= n).  Row i: its members are the first clamp(found, 0, nsample) slots; a slot whose index is < 0 or >= the sample's
+ * count is dropped; k members remain.  Pivot = the point of the first member kept, d_j = double(x_j) - double(pivot),
+ * m = sum d_j / k, C = sum d_j d_j^T - k m m^T, all double and uncontracted.  C's eigenvalues l0 <= l1 <= l2 by cyclic Jacobi
+ * rotations in double; normal = the eigenvector of l0 (the lowest column among equal eigenvalues), its sign such that the
+ * component of largest magnitude (the lowest index among equals) is positive, rounded to float32 once; quality (optional,
+ * [B][S]) = (l1 - l0) / l2.  A row with k < 3, a non-finite C, or l1 <= rank_tol l2 (collinear or coincident members) gets
+ * the normal (0, 0, 0) and quality 0 -- as does every row beyond a sample's queries, whose found is 0.  The normals are NOT
+ * oriented: n and -n describe the same plane, and the point-to-plane residual does not tell them apart.
+ * RRL_E_ARG before the launch: NULL pts / idx / found / normals; B outside 1..32767; n < 1 or beyond rrl_sort_capacity();
+ * S < 0; stride < 3; nsample outside 1..RRL_GROUP_MAX_SAMPLE; rank_tol negative, NaN or >= 1.  S == 0: no launch. */
+int rrl_idx_normals(const float *pts, int stride, const int32_t *idx, const int32_t *found, const int32_t *counts, int nsample,
+                    float rank_tol, float *normals, float *quality, int B, int n, int S, void *stream);
+
+/* rrl_plane_normal_eq: the sums of ONE linearised point-to-plane fit of moved [B][N][3] onto the planes (tar [B][M][tar_stride],
+ * normals [B][M][3]).  Pairs, skips, weights w [B][N] (NULL = 1) and the gate are rrl_kabsch_fwd's: keys [B][N] are the u64
+ * keys a Chamfer walk left for the rows of moved (NULL: partner i <-> i, then M == N); a row at or beyond count1[b], an all-ones
+ * key, a key whose index is >= M or >= count2[b] contributes nothing and is counted in info[b][3]; a pair whose key distance
+ * word exceeds gate_sq[b] (keys only) gets weight 0.  In addition a partner whose normal is (0, 0, 0) or not finite gets weight
+ * 0: it is neither used nor skipped.  Per used pair, in double from the float32 values, with c = pivot[b] ([B][3]; NULL: the
+ * origin): p = y - c, e = y - b, r = (e0 n0 + e1 n1) + e2 n2, a = p x n, J = (a, n); the step it linearises is
+ * y -> c + Rot(omega)(y - c) + v, so that r changes by J . (omega, v): a rotation about the pivot, which keeps a cloud far from
+ * the origin well conditioned.  The 32 sums: w J J^T (upper triangle, row-major, 21), w J r (6), w, w r^2, w (key distance
+ * word), pairs used, pairs skipped.  Launches: partials (grid ceil(N / 512) x B) into part, then one wavefront per sample; ONE
+ * launch when N <= 512.
+ * neq [B][32] double (RRL_PLANE_*): H / W, g / W, W = sum w, the mean squared plane residual, the key mean, used, skipped.
+ * info [B][4] int32: pairs used, status, 0, pairs skipped.  Status: RRL_FIT_OK, or RRL_FIT_FEW -- fewer than 6 used pairs, or
+ * W <= 0 or NaN: H, g, the residual and the key mean are then 0.
+ * Refusals, before any launch: RRL_E_ARG -- a NULL args / moved / tar / normals / neq / info / part, struct_bytes != sizeof,
+ * B < 0 or > 32767, N <= 0, M <= 0, tar_stride < 3, a misaligned neq or part, no keys and M != N, gate_sq without keys --, then
+ * RRL_E_WS: part_bytes < rrl_plane_part_bytes(B, N).  B == 0 returns 0 without a launch. */
+#define RRL_PLANE_H 0
+#define RRL_PLANE_G 21
+#define RRL_PLANE_W 27
+#define RRL_PLANE_RES 28
+#define RRL_PLANE_KEYMEAN 29
+#define RRL_PLANE_USED 30
+#define RRL_PLANE_SKIPPED 31
+#define RRL_PLANE_DOUBLES 32
+typedef struct rrl_plane_args {
+    int32_t struct_bytes, B, N, M, tar_stride, reserved;
+    const float *moved; const uint64_t *keys; const float *tar, *normals; const int32_t *count1, *count2;
+    const float *w, *gate_sq, *pivot;
+    void *part; size_t part_bytes;
+    double *neq; int32_t *info;
+} rrl_plane_args;
+size_t rrl_plane_part_bytes(int B, int N);
+int rrl_plane_normal_eq(const rrl_plane_args *args, void *stream);
+
+/* rrl_plane_step_batch: the pose step of point-to-plane ICP for a batch, one launch, one wavefront per pair: from neq and
+ * info of rrl_plane_normal_eq and the current pose R [B][9], T [B][3] (x -> x R + T).  Pair b, unless done, with status
+ * RRL_FIT_OK: (H + damping[b] diag(H) + eps I) x = -g by Cholesky in double (the solver, the step scale and the two clamps of
+ * rrl_se3_newton_step_batch: (omega, v) = step[b] x, |omega| <= max_rot[b], |v| <= max_trans[b]); then with the exact Rodrigues
+ * rotation and c = pivot[b] (NULL: the origin)
+ *   R <- R Rot^T,   T <- (T - c) Rot^T + c + v,
+ * one Gram-Schmidt pass over the rows of R, rounded to float32 once.  last_step[b] = (|omega|, |v|) as applied; the stopping
+ * rule, the state words and the log row -- (the mean squared plane residual, value[b], status of the sums == RRL_FIT_OK) into
+ * table[cursor[b]][b] and row[b], cursor[b] += 1 -- are the pose-step state's (above).  state[b][3]: RRL_PLANE_STEPPED,
+ * RRL_PLANE_FEW (the sums' RRL_FIT_FEW: pose kept), RRL_PLANE_FAILED (a pivot of the factorisation that does not exceed eps --
+ * a singular H: all normals parallel --, or a non-finite sum, solution or pose: pose kept) or RRL_PLANE_DONE.
+ * pivot, value, table, cursor, row, last_step, tol_rot / tol_trans (patience <= 0) may be NULL.  RRL_E_ARG before the launch:
+ * B < 0, a NULL neq / info / damping / step / max_rot / max_trans / R / T / state, a misaligned neq, eps < 0 or NaN,
+ * patience > 0 without both tolerances; B == 0 returns 0 without a launch. */
+#define RRL_PLANE_STEPPED RRL_POSE_STEPPED
+#define RRL_PLANE_FEW RRL_POSE_SKIPPED
+#define RRL_PLANE_FAILED RRL_POSE_FAILED
+#define RRL_PLANE_DONE RRL_POSE_DONE
+int rrl_plane_step_batch(const double *neq, const int32_t *info, const float *pivot, const float *damping, const float *step,
+                         const float *max_rot, const float *max_trans, const float *tol_rot, const float *tol_trans, int patience,
+                         double eps, float *R, float *T, const float *value, float *table, long long *cursor, long long nrows,
+                         float *row, float *last_step, int32_t *state, int B, void *stream);
+
+/* One point-to-plane ICP epoch for a batch of B pairs as ONE call: the entries back to back on the caller's stream, nothing
+ * else --
+ *   1. rrl_rigid_apply_fwd: moved = src R + T                                   (src [B][N][3], transpose_r = 0);
+ *   2. rrl_chamfer_tree_fwd_counted on (moved, tar, count1, count2) with the prepared orders -> best_x, best_y, values [B];
+ *   3. rrl_plane_normal_eq with keys = best_x, tar [B][M][3], normals [B][M][3], the counts, w, gate_sq, pivot -> neq, info;
+ *   4. rrl_plane_step_batch with value = values (the pair's Chamfer distance, which the walk's other half supplies).
+ * No host read-back.  Refusals, all before the first launch: RRL_E_ARG -- a NULL or wrongly sized struct, B <= 0 or > 32767,
+ * N or M <= 0 or beyond rrl_sort_capacity(), any NULL pointer among src, tar, normals, R, T, moved, cham_ws, best_x, best_y,
+ * values, part, neq, info, damping, step, max_rot, max_trans, state, exactly one count or one order, eps < 0 or NaN,
+ * patience > 0 without both tolerances, a misaligned part or neq --, then RRL_E_WS: a short cham_ws or part. */
+typedef struct rrl_plane_epoch_args {
+    int32_t struct_bytes, B, N, M, patience, reserved;
+    const float *src, *tar, *normals; const int32_t *count1, *count2; float *R, *T, *moved;
+    void *cham_ws; size_t cham_ws_bytes; uint64_t *best_x, *best_y; float *values; const int32_t *order_x, *order_y;
+    const float *w, *gate_sq, *pivot;
+    void *part; size_t part_bytes; double *neq; int32_t *info;
+    const float *damping, *step, *max_rot, *max_trans, *tol_rot, *tol_trans; double eps; float *last_step; int32_t *state;
+    float *table; long long *cursor; long long table_rows; float *row;
+} rrl_plane_epoch_args;
+int rrl_plane_icp_epoch(const rrl_plane_epoch_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
