@@ -3,15 +3,17 @@
 // (rpm/models/rpmnet.py:121-157 compute_rigid_transform, dcp/model.py:405-455 SVDHead), batched, ragged, from dense pairs or
 // from the keys a Chamfer walk left -- and, around the keyed form, one epoch of point-to-point ICP as one C call.
 //
-// The arithmetic rule: every sum is a fixed-order double sum (kabsch_part_kernel has pose_normal_eq_kernel's shape: per-lane
-// double accumulators, wave_sum_d, four wavefronts, one partial row per workgroup, no atomics), and everything after the
+// The arithmetic rule: every sum is a fixed-order double sum (kabsch_part_kernel has pose_normal_eq_kernel's shape, and its
+// block sum, rrl_pair_sums.h: per-lane double accumulators, wave_sum_d, four wavefronts, one partial row per workgroup, no
+// atomics; the pair walk and the total of the partial rows sit there too, shared with rrl_plane.hip), and everything after the
 // sums -- H, its SVD, delta, R, T -- is double on one lane, rounded to float32 once.
 #include <cstddef>
 #include <cstdint>
 
 #include "rrl_ws.h"
 #include "rrl_pose_tail.h"
-#include "rrl_wave_sum_d.h"
+#include "rrl_pair_sums.h"
+#include "rrl_cloud_epoch.h"
 
 #define KB_ROWS 512  // rows of `a` per 256-lane workgroup (two rounds)
 // the sums of a sample, about the pivots pa, pb (q = a - pa, r = b - pb): sum w, sum w q (3), sum w r (3), sum w q^T r (9),
@@ -206,8 +208,7 @@ __device__ void kabsch_finish(const KabschArgs &a, int b, const double (&S)[KB_S
 __global__ __launch_bounds__(256) void kabsch_part_kernel(const KabschArgs a) {
     __shared__ double s_red[4][KB_SUMS];
     __shared__ double s_tot[KB_SUMS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int bx = blockIdx.x, b = blockIdx.y, n = a.n, m = a.m;
+    const int tid = threadIdx.x, bx = blockIdx.x, b = blockIdx.y, n = a.n, m = a.m;
     const int ca = rrl_rows(a.count_a, b, n), cb = rrl_rows(a.count_b, b, m);
     const float *__restrict__ A = a.a + (size_t)b * n * a.sa;
     const float *__restrict__ Bp = a.b + (size_t)b * m * a.sb;
@@ -222,33 +223,20 @@ __global__ __launch_bounds__(256) void kabsch_part_kernel(const KabschArgs a) {
     for (int r = 0; r < KB_ROWS / 256; ++r) {
         const int i = bx * KB_ROWS + r * 256 + tid;
         if (i >= n) continue;
-        bool skip = i >= ca, gated = false;
-        unsigned idx = (unsigned)i;
-        float dist = 0.0f;
-        if (!skip) {
-            if (a.keys) {
-                const unsigned long long key = a.keys[(size_t)b * n + i];
-                idx = (unsigned)(key & 0xffffffffull);
-                dist = __uint_as_float((unsigned)(key >> 32));
-                skip = key == ~0ull || idx >= (unsigned)m || idx >= (unsigned)cb;
-                gated = dist > gate;
-            } else {
-                skip = i >= cb;
-            }
-        }
-        if (skip) {
+        const PairRow pair = pair_walk(a.keys, b, n, i, ca, m, cb, gate);
+        if (pair.skip) {
             acc[KB_SKIP] += 1.0;
             continue;
         }
-        if (gated) continue;
+        if (pair.gated) continue;
         const double w = a.w ? (double)a.w[(size_t)b * n + i] : 1.0;
         const float *__restrict__ pr = A + (size_t)i * a.sa;
-        const float *__restrict__ qr = Bp + (size_t)idx * a.sb;  // idx < min(m, cb): inside sample b's rows
+        const float *__restrict__ qr = Bp + (size_t)pair.idx * a.sb;  // idx < min(m, cb): inside sample b's rows
         const double q[3] = {(double)pr[0] - pa[0], (double)pr[1] - pa[1], (double)pr[2] - pa[2]};
         const double t[3] = {(double)qr[0] - pb[0], (double)qr[1] - pb[1], (double)qr[2] - pb[2]};
         acc[KB_W] += w;
         acc[KB_USED] += 1.0;
-        acc[KB_KD] += w * (double)dist;
+        acc[KB_KD] += w * (double)pair.dist;
         acc[KB_QQ] += w * ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
         acc[KB_RR] += w * ((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
 #pragma unroll
@@ -260,18 +248,9 @@ __global__ __launch_bounds__(256) void kabsch_part_kernel(const KabschArgs a) {
             for (int k = 0; k < 3; ++k) acc[KB_QR + 3 * j + k] += wq * t[k];
         }
     }
-#pragma unroll
-    for (int q = 0; q < KB_SUMS; ++q) acc[q] = wave_sum_d(acc[q]);
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < KB_SUMS; ++q) s_red[wave][q] = acc[q];
-    __syncthreads();
-    if (tid < KB_SUMS) {
-        const double tot = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
-        a.part[((size_t)b * gridDim.x + bx) * KB_SUMS + tid] = tot;
-        s_tot[tid] = tot;
-    }
+    const double tot = block_sum_d(acc, s_red, a.part + ((size_t)b * gridDim.x + bx) * KB_SUMS);
     if (gridDim.x != 1) return;  // (uniform)
+    if (tid < KB_SUMS) s_tot[tid] = tot;
     __syncthreads();
     if (tid == 0) {
         double S[KB_SUMS];
@@ -285,11 +264,7 @@ __global__ __launch_bounds__(256) void kabsch_part_kernel(const KabschArgs a) {
 __global__ __launch_bounds__(64) void kabsch_finish_kernel(const KabschArgs a, int nblk) {
     __shared__ double s_tot[KB_SUMS];
     const int b = blockIdx.x, lane = threadIdx.x;
-    if (lane < KB_SUMS) {
-        double s = 0.0;
-        for (int k = 0; k < nblk; ++k) s += a.part[((size_t)b * nblk + k) * KB_SUMS + lane];
-        s_tot[lane] = s;
-    }
+    if (lane < KB_SUMS) s_tot[lane] = part_rows_total<KB_SUMS>(a.part, b, nblk, lane);
     __syncthreads();
     if (lane != 0) return;
     double pa[3], pb[3], S[KB_SUMS];
@@ -576,20 +551,12 @@ extern "C" int rrl_icp_step_batch(const float *Rk, const float *Tk, const int32_
 
 // One ICP epoch: four public entries back to back, every refusal before the first launch (host code only).
 extern "C" int rrl_icp_epoch(const rrl_icp_epoch_args *a, void *stream) {
-    if (!a || a->struct_bytes != (int32_t)sizeof(rrl_icp_epoch_args)) return RRL_E_ARG;
+    if (!cloud_epoch_front_ok(a)) return RRL_E_ARG;
     const int B = a->B, N = a->N, M = a->M;
-    if (B <= 0 || B > 32767 || N <= 0 || M <= 0 || (N > M ? N : M) > rrl_sort_capacity()) return RRL_E_ARG;
-    if (!a->src || !a->tar || !a->R || !a->T || !a->moved || !a->cham_ws || !a->best_x || !a->best_y || !a->values || !a->part ||
-        !a->Rk || !a->Tk || !a->fit || !a->info || !a->state)
-        return RRL_E_ARG;
-    if ((a->count1 == nullptr) != (a->count2 == nullptr) || (a->order_x == nullptr) != (a->order_y == nullptr)) return RRL_E_ARG;
+    if (!a->R || !a->T || !a->Rk || !a->Tk || !a->fit || !a->info || !a->state || (((uintptr_t)a->fit) & 7) != 0) return RRL_E_ARG;
     if (!pose_stop_args_ok(a->patience, a->tol_rot, a->tol_trans)) return RRL_E_ARG;
-    if ((((uintptr_t)a->part) & 7) != 0 || (((uintptr_t)a->fit) & 7) != 0) return RRL_E_ARG;
-    if (a->cham_ws_bytes < rrl_chamfer_workspace_bytes(B, N, M) || a->part_bytes < rrl_kabsch_part_bytes(B, N)) return RRL_E_WS;
-    int rc = rrl_rigid_apply_fwd(a->src, a->R, a->T, a->moved, B, N, 0, 0, stream);
-    if (rc) return rc;
-    rc = rrl_chamfer_tree_fwd_counted(a->moved, a->tar, a->count1, a->count2, a->cham_ws, a->cham_ws_bytes, a->best_x, a->best_y,
-                                      a->values, nullptr, B, N, M, a->order_x, a->order_y, stream);
+    if (!cloud_epoch_cham_ws_ok(a) || a->part_bytes < rrl_kabsch_part_bytes(B, N)) return RRL_E_WS;
+    int rc = cloud_epoch_pair(a, stream);
     if (rc) return rc;
     rrl_kabsch_args k = {};
     k.struct_bytes = (int32_t)sizeof(k);

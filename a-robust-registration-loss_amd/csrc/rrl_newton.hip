@@ -14,7 +14,7 @@
 #include "rrl_ws.h"
 #include "rrl_pose_tail.h"
 #include "rrl_pose_solve.h"
-#include "rrl_wave_sum_d.h"
+#include "rrl_pair_sums.h"
 
 #define NEQ_LINES 64  // selected lines per 256-lane workgroup (four hit slots each): loss_bwd_rt_kernel's BWD_LINES
 #define NEQ_SUBS 16   // workgroups per 1024-line tile: every selected line of a tile has one (64 x 16 = 1024)
@@ -168,14 +168,7 @@ __global__ __launch_bounds__(256) void pose_normal_eq_kernel(const NeqArgs a) {
             acc[15] += (double)(as * ez);
         }
     }
-#pragma unroll
-    for (int q = 0; q < NEQ_SUMS; ++q) acc[q] = wave_sum_d(acc[q]);
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < NEQ_SUMS; ++q) s_red[wave][q] = acc[q];
-    __syncthreads();
-    if (tid < NEQ_SUMS)
-        a.part[((size_t)b * gridDim.x + bx) * NEQ_SUMS + tid] = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
+    block_sum_d(acc, s_red, a.part + ((size_t)b * gridDim.x + bx) * NEQ_SUMS);
 }
 
 // The fixed-order tail (a launch of its own, like loss_bwd_rt_finalize_kernel: the stream orders it behind the partials):
@@ -218,8 +211,9 @@ extern "C" int rrl_pose_normal_eq(const void *ws, size_t ws_bytes, int B, int N,
 // ---------------------------------------------------------------------------------------
 // The batched Gauss-Newton pose step: one wavefront per pose, grid B (se3_adam_step_kernel<Se3Batch>'s shape).  Lanes 8 .. 13
 // reduce the next sampler box from the step's partial rows and lane 0 logs (rrl_pose_tail.h); lane 0 does the pose: H (6 x 6) and g from the
-// sixteen sums, H + damping diag(H) + eps I, Cholesky and both substitutions in double, step scale, clamps, the exact
-// Rodrigues rotation, R <- R Rot^T, T <- T Rot^T + v, one Gram-Schmidt pass over R's rows, the log row, the stopping rule.
+// sixteen sums, then rrl_pose_solve.h: H + damping diag(H) + eps I, Cholesky and both substitutions in double (newton_solve),
+// step scale, clamps, the exact Rodrigues rotation, R <- R Rot^T, T <- T Rot^T + v, one Gram-Schmidt pass over R's rows
+// (pose_compose<false>: no pivot); the log row, the stopping rule.
 // state [B][4] int32: the pose-step state words and their rule, rrl_pose_tail.h (PoseStop); [3] = RRL_NEWTON_*.
 // ---------------------------------------------------------------------------------------
 struct NewtonArgs {
@@ -289,81 +283,12 @@ __global__ __launch_bounds__(64) void se3_newton_step_kernel(const NewtonArgs a)
             if (a.delta)
 #pragma unroll
                 for (int i = 0; i < 6; ++i) a.delta[s * 6 + i] = (float)x[i];
-            const double sc = (double)a.step[s];
-            double w[3] = {sc * x[0], sc * x[1], sc * x[2]}, v[3] = {sc * x[3], sc * x[4], sc * x[5]};
-            double nw = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), nv = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            const double mr = (double)a.max_rot[s], mt = (double)a.max_trans[s];
-            if (nw > mr) {
-                const double f = mr / nw;
-                w[0] *= f; w[1] *= f; w[2] *= f;
-                nw = mr;
-            }
-            if (nv > mt) {
-                const double f = mt / nv;
-                v[0] *= f; v[1] *= f; v[2] *= f;
-                nv = mt;
-            }
-            // Rot = I + A K + Bc K K, K = [w]x, theta = |w| as composed (Rodrigues; the series below 1e-4: their next terms are < 1e-26)
-            const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
-            double A, Bc;
-            if (th < 1e-4) {
-                A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0);
-                Bc = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0);
-            } else {
-                A = sin(th) / th;
-                Bc = (1.0 - cos(th)) / th2;
-            }
-            const double K[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
-            double Rot[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const double kk = K[i][0] * K[0][j] + K[i][1] * K[1][j] + K[i][2] * K[2][j];
-                    Rot[i][j] = (i == j ? 1.0 : 0.0) + A * K[i][j] + Bc * kk;
-                }
-            double Ro[3][3], To[3], Rn[3][3], Tn[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                To[i] = (double)a.T[s * 3 + i];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) Ro[i][j] = (double)a.R[s * 9 + 3 * i + j];
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                Tn[j] = (To[0] * Rot[j][0] + To[1] * Rot[j][1] + To[2] * Rot[j][2]) + v[j];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) Rn[i][j] = Ro[i][0] * Rot[j][0] + Ro[i][1] * Rot[j][1] + Ro[i][2] * Rot[j][2];
-            }
-            // one Gram-Schmidt pass over the rows: hundreds of compositions of float-rounded matrices do not drift
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int p = 0; p < i; ++p) {
-                    const double d = Rn[i][0] * Rn[p][0] + Rn[i][1] * Rn[p][1] + Rn[i][2] * Rn[p][2];
-                    Rn[i][0] -= d * Rn[p][0]; Rn[i][1] -= d * Rn[p][1]; Rn[i][2] -= d * Rn[p][2];
-                }
-                const double n = sqrt(Rn[i][0] * Rn[i][0] + Rn[i][1] * Rn[i][1] + Rn[i][2] * Rn[i][2]);
-                Rn[i][0] /= n; Rn[i][1] /= n; Rn[i][2] /= n;
-            }
-            bool finite = true;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                finite = finite && fabs(Tn[i]) < (double)INFINITY;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) finite = finite && fabs(Rn[i][j]) < (double)INFINITY;
-            }
-            if (!finite) {  // (a non-finite step length, clamp or pose: nothing is written)
+            double nw, nv;
+            if (!pose_compose<false>(x, (double)a.step[s], (double)a.max_rot[s], (double)a.max_trans[s], nullptr, a.R + s * 9,
+                                     a.T + s * 3, nw, nv))
                 status = RRL_NEWTON_FAILED;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    a.T[s * 3 + i] = (float)Tn[i];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) a.R[s * 9 + 3 * i + j] = (float)Rn[i][j];
-                }
+            else
                 pose_stop_update(stop, s, (float)nw, (float)nv, a.last_step, a.tol_rot, a.tol_trans, a.patience);
-            }
         }
     }
     pose_stop_store(stop, status, st);

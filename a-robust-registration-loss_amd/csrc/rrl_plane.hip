@@ -4,17 +4,18 @@
 // 6 x 6 pose step about a pivot, and the four entries of an epoch as one C call.
 //
 // The arithmetic rule is rrl_kabsch.hip's: every sum is a fixed-order double sum of double terms formed from float32 inputs
-// (per-lane accumulators, wave_sum_d, four wavefronts, one partial row per workgroup, the partial rows in index order, no
-// atomics); everything after the sums is double on one lane, rounded to float32 once.  The solver is se3_newton_step_kernel's
-// (rrl_pose_solve.h); the pose composition is restated here, about a pivot: as helpers shared with rrl_newton.hip it moved that
-// unit's machine code (tools/device_asm_digest.py), so that unit keeps its own.
+// (rrl_pair_sums.h: the pair walk, per-lane accumulators, wave_sum_d, four wavefronts, one partial row per workgroup, the
+// partial rows in index order, no atomics); everything after the sums is double on one lane, rounded to float32 once.  The
+// solver and the pose composition are se3_newton_step_kernel's (rrl_pose_solve.h), the composition in its form about a pivot;
+// the epoch's host front is rrl_icp_epoch's (rrl_cloud_epoch.h).
 #include <cstddef>
 #include <cstdint>
 
 #include "rrl_ws.h"
 #include "rrl_pose_tail.h"
 #include "rrl_pose_solve.h"
-#include "rrl_wave_sum_d.h"
+#include "rrl_pair_sums.h"
+#include "rrl_cloud_epoch.h"
 
 // ---------------------------------------------------------------------------------------
 // 1. Normals.  Grid (ceil(S / 4), B): one wavefront per row, lane = slot of the row's index list, the four waves of a
@@ -175,8 +176,7 @@ __device__ __forceinline__ void plane_finish(const PlaneArgs &a, int b, const do
 __global__ __launch_bounds__(256) void plane_part_kernel(const PlaneArgs a) {
     __shared__ double s_red[4][PL_SUMS];
     __shared__ double s_tot[PL_SUMS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int bx = blockIdx.x, b = blockIdx.y, N = a.N, M = a.M;
+    const int tid = threadIdx.x, bx = blockIdx.x, b = blockIdx.y, N = a.N, M = a.M;
     const int c1 = rrl_rows(a.count1, b, N), c2 = rrl_rows(a.count2, b, M);
     const float *__restrict__ Y = a.moved + (size_t)b * N * 3;
     const float *__restrict__ Tp = a.tar + (size_t)b * M * a.st;
@@ -193,32 +193,19 @@ __global__ __launch_bounds__(256) void plane_part_kernel(const PlaneArgs a) {
     for (int r = 0; r < PL_ROWS / 256; ++r) {
         const int i = bx * PL_ROWS + r * 256 + tid;
         if (i >= N) continue;
-        bool skip = i >= c1, gated = false;
-        unsigned idx = (unsigned)i;
-        float dist = 0.0f;
-        if (!skip) {
-            if (a.keys) {
-                const unsigned long long key = a.keys[(size_t)b * N + i];
-                idx = (unsigned)(key & 0xffffffffull);
-                dist = __uint_as_float((unsigned)(key >> 32));
-                skip = key == ~0ull || idx >= (unsigned)M || idx >= (unsigned)c2;
-                gated = dist > gate;
-            } else {
-                skip = i >= c2;
-            }
-        }
-        if (skip) {
+        const PairRow pair = pair_walk(a.keys, b, N, i, c1, M, c2, gate);
+        if (pair.skip) {
             acc[RRL_PLANE_SKIPPED] += 1.0;
             continue;
         }
-        if (gated) continue;
-        const float *__restrict__ nr = Np + (size_t)idx * 3;  // idx < min(M, c2): inside sample b's rows
+        if (pair.gated) continue;
+        const float *__restrict__ nr = Np + (size_t)pair.idx * 3;  // idx < min(M, c2): inside sample b's rows
         const float n0 = nr[0], n1 = nr[1], n2 = nr[2];
         if (!(fabsf(n0) < INFINITY && fabsf(n1) < INFINITY && fabsf(n2) < INFINITY) || (n0 == 0.0f && n1 == 0.0f && n2 == 0.0f))
             continue;  // a partner without a normal: weight 0, neither used nor skipped
         const double w = a.w ? (double)a.w[(size_t)b * N + i] : 1.0;
         const float *__restrict__ yr = Y + (size_t)i * 3;
-        const float *__restrict__ br = Tp + (size_t)idx * a.st;
+        const float *__restrict__ br = Tp + (size_t)pair.idx * a.st;
         const double y[3] = {(double)yr[0], (double)yr[1], (double)yr[2]};
         const double nn[3] = {(double)n0, (double)n1, (double)n2};
         const double p[3] = {y[0] - c[0], y[1] - c[1], y[2] - c[2]};
@@ -235,21 +222,12 @@ __global__ __launch_bounds__(256) void plane_part_kernel(const PlaneArgs a) {
         }
         acc[RRL_PLANE_W] += w;
         acc[RRL_PLANE_RES] += w * (res * res);
-        acc[RRL_PLANE_KEYMEAN] += w * (double)dist;
+        acc[RRL_PLANE_KEYMEAN] += w * (double)pair.dist;
         acc[RRL_PLANE_USED] += 1.0;
     }
-#pragma unroll
-    for (int q = 0; q < PL_SUMS; ++q) acc[q] = wave_sum_d(acc[q]);
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < PL_SUMS; ++q) s_red[wave][q] = acc[q];
-    __syncthreads();
-    if (tid < PL_SUMS) {
-        const double tot = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
-        a.part[((size_t)b * gridDim.x + bx) * PL_SUMS + tid] = tot;
-        s_tot[tid] = tot;
-    }
+    const double tot = block_sum_d(acc, s_red, a.part + ((size_t)b * gridDim.x + bx) * PL_SUMS);
     if (gridDim.x != 1) return;  // (uniform)
+    if (tid < PL_SUMS) s_tot[tid] = tot;
     __syncthreads();
     if (tid < PL_SUMS) plane_finish(a, b, s_tot, tid);
 }
@@ -258,11 +236,7 @@ __global__ __launch_bounds__(256) void plane_part_kernel(const PlaneArgs a) {
 __global__ __launch_bounds__(64) void plane_finish_kernel(const PlaneArgs a, int nblk) {
     __shared__ double s_tot[PL_SUMS];
     const int b = blockIdx.x, lane = threadIdx.x;
-    if (lane < PL_SUMS) {
-        double s = 0.0;
-        for (int k = 0; k < nblk; ++k) s += a.part[((size_t)b * nblk + k) * PL_SUMS + lane];
-        s_tot[lane] = s;
-    }
+    if (lane < PL_SUMS) s_tot[lane] = part_rows_total<PL_SUMS>(a.part, b, nblk, lane);
     __syncthreads();
     if (lane < PL_SUMS) plane_finish(a, b, s_tot, lane);
 }
@@ -335,82 +309,12 @@ __global__ __launch_bounds__(64) void plane_step_kernel(const PlaneStepArgs a) {
         if (!newton_solve(H, g, (double)a.damping[s], a.eps, x)) {
             status = RRL_PLANE_FAILED;
         } else {
-            const double sc = (double)a.step[s];
-            double w[3] = {sc * x[0], sc * x[1], sc * x[2]}, v[3] = {sc * x[3], sc * x[4], sc * x[5]};
-            double nw = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), nv = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            const double mr = (double)a.max_rot[s], mt = (double)a.max_trans[s];
-            if (nw > mr) {
-                const double f = mr / nw;
-                w[0] *= f; w[1] *= f; w[2] *= f;
-                nw = mr;
-            }
-            if (nv > mt) {
-                const double f = mt / nv;
-                v[0] *= f; v[1] *= f; v[2] *= f;
-                nv = mt;
-            }
-            // Rot = I + A K + Bc K K, K = [w]x (Rodrigues; the series below 1e-4: their next terms are < 1e-26)
-            const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
-            double A, Bc;
-            if (th < 1e-4) {
-                A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0);
-                Bc = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0);
-            } else {
-                A = sin(th) / th;
-                Bc = (1.0 - cos(th)) / th2;
-            }
-            const double K[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
-            double Rot[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const double kk = K[i][0] * K[0][j] + K[i][1] * K[1][j] + K[i][2] * K[2][j];
-                    Rot[i][j] = (i == j ? 1.0 : 0.0) + A * K[i][j] + Bc * kk;
-                }
-            double Ro[3][3], To[3], Rn[3][3], Tn[3], c[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                c[i] = a.pivot ? (double)a.pivot[s * 3 + i] : 0.0;
-                To[i] = (double)a.T[s * 3 + i] - c[i];  // about the pivot
-#pragma unroll
-                for (int j = 0; j < 3; ++j) Ro[i][j] = (double)a.R[s * 9 + 3 * i + j];
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                Tn[j] = ((To[0] * Rot[j][0] + To[1] * Rot[j][1] + To[2] * Rot[j][2]) + c[j]) + v[j];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) Rn[i][j] = Ro[i][0] * Rot[j][0] + Ro[i][1] * Rot[j][1] + Ro[i][2] * Rot[j][2];
-            }
-            // one Gram-Schmidt pass over the rows: compositions of float-rounded matrices do not drift
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int p = 0; p < i; ++p) {
-                    const double d = Rn[i][0] * Rn[p][0] + Rn[i][1] * Rn[p][1] + Rn[i][2] * Rn[p][2];
-                    Rn[i][0] -= d * Rn[p][0]; Rn[i][1] -= d * Rn[p][1]; Rn[i][2] -= d * Rn[p][2];
-                }
-                const double n = sqrt(Rn[i][0] * Rn[i][0] + Rn[i][1] * Rn[i][1] + Rn[i][2] * Rn[i][2]);
-                Rn[i][0] /= n; Rn[i][1] /= n; Rn[i][2] /= n;
-            }
-            bool finite = true;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                finite = finite && fabs(Tn[i]) < (double)INFINITY;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) finite = finite && fabs(Rn[i][j]) < (double)INFINITY;
-            }
-            if (!finite) {  // (a non-finite step length, clamp, pivot or pose: nothing is written)
+            double nw, nv;
+            if (!pose_compose<true>(x, (double)a.step[s], (double)a.max_rot[s], (double)a.max_trans[s],
+                                    a.pivot ? a.pivot + s * 3 : nullptr, a.R + s * 9, a.T + s * 3, nw, nv))
                 status = RRL_PLANE_FAILED;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    a.T[s * 3 + i] = (float)Tn[i];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) a.R[s * 9 + 3 * i + j] = (float)Rn[i][j];
-                }
+            else
                 pose_stop_update(stop, s, (float)nw, (float)nv, a.last_step, a.tol_rot, a.tol_trans, a.patience);
-            }
         }
     }
     pose_stop_store(stop, status, st);
@@ -443,20 +347,13 @@ extern "C" int rrl_plane_step_batch(const double *neq, const int32_t *info, cons
 
 // One point-to-plane epoch: four public entries back to back, every refusal before the first launch (host code only).
 extern "C" int rrl_plane_icp_epoch(const rrl_plane_epoch_args *a, void *stream) {
-    if (!a || a->struct_bytes != (int32_t)sizeof(rrl_plane_epoch_args)) return RRL_E_ARG;
+    if (!cloud_epoch_front_ok(a) || !a->normals) return RRL_E_ARG;
     const int B = a->B, N = a->N, M = a->M;
-    if (B <= 0 || B > 32767 || N <= 0 || M <= 0 || (N > M ? N : M) > rrl_sort_capacity()) return RRL_E_ARG;
-    if (!a->src || !a->tar || !a->normals || !a->moved || !a->cham_ws || !a->best_x || !a->best_y || !a->values || !a->part) return RRL_E_ARG;
-    if ((a->count1 == nullptr) != (a->count2 == nullptr) || (a->order_x == nullptr) != (a->order_y == nullptr)) return RRL_E_ARG;
     if (!plane_step_args_ok(a->neq, a->info, a->damping, a->step, a->max_rot, a->max_trans, a->tol_rot, a->tol_trans, a->patience, a->eps,
                             a->R, a->T, a->state))
         return RRL_E_ARG;
-    if ((((uintptr_t)a->part) & 7) != 0) return RRL_E_ARG;
-    if (a->cham_ws_bytes < rrl_chamfer_workspace_bytes(B, N, M) || a->part_bytes < rrl_plane_part_bytes(B, N)) return RRL_E_WS;
-    int rc = rrl_rigid_apply_fwd(a->src, a->R, a->T, a->moved, B, N, 0, 0, stream);
-    if (rc) return rc;
-    rc = rrl_chamfer_tree_fwd_counted(a->moved, a->tar, a->count1, a->count2, a->cham_ws, a->cham_ws_bytes, a->best_x, a->best_y,
-                                      a->values, nullptr, B, N, M, a->order_x, a->order_y, stream);
+    if (!cloud_epoch_cham_ws_ok(a) || a->part_bytes < rrl_plane_part_bytes(B, N)) return RRL_E_WS;
+    int rc = cloud_epoch_pair(a, stream);
     if (rc) return rc;
     rrl_plane_args k = {};
     k.struct_bytes = (int32_t)sizeof(k);

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+import newton_refs as NR
 import plane_refs as PR
 from test_plane_refs_host import lattice
 
@@ -341,6 +342,42 @@ def test_step_against_the_twin_on_the_device_sums(mods):
     assert cursor.tolist() == [1, 2, 3, 2, 1, 4]
     assert table[0, 0].tolist() == row[0].tolist() and table[1, 1].tolist() == row[1].tolist() and table[2, 2].tolist() == row[2].tolist()
     assert table[1, 3].tolist() == row[3].tolist() and not table[:, 5].any()  # (pair 5's cursor is past the table: unlogged)
+
+
+def test_both_steps_apply_one_composition(mods):
+    """rrl_se3_newton_step_batch and rrl_plane_step_batch (no pivot) fed ONE system -- NR.diagonal_neq as the sixteen sums of
+    the one, its H and g packed into the 32-double row of the other -- with the same damping, scale, clamps and tolerances, on
+    three generic poses, pose 1 clamped in rotation: R, T and last_step leave both with the same bytes, state words 0 .. 2 agree.
+    Every given value is exact in float32 (the sums reach the Newton step as floats)."""
+    _, _, _, ops = mods
+    rs = np.random.default_rng(21)
+    B, patience = 3, 2
+    lengths = [(0.125, 0.25), (0.5, 0.0625), (0.03125, 0.375)]
+    sums = np.stack([NR.diagonal_neq(*x) for x in lengths])
+    rows = np.zeros((B, 32))
+    for b in range(B):
+        H, g = NR.assemble(sums[b])
+        rows[b, PR.H0:PR.H0 + 21], rows[b, PR.G0:PR.G0 + 6] = H[np.triu_indices(6)], g
+    info = np.zeros((B, 4), np.int32)  # [1] = RRL_FIT_OK
+    R0 = np.stack([PR.rodrigues(0.4 * rs.standard_normal(3)).T for _ in range(B)]).astype(np.float32)
+    T0 = (3.0 * rs.standard_normal((B, 3))).astype(np.float32)
+    state0 = np.array([[4, 1, -1, 0]] * B, np.int32)
+    damping, step, max_trans, tol = (np.full(B, v, np.float32) for v in (0.25, 0.5, 1.0, 2.0 ** -10))
+    max_rot = np.array([1.0, 0.03125, 1.0], np.float32)
+    tsum, trow, tinfo, tdamp, tstep, tmr, tmt, ttol = cuda(sums, rows, info, damping, step, max_rot, max_trans, tol)
+    Rn, Tn, sn, Rp, Tp, sp = cuda(R0, T0, state0, R0, T0, state0)
+    ln, lp = torch.full((B, 2), -1.0, device="cuda"), torch.full((B, 2), -1.0, device="cuda")
+    P = ops._p
+    ops.se3_newton_step_batch(tsum, None, Rn, Tn, sn, damping=tdamp, step=tstep, max_rot=tmr, max_trans=tmt, tol_rot=ttol, tol_trans=ttol,
+                              patience=patience, eps=1e-12, last_step=ln)
+    ops._run(Rp.device, "rrl_plane_step_batch", P(trow), P(tinfo), None, P(tdamp), P(tstep), P(tmr), P(tmt), P(ttol), P(ttol), patience,
+             1e-12, P(Rp), P(Tp), None, None, None, 0, None, P(lp), P(sp), B)
+    torch.cuda.synchronize()
+    assert sn[:, 3].tolist() == [NR.STEPPED] * B and sp[:, 3].tolist() == [PR.STEPPED] * B
+    assert bits(Rn) == bits(Rp) and bits(Tn) == bits(Tp) and bits(ln) == bits(lp), (Rn - Rp, Tn - Tp, ln - lp)
+    assert torch.equal(sn[:, :3], sp[:, :3]) and sn[:, 0].tolist() == [5] * B
+    assert bits(Rn) != R0.tobytes() and bits(Tn) != T0.tobytes()  # (a step was applied)
+    assert ln[1, 0].item() == 0.03125 and 0.0 < ln[0, 0].item() < 1.0 and 0.0 < ln[2, 0].item() < 1.0  # pose 1 alone is clamped
 
 
 # ---- the epoch --------------------------------------------------------------------------------------------------------------------
