@@ -17,6 +17,7 @@ CSRC = os.environ.get("RRL_CSRC") or os.path.join(PKG, "csrc")  # (RRL_CSRC: A/B
 EXP_FLAGS = os.environ.get("RRL_HIPCC_FLAGS", "").split()
 LIBDIR = os.path.join(PKG, "lib_exp" if EXP_FLAGS else "lib")
 LIB = os.path.join(LIBDIR, "librrl_hip.so")
+HEADER = os.path.join(os.path.dirname(PKG), "include", "rrl.h")  # the C ABI: the library's and, through _abi.py, the binding's
 SOURCES = ["rrl_scan.hip", "rrl_cull.hip", "rrl_sparse.hip", "rrl_geom.hip", "rrl_neigh.hip", "rrl_knn_tree.hip", "rrl_chamfer.hip", "rrl_order.hip", "rrl_epoch.hip",
            "rrl_wide.hip", "rrl_call.hip", "rrl_newton.hip", "rrl_kabsch.hip", "rrl_sinkhorn.hip", "rrl_group.hip", "rrl_plane.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
@@ -32,7 +33,7 @@ def needs_build():
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-    deps.append(os.path.join(os.path.dirname(PKG), "include", "rrl.h"))
+    deps.append(HEADER)
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -7,8 +7,7 @@ rrl_register_newton_epoch; rrl_hip/newton.py).
    objective with the linearised residual IS F(0) + g delta + delta^T H delta / 2, and the linearisation is the derivative
    of Q1(delta); and the loss twin's own directional derivative along -H^-1 g is negative.
 2. What the three entries refuse and with which code -- fake pointers, no GPU: every refusal happens on the host before the
-   first launch, RRL_E_ARG before RRL_E_WS --, the ctypes mirror of rrl_register_newton_args against the header compiled by
-   gcc, and the ValueErrors of NewtonRegistration that need no GPU.  tools/register_newton_refusals.cpp makes the same calls
+   first launch, RRL_E_ARG before RRL_E_WS --, the header's status codes against the twin's, and the ValueErrors of NewtonRegistration that need no GPU.  tools/register_newton_refusals.cpp makes the same calls
    from a stand-alone program, which tools/refusals_sanitize.sh runs under AddressSanitizer + UBSan."""
 import ctypes
 
@@ -16,7 +15,6 @@ import numpy as np
 import pytest
 import torch
 
-import abi_layout
 import loss_refs
 import newton_refs as NR
 from conftest import load_golden
@@ -332,13 +330,11 @@ def test_the_newton_epoch_refuses_before_its_first_launch(lib, row):
     assert call_epoch(lib, over) == code
 
 
-def test_the_epoch_struct_matches_the_header(tmp_path):
-    """rrl_register_newton_args as rrl_hip/_lib.py declares it against include/rrl.h compiled by gcc: same size, same offset
-    of every field; the status codes and the number of sums as the header defines them."""
-    from rrl_hip import _lib
-    codes = '  printf("codes %d%d%d%d%d\\n", RRL_NEWTON_STEPPED, RRL_NEWTON_GATED, RRL_NEWTON_FAILED, RRL_NEWTON_DONE, RRL_NEQ_SUMS);'
-    got = abi_layout.assert_struct_matches_header(_lib.RegisterNewtonArgs, "rrl_register_newton_args", tmp_path, [codes])
-    assert got["codes"] == f"{_lib.NEWTON_STEPPED}{_lib.NEWTON_GATED}{_lib.NEWTON_FAILED}{_lib.NEWTON_DONE}{NR.NSUMS}"
+def test_the_twin_uses_the_headers_codes():
+    """The status codes and the number of sums as the header defines them (each against gcc's value, and the layout of
+    rrl_register_newton_args: tests/test_abi_host.py) are the float64 twin's."""
+    from rrl_hip import _abi, _lib
+    assert _abi.CONSTANTS["RRL_NEQ_SUMS"] == NR.NSUMS
     assert (NR.STEPPED, NR.GATED, NR.FAILED, NR.DONE) == (_lib.NEWTON_STEPPED, _lib.NEWTON_GATED, _lib.NEWTON_FAILED, _lib.NEWTON_DONE)
 
 

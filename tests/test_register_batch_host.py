@@ -1,15 +1,12 @@
 """CPU-side checks of the batched registration loop (include/rrl.h rrl_se3_adam_step_batch / rrl_register_epoch,
 rrl_hip/register.py): what the two entries refuse and with which code -- fake pointers, no GPU: every refusal happens on the
-host before the first launch, in the documented order RRL_E_ARG, RRL_E_RANGE, RRL_E_WS --, the ctypes mirror of
-rrl_register_epoch_args against the header compiled by gcc, the ValueErrors of PairRegistration that need no GPU, and the
+host before the first launch, in the documented order RRL_E_ARG, RRL_E_RANGE, RRL_E_WS --, the ValueErrors of PairRegistration that need no GPU, and the
 learning-rate schedule of PairRegistration.run against the demo's adjust_learning_rate."""
 import ctypes
 import importlib
 
 import pytest
 import torch
-
-import abi_layout
 
 FAKE = ctypes.c_void_p(256)
 BIG = 1 << 50
@@ -142,13 +139,6 @@ def test_the_batched_pose_step_refuses_before_any_launch(lib, row):
 def test_the_batched_epoch_refuses_before_its_first_launch(lib, row):
     _, over, code = row
     assert call_epoch(lib, over) == code
-
-
-def test_the_epoch_struct_matches_the_header(tmp_path):
-    """rrl_register_epoch_args as rrl_hip/_lib.py declares it against include/rrl.h compiled by gcc: same size, same
-    offset of every field."""
-    from rrl_hip import _lib
-    abi_layout.assert_struct_matches_header(_lib.RegisterEpochArgs, "rrl_register_epoch_args", tmp_path)
 
 
 def test_pair_registration_refuses_with_the_alternative(lib):
