@@ -170,6 +170,128 @@ def icp_pairs(src, tar, n_epoch=60, check_every=0, **kw):
     return reg.R, reg.T, reg.history()
 
 
+# ---- robust ICP: Welsch weights with an annealed scale (include/rrl.h rrl_robust_icp_epoch) ----------
+# The defaults are the settings of the float64 twin's acceptance run (tests/robust_refs.py outlier_pair: a 10 degree pose, 20 %
+# of the source replaced by uniform outliers): at a starting scale of three median residuals a pair at the median still weighs
+# exp(-1 / 18), halving reaches the end scale in four or five levels, and the level cap ends a level whose
+# pairing cycles instead of settling.
+NU_START = 3.0    # times the first epoch's median residual
+ANNEAL = 0.5
+LEVEL_CAP = 10    # epochs at one scale, at the most (0: no cap)
+
+
+def check_robust_request(nu_start=NU_START, nu_end=None, anneal=ANNEAL, level_cap=LEVEL_CAP, patience=PATIENCE, B=None):
+    """The refusals of RobustIcpRegistration beyond check_request's that need no GPU (ValueError)."""
+    if not float(nu_start) > 0.0:
+        raise ValueError("nu_start must be positive (a multiple of the first epoch's median residual)")
+    if not 0.0 < float(anneal) < 1.0:
+        raise ValueError("anneal must lie in (0, 1): the factor a settled pair's scale is multiplied by")
+    if isinstance(level_cap, bool) or int(level_cap) != level_cap or int(level_cap) < 0:
+        raise ValueError("level_cap must be a non-negative integer (0: no cap)")
+    if int(patience) <= 0 and int(level_cap) == 0:
+        raise ValueError("patience = 0 with level_cap = 0: no level would ever end, nothing would anneal")
+    if nu_end is not None:
+        ends = nu_end.detach().reshape(-1).tolist() if isinstance(nu_end, torch.Tensor) else \
+            [float(x) for x in (nu_end if isinstance(nu_end, (list, tuple)) else [nu_end])]
+        if B is not None and len(ends) not in (1, int(B)):
+            raise ValueError(f"nu_end must be a number or one per pair ({B}); got {len(ends)}")
+        if not all(x > 0.0 for x in ends):
+            raise ValueError("nu_end must be positive (the final scale, in the clouds' units), or None for the target's spacing")
+
+
+def target_spacing(tar, counts=None):
+    """(B,) float32: per cloud, the lower median distance from a point to its nearest OTHER point of the cloud (tar (B, M, 3),
+    counts (B,) int32 or None), from the library's own 3-NN; 0 where no point has another (a capacity below three, a count below two)."""
+    from .neighbors import knn3_self
+    B, M = tar.shape[0], tar.shape[1]
+    if M < 3:
+        return torch.zeros(B, dtype=torch.float32, device=tar.device)
+    nn = knn3_self(tar, counts=counts).to(torch.int64)
+    rows = torch.arange(M, device=tar.device)[None, :, None]
+    d = (tar[torch.arange(B, device=tar.device)[:, None, None], nn] - tar[:, :, None, :]).norm(dim=3)  # (B, M, 3)
+    inf = torch.full_like(d[:, :, 0], float("inf"))
+    d = torch.where(nn == rows, float("inf"), d).amin(dim=2)  # (the point itself is among its three nearest)
+    if counts is not None:
+        d = torch.where(rows[:, :, 0] < counts[:, None], d, inf)
+    d = torch.where(torch.isfinite(d), d, inf)  # (NaN filler, a cloud of one point's copies)
+    k = torch.isfinite(d).sum(1)
+    med = torch.gather(torch.sort(d, dim=1).values, 1, ((k - 1).clamp(min=0) // 2)[:, None])[:, 0]
+    return torch.where(k > 0, med, torch.zeros_like(med)).contiguous()
+
+
+class RobustIcpRegistration(_CloudLoop):
+    """IcpRegistration whose pairs carry Welsch weights exp(-d^2 / (2 nu^2)) -- the loss's own function of the nearest
+    neighbour's distance d -- with a per-pair scale nu annealed from coarse to fine (Fast-Robust-ICP without its Anderson
+    acceleration): source points with no partner in the target fade out instead of pulling the pose.  One C call per epoch.
+
+    src, tar, counts1, counts2, R0 / T0 / xi0, max_dist, tol_rot, tol_trans, patience, table_rows: as IcpRegistration; here
+    `patience` calm epochs end a LEVEL, and the pair is done when a level ends at the final scale.
+    nu_start: the first epoch sets nu = nu_start x the median residual of its pairing (never below nu_end).  nu_end: the
+    final scale, a number or one per pair, in the clouds' units; None: each target's median nearest-neighbour spacing over
+    3 sqrt(3), computed once here.  anneal: the factor of a level's end.  level_cap: a level also ends after this many epochs
+    (0: only by patience).
+
+    .nu (B,): the current scales; .weights (B, N): the latest epoch's weights (0 on rows without a partner); .levels (B,)
+    int32: levels finished; .level (B, 2) int32: (epochs at this scale, levels finished); .med_sq (B,): the first epoch's median
+    squared residual.  Everything else as IcpRegistration; .history()'s residual is the fit's WEIGHTED mean squared residual."""
+
+    _ARGS, _ENTRY = _lib.IcpEpochArgs, "rrl_robust_icp_epoch"  # .epoch(): ONE C call, on rrl_icp_epoch's own struct
+
+    def __init__(self, src, tar, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, max_dist=None, tol_rot=TOL_ROT,
+                 tol_trans=TOL_TRANS, patience=PATIENCE, table_rows=4096, nu_start=NU_START, nu_end=None, anneal=ANNEAL,
+                 level_cap=LEVEL_CAP):
+        check_robust_request(nu_start, nu_end, anneal, level_cap, patience,
+                             src.shape[0] if isinstance(src, torch.Tensor) and src.dim() == 3 else None)
+        lib = self._init_clouds(src, tar, counts1, counts2, R0, T0, xi0, max_dist, tol_rot, tol_trans, patience, table_rows)
+        B, dev, f32 = self.B, self.dev, dict(dtype=torch.float32, device=self.dev)
+        self.nu_start, self.anneal, self.level_cap = float(nu_start), float(anneal), int(level_cap)
+        if nu_end is None:
+            self.nu_end = (target_spacing(self.tar, self.counts2) / (3.0 * 3.0 ** 0.5)).contiguous()
+        else:
+            self.nu_end = self._per_pair(nu_end)
+        self.nu = self.nu_end.clone()
+        self.weights = torch.zeros(B, self.N, **f32)
+        self.med_sq = torch.zeros(B, **f32)
+        self.med_info = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+        self.level = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+        self.part = torch.empty(max(int(lib.rrl_kabsch_part_bytes(B, self.N)) // 8, 1), dtype=torch.float64, device=dev)
+        self.Rk, self.Tk = torch.zeros(B, 3, 3, **f32), torch.zeros(B, 3, **f32)
+        self.fit = torch.zeros(B, _lib.FIT_DOUBLES, dtype=torch.float64, device=dev)
+        self.info = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        self._init_log(table_rows)
+        self._bind()
+
+    def _make_args(self):
+        P = ops._p
+        a = self._ARGS()
+        self._cloud_args(a)
+        a.eps_w, a.rank_tol = 0.0, RANK_TOL
+        a.part, a.part_bytes = P(self.part), self.part.numel() * 8
+        a.Rk, a.Tk, a.fit, a.info = P(self.Rk), P(self.Tk), P(self.fit), P(self.info)
+        # what the annealing adds travels as plain arguments, after `init`; the struct's w stays NULL
+        self._extra = (P(self.weights), P(self.nu), P(self.nu_end), P(self.med_sq), P(self.med_info), self.nu_start, self.anneal,
+                       self.level_cap, P(self.level))
+        return a
+
+    def epoch(self):
+        """One epoch of all B pairs: ONE C call, nothing read back.  The first sets the starting scales from its own pairing
+        (init = 1); every later one is the steady epoch, which is what a graph captured after the first replays."""
+        with ops._guard(self.dev):
+            _lib.check(self._call(self._aref, 1 if self.epochs == 0 else 0, *self._extra, ops._stream(self.dev)), self._ENTRY)
+        self.epochs += 1
+
+    @property
+    def levels(self):
+        return self.level[:, 1]
+
+
+def robust_icp_pairs(src, tar, n_epoch=80, check_every=0, **kw):
+    """RobustIcpRegistration(...).run(n_epoch, check_every) -> (R (B, 3, 3), T (B, 3), history)."""
+    reg = RobustIcpRegistration(src, tar, **kw)
+    reg.run(n_epoch, check_every)
+    return reg.R, reg.T, reg.history()
+
+
 def check_plane_request(tar_shape, normals_shape, normal_radius, nsample, eps=NEWTON_EPS):
     """The refusals of PlaneIcpRegistration beyond check_request's that need no GPU (ValueError)."""
     if normals_shape is None and normal_radius is None:

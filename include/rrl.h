@@ -1361,6 +1361,60 @@ typedef struct rrl_plane_epoch_args {
 } rrl_plane_epoch_args;
 int rrl_plane_icp_epoch(const rrl_plane_epoch_args *args, void *stream);
 
+/* ---- Robust ICP: Welsch weights with an annealed scale around the keyed Kabsch fit ----------
+ * Point-to-point ICP whose pairs carry the weights w = exp(-d^2 / (2 nu^2)) of the loss's own Welsch function, d^2 the key's
+ * distance word, with a per-pair scale nu that starts at a multiple of the first epoch's median residual and is multiplied
+ * by `anneal` whenever the pose has settled at the current scale, down to nu_end (Fast-Robust-ICP without its Anderson
+ * acceleration).  A VALID row, everywhere below, is a row rrl_kabsch_fwd would not skip: below count_a[b], its key not all
+ * ones, its key's index < m and < count_b[b] (counts NULL: n / m; clamped to [0, n] / [0, m] by the kernels).
+ *
+ * rrl_key_median: for each pair b the exact LOWER median of the distance words (key >> 32) of the valid rows of keys [B][n]:
+ * the word of 0-based rank (k - 1) / 2 among the k valid words sorted as uint32 (non-negative floats sort alike; torch.median's
+ * rule), bit for bit -> med_sq [B]; info [B][2] = (k, k == 0); med_sq = 0 when k == 0.  With nu != NULL also
+ * nu[b] = max(float32(nu_scale * sqrt(double(med_sq[b]))), nu_end[b]) (nu_end[b] when the left side is NaN).  One workgroup
+ * per pair, four 8-bit digit passes over an LDS histogram of integer counts: no floating atomics, the same bits on every call.
+ * RRL_E_ARG before the launch: B < 0 or > 32767, n <= 0 or beyond rrl_sort_capacity(), m <= 0, a NULL keys / med_sq / info,
+ * exactly one count, nu without nu_end or with nu_scale <= 0 (or NaN).  B == 0 returns 0 without a launch. */
+int rrl_key_median(const uint64_t *keys, const int32_t *count_a, const int32_t *count_b, int B, int n, int m, float *med_sq,
+                   int32_t *info, float *nu, double nu_scale, const float *nu_end, void *stream);
+
+/* w [B][n]: w[b][i] = float32(exp(-double(d^2) / (2 double(nu[b])^2))) for a valid row whose distance word d^2 is a number,
+ * exactly 0 for every other row, and 0 on all rows of a pair whose nu[b] is <= 0 or not finite (the fit then reports
+ * RRL_FIT_FEW).  Grid (ceil(n / 256), B).  RRL_E_ARG before the launch: B < 0 or > 32767, n <= 0, m <= 0, a NULL keys / nu / w,
+ * exactly one count.  B == 0 returns 0 without a launch. */
+int rrl_welsch_weights(const uint64_t *keys, const int32_t *count_a, const int32_t *count_b, const float *nu, float *w, int B,
+                       int n, int m, void *stream);
+
+/* rrl_icp_step_batch's step -- the same arguments, step lengths, log row and status words -- with the annealing rule in
+ * place of its stopping rule.  nu [B] (in / out), nu_end [B], level [B][2] int32 = (epochs at this nu, levels finished).
+ * Pair b, unless done: the ICP step updates the pose and the calm count (a failed or skipped fit keeps the pose and nu and
+ * resets the calm count); level[b][0] += 1; the level is OVER when patience > 0 and calm >= patience, or when level_cap > 0
+ * and level[b][0] >= level_cap.  Over with nu[b] > nu_end[b]: nu[b] = max(nu[b] * anneal, nu_end[b]) in float32, calm = 0,
+ * level[b] = (0, level[b][1] + 1), the pair is NOT done.  Over otherwise: the pair is done as rrl_icp_step_batch marks it
+ * (state word 2 = the epochs issued; from the next call on the pose, nu and level keep their bits and the status is
+ * RRL_POSE_DONE).  RRL_E_ARG before the launch: what rrl_icp_step_batch refuses, a NULL nu / nu_end / level, anneal outside
+ * (0, 1), level_cap < 0, patience <= 0 together with level_cap == 0. */
+int rrl_robust_step_batch(const float *Rk, const float *Tk, const int32_t *info, const double *fit, float *R, float *T,
+                          const float *tol_rot, const float *tol_trans, int patience, const float *value, float *table,
+                          long long *cursor, long long nrows, float *row, float *last_step, int32_t *state, float *nu,
+                          const float *nu_end, float anneal, int level_cap, int32_t *level, int B, void *stream);
+
+/* One robust ICP epoch for a batch of B pairs as ONE call: the entries back to back on the caller's stream, nothing else --
+ *   1. rrl_rigid_apply_fwd: moved = src R + T;
+ *   2. rrl_chamfer_tree_fwd_counted on (moved, tar, count1, count2) with the prepared orders -> best_x, best_y, values [B];
+ *   3. when init != 0, rrl_key_median on best_x -> med_sq, med_info and the starting nu (nu_scale, nu_end);
+ *   4. rrl_welsch_weights -> w [B][N];
+ *   5. rrl_kabsch_fwd with a = src (as given), keys = best_x, b = tar, the counts, w, gate_sq -> Rk, Tk, fit, info;
+ *   6. rrl_robust_step_batch with value = values.
+ * args: rrl_icp_epoch's own argument struct, every field with its meaning there -- the clouds, the walk's buffers, the fit's
+ * and the step's -- except w, which must be NULL: the weights are this epoch's OUTPUT and arrive, with everything the
+ * annealing adds, as plain arguments (the library keeps one struct per epoch shape; this epoch has rrl_icp_epoch's shape).
+ * No host read-back.  Refusals, all before the first launch: RRL_E_ARG -- what rrl_icp_epoch refuses, args->w != NULL, a NULL
+ * w / nu / nu_end / level / med_sq / med_info, anneal outside (0, 1), level_cap < 0, nu_scale <= 0, patience <= 0 together with
+ * level_cap == 0 --, then RRL_E_WS: a short cham_ws or part. */
+int rrl_robust_icp_epoch(const rrl_icp_epoch_args *args, int init, float *w, float *nu, const float *nu_end, float *med_sq,
+                         int32_t *med_info, double nu_scale, float anneal, int level_cap, int32_t *level, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
