@@ -1,8 +1,9 @@
-// rrl_cloud_epoch.h -- the host front the two cloud epochs share (rrl_icp_epoch, rrl_kabsch.hip; rrl_plane_icp_epoch,
-// rrl_plane.hip), host code only, rrl_epoch.hip's idiom: templates over the argument structs, which name every shared field
-// alike (include/rrl.h rrl_icp_epoch_args, rrl_plane_epoch_args).  An epoch asks cloud_epoch_front_ok and its fit's own
-// RRL_E_ARG checks, then cloud_epoch_cham_ws_ok and its fit's own RRL_E_WS check, and only then cloud_epoch_pair: every
-// refusal before the first launch, RRL_E_ARG first.
+// rrl_cloud_epoch.h -- the host front the three cloud epochs share (rrl_icp_epoch, rrl_kabsch.hip; rrl_robust_icp_epoch,
+// rrl_robust.hip; rrl_plane_icp_epoch, rrl_plane.hip), host code only, rrl_epoch.hip's idiom: templates over the argument
+// structs, which name every shared field alike (include/rrl.h rrl_icp_epoch_args, rrl_plane_epoch_args).  An epoch asks
+// cloud_epoch_front_ok and its fit's own RRL_E_ARG checks, then cloud_epoch_cham_ws_ok and its fit's own RRL_E_WS check, and
+// only then cloud_epoch_pair: every refusal before the first launch, RRL_E_ARG first.  What the two point-to-point epochs
+// share beyond this is rrl_icp_step.h's.
 #pragma once
 
 // RRL_E_ARG: the struct, the shape, what both fits take (the clouds, the moved source, the Chamfer walk's outputs, the partial

@@ -14,6 +14,7 @@
 #include "rrl_pose_tail.h"
 #include "rrl_pair_sums.h"
 #include "rrl_cloud_epoch.h"
+#include "rrl_icp_step.h"
 
 #define KB_ROWS 512  // rows of `a` per 256-lane workgroup (two rounds)
 // the sums of a sample, about the pivots pa, pb (q = a - pa, r = b - pb): sum w, sum w q (3), sum w r (3), sum w q^T r (9),
@@ -458,90 +459,16 @@ extern "C" int rrl_kabsch_bwd(const rrl_kabsch_args *p, const float *gR, const f
 }
 
 // ---------------------------------------------------------------------------------------
-// The ICP pose step: one wavefront per pair, lane 0 works (se3_newton_step_kernel's shape; the state words and the stopping
-// rule are rrl_pose_tail.h's PoseStop, [3] = the fit's status or RRL_ICP_DONE).
+// The ICP pose step and epoch: the step's body, its refusals and the epoch's front are rrl_icp_step.h's, shared with the robust
+// loop of rrl_robust.hip; the kernel here is that body without the annealing rule, in its own launch.
 // ---------------------------------------------------------------------------------------
-struct IcpStepArgs {
-    const float *Rk, *Tk;
-    const int32_t *info;
-    const double *fit;
-    float *R, *T;
-    const float *tol_rot, *tol_trans;
-    int patience;
-    const float *value;
-    float *table;
-    long long *cursor, nrows;
-    float *row, *last_step;
-    int32_t *state;
-    int B;
-};
-
-__global__ __launch_bounds__(64) void icp_step_kernel(const IcpStepArgs a) {
-    const int b = blockIdx.x;
-    if (b >= a.B || threadIdx.x != 0) return;
-    const size_t s = (size_t)b;
-    int32_t *__restrict__ st = a.state + s * 4;
-    const double *__restrict__ fit = a.fit + s * RRL_FIT_DOUBLES;
-    const int fstat = a.info[s * 4 + 1];
-    PoseLog plog = {-1, (float)fit[RRL_FIT_RES], a.value ? a.value[s] : 0.0f};
-    if (a.table && a.cursor) plog.at = a.cursor[s];
-    PoseStop stop = pose_stop_load(st);
-    int status = stop.done ? RRL_ICP_DONE : fstat;
-    if (!stop.done && fstat == RRL_FIT_OK) {
-        double Rk[3][3], Ro[3][3], Tk[3], To[3], ab[3];
-        bool finite = true;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            Tk[i] = (double)a.Tk[s * 3 + i];
-            To[i] = (double)a.T[s * 3 + i];
-            ab[i] = fit[RRL_FIT_ABAR + i];
-            finite = finite && fabs(Tk[i]) < (double)INFINITY;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                Rk[i][j] = (double)a.Rk[s * 9 + 3 * i + j];
-                Ro[i][j] = (double)a.R[s * 9 + 3 * i + j];
-                finite = finite && fabs(Rk[i][j]) < (double)INFINITY;
-            }
-        }
-        if (!finite) {
-            status = RRL_FIT_DEGENERATE;
-        } else {
-            // E = R^T Rk: the rotation from the old pose to the new; angle = atan2(|vee(E - E^T)| / 2, (tr E - 1) / 2)
-            double E[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) E[i][j] = (Ro[0][i] * Rk[0][j] + Ro[1][i] * Rk[1][j]) + Ro[2][i] * Rk[2][j];
-            const double vx = E[2][1] - E[1][2], vy = E[0][2] - E[2][0], vz = E[1][0] - E[0][1];
-            const double ang = atan2(0.5 * sqrt((vx * vx + vy * vy) + vz * vz), 0.5 * (((E[0][0] + E[1][1]) + E[2][2]) - 1.0));
-            double mv2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double now = ((ab[0] * Rk[0][k] + ab[1] * Rk[1][k]) + ab[2] * Rk[2][k]) + Tk[k];
-                const double was = ((ab[0] * Ro[0][k] + ab[1] * Ro[1][k]) + ab[2] * Ro[2][k]) + To[k];
-                mv2 += (now - was) * (now - was);
-            }
-            const double mv = sqrt(mv2);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                a.T[s * 3 + i] = a.Tk[s * 3 + i];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) a.R[s * 9 + 3 * i + j] = a.Rk[s * 9 + 3 * i + j];
-            }
-            pose_stop_update(stop, s, (float)ang, (float)mv, a.last_step, a.tol_rot, a.tol_trans, a.patience);
-        }
-    }
-    pose_stop_store(stop, status, st);
-    pose_log_store(plog, fstat == RRL_FIT_OK, a.table ? a.table + s * 3 : nullptr, 3ll * a.B, a.nrows, a.cursor ? a.cursor + s : nullptr,
-                   a.row ? a.row + s * 3 : nullptr);
-}
+__global__ __launch_bounds__(64) void icp_step_kernel(const IcpStepArgs a) { icp_step_one<false>(a, IcpAnneal{}); }
 
 extern "C" int rrl_icp_step_batch(const float *Rk, const float *Tk, const int32_t *info, const double *fit, float *R, float *T,
                                   const float *tol_rot, const float *tol_trans, int patience, const float *value, float *table,
                                   long long *cursor, long long nrows, float *row, float *last_step, int32_t *state, int B,
                                   void *stream) {
-    if (B < 0 || !Rk || !Tk || !info || !fit || !R || !T || !state) return RRL_E_ARG;
-    if (!pose_stop_args_ok(patience, tol_rot, tol_trans)) return RRL_E_ARG;
+    if (B < 0 || !icp_step_args_ok(Rk, Tk, info, fit, R, T, state, patience, tol_rot, tol_trans)) return RRL_E_ARG;
     if (B == 0) return 0;
     const IcpStepArgs a = {Rk, Tk, info, fit, R, T, tol_rot, tol_trans, patience, value, table, cursor, nrows, row, last_step, state, B};
     hipLaunchKernelGGL(icp_step_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, a);
@@ -552,20 +479,13 @@ extern "C" int rrl_icp_step_batch(const float *Rk, const float *Tk, const int32_
 // One ICP epoch: four public entries back to back, every refusal before the first launch (host code only).
 extern "C" int rrl_icp_epoch(const rrl_icp_epoch_args *a, void *stream) {
     if (!cloud_epoch_front_ok(a)) return RRL_E_ARG;
-    const int B = a->B, N = a->N, M = a->M;
-    if (!a->R || !a->T || !a->Rk || !a->Tk || !a->fit || !a->info || !a->state || (((uintptr_t)a->fit) & 7) != 0) return RRL_E_ARG;
-    if (!pose_stop_args_ok(a->patience, a->tol_rot, a->tol_trans)) return RRL_E_ARG;
-    if (!cloud_epoch_cham_ws_ok(a) || a->part_bytes < rrl_kabsch_part_bytes(B, N)) return RRL_E_WS;
+    if (!icp_step_args_ok(a->Rk, a->Tk, a->info, a->fit, a->R, a->T, a->state, a->patience, a->tol_rot, a->tol_trans)) return RRL_E_ARG;
+    if ((((uintptr_t)a->fit) & 7) != 0) return RRL_E_ARG;
+    if (!icp_epoch_ws_ok(a)) return RRL_E_WS;
     int rc = cloud_epoch_pair(a, stream);
     if (rc) return rc;
-    rrl_kabsch_args k = {};
-    k.struct_bytes = (int32_t)sizeof(k);
-    k.B = B; k.n = N; k.m = M; k.a_stride = 3; k.b_stride = 3; k.transpose_r = 0;
-    k.a = a->src; k.b = a->tar; k.w = a->w; k.keys = a->best_x; k.count_a = a->count1; k.count_b = a->count2; k.gate_sq = a->gate_sq;
-    k.eps_w = a->eps_w; k.rank_tol = a->rank_tol;
-    k.part = a->part; k.part_bytes = a->part_bytes; k.R = a->Rk; k.T = a->Tk; k.fit = a->fit; k.info = a->info;
-    rc = rrl_kabsch_fwd(&k, stream);
+    rc = icp_epoch_fit(a, a->w, stream);
     if (rc) return rc;
     return rrl_icp_step_batch(a->Rk, a->Tk, a->info, a->fit, a->R, a->T, a->tol_rot, a->tol_trans, a->patience, a->values, a->table,
-                              a->cursor, a->table_rows, a->row, a->last_step, a->state, B, stream);
+                              a->cursor, a->table_rows, a->row, a->last_step, a->state, a->B, stream);
 }

@@ -2,8 +2,8 @@
 // se3_newton_step_kernel, rrl_newton.hip; the store also log_row_kernel): the epoch's log row and the next epoch's sampler
 // box, for ONE sample on that sample's own pointers -- the caller advances them to its slices; k = the lane of the step's
 // single wavefront.  Lane 0 logs, lanes 8 .. 13 reduce the box; the pose arithmetic sits between the load and the store.
-// Below them: the state words and the stopping rule of the two steps that stop by themselves (also icp_step_kernel,
-// rrl_kabsch.hip), and that rule's host-side refusal.
+// Below them: the state words and the stopping rule of the steps that stop by themselves (also icp_step_one, rrl_icp_step.h:
+// icp_step_kernel and robust_step_kernel; plane_step_kernel, rrl_plane.hip), and that rule's host-side refusal.
 #pragma once
 
 struct PoseLog {
@@ -60,7 +60,7 @@ __device__ __forceinline__ void pose_log_store(const PoseLog &p, bool ok, float 
 }
 
 // ---------------------------------------------------------------------------------------
-// The state words and the stopping rule of the steps that stop by themselves (se3_newton_step_kernel, icp_step_kernel;
+// The state words and the stopping rule of the steps that stop by themselves (se3_newton_step_kernel, icp_step_one;
 // include/rrl.h "pose-step state").  state [B][4] int32: [0] epochs issued, [1] consecutive calm epochs, [2] the epoch count
 // at which the pair was declared done (-1: not yet), [3] what this call did (RRL_POSE_*, or the caller's own failure code).
 // Lane 0 of a pose's wavefront: load, the kernel's own arithmetic and pose write, pose_stop_update where a step was applied,

@@ -13,6 +13,7 @@
 #include "rrl_pose_tail.h"
 #include "rrl_pair_sums.h"
 #include "rrl_cloud_epoch.h"
+#include "rrl_icp_step.h"
 
 // the distance word of row i of sample b when the fit would use the row (gate aside), else false
 __device__ __forceinline__ bool valid_word(const unsigned long long *__restrict__ keys, int b, int n, int i, int ca, int m, int cb,
@@ -129,106 +130,10 @@ extern "C" int rrl_welsch_weights(const uint64_t *keys, const int32_t *count_a, 
 }
 
 // ---------------------------------------------------------------------------------------
-// The robust pose step: icp_step_kernel's step (rrl_kabsch.hip; restated, that kernel is its own launch) up to the calm
-// count, then the annealing rule where that kernel declares a pair done.
+// The robust pose step: rrl_icp_step.h's body with the annealing rule where icp_step_kernel (rrl_kabsch.hip) declares a pair
+// done, in its own launch.
 // ---------------------------------------------------------------------------------------
-struct RobustStepArgs {
-    const float *Rk, *Tk;
-    const int32_t *info;
-    const double *fit;
-    float *R, *T;
-    const float *tol_rot, *tol_trans;
-    int patience;
-    const float *value;
-    float *table;
-    long long *cursor, nrows;
-    float *row, *last_step;
-    int32_t *state;
-    float *nu;
-    const float *nu_end;
-    float anneal;
-    int level_cap;
-    int32_t *level;
-    int B;
-};
-
-__global__ __launch_bounds__(64) void robust_step_kernel(const RobustStepArgs a) {
-    const int b = blockIdx.x;
-    if (b >= a.B || threadIdx.x != 0) return;
-    const size_t s = (size_t)b;
-    int32_t *__restrict__ st = a.state + s * 4;
-    const double *__restrict__ fit = a.fit + s * RRL_FIT_DOUBLES;
-    const int fstat = a.info[s * 4 + 1];
-    PoseLog plog = {-1, (float)fit[RRL_FIT_RES], a.value ? a.value[s] : 0.0f};
-    if (a.table && a.cursor) plog.at = a.cursor[s];
-    PoseStop stop = pose_stop_load(st);
-    int status = stop.done ? RRL_POSE_DONE : fstat;
-    if (!stop.done && fstat == RRL_FIT_OK) {
-        double Rk[3][3], Ro[3][3], Tk[3], To[3], ab[3];
-        bool finite = true;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            Tk[i] = (double)a.Tk[s * 3 + i];
-            To[i] = (double)a.T[s * 3 + i];
-            ab[i] = fit[RRL_FIT_ABAR + i];
-            finite = finite && fabs(Tk[i]) < (double)INFINITY;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                Rk[i][j] = (double)a.Rk[s * 9 + 3 * i + j];
-                Ro[i][j] = (double)a.R[s * 9 + 3 * i + j];
-                finite = finite && fabs(Rk[i][j]) < (double)INFINITY;
-            }
-        }
-        if (!finite) {
-            status = RRL_FIT_DEGENERATE;
-        } else {
-            double E[3][3];  // E = R^T Rk: the rotation from the old pose to the new
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) E[i][j] = (Ro[0][i] * Rk[0][j] + Ro[1][i] * Rk[1][j]) + Ro[2][i] * Rk[2][j];
-            const double vx = E[2][1] - E[1][2], vy = E[0][2] - E[2][0], vz = E[1][0] - E[0][1];
-            const double ang = atan2(0.5 * sqrt((vx * vx + vy * vy) + vz * vz), 0.5 * (((E[0][0] + E[1][1]) + E[2][2]) - 1.0));
-            double mv2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double now = ((ab[0] * Rk[0][k] + ab[1] * Rk[1][k]) + ab[2] * Rk[2][k]) + Tk[k];
-                const double was = ((ab[0] * Ro[0][k] + ab[1] * Ro[1][k]) + ab[2] * Ro[2][k]) + To[k];
-                mv2 += (now - was) * (now - was);
-            }
-            const double mv = sqrt(mv2);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                a.T[s * 3 + i] = a.Tk[s * 3 + i];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) a.R[s * 9 + 3 * i + j] = a.Rk[s * 9 + 3 * i + j];
-            }
-            pose_stop_update(stop, s, (float)ang, (float)mv, a.last_step, a.tol_rot, a.tol_trans, a.patience);
-        }
-    }
-    if (!stop.done) {  // the annealing rule decides what the calm count means
-        int32_t *__restrict__ lv = a.level + s * 2;
-        int at_nu = lv[0] + 1, levels = lv[1];
-        stop.done_new = -1;
-        if ((a.patience > 0 && stop.calm >= a.patience) || (a.level_cap > 0 && at_nu >= a.level_cap)) {
-            const float nu = a.nu[s], end = a.nu_end[s];
-            if (nu > end) {
-                const float next = nu * a.anneal;
-                a.nu[s] = next > end ? next : end;
-                stop.calm = 0;
-                at_nu = 0;
-                levels += 1;
-            } else {
-                stop.done_new = stop.epochs;
-            }
-        }
-        lv[0] = at_nu;
-        lv[1] = levels;
-    }
-    pose_stop_store(stop, status, st);
-    pose_log_store(plog, fstat == RRL_FIT_OK, a.table ? a.table + s * 3 : nullptr, 3ll * a.B, a.nrows, a.cursor ? a.cursor + s : nullptr,
-                   a.row ? a.row + s * 3 : nullptr);
-}
+__global__ __launch_bounds__(64) void robust_step_kernel(const IcpStepArgs a, const IcpAnneal n) { icp_step_one<true>(a, n); }
 
 // RRL_E_ARG of the annealing rule (host)
 static bool anneal_args_ok(const float *nu, const float *nu_end, const int32_t *level, float anneal, int level_cap, int patience) {
@@ -240,12 +145,12 @@ extern "C" int rrl_robust_step_batch(const float *Rk, const float *Tk, const int
                                      const float *tol_rot, const float *tol_trans, int patience, const float *value, float *table,
                                      long long *cursor, long long nrows, float *row, float *last_step, int32_t *state, float *nu,
                                      const float *nu_end, float anneal, int level_cap, int32_t *level, int B, void *stream) {
-    if (B < 0 || !Rk || !Tk || !info || !fit || !R || !T || !state) return RRL_E_ARG;
-    if (!pose_stop_args_ok(patience, tol_rot, tol_trans) || !anneal_args_ok(nu, nu_end, level, anneal, level_cap, patience)) return RRL_E_ARG;
+    if (B < 0 || !icp_step_args_ok(Rk, Tk, info, fit, R, T, state, patience, tol_rot, tol_trans)) return RRL_E_ARG;
+    if (!anneal_args_ok(nu, nu_end, level, anneal, level_cap, patience)) return RRL_E_ARG;
     if (B == 0) return 0;
-    const RobustStepArgs a = {Rk, Tk, info, fit, R, T, tol_rot, tol_trans, patience, value, table, cursor, nrows, row, last_step, state,
-                              nu, nu_end, anneal, level_cap, level, B};
-    hipLaunchKernelGGL(robust_step_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, a);
+    const IcpStepArgs a = {Rk, Tk, info, fit, R, T, tol_rot, tol_trans, patience, value, table, cursor, nrows, row, last_step, state, B};
+    const IcpAnneal n = {nu, nu_end, anneal, level_cap, level};
+    hipLaunchKernelGGL(robust_step_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, a, n);
     RRL_LAUNCH_CHECK();
     return 0;
 }
@@ -255,12 +160,11 @@ extern "C" int rrl_robust_step_batch(const float *Rk, const float *Tk, const int
 extern "C" int rrl_robust_icp_epoch(const rrl_icp_epoch_args *a, int init, float *w, float *nu, const float *nu_end, float *med_sq,
                                     int32_t *med_info, double nu_scale, float anneal, int level_cap, int32_t *level, void *stream) {
     if (!cloud_epoch_front_ok(a)) return RRL_E_ARG;
-    const int B = a->B, N = a->N, M = a->M;
-    if (!a->R || !a->T || !a->Rk || !a->Tk || !a->fit || !a->info || !a->state || (((uintptr_t)a->fit) & 7) != 0) return RRL_E_ARG;
-    if (a->w || !w || !med_sq || !med_info || !(nu_scale > 0.0)) return RRL_E_ARG;
-    if (!pose_stop_args_ok(a->patience, a->tol_rot, a->tol_trans)) return RRL_E_ARG;
+    if (!icp_step_args_ok(a->Rk, a->Tk, a->info, a->fit, a->R, a->T, a->state, a->patience, a->tol_rot, a->tol_trans)) return RRL_E_ARG;
+    if ((((uintptr_t)a->fit) & 7) != 0 || a->w || !w || !med_sq || !med_info || !(nu_scale > 0.0)) return RRL_E_ARG;
     if (!anneal_args_ok(nu, nu_end, level, anneal, level_cap, a->patience)) return RRL_E_ARG;
-    if (!cloud_epoch_cham_ws_ok(a) || a->part_bytes < rrl_kabsch_part_bytes(B, N)) return RRL_E_WS;
+    if (!icp_epoch_ws_ok(a)) return RRL_E_WS;
+    const int B = a->B, N = a->N, M = a->M;
     int rc = cloud_epoch_pair(a, stream);
     if (rc) return rc;
     if (init) {
@@ -269,13 +173,7 @@ extern "C" int rrl_robust_icp_epoch(const rrl_icp_epoch_args *a, int init, float
     }
     rc = rrl_welsch_weights(a->best_x, a->count1, a->count2, nu, w, B, N, M, stream);
     if (rc) return rc;
-    rrl_kabsch_args k = {};
-    k.struct_bytes = (int32_t)sizeof(k);
-    k.B = B; k.n = N; k.m = M; k.a_stride = 3; k.b_stride = 3; k.transpose_r = 0;
-    k.a = a->src; k.b = a->tar; k.w = w; k.keys = a->best_x; k.count_a = a->count1; k.count_b = a->count2; k.gate_sq = a->gate_sq;
-    k.eps_w = a->eps_w; k.rank_tol = a->rank_tol;
-    k.part = a->part; k.part_bytes = a->part_bytes; k.R = a->Rk; k.T = a->Tk; k.fit = a->fit; k.info = a->info;
-    rc = rrl_kabsch_fwd(&k, stream);
+    rc = icp_epoch_fit(a, w, stream);
     if (rc) return rc;
     return rrl_robust_step_batch(a->Rk, a->Tk, a->info, a->fit, a->R, a->T, a->tol_rot, a->tol_trans, a->patience, a->values, a->table,
                                  a->cursor, a->table_rows, a->row, a->last_step, a->state, nu, nu_end, anneal, level_cap, level, B, stream);

@@ -145,6 +145,10 @@ class IcpRegistration(_CloudLoop):
     def __init__(self, src, tar, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, max_dist=None, tol_rot=TOL_ROT,
                  tol_trans=TOL_TRANS, patience=PATIENCE, table_rows=4096):
         lib = self._init_clouds(src, tar, counts1, counts2, R0, T0, xi0, max_dist, tol_rot, tol_trans, patience, table_rows)
+        self._init_fit(lib, table_rows)
+
+    def _init_fit(self, lib, table_rows):
+        """The closed-form fit's buffers, the log and the bound call: what a constructor does last."""
         B, dev, f32 = self.B, self.dev, dict(dtype=torch.float32, device=self.dev)
         self.part = torch.empty(max(int(lib.rrl_kabsch_part_bytes(B, self.N)) // 8, 1), dtype=torch.float64, device=dev)
         self.Rk, self.Tk = torch.zeros(B, 3, 3, **f32), torch.zeros(B, 3, **f32)
@@ -219,7 +223,7 @@ def target_spacing(tar, counts=None):
     return torch.where(k > 0, med, torch.zeros_like(med)).contiguous()
 
 
-class RobustIcpRegistration(_CloudLoop):
+class RobustIcpRegistration(IcpRegistration):
     """IcpRegistration whose pairs carry Welsch weights exp(-d^2 / (2 nu^2)) -- the loss's own function of the nearest
     neighbour's distance d -- with a per-pair scale nu annealed from coarse to fine (Fast-Robust-ICP without its Anderson
     acceleration): source points with no partner in the target fade out instead of pulling the pose.  One C call per epoch.
@@ -235,7 +239,7 @@ class RobustIcpRegistration(_CloudLoop):
     int32: levels finished; .level (B, 2) int32: (epochs at this scale, levels finished); .med_sq (B,): the first epoch's median
     squared residual.  Everything else as IcpRegistration; .history()'s residual is the fit's WEIGHTED mean squared residual."""
 
-    _ARGS, _ENTRY = _lib.IcpEpochArgs, "rrl_robust_icp_epoch"  # .epoch(): ONE C call, on rrl_icp_epoch's own struct
+    _ENTRY = "rrl_robust_icp_epoch"  # .epoch(): ONE C call, on rrl_icp_epoch's own struct (_ARGS)
 
     def __init__(self, src, tar, *, counts1=None, counts2=None, R0=None, T0=None, xi0=None, max_dist=None, tol_rot=TOL_ROT,
                  tol_trans=TOL_TRANS, patience=PATIENCE, table_rows=4096, nu_start=NU_START, nu_end=None, anneal=ANNEAL,
@@ -254,20 +258,11 @@ class RobustIcpRegistration(_CloudLoop):
         self.med_sq = torch.zeros(B, **f32)
         self.med_info = torch.zeros(B, 2, dtype=torch.int32, device=dev)
         self.level = torch.zeros(B, 2, dtype=torch.int32, device=dev)
-        self.part = torch.empty(max(int(lib.rrl_kabsch_part_bytes(B, self.N)) // 8, 1), dtype=torch.float64, device=dev)
-        self.Rk, self.Tk = torch.zeros(B, 3, 3, **f32), torch.zeros(B, 3, **f32)
-        self.fit = torch.zeros(B, _lib.FIT_DOUBLES, dtype=torch.float64, device=dev)
-        self.info = torch.zeros(B, 4, dtype=torch.int32, device=dev)
-        self._init_log(table_rows)
-        self._bind()
+        self._init_fit(lib, table_rows)
 
     def _make_args(self):
         P = ops._p
-        a = self._ARGS()
-        self._cloud_args(a)
-        a.eps_w, a.rank_tol = 0.0, RANK_TOL
-        a.part, a.part_bytes = P(self.part), self.part.numel() * 8
-        a.Rk, a.Tk, a.fit, a.info = P(self.Rk), P(self.Tk), P(self.fit), P(self.info)
+        a = super()._make_args()
         # what the annealing adds travels as plain arguments, after `init`; the struct's w stays NULL
         self._extra = (P(self.weights), P(self.nu), P(self.nu_end), P(self.med_sq), P(self.med_info), self.nu_start, self.anneal,
                        self.level_cap, P(self.level))

@@ -130,6 +130,23 @@ def rotation_angle(R0, R1):
     return float(np.arctan2(0.5 * np.linalg.norm(v), 0.5 * (np.trace(E) - 1.0)))
 
 
+def step_lengths(Rk, Tk, abar, R, T):
+    """(angle, centroid motion) in float64, the additions in the kernel's order."""
+    Rk, Tk, R, T, ab = (np.asarray(x, np.float64) for x in (Rk, Tk, R, T, abar))
+    E = np.empty((3, 3))
+    for i in range(3):
+        for j in range(3):
+            E[i, j] = (R[0, i] * Rk[0, j] + R[1, i] * Rk[1, j]) + R[2, i] * Rk[2, j]
+    vx, vy, vz = E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]
+    ang = np.arctan2(0.5 * np.sqrt((vx * vx + vy * vy) + vz * vz), 0.5 * (((E[0, 0] + E[1, 1]) + E[2, 2]) - 1.0))
+    mv2 = 0.0
+    for k in range(3):
+        now = ((ab[0] * Rk[0, k] + ab[1] * Rk[1, k]) + ab[2] * Rk[2, k]) + Tk[k]
+        was = ((ab[0] * R[0, k] + ab[1] * R[1, k]) + ab[2] * R[2, k]) + T[k]
+        mv2 += (now - was) * (now - was)
+    return float(ang), float(np.sqrt(mv2))
+
+
 def icp_step(Rk, Tk, status, abar, R, T, state, tol_rot, tol_trans, patience):
     """The step rule of rrl_icp_step_batch for one pair, float64: -> (R, T, last_step or None, state).  state = [epochs, calm
     epochs, done epoch or -1, what this call did]."""
@@ -138,9 +155,7 @@ def icp_step(Rk, Tk, status, abar, R, T, state, tol_rot, tol_trans, patience):
         return R, T, None, [epochs, state[1], done_at, ICP_DONE]
     if status != FIT_OK or not (np.isfinite(Rk).all() and np.isfinite(Tk).all()):
         return R, T, None, [epochs, 0, -1, status if status != FIT_OK else FIT_DEGENERATE]
-    Rk64, Tk64, R64, T64 = (np.asarray(x, np.float64) for x in (Rk, Tk, R, T))
-    ang = rotation_angle(R64, Rk64)
-    mv = float(np.linalg.norm(abar @ Rk64 + Tk64 - abar @ R64 - T64))
+    ang, mv = step_lengths(Rk, Tk, abar, R, T)
     calm = state[1] + 1 if (patience > 0 and np.float32(ang) < np.float32(tol_rot) and np.float32(mv) < np.float32(tol_trans)) else 0
     done = epochs if (patience > 0 and calm >= patience) else -1
     return Rk, Tk, (ang, mv), [epochs, calm, done, FIT_OK]

@@ -66,40 +66,16 @@ def welsch_weights_ref(keys, nu, m, count_a=None, count_b=None):
     return w
 
 
-def step_lengths(Rk, Tk, abar, R, T):
-    """(angle, centroid motion) in float64, the additions in the kernel's order."""
-    Rk, Tk, R, T, ab = (np.asarray(x, np.float64) for x in (Rk, Tk, R, T, abar))
-    E = np.empty((3, 3))
-    for i in range(3):
-        for j in range(3):
-            E[i, j] = (R[0, i] * Rk[0, j] + R[1, i] * Rk[1, j]) + R[2, i] * Rk[2, j]
-    vx, vy, vz = E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]
-    ang = np.arctan2(0.5 * np.sqrt((vx * vx + vy * vy) + vz * vz), 0.5 * (((E[0, 0] + E[1, 1]) + E[2, 2]) - 1.0))
-    mv2 = 0.0
-    for k in range(3):
-        now = ((ab[0] * Rk[0, k] + ab[1] * Rk[1, k]) + ab[2] * Rk[2, k]) + Tk[k]
-        was = ((ab[0] * R[0, k] + ab[1] * R[1, k]) + ab[2] * R[2, k]) + T[k]
-        mv2 += (now - was) * (now - was)
-    return float(ang), float(np.sqrt(mv2))
-
-
 def robust_step_rule_ref(Rk, Tk, status, abar, R, T, state, level, nu, nu_end, tol_rot, tol_trans, patience, anneal, level_cap):
-    """rrl_robust_step_batch for one pair, the integer and float32 state machine exactly:
+    """rrl_robust_step_batch for one pair, the integer and float32 state machine exactly: KR.icp_step up to its calm count, then
+    the annealing rule where that one declares a pair done:
     -> (R, T, last_step (float32, float32) or None, state [4], level [2], nu float32)."""
     nu, nu_end = np.float32(nu), np.float32(nu_end)
-    epochs, done_at = state[0] + 1, state[2]
-    if done_at >= 0:
-        return R, T, None, [epochs, state[1], done_at, KR.ICP_DONE], list(level), nu
-    calm, last, out = 0, None, status
-    if status == KR.FIT_OK:
-        if not (np.isfinite(Rk).all() and np.isfinite(Tk).all()):
-            out = KR.FIT_DEGENERATE
-        else:
-            ang, mv = step_lengths(Rk, Tk, abar, R, T)
-            last = (np.float32(ang), np.float32(mv))
-            R, T = Rk, Tk
-            if patience > 0:
-                calm = state[1] + 1 if (last[0] < np.float32(tol_rot) and last[1] < np.float32(tol_trans)) else 0
+    R, T, last, (epochs, calm, done, out) = KR.icp_step(Rk, Tk, status, abar, R, T, state, tol_rot, tol_trans, patience)
+    if state[2] >= 0:
+        return R, T, None, [epochs, calm, done, out], list(level), nu
+    if last is not None:
+        last = (np.float32(last[0]), np.float32(last[1]))
     at_nu, levels, done = level[0] + 1, level[1], -1
     if (patience > 0 and calm >= patience) or (level_cap > 0 and at_nu >= level_cap):
         if nu > nu_end:

@@ -229,6 +229,7 @@ def test_icp_epoch_refuses_before_its_first_launch(lib):
                                      "info", "state")]
     for over in refusals:
         assert lib.rrl_icp_epoch(ctypes.byref(icp_args(lib, **over)), None) == E_ARG, over
+        assert lib.rrl_icp_epoch(ctypes.byref(icp_args(lib, cham_ws_bytes=64, part_bytes=8, **over)), None) == E_ARG, over  # RRL_E_ARG comes before RRL_E_WS
     assert lib.rrl_icp_epoch(ctypes.byref(icp_args(lib, cham_ws_bytes=64)), None) == E_WS
     assert lib.rrl_icp_epoch(ctypes.byref(icp_args(lib, part_bytes=8)), None) == E_WS
 
