@@ -422,3 +422,32 @@ def rpm_raw_features(xyz, normals, features, radius=0.3, nsample=64):
     directly -- no expand, no cat."""
     from . import neighbors
     return neighbors.ball_group(xyz, normals, radius, nsample, features=features)[0]
+
+
+# ---- DCP's feature extractor: the k-NN graph and its edge features in front of DGCNN's convolutions ------------------------
+def _dcp_cloud(x, k):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != 3:
+        raise ValueError("x must be a (B, 3, N) tensor, channel-first as DCP holds its clouds")
+    if isinstance(k, bool) or int(k) != k or k < 1:
+        raise ValueError(f"k must be a positive integer, got {k!r}")
+    if k > x.shape[2]:  # (the reference's topk raises here)
+        raise ValueError(f"k = {k} neighbours out of {x.shape[2]} points: selected index k out of range")
+    return x.detach().transpose(2, 1).contiguous()
+
+
+def dcp_knn(x, k):
+    """dcp/model.py:46-52 knn(x, k) as one call (neighbors.knn): x (B, 3, N) -> (B, N, k) int64, every point's k nearest
+    points, itself first -- by exact float64 distances with ties to the lower index, where the reference ranks the float32
+    matmul expansion -xx - inner - xx^T with topk (rows with two candidates within a few float32 roundings of each other can
+    differ).  No (B, N, N) matrix.  ValueError for k > N.  Forward only."""
+    from . import neighbors
+    return neighbors.knn(_dcp_cloud(x, k), k)[0].long()
+
+
+def dcp_graph_feature(x, k=20):
+    """dcp/model.py:55-78 get_graph_feature(x, k) as one call (neighbors.knn_group): x (B, 3, N) -> (B, 6, N, k) float32, the
+    neighbours' coordinates on channels 0-2 and the centre's own on 3-5, channel-first as the reference's permute leaves it --
+    written by the kernel directly: no distance matrix, no topk, no index-offset tensor, no repeat, no cat.  ValueError for
+    k > N.  Forward only: the reference feeds the input clouds, which carry no gradient."""
+    from . import neighbors
+    return neighbors.knn_group(_dcp_cloud(x, k), k, features=("nbr", "ctr"), channel_first=True)[0]

@@ -277,6 +277,105 @@ def estimate_normals(points, radius, nsample=64, *, counts=None, return_quality=
     return normals_from_groups(points, idx, found, counts=counts, return_quality=return_quality)
 
 
+# ---- k nearest neighbours, any k up to 32, and DCP's graph features (include/rrl.h rrl_knn) ---------
+KNN_FEATURES = ("nbr", "dxyz", "ctr")  # the kernel's channel order: x_j, x_j - x_i, x_i; 3 channels each
+MAX_K = _lib.CONSTANTS["RRL_KNN_MAX_K"]
+# method="auto" takes the tree from this many reference points per cloud (the capacity n): the smallest measured size from
+# which the tree was faster than brute force on BOTH cloud kinds (a volume and a surface), at k = 20 and k = 3, at B = 1 and
+# B = 8 -- profiles/knn_timing.json, written by tools/knn_timing.py: 256 is the smallest size measured, and the tree won
+# there and at every larger one (k = 20: 280 .. 322 us against 364 .. 368 at n = 256, 447 .. 539 against 1230 .. 1253 at 1024,
+# 2.3 .. 17.9 ms against 108 .. 661 at 262144; k = 3: 77 .. 84 against 89 .. 96 at n = 256).  None: never.
+KNN_TREE_MIN_POINTS = 256
+
+
+def _knn_channel_mask(features):
+    if isinstance(features, str):
+        features = (features,)
+    features = tuple(features)
+    if not features or len(set(features)) != len(features) or any(f not in KNN_FEATURES for f in features):
+        raise ValueError(f"features must be distinct names out of {KNN_FEATURES}, got {features!r}")
+    return sum(1 << KNN_FEATURES.index(f) for f in features), 3 * len(features)
+
+
+def _knn(points, k, query, counts, qcounts, exclude_self, want_dist, method, mask, C, channel_first):
+    """Every host-side refusal, then the launches of rrl_knn: (feat or None, idx, found, dist2 or None)."""
+    B, n = _points3(points)
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must be an integer in [1, {MAX_K}], got {k!r}")
+    k = int(k)
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if not 1 <= B <= 32767 or n < 1:
+        raise ValueError(f"knn serves 1 .. 32767 clouds of at least one point, got {B} of {n}")
+    if query is None:
+        if qcounts is not None:
+            raise ValueError("qcounts belongs to query: the self form's queries are the points, counted by counts")
+        S = n
+    else:
+        if _points3(query)[0] != B:
+            raise ValueError(f"query must be a ({B}, S, 3) tensor, got {tuple(query.shape)}")
+        if exclude_self:
+            raise ValueError("exclude_self belongs to the self form (query=None): a query cloud has no row of its own")
+        S = query.shape[1]
+    cap = _ops.sort_capacity()
+    if method == "tree" and max(n, S) > cap:
+        raise ValueError(f"the tree serves clouds up to {cap} points, got {max(n, S)}")
+    tree = method == "tree" or (method == "auto" and KNN_TREE_MIN_POINTS is not None and KNN_TREE_MIN_POINTS <= n and max(n, S) <= cap)
+    hc = _host_counts(counts, B, n, "counts")
+    hq = _host_counts(qcounts, B, S, "qcounts")
+    dev = _home(points, query, counts, qcounts)
+    pts = _ops._prep(points, "points", 3, dev)
+    qry = None if query is None else _ops._prep(query, "query", 3, dev)
+    cnt = _ops.check_counts(counts if hc is None else hc, B, n, dev, "counts")
+    qcnt = _ops.check_counts(qcounts if hq is None else hq, B, S, dev, "qcounts")
+    flags = (_lib.CONSTANTS["RRL_KNN_EXCLUDE_SELF"] if exclude_self else 0) | (_lib.CONSTANTS["RRL_KNN_CHANNEL_FIRST"] if channel_first else 0) | \
+        (0 if tree else _lib.CONSTANTS["RRL_KNN_BRUTE"])
+    idx = torch.empty(B, S, k, dtype=torch.int32, device=dev)
+    found = torch.empty(B, S, dtype=torch.int32, device=dev)
+    dist2 = torch.empty(B, S, k, dtype=torch.float32, device=dev) if want_dist else None
+    feat = torch.empty((B, C, S, k) if channel_first else (B, S, k, C), dtype=torch.float32, device=dev) if mask else None
+    ws = torch.empty(_ops._scratch_size("rrl_knn_workspace_bytes", B, n, S), dtype=torch.uint8, device=dev)
+    _run(dev, "rrl_knn", _p(pts), _p(cnt), _p(qry), _p(qcnt), k, flags, mask, _p(ws), ws.numel(), _p(idx), _p(found), _p(dist2),
+         _p(feat), B, n, S)
+    return feat, idx, found, dist2
+
+
+def knn(points, k, *, query=None, counts=None, qcounts=None, exclude_self=False, return_dist=False, method="auto"):
+    """points (B, n, 3) -> (idx (B, S, k) int32, found (B, S) int32[, dist2 (B, S, k) float32]): for every query the k nearest
+    points of its cloud -- the k smallest keys (d, j), d the float64 squared distance (dx dx + dy dy) + dz dz from the float32
+    coordinates, j the row: ascending distance, the lowest index among equal distances (include/rrl.h rrl_knn).  A pair whose
+    distance is NaN or infinite is no neighbour.  found = min(k, neighbours): k > n is legal.  The slots beyond found repeat
+    slot 0; a row without any neighbour (an empty cloud, a NaN query, a row beyond a count) is zero.
+
+    query=None: every point is a query (S = n) and finds itself first at d = 0 -- unless a duplicate has a lower index --;
+    exclude_self=True removes the row's own index, not its duplicates.  query (B, S, 3): another cloud's points, with qcounts.
+    counts / qcounts (B,): as ball_query takes them -- on the GPU read by the kernels only and clamped, on the host validated
+    (ValueError before any launch).  method: "brute", "tree" (both clouds within ops.sort_capacity()) or "auto"
+    (KNN_TREE_MIN_POINTS); the same bits.  dist2 is d rounded once.  Nothing synchronises: the call can be captured in a graph."""
+    _, idx, found, dist2 = _knn(points, k, query, counts, qcounts, exclude_self, return_dist, method, 0, 0, False)
+    return (idx, found, dist2) if return_dist else (idx, found)
+
+
+def knn_group(points, k, *, features=("nbr", "ctr"), channel_first=False, query=None, counts=None, qcounts=None,
+              exclude_self=False, method="auto"):
+    """knn plus the features of its groups from the same kernel: (feat, idx, found) with feat (B, S, k, C) float32 -- or
+    (B, C, S, k) with channel_first, the layout DCP's get_graph_feature ends in -- and the chosen channels in the kernel's
+    order whatever the order of `features`: "nbr" (3) x_j, "dxyz" (3) x_j - x_i (the float32 subtraction), "ctr" (3) x_i on
+    every slot.  Pad slots repeat slot 0, rows without a neighbour are zero.  No gradient flows."""
+    mask, C = _knn_channel_mask(features)
+    return _knn(points, k, query, counts, qcounts, exclude_self, False, method, mask, C, bool(channel_first))[:3]
+
+
+def estimate_normals_knn(points, k, *, counts=None, return_quality=False):
+    """estimate_normals with "the k nearest" in place of a radius ball, which needs no radius tuned to the data's scale:
+    points (B, n, 3) -> unit normals (B, n, 3) float32 [, quality (B, n)] from every point's k nearest points (itself among
+    them: knn(exclude_self=False)) by normals_from_groups -- same scatter matrix, same eigenvector, same sign convention, same
+    zero rows (fewer than three members, collinear or coincident members).  k <= MAX_K.  The k-NN launches plus one, no
+    read-back: the call can be captured in a graph."""
+    idx, found = knn(points, k, counts=counts)
+    return normals_from_groups(points, idx, found, counts=counts, return_quality=return_quality)
+
+
 def _neighbours(points, num_sample, counts, start, method, want_tri):
     """The launches of pseudo_triangles / knn3_self after every host-side refusal: (sample_idx or None, tri or None, nn,
     tri_counts)."""

@@ -1261,6 +1261,52 @@ int rrl_ball_group(const float *pts, const float *normals, const int32_t *counts
                    const int32_t *qcounts, float r2, int nsample, int exclude_self, int channels, int32_t *idx, int32_t *found,
                    float *feat, int B, int n, int S, void *stream);
 
+/* ---- k nearest neighbours, any k up to RRL_KNN_MAX_K, and DCP's graph features ------------
+ * DCP's feature extractor starts with get_graph_feature(x, k = 20) (dcp/model.py:46-78): a (B, N, N) float32 distance
+ * matrix by matmul, topk, an index-offset tensor, a gather, repeat, cat and permute.  rrl_knn is the exact k-NN behind it with
+ * the features written by the same kernel, forward only: plain device pointers, sizes and a stream; nothing is allocated,
+ * read back or synchronised, there are no atomics, and every refusal happens on the host before any HIP call.
+ *
+ * ref [B][n][3]; count_ref [B] (device int32 or NULL = n): sample b has n_b = clamp(count_ref[b], 0, n) reference points, the
+ * rows beyond are never read.  Self form, qry == NULL: the queries are the reference's own rows, S must equal n, sample b has
+ * n_b queries and count_qry is not read.  Cross form: qry [B][S][3], count_qry [B] (or NULL = S): S_b = clamp(count_qry[b], 0, S).
+ *
+ * The result: for query q the k smallest keys (d, j) in lexicographic order over the sample's reference points, d =
+ * (dx dx + dy dy) + dz dz in double from the double differences of the float32 coordinates, uncontracted (rrl_knn3's distance),
+ * j the original row: ascending distance, the lowest index among equal distances.  A pair whose d is NaN or +inf is no
+ * neighbour.  In the self form the point itself is a neighbour at d = 0 unless RRL_KNN_EXCLUDE_SELF is set, which removes the
+ * row's own index only (a duplicate of it at another index stays); the flag means nothing in the cross form.
+ * found [B][S] (optional) = min(k, neighbours); k > n is legal.  idx [B][S][k]; dist2 [B][S][k] (optional) = d rounded once to
+ * float32.  The slots at or beyond found repeat slot 0 in every output.  A row with found == 0 -- an empty reference, a NaN
+ * query, a row beyond S_b -- is zero in every output.
+ * feat (optional; NULL iff channels == 0) [B][S][k][C], the chosen channels always in this order:
+ *   RRL_KNN_NBR  (3) x_j;
+ *   RRL_KNN_DXYZ (3) x_j - x_i, the float32 subtraction;
+ *   RRL_KNN_CTR  (3) x_i, repeated over the slots.
+ * With RRL_KNN_CHANNEL_FIRST feat is [B][C][S][k]: the tensor DCP's permute(0, 3, 1, 2) produces, written directly.
+ *
+ * Method: the sorted layout's sphere tree (16^3-cell Hilbert sort of both clouds, supergroups of 64 records; the walk and
+ * its bound for k keys are in csrc/rrl_knn.hip) wherever max(n, S) <= rrl_sort_capacity(), else -- and with RRL_KNN_BRUTE --
+ * brute force, one lane per query.  Both give the same bits; a sample with a NaN, an infinite or a huge (|P| > 1e15)
+ * coordinate within its counts takes the brute loop inside the tree's launch.  Launches: 1 for brute force; the tree 3 up to
+ * 4096 points and 5 beyond (6 in the cross form).  Two calls give the same bits; sample b of a ragged batch has the bits of
+ * its own call.  ws: scratch of rrl_knn_workspace_bytes(B, n, S) bytes, needed by either method.
+ *
+ * RRL_E_ARG: NULL ref / idx / ws; B outside 0..32767; n < 1; S < 0; k outside 1..RRL_KNN_MAX_K; qry == NULL with S != n; flags
+ * or channels outside their masks, channels without feat or feat without channels.  Then RRL_E_WS: a short ws.  B == 0 or
+ * S == 0 returns 0 without a launch. */
+#define RRL_KNN_MAX_K 32
+#define RRL_KNN_EXCLUDE_SELF 1
+#define RRL_KNN_CHANNEL_FIRST 2
+#define RRL_KNN_BRUTE 4 /* force brute force; default: the tree where it serves */
+#define RRL_KNN_NBR 1
+#define RRL_KNN_DXYZ 2
+#define RRL_KNN_CTR 4
+size_t rrl_knn_workspace_bytes(int B, int n, int S);
+int rrl_knn(const float *ref, const int32_t *count_ref, const float *qry, const int32_t *count_qry, int k, int flags,
+            int channels, void *ws, size_t ws_bytes, int32_t *idx, int32_t *found, float *dist2, float *feat,
+            int B, int n, int S, void *stream);
+
 /* ---- Point-to-plane ICP: normals from ball groups, the linearised fit, its pose step, an epoch ----
  * The house rules of the closed-form fits hold for all four entries: float32 in, every sum a fixed-order DOUBLE sum
  * (per-lane accumulators, the wavefront's DPP tree, four wavefronts, partial rows in index order), rounded once; no atomics,
