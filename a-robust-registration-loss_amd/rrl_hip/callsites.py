@@ -375,6 +375,20 @@ def dcp_svd_head_pose(src, src_corr):
     return kabsch(src.transpose(2, 1).contiguous(), src_corr.transpose(2, 1).contiguous(), None, eps=0.0, transpose_r=True)
 
 
+def dcp_soft_pointer(src_embedding, tgt_embedding, tgt):
+    """dcp/model.py:419-425, SVDHead's correspondences as ONE node (rrl_hip.pointer): src_embedding (B, C, N), tgt_embedding
+    (B, C, M), tgt (B, 3, M) -> src_corr (B, 3, N) = tgt softmax(src_embedding^T tgt_embedding / sqrt(C), dim=2)^T,
+    differentiable in all three; the (B, N, M) score matrix is never stored."""
+    from .pointer import soft_pointer
+    return soft_pointer(src_embedding, tgt_embedding, tgt)
+
+
+def dcp_svd_head(src_embedding, tgt_embedding, src, tgt):
+    """SVDHead.forward (dcp/model.py:414-455) as TWO nodes: dcp_soft_pointer, then dcp_svd_head_pose(src, src_corr).
+    src (B, 3, N), tgt (B, 3, M) -> (R (B, 3, 3), t (B, 3))."""
+    return dcp_svd_head_pose(src, dcp_soft_pointer(src_embedding, tgt_embedding, tgt))
+
+
 # ---- RPM's match head: Sinkhorn soft assignment in front of the solve above ----------------------------------------------
 def rpm_soft_correspondences(affinity, xyz_ref, n_iters=5, slack=True):
     """rpm/models/rpmnet.py:211-222 up to the solve, as ONE node (rrl_hip.sinkhorn): affinity (B, J, K), xyz_ref (B, K, 3) ->

@@ -1461,6 +1461,53 @@ int rrl_robust_step_batch(const float *Rk, const float *Tk, const int32_t *info,
 int rrl_robust_icp_epoch(const rrl_icp_epoch_args *args, int init, float *w, float *nu, const float *nu_end, float *med_sq,
                          int32_t *med_info, double nu_scale, float anneal, int level_cap, int32_t *level, void *stream);
 
+/* ---- DCP's softmax pointer: the SVD head's correspondences without the score matrix ---------
+ * SVDHead.forward (dcp/model.py:419-425): scores = softmax(src_emb^T tgt_emb / sqrt(C), dim = 2), src_corr = tgt scores^T.
+ * Channel-first as DCP holds them: src_emb [B][C][N], tgt_emb [B][C][M], tgt [B][3][M], corr and g_corr [B][3][N].
+ * count_src / count_tgt: device int32 [B] or NULL (= N / M), clamped by the kernels to [0, N] / [0, M], never read on the host;
+ * what lies beyond a count is never read.  Plain device pointers, sizes and a stream: nothing is allocated, read back or
+ * synchronised, there are no atomics, nothing is indexed by data, every launch goes to the caller's stream.
+ *
+ * The rule (the library's first matrix-core kernel: gfx950's f32-input MFMA v_mfma_f32_32x32x2_f32 IS this chain, bit for bit):
+ *  1. chain[j][k] starts at +0 and runs over the channels c = 0 .. C - 1 in ascending order, chain = fmaf(src_emb[c][j],
+ *     tgt_emb[c][k], chain): ONE chain per score, never split over wavefronts or channel blocks, so a score does not depend on
+ *     the tiling.  An odd C is padded with a zero channel in BOTH operands (0 * inf would be NaN).
+ *  2. z[j][k] = chain * sc, one float32 multiplication, sc = float32(1 / sqrt(double(C))).
+ *  3. A softmax state is (m, l, n[3]), one per row and slice of RRL_POINTER_SLICE columns: m the largest score of the row's
+ *     columns in the slice (a lane keeps the slice's scores in registers, so the maximum is final before the first term: the
+ *     running maximum of a state rises once, from -inf, and no rescaling factor is ever applied inside a state), l = sum p and
+ *     n = sum p x in double, p the float32 expf of the float32 difference z - m; a -inf score and a masked column give p = 0
+ *     without forming -inf - (-inf).  A lane sums its columns ascending (columns 4 h .. 4 h + 3 of every eight, h = lane >> 5),
+ *     the row's two half-waves are added h = 0 first.  The slices are merged in index order: M = max m_s, L = sum l_s expf(m_s -
+ *     M), likewise n: ONE float32 factor per slice, common to l and n.  corr[j] = float32(n / L); a row at or beyond count_src,
+ *     and every row when count_tgt[b] == 0, is exactly 0.
+ *  4. Backward, on z recomputed by the same chain (the same bits) and the row's final M_j, L_j and corr_j kept in ws:
+ *     P = expf(z - M_j) (1 / L_j) (the reciprocal taken once per row, in double), delta_j = g_j . corr_j, ds[j][k] = float32(P (g_j . x_k - delta_j) sc), all in double from the
+ *     float32 expf; d_tgt[k] = sum_j P g_j in double (per lane over its rows ascending, then the lane halves, then the four
+ *     wavefronts), rounded once; d_src_emb[c][j] = the float32 fmaf chain over k ascending of ds[j][k] tgt_emb[c][k], and
+ *     d_tgt_emb[c][k] the chain over j ascending of ds[j][k] src_emb[c][j]: whole chains, never cut (an MFMA again).  Rows and
+ *     columns beyond the counts get zero gradient.  Every element of every output is written; nothing is pre-zeroed.
+ * Two calls give the same bits; sample b of a ragged batch has the bits of its own B = 1 call.
+ *
+ * scores (optional) [B][N][M]: z, -inf at and beyond the counts -- detached, for a trainer's endpoints.  info (optional) [B]:
+ * 1 where a score inside the counts is NaN or +-inf (the sample's outputs are then NaN where it reaches), else 0.
+ * d_src_emb, d_tgt_emb, d_tgt: each may be NULL.
+ * ws: rrl_pointer_workspace_bytes(B, C, N, M) bytes, 8-byte aligned: six doubles per (row, slice) and five per row -- no
+ * (B, N, M) array in either direction (except scores when asked for).  The backward takes the ws its forward filled.
+ * Launches: forward 2 (tiles, then the slices' merge); backward 1 per pass (d_src_emb; d_tgt_emb with d_tgt).
+ * Refusals, on the host before any HIP call: RRL_E_ARG -- NULL src_emb / tgt_emb / tgt / ws / corr (backward: g_corr); B outside
+ * 0..32767; C outside 1..RRL_POINTER_MAX_C; N or M outside 1..16384 --, then RRL_E_WS: a short or misaligned ws.  B == 0
+ * returns 0 without a launch. */
+#define RRL_POINTER_MAX_C 1024
+#define RRL_POINTER_SLICE 128 /* columns per slice of the forward */
+size_t rrl_pointer_workspace_bytes(int B, int C, int N, int M);
+int rrl_pointer_fwd(const float *src_emb, const float *tgt_emb, const float *tgt, const int32_t *count_src,
+                    const int32_t *count_tgt, void *ws, size_t ws_bytes, float *corr, float *scores, int32_t *info, int B, int C,
+                    int N, int M, void *stream);
+int rrl_pointer_bwd(const float *src_emb, const float *tgt_emb, const float *tgt, const int32_t *count_src,
+                    const int32_t *count_tgt, void *ws, size_t ws_bytes, const float *g_corr, float *d_src_emb, float *d_tgt_emb,
+                    float *d_tgt, int B, int C, int N, int M, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
