@@ -465,3 +465,50 @@ def dcp_graph_feature(x, k=20):
     k > N.  Forward only: the reference feeds the input clouds, which carry no gradient."""
     from . import neighbors
     return neighbors.knn_group(_dcp_cloud(x, k), k, features=("nbr", "ctr"), channel_first=True)[0]
+
+
+# ---- FMR's pose head: the inverse-compositional solver around its encoder (DESIGN.md section 23) ------------------------------
+def fmr_approx_jac(encoder, p0, f0, dt, features_only=False):
+    """fmr/model.py:408-433 approx_Jac(p0, f0, dt): the finite-difference Jacobian of the encoder's features in the six twist
+    coordinates, J (B, K, 6) = (f0 - f(exp(-dt_i e_i) p0)) / dt_i, from p0 (B, N, 3), f0 (B, K) and dt (B, 6).  The six perturbed
+    clouds are ONE launch (fmr.ic_perturb: no Python loop over the batch, no diag / exp / matmul per sample) and one encoder call
+    on (6 B, N, 3), as in the reference.  features_only=True returns the perturbed features fp (B, 6, K) instead -- what
+    fmr.ic_pinv takes: it forms J itself, in double."""
+    from . import fmr
+    B, N = p0.shape[0], p0.shape[1]
+    fp = encoder(fmr.ic_perturb(p0, dt).reshape(6 * B, N, 3)).reshape(B, 6, -1)
+    if features_only:
+        return fp
+    return (f0.unsqueeze(-1) - fp.transpose(1, 2)) / dt.to(fp).unsqueeze(1)
+
+
+def fmr_ic_algo(encoder, p0, p1, maxiter=5, xtol=1e-7, dt=None, g0=None):
+    """fmr/model.py:318-405 SolveRegistration.ic_algo behind the decoder branch, as 2 + 2 maxiter launches of the head (perturb 1,
+    pinv 1, update 2 per iteration; 12 at maxiter = 5) plus one ops.rigid_apply per iteration, around the encoder's calls:
+    f0 = encoder(p0); the perturbed features (fmr_approx_jac); pinv (fmr.ic_pinv); then `maxiter` times
+    p = g p1 (ops.rigid_apply with R and t sliced from g, so gradients reach g through it), f1 = encoder(p) and fmr.ic_update.
+    p0, p1 (B, N, 3) on the GPU; dt the reference's (1, 6) parameter or (B, 6) (default 1e-2 everywhere); g0 (B, 4, 4) (default
+    the identity).  Returns (r (B, K), g (B, 4, 4), g_series (maxiter, B, 4, 4), stop int32 (1,), info int32 (B,)).
+
+    No host read-back: the reference's `float(check) < xtol` is evaluated on the device, every iteration is issued, and a loop
+    that has stopped leaves g unchanged bit for bit -- so g_series holds the LAST pose where the reference's g_series_gpu keeps
+    zeros (`stop` is 1 then: torch.where puts the zeros back), r is the stopping iteration's, and the call can be captured
+    (rrl_hip/graph.py) when the encoder can.  A singular H does not raise: info is 1 for that sample and its pose stays g0."""
+    from . import fmr
+    if isinstance(maxiter, bool) or int(maxiter) != maxiter or maxiter < 1:
+        raise ValueError(f"maxiter must be a positive integer, got {maxiter!r}")
+    B = p0.shape[0]
+    if dt is None:
+        dt = torch.full((1, 6), 1.0e-2, device=p0.device)
+    dt = dt.to(p0).reshape(-1, 6).expand(B, 6)
+    g = torch.eye(4, device=p0.device).expand(B, 4, 4).contiguous() if g0 is None else g0
+    f0 = encoder(p0)
+    fp = fmr_approx_jac(encoder, p0, f0, dt, features_only=True)
+    pinv, info = fmr.ic_pinv(f0, fp, dt, with_info=True)
+    stop = fmr.new_stop(p0.device)
+    series, r = [], None
+    for _ in range(int(maxiter)):
+        p = _ops.rigid_apply(p1, g[:, :3, :3], g[:, :3, 3], transpose_r=True)
+        r, _, g, stop = fmr.ic_update(pinv, f0, encoder(p), g, stop, xtol)
+        series.append(g)
+    return r, g, torch.stack(series), stop, info

@@ -1508,6 +1508,72 @@ int rrl_pointer_bwd(const float *src_emb, const float *tgt_emb, const float *tgt
                     const int32_t *count_tgt, void *ws, size_t ws_bytes, const float *g_corr, float *d_src_emb, float *d_tgt_emb,
                     float *d_tgt, int B, int C, int N, int M, void *stream);
 
+/* ---- FMR's inverse-compositional solver: the pose head as three pairs of entries -------------
+ * SolveRegistration.ic_algo / approx_Jac (fmr/model.py:318-439) with se_math/se3.py:57-80, 133-165 (exp, ExpMap) and
+ * se_math/invmat.py:6-13, 83-112 (InvMatrix), everything between the encoder's outputs and the poses; the encoder stays the
+ * caller's.  Features f32 [B][K]; perturbed features fp [B][6][K] (the encoder's output on the perturbed clouds viewed as
+ * (B, 6, K): no transpose); dt [B][6]; poses 4 x 4 row-major [B][4][4], p' = R p + t, fourth row (0, 0, 0, 1); clouds [B][N][3].
+ * Plain device pointers, sizes and a stream: nothing is allocated, read back or synchronised, there are no atomics, every
+ * element of every output is written and nothing is pre-zeroed, every launch goes to the caller's stream and is capturable.
+ * A sum over K or N is a fixed-order double sum: a workgroup of 256 lanes per sample, lane l takes l, l + 256, ... ascending,
+ * the 64 lanes of a wavefront are added by one fixed tree, the four wavefronts in index order.  Two calls give the same bits;
+ * sample b of a batch has the bits of its own B = 1 call (rrl_ic_update_fwd: where the stop rule decides alike).
+ *
+ * exp(x), x = (w, v): rrl_se3_exp's rule in DOUBLE -- t = |w|, W = [w]x, R = I + s1 W + s2 W W, V = I + s2 W + s3 W W, p = V v,
+ * s1 = sin t / t, s2 = (1 - cos t) / t^2, s3 = (t - sin t) / t^3, the reference's Taylor polynomials inside |t| < 0.01
+ * (se_math/sinc.py) --, rows (R | p) and (0, 0, 0, 1).  gen_k = the k-th generator (se3.py genmat): for k < 3, with a = (k + 1) % 3
+ * and b = (k + 2) % 3, row b of gen_k X is row a of X and row a is minus row b; for k >= 3, row k - 3 is X's fourth row.
+ *
+ * 1. rrl_ic_perturb_fwd: out [B][6][N][3] = D_i applied to p0 [B][N][3], D_i = exp(-dt_i e_i) evaluated in double and rounded
+ *    ONCE to float32; a point is the float32 chain of rrl_rigid_apply_fwd in this convention,
+ *        out_j = fmaf(p_2, D[j][2], fmaf(p_1, D[j][1], p_0 * D[j][0])) + D[j][3].                                One launch.
+ *    rrl_ic_perturb_bwd: to dt only (p0 carries no gradient in the reference).  M = sum_n g_out[b][i][n] (x) [p_n; 1], twelve
+ *    double sums over n; g_dt[b][i] = float32(-sum_jk M_jk [gen_i D_i]_jk), D_i in double (not rounded).  For a single-axis
+ *    twist ExpMap's rule IS the derivative.                                                                      One launch.
+ * 2. rrl_ic_pinv_fwd: all in double.  J[k][i] = (double(f0[k]) - double(fp[i][k])) / double(dt[i]); H = the 21 sums sum_k
+ *    J_ki J_kj; H^-1 by the unpivoted, undamped Cholesky (the loops of the pose steps' solver), column c solved from e_c;
+ *    pinv[i][k] = float32(sum_j H^-1_ij J_kj), j ascending.  info[b] = 1 (info may be NULL) and that sample's pinv is exactly 0
+ *    -- its pose will not move -- when a pivot p_j fails p_j > (K + 6) 2^-52 H_jj (the rounding of H's own sums: below it a
+ *    pivot is not told from 0), is not finite, or an entry of H^-1 is not finite; when an input of the sample (f0, fp, dt) is
+ *    NaN or +-inf; when a dt_i is 0; when K < 6.  This replaces the reference's `except RuntimeError`.
+ *    ws: RRL_IC_WS_DOUBLES doubles per sample, 8-byte aligned -- H^-1 (36, zeros when flagged), the flag, padding; J is not
+ *    kept: the backward recomputes it by the same expression.                                                    One launch.
+ *    rrl_ic_pinv_bwd, G = g_pinv: P = G J (36 double sums over k); S = -(H^-1 P) H^-1; dJ[k][i] = sum_j G[j][k] H^-1_ji + sum_j
+ *    J[k][j] (S + S^T)_ji; d_f0[k] = float32(sum_i dJ_ki / dt_i); d_fp[i][k] = float32(-(dJ_ki / dt_i)); d_dt[i] =
+ *    float32(-(sum_k dJ_ki J_ki) / dt_i).  InvMatrix.backward composed with the two bmm's.  A flagged sample gets zeros.
+ *    d_f0, d_fp, d_dt: each may be NULL.                                                                         One launch.
+ * 3. rrl_ic_update_fwd: r = f1 - f0 (one float32 subtraction); dx_i = float32(-sum_k double(pinv[i][k]) double(r[k])); a
+ *    sample's step length n_b = float32(sqrt(sum_i double(dx_i)^2)).  The batch-wide rule of the reference (check = max_b n_b,
+ *    stop when check < xtol; a NaN n_b makes check NaN, which is not < xtol): the batch stops when `stop` (a device int32 the
+ *    caller zeroes once per loop) is already set or EVERY n_b < xtol.  Then stop = 1 and g_new = g bit for bit for every sample;
+ *    else stop = 0 and g_new = float32(exp(dx) g), exponential and product in double (rows 0..2: sum over m ascending of
+ *    exp_im g_mj; the fourth row is g's).  A NaN dx therefore does not stop: that sample's pose becomes NaN.  `stopped` (int32,
+ *    one word per CALL) receives this call's decision for its backward.  Deviation from the reference: after the stop its
+ *    g_series_gpu keeps zeros; here the later poses hold the last pose and `stop` lets a caller put the zeros back.
+ *    ws: rrl_ic_update_workspace_bytes(B), 8-byte aligned (the n_b).   Two launches: per-sample sums, then one workgroup.
+ *    rrl_ic_update_bwd, on the r, dx and `stopped` the forward left; G' = g_g_new, Gr = g_r, Gdx = g_dx (each may be NULL = 0).
+ *    Stopped: d_g = G', d_f1 = Gr, d_f0 = -Gr, d_pinv = 0.  Else d_g = exp(dx)^T G'; q_k = sum_ij (G' g^T)_ij [gen_k exp(dx)]_ij
+ *    + Gdx_k -- ExpMap.backward's rule word for word: for a general twist NOT the exact derivative of exp --; d_pinv[i][k] =
+ *    float32(-(q_i r_k)); d_f1[k] = float32(Gr_k - sum_i pinv[i][k] q_i); d_f0 = -d_f1.  d_g, d_pinv, d_f0, d_f1: each may be
+ *    NULL.                                                                                                       One launch.
+ * Refusals, on the host before any HIP call: RRL_E_ARG -- a NULL pointer that is not marked optional, B outside 0..65535,
+ * N < 1, K outside 1..RRL_IC_MAX_K --, then RRL_E_WS: a short or misaligned ws.  B == 0 returns 0 without a launch. */
+#define RRL_IC_MAX_K 16384
+#define RRL_IC_WS_DOUBLES 40 /* per sample: H^-1 [36], the flag, padding */
+int rrl_ic_perturb_fwd(const float *p0, const float *dt, float *out, int B, int N, void *stream);
+int rrl_ic_perturb_bwd(const float *p0, const float *dt, const float *g_out, float *g_dt, int B, int N, void *stream);
+size_t rrl_ic_pinv_workspace_bytes(int B, int K);
+int rrl_ic_pinv_fwd(const float *f0, const float *fp, const float *dt, void *ws, size_t ws_bytes, float *pinv, int32_t *info,
+                    int B, int K, void *stream);
+int rrl_ic_pinv_bwd(const float *f0, const float *fp, const float *dt, const void *ws, size_t ws_bytes, const float *g_pinv,
+                    float *d_f0, float *d_fp, float *d_dt, int B, int K, void *stream);
+size_t rrl_ic_update_workspace_bytes(int B);
+int rrl_ic_update_fwd(const float *pinv, const float *f0, const float *f1, const float *g, float xtol, int32_t *stop, void *ws,
+                      size_t ws_bytes, float *r, float *dx, float *g_new, int32_t *stopped, int B, int K, void *stream);
+int rrl_ic_update_bwd(const float *pinv, const float *r, const float *dx, const float *g, const int32_t *stopped,
+                      const float *g_g_new, const float *g_r, const float *g_dx, float *d_g, float *d_pinv, float *d_f0,
+                      float *d_f1, int B, int K, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
