@@ -512,3 +512,16 @@ def fmr_ic_algo(encoder, p0, p1, maxiter=5, xtol=1e-7, dt=None, g0=None):
         r, _, g, stop = fmr.ic_update(pinv, f0, encoder(p), g, stop, xtol)
         series.append(g)
     return r, g, torch.stack(series), stop, info
+
+
+# ---- FMR's feature extractor: the PointNet encoder as one node ------------------------------------------
+def fmr_encoder(dim_k=1024, state_dict=None):
+    """fmr/model.py:105-126 PointNet(dim_k) as pointnet.Encoder: a torch.nn.Module with the reference's state_dict keys and shapes
+    (h1.0.weight (64, 3, 1) ... h2.7.bias), on the current GPU, whose forward (B, N, 3) -> (B, dim_k) is ONE node of the library.
+    state_dict: a reference checkpoint's encoder weights, loaded with strict=True.  fmr_ic_algo(fmr_encoder(...), p0, p1) is then
+    the whole ic_algo with nothing of it in eager torch."""
+    from . import pointnet
+    net = pointnet.Encoder.fmr(dim_k)
+    if state_dict is not None:
+        net.load_state_dict({k: torch.as_tensor(v) for k, v in state_dict.items()}, strict=True)
+    return net.to(_ops.require_gpu())

@@ -1574,6 +1574,80 @@ int rrl_ic_update_bwd(const float *pinv, const float *r, const float *dx, const 
                       const float *g_g_new, const float *g_r, const float *g_dx, float *d_g, float *d_pinv, float *d_f0,
                       float *d_f1, int B, int K, void *stream);
 
+/* ---- A shared-MLP + GroupNorm + ReLU + max-pool encoder: FMR's PointNet, RPM's prepool ---------
+ * fmr/model.py:57-126 PointNet (3 -> 64 -> 64 -> 64 -> 128 -> K, GroupNorm(8, .)) and rpm/models/feature_nets.py:31-52
+ * ParameterPredictionNet.prepool (4 -> 64 -> 64 -> 64 -> 128 -> 1024, 8 / 8 / 8 / 8 / 16 groups), followed by the max over the
+ * points.  points f32 [B][N][c0], 1 <= c0 <= RRL_PN_MAX_C0; layers l = 1 .. L, 2 <= L <= RRL_PN_MAX_LAYERS, widths[l - 1] = c_l
+ * a multiple of groups[l - 1] = G_l, hidden widths <= RRL_PN_MAX_HIDDEN, the last K = c_L <= RRL_IC_MAX_K.  widths and groups
+ * are HOST arrays of L ints; params is a HOST array of 4 L DEVICE pointers, params[4 (l - 1) + 0 .. 3] = W_l [c_l][c_{l-1}] (a
+ * Conv1d weight as torch holds it), b_l, gamma_l, beta_l [c_l]: they reach the kernels as arguments -- nothing is allocated,
+ * copied, read back or synchronised, there are no atomics, every launch goes to the caller's stream and is capturable.
+ *
+ * The rule:
+ *  1. y_l[c][n] is ONE float32 fmaf chain that starts at b_l[c] and runs over the input channels k ascending,
+ *     y = fmaf(W_l[c][k], h_{l-1}[k][n], y), h_0 = the points; never split over wavefronts or tiles.  From 64 input channels
+ *     upward it is gfx950's f32-input MFMA (bit for bit this chain, as for rrl_pointer_fwd; an odd count is padded with a zero
+ *     channel in both operands), below plain fmaf.
+ *  2. Per (sample, layer, group), over the m = (c_l / G_l) N values of the group: sum y and sum y^2 are fixed-order double
+ *     sums (a lane over its points ascending, one butterfly over the 32 lanes of a tile, one partial per chunk of 128 points
+ *     and channel in ws; then a channel's chunks ascending, per group lane i of a wavefront adds the channels i, i + 64, ...
+ *     ascending, and the lanes are added by one fixed tree).  mu = sum y / m, var = max(0, sum y^2 / m - mu^2), r = 1 /
+ *     sqrt(var + eps), in double.
+ *  3. h_l[c][n] = float32(max(0, double(y) a_c + d_c)), a_c = double(gamma_c) r, d_c = double(beta_c) - mu a_c: a double
+ *     multiplication, a double addition (not fused), one rounding to float32; max(0, t) is 0 where t < 0, else t (a NaN stays).
+ *  4. y_L is never stored.  The map of 3 is monotone, so max_n h_L[c][n] is 3 at ext_c = max_n y_L[c][n] where a_c >= 0 and
+ *     min_n y_L[c][n] where a_c < 0: feat[b][c] = float32(max(0, double(ext_c) a_c + d_c)), arg[b][c] = the LOWEST n that
+ *     attains ext_c.  Deviation: where several points tie (or gamma_c = 0) torch's max-pool picks its own index among equal
+ *     values; where feat = 0 no gradient flows either way.
+ *  5. info[b] = 1 (info may be NULL) and feat[b][.] is NaN when a sum y or sum y^2, or an a_c or d_c, of ANY layer of the
+ *     sample is not finite (a NaN or +-inf among the sample's points poisons that sample only, one in a parameter every
+ *     sample); else info = 0.
+ * ws: rrl_pointnet_workspace_bytes(...) bytes, 16-byte aligned; every byte is written by the forward.  offsets (optional):
+ * RRL_PN_FIELDS byte offsets of its fields --
+ *   RRL_PN_STAT  f64 [B][sum G_l][4]: sum y, sum y^2, mu, r per group, the layers' groups one after the other;
+ *   RRL_PN_COEF  f64 [B][sum c_l][2]: a_c, d_c, the layers' channels one after the other;
+ *   RRL_PN_PART  f64, per layer [B][chunks][c_l][2]: the per-chunk partial sums;
+ *   RRL_PN_EPART per (sample, chunk, channel of the last layer): the chunk's extremum as z = y (gamma_c >= 0) or -y (gamma_c <
+ *                0) f32, its lowest index int32 (r > 0, so a_c >= 0 exactly where gamma_c >= 0);
+ *   RRL_PN_EXT   f32 [B][K]: ext_c;   RRL_PN_FLAG int32 [B]: info;
+ *   RRL_PN_Y     f32 [B][sum hidden c_l][N]: y_1 .. y_{L-1} channel-first -- 4 sum hidden c_l bytes per point (1280 for FMR),
+ *                nothing K wide per point.
+ * Two calls give the same bits; sample b of a batch has the bits of its own B = 1 call.  Launches: two per layer.
+ * Refusals, on the host before any HIP call: RRL_E_ARG -- a NULL points / params / params[i] / widths / groups / ws / feat /
+ * arg, B outside 0..65535, N outside 1..2^20, c0, L, a width or a group count outside the limits above, eps <= 0 --, then
+ * RRL_E_WS: a short or misaligned ws (rrl_pointnet_workspace_bytes is 0 for a shape that is refused).  B == 0 returns 0
+ * without a launch. */
+#define RRL_PN_MAX_C0 8
+#define RRL_PN_MAX_LAYERS 8
+#define RRL_PN_MAX_HIDDEN 128
+enum { RRL_PN_STAT, RRL_PN_COEF, RRL_PN_PART, RRL_PN_EPART, RRL_PN_EXT, RRL_PN_FLAG, RRL_PN_Y, RRL_PN_FIELDS };
+size_t rrl_pointnet_workspace_bytes(int B, int N, int c0, int L, const int32_t *widths, const int32_t *groups, size_t *offsets);
+int rrl_pointnet_fwd(const float *points, const float **params, const int32_t *widths, const int32_t *groups, double eps,
+                     void *ws, size_t ws_bytes, float *feat, int32_t *arg, int32_t *info, int B, int N, int c0, int L,
+                     void *stream);
+/* The backward of rrl_pointnet_fwd, on the ws its forward filled (16-byte aligned) and the forward's arg: from g_feat [B][K] to
+ * d_points [B][N][c0] and, through d_params -- a HOST array of 4 L device pointers in params' order, or NULL --, dW_l, db_l,
+ * dgamma_l, dbeta_l.  d_points, d_params and every entry of d_params may be NULL; what is asked for is written in full, nothing
+ * is pre-zeroed.  All arithmetic is double on the kept float32 y_l, mu, r, a, d, ext and arg, one rounding per output; every sum
+ * runs over its reduced index ascending in one thread, or lane l of a wavefront over n = l, l + 64, ... (sample after sample
+ * where the batch is summed) and then one fixed tree; parameter gradients sum the samples b ascending.  No atomics.
+ *  Per layer GroupNorm's rule with xhat = (y - mu) r, dxhat = gamma dout: dgamma_c = sum_n dout xhat, dbeta_c = sum_n dout,
+ *  dy = r (dxhat - P / m - xhat Q / m), P = sum_group gamma dbeta, Q = sum_group gamma dgamma; dW = sum_{b,n} dy (x) h_{l-1},
+ *  db = sum dy, dh_{l-1} = W^T dy (c ascending) gated by h_{l-1} > 0.
+ *  The last layer needs no N x K work: dout is s_c = g_feat[c] [feat[c] > 0] at (c, arg_c) only, so with x_c = (ext_c - mu) r,
+ *  t_c = r gamma_c s_c, A_g = -r P / m + r^2 Q mu / m, B_g = -r^2 Q / m, S1 = sum_n h_{L-1}[n] and S2 = sum_n h h^T (per sample):
+ *  dW_L[c] = t_c h[arg_c] + A_g S1 + B_g (W_L[c] S2 + b_c S1), db_L[c] = t_c + N A_g + B_g (W_L[c] . S1 + N b_c), dgamma_c = s_c x_c,
+ *  dbeta_c = s_c, dh_{L-1}[n] = M h[n] + v + sum over the channels c ascending with arg_c = n of t_c W_L[c], M = sum_c B_g W_L[c]^T
+ *  W_L[c], v = sum_c (A_g + B_g b_c) W_L[c].  A sample the forward flagged has s_c = NaN: its d_points and every parameter
+ *  gradient become NaN, as torch's would.
+ * bws: rrl_pointnet_bwd_workspace_bytes(...) bytes, 8-byte aligned: 3 K + 2 G_L + 2 H (H + 1) + 2 hmax doubles per sample (H =
+ * c_{L-1}, hmax the widest hidden layer) and two buffers of hmax N doubles per sample -- nothing K wide per point.
+ * Refusals as the forward's (NULL arg / g_feat / bws: RRL_E_ARG; a short or misaligned ws or bws: RRL_E_WS); B == 0 returns 0. */
+size_t rrl_pointnet_bwd_workspace_bytes(int B, int N, int c0, int L, const int32_t *widths, const int32_t *groups);
+int rrl_pointnet_bwd(const float *points, const float **params, const int32_t *widths, const int32_t *groups, const void *ws,
+                     size_t ws_bytes, const int32_t *arg, const float *g_feat, void *bws, size_t bws_bytes, float *d_points,
+                     float **d_params, int B, int N, int c0, int L, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
