@@ -438,6 +438,25 @@ def rpm_raw_features(xyz, normals, features, radius=0.3, nsample=64):
     return neighbors.ball_group(xyz, normals, radius, nsample, features=features)[0]
 
 
+def rpm_feat_prepool_pool(net, raw):
+    """rpm/models/feature_nets.py:196-199 -- the permute to (B, C, nsample, N), self.prepool and torch.max(new_feat, 2)[0] -- as
+    ONE node (pointnet.encode_grouped): raw (B, N, nsample, C) from rpm_raw_features, net a
+    pointnet.GroupedEncoder (GroupedEncoder.rpm_feat_prepool loads the reference's prepool weights with strict=True) -> the pooled
+    features (B, 2 feature_dim, N).  No (B, C, nsample, N) activation is written; where slots tie (ball-query pads short groups
+    with repeated slots) the gradient goes to the lowest slot, where torch picks its own."""
+    return net(raw)
+
+
+def rpm_feat_extractor(net, postpool, xyz, normals, features, radius=0.3, nsample=64):
+    """rpm/models/feature_nets.py:173-205 FeatExtractionEarlyFusion.forward: xyz, normals (B, N, 3) -> cluster features (B, N, C).
+    Lines 184-193 are one launch (rpm_raw_features), lines 196-199 one node (rpm_feat_prepool_pool); `postpool` is the reference's
+    torch module of line 201 (get_postpool, :134-152), which works on N positions only and stays in torch; then the permute and
+    the division by the norm of lines 202-203."""
+    raw = rpm_raw_features(xyz, normals, features, radius, nsample)
+    post = postpool(rpm_feat_prepool_pool(net, raw)).permute(0, 2, 1)
+    return post / torch.norm(post, dim=-1, keepdim=True)
+
+
 # ---- DCP's feature extractor: the k-NN graph and its edge features in front of DGCNN's convolutions ------------------------
 def _dcp_cloud(x, k):
     if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != 3:

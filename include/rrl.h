@@ -1648,6 +1648,61 @@ int rrl_pointnet_bwd(const float *points, const float **params, const int32_t *w
                      size_t ws_bytes, const int32_t *arg, const float *g_feat, void *bws, size_t bws_bytes, float *d_points,
                      float **d_params, int B, int N, int c0, int L, void *stream);
 
+/* ---- The grouped PointNet: shared layers over every (point, neighbour slot) position, max over each point's slots -------------
+ * RPM's FeatExtractionEarlyFusion.prepool followed by torch.max(new_feat, 2)[0] (rpm/models/feature_nets.py:118-131, 196-199;
+ * DESIGN.md section 25).  x f32 [B][N][S][c0], the layout rrl_ball_group writes: N points of S slots, 1 <= S <= RRL_PG_MAX_S, 1 <=
+ * c0 <= RRL_PG_MAX_C0, N <= 2^20, N S <= 2^22.  Layers, widths, groups, params and the conventions as rrl_pointnet_fwd (2 <= L <=
+ * RRL_PN_MAX_LAYERS, hidden widths <= RRL_PN_MAX_HIDDEN); the last width K <= RRL_PG_MAX_K.  Position p = n S + s takes the place
+ * of rrl_pointnet_fwd's point: rules 1 and 3 hold as stated there over the P = N S positions, and
+ *  2. per (sample, layer, group), over the m = (c_l / G_l) N S values of the group, sum y and sum y^2 are fixed-order double sums:
+ *     a chunk is floor(128 / S) whole points (its positions in 32-position tiles from the chunk's start); a lane adds its
+ *     positions of the chunk ascending (lane q those at offsets q, q + 32, ...), one butterfly over the 32 lanes, one partial per
+ *     (chunk, channel) in ws; then per channel lane i of a wavefront adds the chunks i, i + 64, ... ascending and the lanes are
+ *     added by one fixed tree; per group lane i adds the channels i, i + 64, ... and the same tree.  mu, var, r as there.
+ *  4. y_L is never stored and h_L is never formed per position.  out[b][c][n] = float32(max(0, double(ext) a_c + d_c)), f32
+ *     channel-first (B, K, N), with ext = max_s y_L[c][n S + s] where gamma_c >= 0 and min_s where gamma_c < 0; arg[b][c][n]
+ *     int32 is the LOWEST slot s that attains it.  A point's slots are pooled inside one workgroup, never by atomics.
+ *     Deviation: rrl_ball_group pads a short group with repeated slots, equal slots give exactly equal y, so ties are the normal
+ *     case; torch's max picks its own index among equal values, arg is the lowest.  Parameter gradients do not depend on the choice.
+ *  5. info[b] = 1 (info may be NULL) and out[b] is NaN throughout when a sum or coefficient of ANY layer of the sample is not finite.
+ * ws: rrl_pointnet_group_workspace_bytes(...) bytes, 16-byte aligned, every byte written by the forward; offsets (optional):
+ * RRL_PG_FIELDS byte offsets --
+ *   RRL_PG_STAT f64 [B][sum G_l][4]; RRL_PG_COEF f64 [B][sum c_l][2]; RRL_PG_PART f64 per layer [B][chunks][c_l][2];
+ *   RRL_PG_EXT f32 [B][K][N]: ext; RRL_PG_FLAG int32 [B]; RRL_PG_Y f32 [B][sum hidden c_l][N S]: y_1 .. y_{L-1} channel-first over
+ *   the positions.  Nothing K wide per position is kept.
+ * Two calls give the same bits; sample b of a batch has the bits of its own B = 1 call.  Launches: two per layer and one.
+ * Refusals, on the host before any HIP call: RRL_E_ARG -- a NULL x / params / params[i] / widths / groups / ws / out / arg, B
+ * outside 0..65535, N, S, N S, c0, L, a width or a group count outside the limits above, eps <= 0 --, then RRL_E_WS: a short or
+ * misaligned ws (the size is 0 for a shape that is refused).  B == 0 returns 0 without a launch. */
+#define RRL_PG_MAX_C0 16
+#define RRL_PG_MAX_S 128
+#define RRL_PG_MAX_K 1024
+enum { RRL_PG_STAT, RRL_PG_COEF, RRL_PG_PART, RRL_PG_EXT, RRL_PG_FLAG, RRL_PG_Y, RRL_PG_FIELDS };
+size_t rrl_pointnet_group_workspace_bytes(int B, int N, int S, int c0, int L, const int32_t *widths, const int32_t *groups,
+                                          size_t *offsets);
+int rrl_pointnet_group_fwd(const float *x, const float **params, const int32_t *widths, const int32_t *groups, double eps, void *ws,
+                           size_t ws_bytes, float *out, int32_t *arg, int32_t *info, int B, int N, int S, int c0, int L,
+                           void *stream);
+/* The backward of rrl_pointnet_group_fwd on the ws its forward filled and the forward's arg: from g_out [B][K][N] to d_x
+ * [B][N][S][c0] and, through d_params (a HOST array of 4 L device pointers, or NULL), dW_l, db_l, dgamma_l, dbeta_l.  d_x,
+ * d_params and every entry of it may be NULL; what is asked for is written in full.  Double arithmetic on the kept float32 y_l,
+ * mu, r, a, d, ext and arg, one rounding per output, no atomics; rrl_pointnet_bwd's rule 5 with P = N S for N and the last
+ * layer's sparse term per point: s_{c,n} = g_out[c][n] [out[c][n] > 0] sits at position n S + arg[c][n];
+ *  dbeta_c = sum_n s_{c,n}, dgamma_c = sum_n s_{c,n} x_{c,n}, x = (ext - mu) r, t_{c,n} = r gamma_c s_{c,n};
+ *  dW_L[c] = sum_n t_{c,n} h[n S + arg_{c,n}] + A_g S1 + B_g (W_L[c] S2 + b_c S1), db_L[c] = sum_n t_{c,n} + P A_g + B_g (W_L[c] . S1
+ *  + P b_c), dh_{L-1}[p] = M h[p] + v + sum over the channels c ASCENDING with arg[c][n(p)] = s(p) of t_{c,n(p)} W_L[c].
+ * Order of the sums: a sum over a point's or a sample's points is lane i of a wavefront over n = i, i + 64, ... and one fixed
+ * tree; the position-summed products (S1, S2, every hidden dW and db, the hidden layers' dgamma and dbeta) are formed per chunk
+ * of 1024 positions (positions ascending inside a thread, or lane i the positions i, i + 64, ... and the tree) as double partials
+ * in bws and added chunk after chunk, sample after sample by a second launch; sums over channels run c ascending.
+ * bws: rrl_pointnet_group_bwd_workspace_bytes(...) bytes, 8-byte aligned: two buffers of hmax N S doubles per sample, the chunk
+ * partials and O(K + H^2) doubles per sample -- nothing K wide per position.  Refusals as the forward's (NULL arg / g_out / bws:
+ * RRL_E_ARG; a short or misaligned ws or bws: RRL_E_WS); B == 0 returns 0. */
+size_t rrl_pointnet_group_bwd_workspace_bytes(int B, int N, int S, int c0, int L, const int32_t *widths, const int32_t *groups);
+int rrl_pointnet_group_bwd(const float *x, const float **params, const int32_t *widths, const int32_t *groups, const void *ws,
+                           size_t ws_bytes, const int32_t *arg, const float *g_out, void *bws, size_t bws_bytes, float *d_x,
+                           float **d_params, int B, int N, int S, int c0, int L, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
