@@ -7,7 +7,8 @@
 //           as the grid is several generations deep (B = 64 at C2's shape: 152 -> 121 us; B = 8: 26.4 -> 28.2, so not there)
 // rrl_launch_cull_scan (rrl_cull.hip) picks the variant per call from the grid size.  Same arithmetic, same labels.
 // Experiment builds override the knobs with -D; every override is read HERE and nowhere else: SPW, WCCAP, QA_CAP, QC_CAP
-// (the lean variant), SCAN16_QA_CAP, SCAN16_QC_CAP, SCAN16_WCCAP (the fat one), WPB, ROWS (both).
+// (the lean variant), SCAN16_QA_CAP, SCAN16_QC_CAP, SCAN16_WCCAP (the fat one), WPB, ROWS, SPLIT_TAIL, SCAN_PARK (both: = 0 gives
+// the former per-pass form of levels B / D back, profiles/scan_issue_budget.md).
 #pragma once
 #ifndef SPW
 #define SPW 8      // supergroups per slice (<= 16: SG_BITS); staged once per workgroup
@@ -33,9 +34,16 @@
 #ifndef SCAN16_WCCAP
 #define SCAN16_WCCAP 128
 #endif
+#ifndef SPLIT_TAIL
+#define SPLIT_TAIL 1  // a partial pass of level B / D spreads its entries over 2, 4 or 8 lanes each (tail_split below)
+#endif
+#ifndef SCAN_PARK
+#define SCAN_PARK 1   // level D parks a pass's candidates behind one prefix scan of the lanes' counts (proc_c)
+#endif
 struct Scan8 {
     static constexpr int kSPW = SPW, kQaCap = QA_CAP, kQcCap = QC_CAP, kWcCap = WCCAP;
     static constexpr bool kRegLines = false;
+    static constexpr bool kSplitTail = SPLIT_TAIL != 0, kScanPark = SCAN_PARK != 0;
 };
 // kRegLines: the wavefront's 128 lines stay in REGISTERS (two per lane) and travel between lanes by ds_bpermute instead of
 // 24 KB of LDS per workgroup -> 62 VGPRs, 4 workgroups = 32 wavefronts per compute unit instead of 3 / 24.  With 8
@@ -44,6 +52,7 @@ struct Scan8 {
 struct Scan16 {
     static constexpr int kSPW = 16, kQaCap = SCAN16_QA_CAP, kQcCap = SCAN16_QC_CAP, kWcCap = SCAN16_WCCAP;
     static constexpr bool kRegLines = true;
+    static constexpr bool kSplitTail = SPLIT_TAIL != 0, kScanPark = SCAN_PARK != 0;
 };
 // common to both variants (a -DWPB=n / -DROWS=n of an experiment build stands in for the constant itself)
 #ifndef WPB
@@ -171,7 +180,9 @@ struct CloudSlack {
 // the four row results meet in scalar registers.  Every lane receives the result.
 __device__ __forceinline__ float wave_max_nonneg(float v) {
     unsigned u = __float_as_uint(v);
-#define RRL_DPP_U(x, ctrl) (unsigned)__builtin_amdgcn_update_dpp((int)(x), (int)(x), ctrl, 0xf, 0xf, false)
+    // (old = 0, the identity of max on unsigned: only then does the compiler fold the lane move into v_max_u32's DPP operand --
+    //  with old = x it issued a copy, the DPP move and the max, three instructions a step; every lane has a source lane here)
+#define RRL_DPP_U(x, ctrl) (unsigned)__builtin_amdgcn_update_dpp(0, (int)(x), ctrl, 0xf, 0xf, false)
     u = max(u, RRL_DPP_U(u, 0xB1)); u = max(u, RRL_DPP_U(u, 0x4E));
     u = max(u, RRL_DPP_U(u, 0x141)); u = max(u, RRL_DPP_U(u, 0x140));
 #undef RRL_DPP_U
@@ -238,6 +249,17 @@ __device__ __forceinline__ void flush_cands(WaveCtx<V> &c) {
 
 // all = false: only while at least 64 entries wait (full lanes); all = true: drain.
 
+// A drain's LAST pass of level B or D holds `take` < 64 entries (one per wavefront and level at C2: 81 pairs and 96 halves
+// wait on average, so the second pass runs 17 and 32 of 64 lanes) and used to issue all 8 tests of an entry for them.
+// kSplitTail: 2^k lanes share an entry (k = 1, 2, 3 while take <= 32, 16, 8), each running 8 >> k of its tests -- the same
+// test on the same operands, only in another lane; the lanes keep their own bits and push them themselves.
+template <int N> struct TailPer { static constexpr int v = N; };  // tests per lane of a pass: 8 (k = 0), 4, 2, 1
+template <class V>
+__device__ __forceinline__ int tail_split(int take) {
+    if constexpr (!V::kSplitTail) return 0;
+    return take <= 8 ? 3 : (take <= 16 ? 2 : (take <= 32 ? 1 : 0));  // uniform
+}
+
 // level D: pops (line, half) pairs, ONE per lane (8 records = 32 registers in flight), and runs the point-0
 // PREFILTER on the half's 8 records: e = fl(Q(P0)) + c by FMAs, with the staged c = -(thr2 - 2e-4 + slack)
 // (see "Point-0 prefilter" above): 10 operations and one v_alignbit per record instead of the 16 + 3 of
@@ -256,34 +278,60 @@ __device__ __forceinline__ void proc_c(WaveCtx<V> &c, bool all) {
         wave_lds_fence();
         uint32_t passbits = 0;
         unsigned lh = 0;  // line << CAND_POS_BITS | first sorted position of the half
+        const int k = tail_split<V>(take), slot = c.lane >> k;  // (k uniform) the lane's entry of this pass
         // (registers: every lane takes part in line_get, so entry and line are fetched in front of the branch; LDS: behind it)
         unsigned e = 0u;
         LineRow lrw;
         if constexpr (V::kRegLines) {
-            e = c.lane < take ? c.qc[base + c.lane] : 0u;
+            e = slot < take ? c.qc[base + slot] : 0u;
             lrw = line_get(c.ln, (int)(e >> HF_BITS));
         }
-        if (c.lane < take) {
+        if (slot < take) {
             if constexpr (!V::kRegLines) {
-                e = c.qc[base + c.lane];
+                e = c.qc[base + slot];
                 lrw = line_row(c.ln.lr, (int)(e >> HF_BITS));
             }
             const int ll = e >> HF_BITS, h = e & ((1 << HF_BITS) - 1);
             const float4 la = lrw.la;
             const float2 lb = lrw.lb;
             const float4 *row = c.recs + (h >> 1) * ROWS + (h & 1) * 8;
-#pragma unroll
-            for (int t = 7; t >= 0; --t) {  // record t ends up in bit t
-                const float4 rec = row[t];
+            auto test = [&](const float4 rec) {  // passbits << 1 | sign(ev)
                 const float ax = rec.x - la.w, ay = rec.y - lb.x, az = rec.z - lb.y;
                 const float dot = fmaf(az, la.z, fmaf(ay, la.y, ax * la.x));
                 const float q = fmaf(az, az, fmaf(ay, ay, fmaf(ax, ax, rec.w)));
                 const float ev = fmaf(-dot, dot, q);
-                passbits = __builtin_amdgcn_alignbit(passbits, __float_as_uint(ev), 31);  // passbits << 1 | sign(ev)
-            }
+                passbits = __builtin_amdgcn_alignbit(passbits, __float_as_uint(ev), 31);
+            };
+            auto part = [&](auto per_) {  // this lane's records t0 .. t0 + per - 1; record t ends up in bit t
+                constexpr int per = decltype(per_)::v;
+                const int t0 = (c.lane & (8 / per - 1)) * per;
+#pragma unroll
+                for (int t = per - 1; t >= 0; --t) test(row[t0 + t]);
+                passbits <<= t0;
+            };
+            if (k == 0) part(TailPer<8>());  // (uniform)
+            else if (k == 1) part(TailPer<4>());
+            else if (k == 2) part(TailPer<2>());
+            else part(TailPer<1>());
             lh = ((unsigned)ll << CAND_POS_BITS) | (unsigned)(c.pos0 + h * 8);
         }
-        while (__any(passbits != 0)) {
+        if constexpr (V::kScanPark) {
+            // usual case: the pass's candidates fit the buffer -- every lane parks its own run behind an exclusive prefix of the
+            // counts (one DPP scan, as push_halves does, instead of a ballot / rank round per candidate of the fullest lane)
+            const int cnt = __popc(passbits);
+            const int incl = wave_incl_scan(cnt);
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            if (c.ncand + total <= V::kWcCap) {  // uniform
+                int at = c.ncand + incl - cnt;
+                while (passbits) {
+                    const int t = __ffs(passbits) - 1;
+                    passbits &= passbits - 1;
+                    c.cands[at++] = lh + (unsigned)t;
+                }
+                c.ncand += total;
+            }
+        }
+        while (__any(passbits != 0)) {  // (kScanPark: only a pass whose candidates do not fit)
             if constexpr (V::kRegLines)  // uniform: room for this round's <= 64 candidates (no inline resolve)
                 if (c.ncand > V::kWcCap - 64) flush_cands<V, COUNT, SC1>(c);
             const bool has = passbits != 0;
@@ -349,30 +397,40 @@ __device__ __forceinline__ void proc_a(WaveCtx<V> &c, bool all) {
         c.na = base;
         if constexpr (COUNT) c.tb += 8u * (unsigned)take;
         wave_lds_fence();
-        unsigned fail = 0xffu;  // bit k: half k cannot be reached (idle lanes: none can)
+        unsigned pass = 0u;  // bit j: half j may be reached (idle lanes: none)
         unsigned e2 = 0;
+        const int k = tail_split<V>(take), slot = c.lane >> k;  // (as in proc_c)
         unsigned e = 0u;  // (fetched as in proc_c)
         LineRow lrw;
         if constexpr (V::kRegLines) {
-            e = c.lane < take ? c.qa[base + c.lane] : 0u;
+            e = slot < take ? c.qa[base + slot] : 0u;
             lrw = line_get(c.ln, (int)(e >> SG_BITS));
         }
-        if (c.lane < take) {
+        if (slot < take) {
             if constexpr (!V::kRegLines) {
-                e = c.qa[base + c.lane];
+                e = c.qa[base + slot];
                 lrw = line_row(c.ln.lr, (int)(e >> SG_BITS));
             }
             const int ll = e >> SG_BITS, sg = e & ((1 << SG_BITS) - 1);
             const float4 la = lrw.la;
             const float2 lb = lrw.lb;
             const float4 *nd = c.nodes + sg * NODE + 5;
-            fail = 0u;
+            auto part = [&](auto per_) {  // this lane's halves j0 .. j0 + per - 1; half j ends up in bit j
+                constexpr int per = decltype(per_)::v;
+                const int j0 = (c.lane & (8 / per - 1)) * per;
+                unsigned fail = 0u;  // bit j - j0: half j cannot be reached
 #pragma unroll
-            for (int k = 7; k >= 0; --k)  // half k ends up in bit k
-                fail = __builtin_amdgcn_alignbit(fail, __float_as_uint(sphere_margin(nd[k], la, lb)), 31);
+                for (int j = per - 1; j >= 0; --j)
+                    fail = __builtin_amdgcn_alignbit(fail, __float_as_uint(sphere_margin(nd[j0 + j], la, lb)), 31);
+                pass = (~fail & ((1u << per) - 1u)) << j0;
+            };
+            if (k == 0) part(TailPer<8>());  // (uniform)
+            else if (k == 1) part(TailPer<4>());
+            else if (k == 2) part(TailPer<2>());
+            else part(TailPer<1>());
             e2 = ((unsigned)ll << HF_BITS) | (unsigned)(8 * sg);
         }
-        push_halves<V, COUNT, SC1>(c, ~fail & 0xffu, e2);
+        push_halves<V, COUNT, SC1>(c, pass, e2);
     }
 }
 
