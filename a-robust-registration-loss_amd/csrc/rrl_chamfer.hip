@@ -43,8 +43,6 @@
 #include "rrl_tree.h"
 #include "rrl_chamfer_walk.h"
 
-typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load
-
 extern "C" size_t rrl_chamfer_workspace_bytes(int B, int N, int M) {
     if (B < 0 || N < 0 || M < 0) return 0;
     return ChamLayout(B, N, M).total;
@@ -193,28 +191,25 @@ static int chamfer_tree_launches(const float *x, const float *y, const int32_t *
     if (order_x && order_y) {  // prepared clouds: records at their sorted positions + tree refit, no sort
         const int npadmax = (nmax + SGT - 1) / SGT * SGT;
         hipLaunchKernelGGL(pts_records_sorted_kernel, dim3((unsigned)((npadmax + 255) / 256), (unsigned)B, 2u), dim3(256), 0, s, x, y,
-                           order_x, order_y, (float4 *)(w + L.p0s1), (float4 *)(w + L.p0s2), (int32_t *)(w + L.idx1),
-                           (int32_t *)(w + L.idx2), (float4 *)(w + L.grp1), (float4 *)(w + L.grp2), (float *)(w + L.apart),
+                           order_x, order_y, (float4 *)(w + L.p0s[0]), (float4 *)(w + L.p0s[1]), (int32_t *)(w + L.idx[0]),
+                           (int32_t *)(w + L.idx[1]), (float4 *)(w + L.grp[0]), (float4 *)(w + L.grp[1]), (float *)(w + L.apart),
                            (uint32_t *)(w + L.ctrl), (int)(L.ctrl_bytes / 4), B, N, M, L.nblk, count_x, count_y);
     } else {
-    if (!small)
+    if (!small)  // (clears HISTG and the counters behind it)
         hipLaunchKernelGGL(pts_records_kernel, dim3((unsigned)((nmax + 255) / 256), (unsigned)B, 2u), dim3(256), 0, s, x,
-                           y, (float4 *)(w + L.crec1), (float4 *)(w + L.crec2), (float *)(w + L.apart),
-                           (uint4 *)(w + L.histg), (L.total - L.histg) / 16, B, N, M, L.nblk, count_x, count_y);
-    rc = rrl_launch_cloud_sort(small ? x : nullptr, small ? y : nullptr, (float4 *)(w + L.crec1), (float4 *)(w + L.crec2), (float *)(w + L.apart), L.nblk,
-                                   (float4 *)(w + L.p0s1), (float4 *)(w + L.p0s2), (int32_t *)(w + L.idx1),
-                                   (int32_t *)(w + L.idx2), (float4 *)(w + L.grp1), (float4 *)(w + L.grp2),
-                                   (uint32_t *)(w + L.pmax), (unsigned *)(w + L.histg),
-                                   small ? (uint32_t *)(w + L.ctrl) : nullptr, (int)(L.ctrl_bytes / 4),  // (large clouds: cleared by pts_records_kernel)
-                                   B, N, M, count_x, count_y, s);
+                           y, (float4 *)(w + L.crec[0]), (float4 *)(w + L.crec[1]), (float *)(w + L.apart),
+                           (uint4 *)(w + L.histg), (L.partial - L.histg) / 16, B, N, M, L.nblk, count_x, count_y);
+    rc = rrl_launch_cloud_sort(L, ws, small ? x : nullptr, small ? y : nullptr,
+                               small ? (uint32_t *)(w + L.ctrl) : nullptr, (int)(L.ctrl_bytes / 4),  // (large clouds: cleared by pts_records_kernel)
+                               count_x, count_y, s);
     }
     if (rc) return rc;
     const int nsgmax = (nmax + SGT - 1) / SGT;
     const ChamTick tick = {(uint32_t *)(w + L.ctrl), (uint32_t *)(w + L.ctrl) + 32, 64, 32};
     if (values) {  // a ragged batch: the grid stays that of the capacities, patches beyond a sample leave through the tickets
         hipLaunchKernelGGL(chamfer_tree_counted_kernel, dim3((unsigned)(2 * B), (unsigned)nsgmax), dim3(64 * NWV), 0, s,
-                           (const float4 *)(w + L.p0s1), (const float4 *)(w + L.p0s2), (const float4 *)(w + L.grp1),
-                           (const float4 *)(w + L.grp2), (const float *)(w + L.apart), L.nblk, (unsigned long long *)best_x,
+                           (const float4 *)(w + L.p0s[0]), (const float4 *)(w + L.p0s[1]), (const float4 *)(w + L.grp[0]),
+                           (const float4 *)(w + L.grp[1]), (const float *)(w + L.apart), L.nblk, (unsigned long long *)best_x,
                            (unsigned long long *)best_y, (double *)(w + L.partial), B, N, M, tick, (double *)(w + L.gpart),
                            values, value, count_x, count_y);
         RRL_LAUNCH_CHECK();
@@ -222,8 +217,8 @@ static int chamfer_tree_launches(const float *x, const float *y, const int32_t *
     }
 #define RRL_NN_LAUNCH(COUNT)                                                                                     \
     hipLaunchKernelGGL((chamfer_tree_kernel<COUNT, false>), dim3((unsigned)(2 * B), (unsigned)nsgmax), dim3(64 * NWV), 0, \
-                       s, (const float4 *)(w + L.p0s1), (const float4 *)(w + L.p0s2),                            \
-                       (const float4 *)(w + L.grp1), (const float4 *)(w + L.grp2), (const float *)(w + L.apart),  \
+                       s, (const float4 *)(w + L.p0s[0]), (const float4 *)(w + L.p0s[1]),                        \
+                       (const float4 *)(w + L.grp[0]), (const float4 *)(w + L.grp[1]), (const float *)(w + L.apart), \
                        L.nblk, (unsigned long long *)best_x, (unsigned long long *)best_y,                       \
                        (double *)(w + L.partial), B, N, M, cnt_buf, cnt_rows, (const int32_t *)nullptr, \
                        (const int32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, tick,      \

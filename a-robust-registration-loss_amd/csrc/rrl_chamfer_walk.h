@@ -5,34 +5,16 @@
 #pragma once
 #include "rrl_tree.h"
 
-typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load
-
-// the Chamfer workspace (include/rrl.h rrl_chamfer_workspace_bytes)
-struct ChamLayout {
-    size_t crec1, crec2, p0s1, p0s2, idx1, idx2, grp1, grp2, apart, pmax, histg, partial, gpart, ctrl, ctrl_bytes, total;
-    int nblk;
-    __host__ ChamLayout(int B, int N, int M) {
-        const size_t b = (size_t)B, n = (size_t)N, m = (size_t)M;
-        const size_t nmax = n > m ? n : m;
-        nblk = (int)((nmax + 255) / 256);
-        size_t o = 0;
-        auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-        crec1 = take(16 * b * ((n + 15) / 16) * 16);
-        crec2 = take(16 * b * ((m + 15) / 16) * 16);
-        p0s1 = take(16 * b * ((n + 63) / 64) * 64);
-        p0s2 = take(16 * b * ((m + 63) / 64) * 64);
-        idx1 = take(4 * b * ((n + 63) / 64) * 64);
-        idx2 = take(4 * b * ((m + 63) / 64) * 64);
-        grp1 = take(16 * b * ((n + 63) / 64) * NODE);
-        grp2 = take(16 * b * ((m + 63) / 64) * NODE);
-        apart = take(4 * 2 * b * 8 * (size_t)nblk);
-        pmax = take(4 * 2 * b);
+// the Chamfer workspace (include/rrl.h rrl_chamfer_workspace_bytes): the pair build's scratch (rrl_tree.h) and the walk's own
+struct ChamLayout : PairLayout {
+    size_t ctrl, ctrl_bytes, partial, gpart, total;
+    __host__ ChamLayout(int B_, int N_, int M_) : PairLayout(B_, N_, M_) {
+        const size_t b = (size_t)B, nmax = (size_t)(N > M ? N : M);
+        ctrl_bytes = 4 * (32 + 64 * b);  // arrival counters of the mean (ChamTick): zero before the walk -- behind HISTG, in the
+        ctrl = take(ctrl_bytes);         //   range pts_records_kernel clears; the small-cloud sort kernel clears them itself
         partial = take(8 * (2 * b * ((nmax + 63) / 64) + 1));  // one per workgroup of the NN launch
         gpart = take(8 * 2 * b);  // per (sample, direction) sum of its patches' partials
-        histg = take(nmax > 4096 ? 4 * 2 * b * 2 * SORT_CELLS : 16);  // cleared by pts_records_kernel
-        ctrl_bytes = 4 * (32 + 64 * b);  // arrival counters of the mean (ChamTick): zero before the walk -- inside the
-        ctrl = take(ctrl_bytes);         //   range pts_records_kernel clears; the small-cloud sort kernel clears them itself
-        total = o;
+        total = end;
     }
 };
 

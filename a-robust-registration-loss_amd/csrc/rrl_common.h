@@ -14,6 +14,7 @@
 #define PTRI_STRIDE 12   // floats per prepared triangle
 
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load (a wave-uniform address)
 
 #define RRL_LAUNCH_CHECK()                         \
     do {                                           \

@@ -910,7 +910,6 @@ __global__ __launch_bounds__(256) void big_sphere_kernel(const BuildArgs a) {
     half_tree([&](int s_) { return r[s_]; }, hh, n, (cloud ? a.grp2 : a.grp1) + (size_t)b * nsgf * NODE);
 }
 
-typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load
 typedef const int __attribute__((address_space(4))) * kiptr;
 
 static BuildArgs make_build_args(const RrlCall &o, const float *tri1, const float *tri2, int clouds, const float *line, bool chunked);
@@ -1166,27 +1165,31 @@ int rrl_launch_pmax_from_partials(const RrlCall &o, int clouds) {
     return 0;
 }
 
-// Sort + sphere tree for callers outside the loss workspace (the Chamfer path, rrl_chamfer.hip): the same
-// kernels as above.  Clouds of <= 4096 points given as raw1 / raw2 ([B][n][3]) are sorted straight from
-// the points (tri_sort_kernel<4, true>: records, AABB and NaN flag built in the kernel); otherwise the
-// (x, y, z, w) records (CREC layout) and per-256-record AABB partials (APART layout, nblk rows per cloud
-// and sample) must already exist and histg (cleared by the caller) is used beyond 4096 records.  cnt1 / cnt2: NULL, or the
-// points sample b really has (N, M stay the strides; pads sort last, nodes only for a sample's own supergroups).
-int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, float4 *crec2, float *apart, int nblk,
-                          float4 *p0s1, float4 *p0s2, int32_t *idx1, int32_t *idx2, float4 *grp1, float4 *grp2,
-                          uint32_t *pmax, unsigned *histg, uint32_t *zwords, int nzwords, int B, int N, int M,
+// Sort + sphere tree for callers outside the loss workspace (the Chamfer path, rrl_chamfer.hip; the k-NN entries,
+// rrl_knn_tree.hip and rrl_knn.hip), in a scratch laid out by PairLayout (rrl_tree.h): the same kernels as above.  Clouds
+// of <= 4096 points given as raw1 / raw2 ([B][n][3]) are sorted straight from the points (tri_sort_kernel<4, true>:
+// records, AABB and NaN flag built in the kernel); otherwise the (x, y, z, w) records (CREC) and per-256-record AABB
+// partials (APART, nblk rows per cloud and sample) must already exist and HISTG (cleared by the caller) is used beyond
+// 4096 records.  cnt1 / cnt2: NULL, or the points sample b really has (N, M stay the strides; pads sort last, nodes only for
+// a sample's own supergroups).  zwords / nzwords: words the sort of <= 4096 points clears besides (or NULL).  An absent
+// second cloud (L.second false) needs cnt2 [B] of zeros on the device: without counts its workgroups would follow the first
+// cloud's arrays, so NULL is refused (RRL_E_ARG).
+int rrl_launch_cloud_sort(const PairLayout &L, void *ws, const float *raw1, const float *raw2, uint32_t *zwords, int nzwords,
                           const int32_t *cnt1, const int32_t *cnt2, hipStream_t s) {
+    const int B = L.B, N = L.N, M = L.M;
     const int nmax = M > N ? M : N;
-    if (nmax > SORT_CAP || B <= 0 || nmax <= 0) return RRL_E_ARG;
+    if (nmax > SORT_CAP || B <= 0 || nmax <= 0 || (!L.second && !cnt2)) return RRL_E_ARG;
     const size_t ngpmax = (size_t)(nmax + SGT - 1) / SGT * SGG;
+    char *w = (char *)ws;
+    unsigned *histg = (unsigned *)(w + L.histg);
     BuildArgs a = {};
-    a.tri1 = raw1; a.tri2 = raw2;  // point clouds [B][n][3]: only read by the RAW sort (nmax <= 4096)
-    a.crec1 = crec1; a.crec2 = crec2;
-    a.apart = apart; a.nblk = nblk;
-    a.p0s1 = p0s1; a.p0s2 = p0s2;
-    a.idx1 = idx1; a.idx2 = idx2;
-    a.grp1 = grp1; a.grp2 = grp2;
-    a.pmax = pmax;
+    a.tri1 = raw1; a.tri2 = L.second ? raw2 : raw1;  // point clouds [B][n][3]: only read by the RAW sort (nmax <= 4096)
+    a.crec1 = (float4 *)(w + L.crec[0]); a.crec2 = (float4 *)(w + L.crec[1]);
+    a.apart = (float *)(w + L.apart); a.nblk = L.nblk;
+    a.p0s1 = (float4 *)(w + L.p0s[0]); a.p0s2 = (float4 *)(w + L.p0s[1]);
+    a.idx1 = (int32_t *)(w + L.idx[0]); a.idx2 = (int32_t *)(w + L.idx[1]);
+    a.grp1 = (float4 *)(w + L.grp[0]); a.grp2 = (float4 *)(w + L.grp[1]);
+    a.pmax = (uint32_t *)(w + L.pmax);
     a.zwords = zwords; a.nzwords = nzwords;
     a.B = B; a.N = N; a.M = M; a.Bt = 0;
     a.cnt1 = cnt1; a.cnt2 = cnt2;  // a ragged batch (rrl_chamfer_tree_fwd_counted): the points each sample has, or NULL
@@ -1194,7 +1197,7 @@ int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, f
     //  pairs on chunked clouds -- 63.0 -> 64.4 us at N = M = 16384, 188 -> 380 at 65536: whole-cloud order stays)
     if (nmax <= 4096) {
         const int parts = sort_parts((int)(ngpmax / SGG), rrl_default_sort_parts());
-        if (raw1 && raw2) hipLaunchKernelGGL((tri_sort_kernel<4, true>), dim3((unsigned)(2 * B), (unsigned)parts), dim3(1024),
+        if (a.tri1 && a.tri2) hipLaunchKernelGGL((tri_sort_kernel<4, true>), dim3((unsigned)(2 * B), (unsigned)parts), dim3(1024),
                                              sort_lds_bytes((int)(ngpmax / SGG), parts, nmax), s, a);
         else hipLaunchKernelGGL((tri_sort_kernel<4, false>), dim3((unsigned)(2 * B), (unsigned)parts), dim3(1024),
                                 sort_lds_bytes((int)(ngpmax / SGG), parts, 0), s, a);

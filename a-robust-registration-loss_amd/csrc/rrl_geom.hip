@@ -7,8 +7,6 @@
 #include "rrl_ws.h"
 #include "rrl_pose_tail.h"
 
-typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load
-
 // ---------------------------------------------------------------------------------------
 // K6 rigid apply
 // ---------------------------------------------------------------------------------------

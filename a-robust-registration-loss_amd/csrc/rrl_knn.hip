@@ -25,65 +25,26 @@
 //          its second cloud is the query cloud, absent -- counts of 0 -- in the self form).  One wavefront owns the 64
 //          consecutive SORTED queries of query supergroup sg.  It first evaluates a SEED supergroup of the reference for all
 //          lanes -- its own in the self form; in the cross form the one whose centre is nearest the query patch's centre (the
-//          Chamfer walk's seed) -- then the others outward along the curve, seed + 1, seed - 1, seed + 2, ...: 64 per round,
-//          one per lane, tested lane-parallel against the QUERY supergroup's sphere with the wavefront's largest bound; per
-//          surviving supergroup every lane tests its own query against the supergroup sphere and the four group spheres, and
-//          a group of 16 records is evaluated for the whole wavefront (scalar loads) when ANY lane needs it.
-//
-// Bound, for k keys (the inequalities of rrl_knn_tree.hip, restated).  Let dk be the d of the lane's k-th key, 1e300 while
-// fewer than k keys are held.  A node is (c, R) with R >= max |p - c| over its records (finish_sphere: conservative by 5e-5
-// relative).  Every record p of the node has |q - p| >= |q - c| - R, so when |q - c| > sqrt(dk) + R every record is STRICTLY
-// farther than the k-th key, cannot be lexicographically below it, and cannot enter the list -- now or later, because dk
-// only decreases.  In float32, arranged so that rounding can only keep a node:
-//   left   D = |q - c|^2 from the float32 coordinates (relative error < 4e-7), shrunk by LB_SCALE = 0.9999;
-//   right  sb = sqrtf(max((float)dk, 1e-30f)) * 1.00001f >= sqrt(dk) (knn_bound; 1e300 becomes +inf: a list that is not full
-//          prunes nothing), t = sb + R;
-//   skip   iff D * LB_SCALE > t * t: STRICT, 1e-4 of relative slack in the squares against 1e-6 of error.  Equality never
-//          prunes, a NaN anywhere keeps the node.
-//   The wavefront-level test is the same inequality between two spheres: |cq - cj| > sbmax + Rq + Rj, with (cq, Rq) the query
-//   supergroup's sphere and sbmax the largest sb of the wavefront's real queries, implies the lane test for every lane.
+//          Chamfer walk's seed) -- then the others by the walk that rrl_knn_walk.h describes, with that header's bound on
+//          the k-th key (knn_bound, knn_reach) and its proof that rounding can only keep a node.
 // A sample whose PMAX word (either cloud's) is not <= 1e30 -- a NaN, an infinity, |P| > 1e15 -- takes the brute loop inside the
 // same launch: a workgroup-uniform branch on a word the build left on the device.
 //
 // Launch behaviour: no atomics, nothing read back, one plain chain on the caller's stream (3 launches up to 4096 points, 5
 // beyond -- 6 in the cross form --, 1 for brute force); two calls give the same bits.
-#include "rrl_tree.h"
-#include "rrl_chamfer_walk.h"  // LB_SCALE, kptr
+#include "rrl_knn_walk.h"
 
 #define KNN_NONE 0x7fffffff  // the index of an open slot (its d is 1e300)
 
-// the scratch of rrl_knn (include/rrl.h rrl_knn_workspace_bytes): the pair build of (reference, queries)
-struct KnnPairLayout {
-    size_t crec1, crec2, p0s1, p0s2, idx1, idx2, grp1, grp2, apart, zero, pmax, histg, zcnt, total;
-    int nblk;
+// the scratch of rrl_knn (include/rrl.h rrl_knn_workspace_bytes): the pair build of (reference, queries) and the counts of the
+// self form's absent second cloud; the launch in front of the sort clears it from PMAX to the end
+struct KnnPairLayout : PairLayout {
+    size_t zcnt, total;
     bool sorted;  // within the sort capacity: else brute force only, and no scratch to speak of
-    __host__ KnnPairLayout(int B, int n_, int S_) {
-        const size_t b = (size_t)B, n = (size_t)n_, m = (size_t)S_;
-        const size_t nmax = n > m ? n : m;
-        sorted = nmax <= (size_t)rrl_sort_capacity();
-        nblk = (int)((nmax + 255) / 256);
-        size_t o = 0;
-        auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-        if (!sorted) {
-            crec1 = crec2 = p0s1 = p0s2 = idx1 = idx2 = grp1 = grp2 = apart = zero = pmax = histg = zcnt = 0;
-            total = 256;
-            return;
-        }
-        const bool big = nmax > 4096;
-        crec1 = take(big ? 16 * b * ((n + 15) / 16) * 16 : 16);
-        crec2 = take(big ? 16 * b * ((m + 15) / 16) * 16 : 16);
-        p0s1 = take(16 * b * ((n + 63) / 64) * 64);
-        p0s2 = take(16 * b * ((m + 63) / 64) * 64);
-        idx1 = take(4 * b * ((n + 63) / 64) * 64);
-        idx2 = take(4 * b * ((m + 63) / 64) * 64);
-        grp1 = take(16 * b * ((n + 63) / 64) * NODE);
-        grp2 = take(16 * b * ((m + 63) / 64) * NODE);
-        apart = take(4 * 2 * b * 8 * (size_t)nblk);
-        zero = o;  // cleared by the launch in front of the sort, up to the end:
-        pmax = take(4 * 2 * b);
-        histg = take(big ? 4 * 2 * b * 2 * SORT_CELLS : 16);
-        zcnt = take(4 * b);  // the counts of the self form's absent second cloud
-        total = o;
+    __host__ KnnPairLayout(int B_, int n, int S) : PairLayout(B_, n, S) {
+        sorted = (n > S ? n : S) <= rrl_sort_capacity();
+        zcnt = take(4 * (size_t)B);
+        total = sorted ? end : 256;
     }
 };
 
@@ -136,16 +97,6 @@ __device__ __forceinline__ void knn_offer(KnnList &L, double d, int j) {
             if (pd[s] > md || (pd[s] == md && pi[s] > mi)) { md = pd[s]; mi = pi[s]; ms = min(s, L.k - 1); }
         L.dk = md; L.ik = mi; L.ms = ms;
     }
-}
-// sb of the header: an upper bound of sqrt(dk) in float32
-static __device__ __forceinline__ float knn_bound(double dk) {
-    return __builtin_amdgcn_sqrtf(fmaxf((float)dk, 1e-30f)) * 1.00001f;
-}
-// may the sphere (cx, cy, cz, R) hold a key not above the bound sb of query (qx, qy, qz)?  (NaN anywhere: yes)
-static __device__ __forceinline__ bool knn_reach(float qx, float qy, float qz, float cx, float cy, float cz, float R, float sb) {
-    const float dx = qx - cx, dy = qy - cy, dz = qz - cz;
-    const float D = dx * dx + dy * dy + dz * dz, t = sb + R;
-    return !(D * LB_SCALE > t * t);
 }
 
 // brute force: the nr points p [nr][3] (wave-uniform: scalar loads) in ascending index, `skip` left out (-1: none)
@@ -294,6 +245,12 @@ __global__ __launch_bounds__(64) void knn_kernel(const KnnArgs a) {
         }
         seed = min(seed, nsg - 1);  // (the self form: nq == nr, so sg < nsg already)
         eval(seed * SGT, min(SGT, nr - seed * SGT));
+        // knn_walk_others (rrl_knn_walk.h) in this kernel's own text: called from here the walk is the same instructions with the
+        // scalar address arithmetic in another order and 8 more bytes, and every k >= 8 shape measured 0.2 .. 0.8 % slower than this
+        // text, outside the spread of two loads of one library (profiles/nn_walk_timing.json: superseded_rows).  Another place
+        // for the query node's load was not measured: the cross form's seed search above needs the centre before the seed is
+        // evaluated, so the load cannot follow the seed as it does in knn3_tree_kernel.  A change to the walk or to the visiting
+        // order is made in both places; the bound and its tests are shared.
         const int kmax = 2 * max(seed, nsg - 1 - seed);  // offsets 1 .. kmax reach every other supergroup
         for (int k0 = 1; k0 <= kmax; k0 += 64) {
             const int kk = k0 + lane;
@@ -333,7 +290,7 @@ extern "C" int rrl_knn(const float *ref, const int32_t *count_ref, const float *
     if (!ref || !idx || !ws || B < 0 || B > 32767 || n < 1 || S < 0 || k < 1 || k > RRL_KNN_MAX_K) return RRL_E_ARG;
     if (!qry && S != n) return RRL_E_ARG;
     if ((flags & ~all_flags) || (channels & ~all_channels) || (channels != 0) != (feat != nullptr)) return RRL_E_ARG;
-    const KnnPairLayout L(B, n, S);
+    KnnPairLayout L(B, n, S);
     if (ws_bytes < L.total) return RRL_E_WS;
     if (B == 0 || S == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -361,28 +318,21 @@ extern "C" int rrl_knn(const float *ref, const int32_t *count_ref, const float *
         RRL_LAUNCH_CHECK();
         return 0;
     }
-    const bool small = (n > S ? n : S) <= 4096;  // the sort kernel reads the points itself: no records launch
-    int rc;
-    if (small) rc = rrl_fill(w + L.zero, 0u, L.total - L.zero, s);
-    else rc = rrl_launch_pts_records(ref, (float4 *)(w + L.crec1), (float *)(w + L.apart), w + L.zero, (L.total - L.zero) / 16, B, n,
+    if (self) L.drop_second();  // the self form's second cloud is absent: counts of 0 (ZCNT, cleared below)
+    int rc;  // up to 4096 points the sort kernel reads the points itself: no records launch
+    if (!L.big) rc = rrl_fill(w + L.pmax, 0u, L.total - L.pmax, s);
+    else rc = rrl_launch_pts_records(ref, (float4 *)(w + L.crec[0]), (float *)(w + L.apart), w + L.pmax, (L.total - L.pmax) / 16, B, n,
                                      L.nblk, count_ref, s);
     if (rc) return rc;
-    if (!small && !self)  // the query cloud's records and its rows of the partial boxes (cloud 1's: behind cloud 0's B nblk rows)
-        rc = rrl_launch_pts_records(qry, (float4 *)(w + L.crec2), (float *)(w + L.apart) + (size_t)B * L.nblk * 8, w + L.zero, 0, B, S,
+    if (L.big && !self)  // the query cloud's records and its rows of the partial boxes (cloud 1's: behind cloud 0's B nblk rows)
+        rc = rrl_launch_pts_records(qry, (float4 *)(w + L.crec[1]), (float *)(w + L.apart) + (size_t)B * L.nblk * 8, w + L.pmax, 0, B, S,
                                     L.nblk, count_qry, s);
     if (rc) return rc;
-    // the pair build; the self form's second cloud is absent (counts of 0: its pointers are never followed)
-    const float *raw2 = self ? ref : qry;
-    float4 *crec2 = (float4 *)(w + (self ? L.crec1 : L.crec2)), *p0s2 = (float4 *)(w + (self ? L.p0s1 : L.p0s2));
-    int32_t *idx2 = (int32_t *)(w + (self ? L.idx1 : L.idx2));
-    float4 *grp2 = (float4 *)(w + (self ? L.grp1 : L.grp2));
-    rc = rrl_launch_cloud_sort(small ? ref : nullptr, small ? raw2 : nullptr, (float4 *)(w + L.crec1), crec2, (float *)(w + L.apart),
-                               L.nblk, (float4 *)(w + L.p0s1), p0s2, (int32_t *)(w + L.idx1), idx2, (float4 *)(w + L.grp1), grp2,
-                               (uint32_t *)(w + L.pmax), (unsigned *)(w + L.histg), nullptr, 0, B, n, S, count_ref,
+    rc = rrl_launch_cloud_sort(L, ws, L.big ? nullptr : ref, L.big ? nullptr : qry, nullptr, 0, count_ref,
                                self ? (const int32_t *)(w + L.zcnt) : count_qry, s);
     if (rc) return rc;
-    a.p0r = (const float4 *)(w + L.p0s1); a.p0q = (const float4 *)p0s2;
-    a.grr = (const float4 *)(w + L.grp1); a.grq = (const float4 *)grp2;
+    a.p0r = (const float4 *)(w + L.p0s[0]); a.p0q = (const float4 *)(w + L.p0s[1]);
+    a.grr = (const float4 *)(w + L.grp[0]); a.grq = (const float4 *)(w + L.grp[1]);
     a.pmax = (const uint32_t *)(w + L.pmax);
     RRL_KNN_LAUNCH(true);
 #undef RRL_KNN_LAUNCH

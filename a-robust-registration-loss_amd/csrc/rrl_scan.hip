@@ -183,8 +183,6 @@ extern "C" int rrl_tri_prepare(const float *tri1, const float *tri2, void *ws, s
 // ---------------------------------------------------------------------------------------
 // K1 scan
 // ---------------------------------------------------------------------------------------
-typedef const float __attribute__((address_space(4))) * kptr;  // constant AS -> s_load
-
 __device__ __forceinline__ uint32_t umax3(uint32_t a, uint32_t b, uint32_t c) {
     return max(max(a, b), c);
 }

@@ -218,3 +218,39 @@ __device__ __forceinline__ void wave_tree(float px, float py, float pz, float th
 }
 
 #define SORT_CELLS 4096  // 16^3 grid cells in Hilbert-curve order
+
+// The scratch of the pair build (rrl_launch_cloud_sort) for callers outside the loss workspace: byte offsets from a
+// 256-byte-aligned base, per cloud c the records in original order CREC (read beyond 4096 points only: 16 bytes below), the
+// sorted records P0S, their original indices IDX and the tree GRP, then the AABB partial rows of both clouds, PMAX [2][B]
+// and the wide sort's histogram (beyond 4096 points; cleared by the caller's launch in front of the sort).  `end` is where a
+// caller's own fields begin (take): the Chamfer walk's counters and partial sums, the k-NN entries' zero counts.
+// The second cloud may be absent -- M < 0, or drop_second() for one call on a layout sized for two: its arrays are then the
+// first cloud's, the launcher passes the first cloud's points for it, and the caller hands the sort counts of 0 for it, so
+// that its workgroups leave at once and none of these pointers is followed.
+struct PairLayout {
+    size_t crec[2], p0s[2], idx[2], grp[2], apart, pmax, histg, end;
+    int B, N, M, nblk;
+    bool big, second;
+    __host__ PairLayout(int B_, int N_, int M_) : end(0), B(B_), N(N_), M(M_ < 0 ? N_ : M_), second(M_ >= 0) {
+        const size_t b = (size_t)B, cap[2] = {(size_t)N, second ? (size_t)M : 0};
+        const size_t nmax = cap[0] > cap[1] ? cap[0] : cap[1];
+        nblk = (int)((nmax + 255) / 256);
+        big = nmax > 4096;
+        for (int c = 0; c <= (int)second; ++c) {
+            const size_t full = 16 * b * ((cap[c] + 15) / 16) * 16;
+            crec[c] = take(big || full < 16 ? full : 16);  // (full < 16 is full == 0: an empty cloud or batch takes no bytes)
+        }
+        for (int c = 0; c <= (int)second; ++c) p0s[c] = take(16 * b * ((cap[c] + 63) / 64) * 64);
+        for (int c = 0; c <= (int)second; ++c) idx[c] = take(4 * b * ((cap[c] + 63) / 64) * 64);
+        for (int c = 0; c <= (int)second; ++c) grp[c] = take(16 * b * ((cap[c] + 63) / 64) * NODE);
+        apart = take(4 * 2 * b * 8 * (size_t)nblk);
+        pmax = take(4 * 2 * b);
+        histg = take(big ? 4 * 2 * b * 2 * SORT_CELLS : 16);
+        if (!second) drop_second();
+    }
+    __host__ size_t take(size_t bytes) { const size_t at = end; end += (bytes + 255) & ~(size_t)255; return at; }
+    __host__ void drop_second() { second = false; M = N; crec[1] = crec[0]; p0s[1] = p0s[0]; idx[1] = idx[0]; grp[1] = grp[0]; }
+};
+// sort + sphere tree of the pair in the scratch at `ws` (rrl_cull.hip, where its contract stands)
+int rrl_launch_cloud_sort(const PairLayout &L, void *ws, const float *raw1, const float *raw2, uint32_t *zwords, int nzwords,
+                          const int32_t *cnt1, const int32_t *cnt2, hipStream_t s);

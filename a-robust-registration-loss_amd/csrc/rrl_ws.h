@@ -218,10 +218,7 @@ int rrl_launch_tri_build(const RrlCall &o, const float *tri1, const float *tri2,
 int rrl_launch_cull_scan(const RrlCall &o, const float *line);
 int rrl_launch_pmax_from_partials(const RrlCall &o, int clouds);
 int rrl_cull_scan_can_fuse(const RrlCall &o);
-int rrl_launch_cloud_sort(const float *raw1, const float *raw2, float4 *crec1, float4 *crec2, float *apart, int nblk,
-                          float4 *p0s1, float4 *p0s2, int32_t *idx1, int32_t *idx2, float4 *grp1, float4 *grp2,
-                          uint32_t *pmax, unsigned *histg, uint32_t *zwords, int nzwords, int B, int N, int M,
-                          const int32_t *cnt1, const int32_t *cnt2, hipStream_t s);
+// (the pair build outside the loss workspace, rrl_launch_cloud_sort: rrl_tree.h, next to its scratch layout)
 // the Chamfer path's records launch for one cloud (rrl_chamfer.hip), for the 3-NN tree's build (rrl_knn_tree.hip)
 int rrl_launch_pts_records(const float *pts, float4 *crec, float *apart, void *zero, size_t zero_vec4, int B, int n, int nblk,
                            const int32_t *cnt, hipStream_t s);

@@ -133,6 +133,16 @@ def test_k3_is_knn3_self(mods):
         for method in METHODS:
             idx, found = nb.knn(tx, 3, method=method)
             assert torch.equal(idx, want) and (found == 3).all()
+    # n = 4225 = 66 supergroups + 1 record: the walk of rrl_knn_walk.h in both tree kernels, its flat loop in a second round,
+    # on the records launch and the wide sort -- against the twin as well as against each other
+    x = cloud("cube", 1, 4225, seed=6)
+    tx = cuda(x)
+    twin = KR.knn(x, 3)
+    for method in METHODS:
+        nn3 = nb.knn3_self(tx, method=method)
+        idx, found = nb.knn(tx, 3, method=method)
+        assert np.array_equal(nn3.cpu().numpy(), twin["idx"]), (method, "knn3_self against the twin")
+        assert torch.equal(idx, nn3) and (found == 3).all(), method
 
 
 def test_exclude_self_with_duplicates(mods):
@@ -148,9 +158,15 @@ def test_exclude_self_with_duplicates(mods):
     assert not twin["found"].any()
 
 
-@pytest.mark.parametrize("n", [130, 1025])
+@pytest.mark.parametrize("n", [130, 1025, 4225])
 def test_cross_form(mods, n):
     nb = mods[2]
+    if n == 4225:  # 66 full supergroups and one record: the walk's flat loop runs a second round; the queries shifted by +3 on
+        x = cloud("sphere", 2, n)  # every axis, so that the seed is not the query supergroup's own index
+        q = cloud("cube", 2, 130, seed=5) + np.float32(3.0)
+        for k in (1, 3, 20):
+            check(nb, x, k, query=q, what=("cross", n, 130, k, "shifted"))
+        return
     x = cloud("sphere", 3, n)
     for S in (1, 70, n):
         q = cloud("cube", 3, S, seed=5)
@@ -190,6 +206,18 @@ def test_ragged_batches(mods):
         i, f = nb.knn(cuda(fx), k, counts=wild.flip(0), method=method)
         j, g = nb.knn(cuda(fx), k, counts=[n, 0], method=method)
         assert torch.equal(i, j) and torch.equal(f, g) and (f[0] == k).all()
+    # the walk's rounds in one ragged batch of capacity 4225: 4225 = 66 supergroups + 1 record; 4161 = 65 + 1 record, where
+    # supergroup 0 has kmax = 130 and a third round of two candidates; 65 = one full supergroup and one record; 64 = a single
+    # supergroup, kmax = 0; 2 = found < k
+    big, qbig = [4225, 4161, 65, 64, 2], [130, 64, 65, 2, 0]
+    x, q = cloud("cube", B, 4225, seed=9), cloud("sphere", B, 130, seed=9)
+    for c in range(B):
+        x[c, big[c]:] = np.nan
+        q[c, qbig[c]:] = np.nan
+    twin = check(nb, x, k, counts=big, what="ragged self, 4225")
+    assert twin["found"][4, :2].tolist() == [2, 2] and (twin["found"][3, :64] == k).all() and not twin["idx"][3, 64:].any()
+    twin = check(nb, x, k, query=q, counts=big, qcounts=qbig, what="ragged cross, 4225")
+    assert (twin["found"][0] == k).all() and twin["found"][3, :2].tolist() == [k, k] and not twin["found"][4].any()
 
 
 def test_features(mods):
@@ -292,6 +320,50 @@ def test_repeats_and_graph_replay(mods):
                 graph.replay()
                 torch.cuda.synchronize()
                 assert all(same_bits(u, v) for u, v in zip(first, outs)), (method, sorted(kw))
+
+
+@pytest.mark.parametrize("n", [65, 4097])
+def test_scratch_guard_band(mods, n):
+    """The three entries that build the sorted layout in a scratch of their own (PairLayout, rrl_tree.h) stay inside the bytes their
+    size functions return: each runs in the first workspace_bytes bytes of a buffer with 4096 more bytes of 0xA5 behind them, which
+    stay 0xA5, and gives the bits of a call on a plain buffer.  n = 65: the sort from the points; n = 4097: records launch + wide sort."""
+    ops = mods[3]
+    B, S, k = 2, 70, 5
+    x, y, q = cuda(cloud("cube", B, n, seed=11)), cuda(cloud("sphere", B, n - 1, seed=12)), cuda(cloud("cube", B, S, seed=13))
+    dev, P = x.device, ops._p
+
+    def chamfer(ws, nb):
+        bx, by = torch.zeros(B, n, dtype=torch.int64, device=dev), torch.zeros(B, n - 1, dtype=torch.int64, device=dev)
+        value = torch.zeros(1, device=dev)
+        ops._run(dev, "rrl_chamfer_tree_fwd_ex", P(x), P(y), P(ws), nb, P(bx), P(by), P(value), B, n, n - 1, None, None, None, 0)
+        return bx, by, value
+
+    def knn3(ws, nb):
+        nn, tri = torch.zeros(B, n, 3, dtype=torch.int32, device=dev), torch.zeros(B, n, 9, device=dev)
+        ops._run(dev, "rrl_knn3_self", P(x), None, P(ws), nb, P(nn), P(tri), None, B, n)
+        return nn, tri
+
+    def knn(query):
+        def call(ws, nb):
+            Sq = n if query is None else S
+            idx, found = torch.zeros(B, Sq, k, dtype=torch.int32, device=dev), torch.zeros(B, Sq, dtype=torch.int32, device=dev)
+            d2 = torch.zeros(B, Sq, k, device=dev)
+            ops._run(dev, "rrl_knn", P(x), None, P(query), None, k, 0, 0, P(ws), nb, P(idx), P(found), P(d2), None, B, n, Sq)
+            return idx, found, d2
+        return call
+
+    for what, call, size in (("chamfer", chamfer, ("rrl_chamfer_workspace_bytes", B, n, n - 1)),
+                             ("knn3_self", knn3, ("rrl_knn3_self_workspace_bytes", B, n)),
+                             ("knn self", knn(None), ("rrl_knn_workspace_bytes", B, n, n)),
+                             ("knn cross", knn(q), ("rrl_knn_workspace_bytes", B, n, S))):
+        nb = ops._scratch_size(*size)
+        assert nb > 0
+        guarded = torch.full((nb + 4096,), 0xA5, dtype=torch.uint8, device=dev)
+        got = call(guarded, nb)
+        want = call(torch.full((nb,), 0x5A, dtype=torch.uint8, device=dev), nb)
+        torch.cuda.synchronize()
+        assert (guarded[nb:] == 0xA5).all(), (what, n, "bytes behind the scratch were written")
+        assert all(same_bits(u, v) for u, v in zip(got, want)), (what, n)
 
 
 def test_c_level_refusals(mods):

@@ -120,3 +120,39 @@ def test_python_refusals_need_no_device():
             fn(torch.zeros(2, 3, 50), 0)
     assert neighbors.MAX_K == 32 and neighbors.KNN_FEATURES == KR.FEATURES
     assert neighbors.KNN_TREE_MIN_POINTS is None or neighbors.KNN_TREE_MIN_POINTS >= 1
+
+
+# (B, n[, S]) -> bytes at the commit before the three scratches shared one layout (PairLayout, csrc/rrl_tree.h): a caller who
+# sized a buffer with that library must still fit, so a size may shrink and never grow
+SCRATCH_BYTES_BEFORE = {
+    "rrl_chamfer_workspace_bytes": {(1, 3): 5376, (3, 64): 17664, (3, 65): 27904, (2, 4096): 648960, (2, 4097): 787200,
+                                    (1, 1 << 20): 82904320, (2, 4097, 130): 475648, (2, 130, 4097): 475648},
+    "rrl_knn3_self_workspace_bytes": {(1, 3): 2816, (3, 64): 5888, (3, 65): 10240, (2, 4096): 193536, (2, 4097): 459008,
+                                      (1, 1 << 20): 41484800},
+    "rrl_knn_workspace_bytes": {(1, 3): 4608, (3, 64): 10752, (3, 65): 19456, (2, 4096): 384256, (2, 4097): 784128,
+                                (1, 1 << 20): 82641408, (2, 4097, 130): 472576, (2, 130, 4097): 472576},
+}
+
+
+@pytest.mark.parametrize("entry", list(SCRATCH_BYTES_BEFORE))
+def test_scratch_sizes_never_grow(entry):
+    """The size functions of the entries that build the sorted layout in their own scratch (the Chamfer walk, the all-points 3-NN,
+    the any-k k-NN): positive, at most what they returned before, 0 for a negative dimension.  No GPU needed."""
+    from rrl_hip import build, _lib
+    build.build_lib()
+    fn = getattr(_lib.load(), entry)
+    pair = entry != "rrl_knn3_self_workspace_bytes"
+    for shape, before in SCRATCH_BYTES_BEFORE[entry].items():
+        dims = shape if len(shape) == 3 or not pair else shape + shape[1:]  # (B, n): both clouds of n points
+        now = int(fn(*dims))
+        print(entry, dims, now, "before", before)
+        assert 0 < now <= before, (entry, dims, now, before)
+        assert now % 256 == 0
+        for at in range(len(dims)):
+            bad = list(dims)
+            bad[at] = -1
+            assert fn(*bad) == 0, (entry, bad)
+    # an empty batch and empty clouds are legal sizes, and were no larger either: 768, 512, 768 bytes
+    empty = int(fn(*([0] * (3 if pair else 2))))
+    before = {"rrl_chamfer_workspace_bytes": 768, "rrl_knn3_self_workspace_bytes": 512, "rrl_knn_workspace_bytes": 768}[entry]
+    assert 0 < empty <= before and empty % 256 == 0, (entry, empty, before)
