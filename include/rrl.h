@@ -208,7 +208,14 @@ enum { RRL_WW_TABLE(RRL_WW_ENUM_) RRL_WW_FIELDS };
 /* ---- control words ---------------------------------------------------------------------------
  * The words inside a sample's MCTL and CHAIN rows (RRL_WS_TABLE above) that kernels of different launches hand to each
  * other: ONE map, so that nobody has to find every user to know that they do not overlap (csrc/rrl_ws.h asserts it).
- * All of them are zero between calls: their last user rewinds them. */
+ * Two disciplines (DESIGN.md "What the workspace promises"; tests/test_gpu_workspace.py holds both):
+ *   - REWOUND by their last user, so they read zero whenever the stream is idle: CURSOR, TICK1, TICK2, ERR, MEDRDY, BAD,
+ *     CHAM_GROUP, CHAM_TOP and every CHAIN word (also MSUM, and STATUS[3], the rigid backward's ticket);
+ *   - CLEARED BY THE NEXT CALL's first launch with the rest of MHIST .. MSUM, and left as they are until then: the sixteen
+ *     BUCKET words, MEDBITS, LSUM (and MHIST).
+ * Neither kind needs the caller's help: the first launch of every call that builds records clears MHIST .. MSUM -- on the
+ * sorted layout the CHAIN rows too -- whatever they hold (the chained step's fused launch excepted: RRL_F_CHAINED promises
+ * it the workspace as the previous step left it).  A workspace may hold anything before the first call into it. */
 enum {
     RRL_MCTL_BUCKET0 = 0,     /* [0..15] lines per (k, j) bucket, index (k - 1) 4 + (j - 1): per-line stage -> reduce */
     RRL_MCTL_CURSOR = 16,     /* exchange reduce: cursor of the sample's candidate list (MCAND) */
