@@ -20,7 +20,7 @@ LIB = os.path.join(LIBDIR, "librrl_hip.so")
 HEADER = os.path.join(os.path.dirname(PKG), "include", "rrl.h")  # the C ABI: the library's and, through _abi.py, the binding's
 SOURCES = ["rrl_scan.hip", "rrl_cull.hip", "rrl_sparse.hip", "rrl_geom.hip", "rrl_neigh.hip", "rrl_knn_tree.hip", "rrl_chamfer.hip", "rrl_order.hip", "rrl_epoch.hip",
            "rrl_wide.hip", "rrl_call.hip", "rrl_newton.hip", "rrl_kabsch.hip", "rrl_sinkhorn.hip", "rrl_group.hip", "rrl_plane.hip", "rrl_robust.hip",
-           "rrl_knn.hip", "rrl_pointer.hip", "rrl_fmr.hip", "rrl_pointnet.hip", "rrl_pointnet_group.hip"]
+           "rrl_knn.hip", "rrl_pointer.hip", "rrl_fmr.hip", "rrl_pointnet.hip", "rrl_pointnet_group.hip", "rrl_attention.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-function"]
 

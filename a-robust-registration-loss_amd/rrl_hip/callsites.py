@@ -389,6 +389,22 @@ def dcp_svd_head(src_embedding, tgt_embedding, src, tgt):
     return dcp_svd_head_pose(src, dcp_soft_pointer(src_embedding, tgt_embedding, tgt))
 
 
+def dcp_attention(query, key, value, n_heads):
+    """dcp/model.py:232-245, the attention step of MultiHeadedAttention.forward as ONE node (rrl_hip.attention): the projected
+    query (B, N, D), key and value (B, M, D) as the nn.Linear layers leave them -> x (B, N, D), what the reference holds after
+    its `x.transpose(1, 2).contiguous().view(nbatches, -1, h * d_k)`; differentiable in all three; neither the (B, h, N, M)
+    matrix nor a head-major copy exists."""
+    from .attention import attend
+    return attend(query, key, value, n_heads)
+
+
+def dcp_transformer(module, src_embedding, tgt_embedding):
+    """Transformer.forward (dcp/model.py:392-401) on an rrl_hip.attention.Transformer (its state_dict is the reference's:
+    module.load_state_dict(dcp_net.pointer.state_dict(), strict=True)): src_embedding (B, C, N), tgt_embedding (B, C, M),
+    channel-first as DCP holds them -> (src_embedding_p, tgt_embedding_p) of the same shapes, six attention nodes."""
+    return module(src_embedding, tgt_embedding)
+
+
 # ---- RPM's match head: Sinkhorn soft assignment in front of the solve above ----------------------------------------------
 def rpm_soft_correspondences(affinity, xyz_ref, n_iters=5, slack=True):
     """rpm/models/rpmnet.py:211-222 up to the solve, as ONE node (rrl_hip.sinkhorn): affinity (B, J, K), xyz_ref (B, K, 3) ->

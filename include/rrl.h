@@ -1710,6 +1710,59 @@ int rrl_pointnet_group_bwd(const float *x, const float **params, const int32_t *
                            size_t ws_bytes, const int32_t *arg, const float *g_out, void *bws, size_t bws_bytes, float *d_x,
                            float **d_params, int B, int N, int S, int c0, int L, void *stream);
 
+/* ---- DCP's multi-head attention: the transformer's core without the score matrix -------------
+ * attention() inside MultiHeadedAttention.forward (dcp/model.py:27-34, 212-246): out = softmax(q k^T / sqrt(DK), dim = -1) v per
+ * head.  Token-major, exactly as the nn.Linear projections leave it: q, out, g_out, d_q [B][N][H DK]; k, v, d_k, d_v
+ * [B][M][H DK]; head h is channels h DK .. (h + 1) DK - 1 of a token's row -- the entries absorb the reference's
+ * view(...).transpose(1, 2).contiguous() on the way in and out, no head-major copy exists.  count_q / count_kv: device int32
+ * [B] or NULL (= N / M), clamped by the kernels to [0, N] / [0, M], never read on the host; rows and columns beyond them are
+ * never read.  Plain device pointers, sizes and a stream: nothing is allocated, read back or synchronised, there are no
+ * atomics, nothing is indexed by data, every launch goes to the caller's stream.
+ *
+ * The rule (v_mfma_f32_32x32x2_f32 is a float32 fmaf chain over its reduction index, bit for bit, as for rrl_pointer_fwd):
+ *  1. z[j][k] = chain * sc: chain starts at +0 and runs over the head's channels c ascending, chain = fmaf(q[j][c], k[k][c],
+ *     chain), ONE chain per score, never split over wavefronts or channel blocks; sc = float32(1 / sqrt(double(DK))), one
+ *     float32 multiplication.  DK is padded with zero channels in BOTH operands up to 32, 64 or 128, the kernel's block (a
+ *     zero step leaves a chain as it is, but for the sign of a zero).
+ *  2. M_j = max_k z[j][k] over the columns below count_kv, taken in a first walk over ALL columns before any term is formed
+ *     (fmaxf: a NaN score does not enter).  p[j][k] = expf(z - M_j), float32 from the float32 difference; a -inf score gives
+ *     0 without forming -inf - (-inf).  L_j = sum_k p in double: a lane sums its columns ascending (columns 4 h .. 4 h + 3 of
+ *     every eight, h = 0, 1), the two halves are then added.
+ *  3. o[j][c] starts at +0 and runs over k = 0 .. count_kv - 1 ascending, o = fmaf(v[k][c], p[j][k], o): whole, the wavefront
+ *     that owns row j walks every column and carries the accumulator; the columns that pad the last tile of 32 are zero in
+ *     BOTH operands.  out[j][c] = float32(double(o) / L_j).  The score product therefore runs twice in the forward.  Rows at
+ *     or beyond count_q, and every row when count_kv[b] == 0, are exactly 0.
+ *  4. Backward, on z recomputed by the same chain (the same bits) and M_j, 1 / L_j (the reciprocal taken once per row, in
+ *     double) kept in ws: delta_j = sum_c g[j][c] out[j][c] in double, c ascending; Pn = float32(double(expf(z - M_j)) (1 / L_j));
+ *     dP[j][k] = the float32 chain over c ascending of g[j][c] v[k][c]; ds[j][k] = float32(double(Pn) (double(dP) - delta_j)
+ *     double(sc)); d_v[k][c] = the chain over j ascending of g[j][c] Pn[j][k], d_q[j][c] the chain over k ascending of k[k][c]
+ *     ds[j][k], d_k[k][c] the chain over j ascending of q[j][c] ds[j][k]: whole chains (one pass owns rows and writes d_q,
+ *     one owns columns and writes d_k and d_v, each walks the other dimension entirely).  Rows and columns beyond the counts
+ *     get zero gradient.  Every element of every output is written; nothing is pre-zeroed.
+ * Two calls give the same bits; sample b of a ragged batch has the bits of its own B = 1 call.
+ *
+ * info (optional) [B]: 1 where a score or an output entry inside the counts is NaN or +-inf, else 0.  d_q, d_k, d_v: each may
+ * be NULL; a pass that serves only NULL outputs is not launched.  The backward takes the forward's out.
+ * ws: rrl_attention_workspace_bytes(B, H, N, M) bytes, 8-byte aligned: two doubles per (sample, head, row) -- M_j and
+ * 1 / L_j, whose SIGN carries the row's info flag (L >= 1 or NaN; the backward takes the magnitude) --, independent of M and DK;
+ * no array of size N M in either direction.  The backward takes the ws its forward filled.
+ * Launches: forward 1, and 1 more when info is asked for; backward 1 per pass (the column pass 1 per output where DK > 64 is
+ * odd or a tensor is not 16-byte aligned).
+ * Refusals, on the host before any HIP call: RRL_E_ARG -- NULL q / k / v / ws / out (backward also g_out); B outside 0..32767;
+ * H outside 1..16; DK outside 1..RRL_ATTENTION_MAX_DK; N or M outside 1..16384 --, then RRL_E_WS: a short or misaligned ws.
+ * B == 0 returns 0 without a launch.
+ * rrl_attention_scores writes z alone, [B][H][N][M], -inf at and beyond the counts, by the same chain: for tests and
+ * endpoints, it is the only (B, H, N, M) array and nothing else reads it. */
+#define RRL_ATTENTION_MAX_DK 128
+size_t rrl_attention_workspace_bytes(int B, int H, int N, int M);
+int rrl_attention_fwd(const float *q, const float *k, const float *v, const int32_t *count_q, const int32_t *count_kv, void *ws,
+                      size_t ws_bytes, float *out, int32_t *info, int B, int H, int DK, int N, int M, void *stream);
+int rrl_attention_bwd(const float *q, const float *k, const float *v, const int32_t *count_q, const int32_t *count_kv, void *ws,
+                      size_t ws_bytes, const float *out, const float *g_out, float *d_q, float *d_k, float *d_v, int B, int H,
+                      int DK, int N, int M, void *stream);
+int rrl_attention_scores(const float *q, const float *k, const int32_t *count_q, const int32_t *count_kv, float *scores, int B,
+                         int H, int DK, int N, int M, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
